@@ -2,6 +2,7 @@
 """bench.py -- the `clustering density` hot path on N MI355X GPUs of one node.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                  (+ the last timed step's outputs as DIR/<name>.npy)
 
 A "step" is one pass of the hot path over one synthetic trajectory:
     populations (one sweep over all radii) -> free energies -> nearest neighbour / nearest
@@ -143,7 +144,46 @@ def parse_args():
     ap.add_argument("--no-nn", action="store_true", help="populations + free energies only (C2-style)")
     ap.add_argument("--no-full-sweep", action="store_true", help="skip the unpruned reference sweeps (roofline_full_sweep)")
     ap.add_argument("--no-fp32-instance", action="store_true", help="skip the fp32-input MFMA instance (fp32_mfma_instance)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in "
+                         "all: a fixed, seeded sample of the rows when the full arrays are larger)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64_000_000      # all .npy files of --dump-outputs together (headers included)
+DUMP_SAMPLE_SEED = 20241015         # the rows kept when the full arrays exceed the budget
+
+
+def dump_outputs(out, n_rows, dirname):
+    """The arrays a caller of ShardedDensity.run receives, as DIR/<name>.npy: pops [n_radii, N] and the neighbour indices
+    as float64 (exact: integers < 2^53), fe and the neighbour d2 as float32 (their own dtype, bit for bit).  If they
+    would exceed DUMP_BUDGET_BYTES, every array keeps the same sorted, seeded sample of rows, listed in rows.npy."""
+    import numpy as np
+    import torch
+    as_f64 = {"pops", "nn_idx", "hd_idx"}
+    names = [k for k in ("pops", "fe", "nn_idx", "nn_d2", "hd_idx", "hd_d2") if k in out]
+    per_row = sum((8 if k in as_f64 else 4) * (out[k].shape[0] if out[k].dim() == 2 else 1) for k in names)
+    header = 128 * (len(names) + 1)
+    rows = None
+    if per_row * n_rows + header > DUMP_BUDGET_BYTES:
+        k = (DUMP_BUDGET_BYTES - header) // (per_row + 8)          # + 8: rows.npy itself
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_rows, size=k, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for k in names:
+        t = out[k]
+        if rows is not None:
+            t = t.index_select(t.dim() - 1, torch.from_numpy(rows).to(t.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, k + ".npy"), a.astype(np.float64 if k in as_f64 else np.float32))
+    if rows is not None:
+        np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    what = f"a sample of {len(rows)} of {n_rows} rows" if rows is not None else f"all {n_rows} rows"
+    print(f"bench.py: outputs of the last timed step ({', '.join(names)}; {what}) written to {dirname}", file=sys.stderr)
 
 
 def cpu_baseline(coords_np, radii, sample_rows, want_nn):
@@ -239,6 +279,9 @@ def main():
     t1 = time.perf_counter()
     if world > 1:
         job.check_layouts(dev)
+    if args.dump_outputs and rank == 0:
+        # (outside the timed region; every rank holds the same merged results)
+        dump_outputs(out, n, args.dump_outputs)
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)

@@ -161,8 +161,8 @@ def test_bench_starts_its_own_ranks_and_the_sharded_step_agrees(tmp_path):
     """`bench.py --gpus N` without a launcher spawns its N ranks itself (torch.distributed.run as a child, before
     anything touches HIP).  On a one-GPU box the ranks share the device and talk over gloo
     (DC_BENCH_ONE_DEVICE=1: timings mean nothing, the sharded step -- segment sweeps, all-reduce(sum) of the
-    populations, all-reduce(min) of the packed neighbour words -- is the real one): its check values must equal
-    the single-rank run's."""
+    populations, all-reduce(min) of the packed neighbour words -- is the real one): its check values and the outputs
+    it dumps (--dump-outputs) must equal the single-rank run's."""
     import json
     env = dict(os.environ, DC_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
@@ -170,7 +170,8 @@ def test_bench_starts_its_own_ranks_and_the_sharded_step_agrees(tmp_path):
     args = ["--steps", "1", "--warmup", "1", "--n-rows", "150000", "--cpu-sample", "0"]
     out = {}
     for n in (1, 4):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + args,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + args
+                           + ["--dump-outputs", str(tmp_path / f"out{n}")],
                            capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
         assert r.returncode == 0, r.stderr[-2000:]
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -178,6 +179,13 @@ def test_bench_starts_its_own_ranks_and_the_sharded_step_agrees(tmp_path):
         assert out[n]["n_gpus"] == n and out[n]["roofline"]["frac"] <= 1.0
     assert out[4]["config"]["rccl_ranks"] == 4 and out[4]["config"]["backend"] == "gloo"
     assert out[1]["check"] == out[4]["check"]        # mean / max population and sigma2 of the merged results
+    names = sorted(os.listdir(tmp_path / "out1"))
+    assert names == sorted(os.listdir(tmp_path / "out4")) == sorted(
+        k + ".npy" for k in ("pops", "fe", "nn_idx", "nn_d2", "hd_idx", "hd_d2"))
+    for f in names:
+        a, b = np.load(tmp_path / "out1" / f), np.load(tmp_path / "out4" / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape[-1] == 150000, f
+        assert a.dtype == b.dtype and (a.view(np.uint8) == b.view(np.uint8)).all(), f
 
 
 HOST_MERGE_CHILD = r"""
