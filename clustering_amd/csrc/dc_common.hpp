@@ -32,6 +32,19 @@ bool launch_nn_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, c
                       uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
                       uint32_t* d_hd_idx, float* d_hd_d2, const uint32_t* gate, hipStream_t stream);
 
+// The radius graph (canonical d2 < r2) without the matrix-core sweep: n_cols > 64, or flagged data behind the gate.
+// pairs: pops[i] for all rows, every unordered pair {i, j} once as (i, j) with i < j; *d_count (zeroed by the caller)
+// grows by the number of pairs, slots < capacity are written (d_pairs == nullptr: counting only).
+bool launch_pairs_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops,
+                         uint2* d_pairs, unsigned long long capacity, unsigned long long* d_count,
+                         const uint32_t* gate, hipStream_t stream);
+// min edge: for the query rows [i_from, i_to), pops[i] and atomicMin(best[comp[i]], (max(rank) << 32 | min(rank)))
+// over the partners j with comp[j] != comp[i] (d_best preset to ~0 by the caller)
+bool launch_min_edge_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2,
+                            const uint32_t* d_comp, const uint32_t* d_rank, uint32_t i_from, uint32_t i_to,
+                            unsigned long long* d_best, uint32_t* d_pops, const uint32_t* gate,
+                            hipStream_t stream);
+
 // fills idx[i] = n_rows+1, d2[i] = FLT_MAX for all rows (density_clustering.cpp:242-245)
 void launch_nn_init(uint32_t n_rows, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                     float* d_hd_d2, hipStream_t stream);

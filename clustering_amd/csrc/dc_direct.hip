@@ -289,6 +289,203 @@ __global__ __launch_bounds__(kGBlock) void nn_generic_kernel(
 }
 
 // -----------------------------------------------------------------------------------------
+// radius graph (canonical d2 < r2, the graph of the reference's screening, density_clustering.cpp:
+// 292-332) for every n_cols the sweeps above accept: the two products of the matrix-core sweep's
+// sinks (dc_mfma.hpp EdgeSink), for n_cols > 64 and for data the operand-image pass flagged.
+// Same tiles and arithmetic as the population kernels, whose output they write as well.
+//   kGraphPairs:   every unordered pair {i, j} once, from its query i < j.  Hits go into a wave-private
+//                  LDS queue (ballot + mbcnt) that is flushed with ONE 64-bit atomicAdd per batch;
+//                  capacity 0 counts only (the flushes still add to the count)
+//   kGraphMinEdge: per query the lightest (max(rank) << 32 | min(rank)) over the partners of another
+//                  component, then one 64-bit atomicMin into best[comp[i]] (a Boruvka round)
+// -----------------------------------------------------------------------------------------
+enum GraphMode { kGraphPairs = 1, kGraphMinEdge = 2 };
+constexpr uint32_t kPairQueue = 256;   // pairs a wave queues before it flushes (uint2 each)
+
+struct GraphOut {
+  uint32_t* pops;
+  uint2* pairs;                  // kGraphPairs: the list, slots < capacity written
+  unsigned long long capacity;
+  unsigned long long* count;     // kGraphPairs: total number of pairs (may exceed capacity)
+  const uint32_t* comp;          // kGraphMinEdge: component id and rank per frame, best per component id
+  const uint32_t* rank;
+  unsigned long long* best;
+};
+
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {   // set bits of m below this lane
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// the wave's queued pairs -> slots [base, base + fill) of the list; fill is wave-uniform
+__device__ __forceinline__ void pair_flush(const uint2* queue, uint32_t& fill, const GraphOut& g) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the queue writes of all lanes before their reads)
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const uint32_t lane = threadIdx.x & 63u;
+  unsigned long long base = 0;
+  if (lane == 0) base = atomicAdd(g.count, (unsigned long long)fill);
+  base = __shfl(base, 0, 64);
+  for (uint32_t k = lane; k < fill; k += 64)
+    if (base + k < g.capacity) g.pairs[base + k] = queue[k];
+  __builtin_amdgcn_wave_barrier();
+  fill = 0;
+}
+
+// one candidate pair per lane (emit: (i, j) is a pair); called by the whole wave
+__device__ __forceinline__ void pair_push(bool emit, uint32_t i, uint32_t j, uint2* queue, uint32_t& fill,
+                                          const GraphOut& g) {
+  const unsigned long long m = __ballot(emit);
+  if (m == 0) return;
+  if (fill + 64u > kPairQueue) pair_flush(queue, fill, g);
+  if (emit) queue[fill + lanes_below(m)] = make_uint2(i, j);
+  fill += (uint32_t)__popcll(m);
+}
+
+template <int D, int Q, int MODE>
+__device__ __forceinline__ void graph_tile(const float* tile, const uint32_t* tile_cr, uint32_t t0, uint32_t nt,
+                                           bool emit, float r2, const float (&q)[Q][D], const uint32_t (&qi)[Q],
+                                           const bool (&live)[Q], const uint32_t (&qc)[Q], const uint32_t (&qr)[Q],
+                                           uint32_t (&cnt)[Q], unsigned long long (&best)[Q], uint2* queue,
+                                           uint32_t& fill, const GraphOut& g) {
+  auto row = [&](uint32_t r) {
+    float ref[D];
+    load_ref<D>(tile, r, ref);
+    const uint32_t j = t0 + r;
+#pragma unroll
+    for (int a = 0; a < Q; ++a) {
+      const float d = dist2_canon<D>(q[a], ref);
+      const bool hit = d < r2;
+      cnt[a] += hit ? 1u : 0u;
+      if constexpr (MODE == kGraphMinEdge) {
+        // (the self pair and every pair inside the component: same id)
+        const uint32_t rr = tile_cr[kTile + r];
+        const unsigned long long key = ((unsigned long long)max(qr[a], rr) << 32) | min(qr[a], rr);
+        best[a] = (hit && tile_cr[r] != qc[a] && key < best[a]) ? key : best[a];
+      } else {
+        if (emit) pair_push(hit && live[a] && j > qi[a], qi[a], j, queue, fill, g);
+      }
+    }
+  };
+  if constexpr (MODE == kGraphMinEdge) {
+#pragma unroll 2
+    for (uint32_t r = 0; r < nt; ++r) row(r);
+  } else {   // (a flush inside the body: no unrolling)
+    for (uint32_t r = 0; r < nt; ++r) row(r);
+  }
+}
+
+template <int D, int MODE>
+__global__ __launch_bounds__(kBlock) void graph_direct_kernel(const float* __restrict__ coords, uint32_t n_rows,
+                                                              uint32_t i_from, uint32_t i_to, float r2, GraphOut g,
+                                                              const uint32_t* __restrict__ gate) {
+  constexpr int S = Cfg<D>::S, Q = Cfg<D>::Q;
+  constexpr bool kMin = MODE == kGraphMinEdge;
+  if (gate && gate[1] == 0) return;
+  __shared__ __attribute__((aligned(16))) float tile[kTile * S];
+  __shared__ uint32_t tile_cr[kMin ? 2 * kTile : 1];                  // comp, rank of the tile's rows
+  __shared__ uint2 queues[kMin ? 1 : (kBlock / 64) * kPairQueue];    // one pair queue per wave
+  uint2* queue = queues + (kMin ? 0u : (threadIdx.x >> 6) * kPairQueue);
+  const uint32_t qbase = i_from + blockIdx.x * (kBlock * Q);
+  const uint32_t wave_lo = qbase + (threadIdx.x & ~63u);   // this wave's lowest query row
+
+  float q[Q][D];
+  uint32_t qi[Q], cnt[Q], qc[Q], qr[Q];
+  bool live[Q];
+  unsigned long long best[Q];
+#pragma unroll
+  for (int a = 0; a < Q; ++a) {
+    qi[a] = qbase + a * kBlock + threadIdx.x;
+    live[a] = qi[a] < i_to;
+    const uint32_t row = live[a] ? qi[a] : i_to - 1;   // clamp: result discarded
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[a][k] = coords[(size_t)row * D + k];
+    cnt[a] = 0;
+    qc[a] = kMin ? g.comp[row] : 0u;
+    qr[a] = kMin ? g.rank[row] : 0u;
+    best[a] = ~0ull;
+  }
+  uint32_t fill = 0;
+  for (uint32_t t0 = 0; t0 < n_rows; t0 += kTile) {
+    const uint32_t nt = min((uint32_t)kTile, n_rows - t0);
+    __syncthreads();
+    stage_tile<D>(coords, t0, nt, tile);
+    if (kMin && threadIdx.x < nt) {
+      tile_cr[threadIdx.x] = g.comp[t0 + threadIdx.x];
+      tile_cr[kTile + threadIdx.x] = g.rank[t0 + threadIdx.x];
+    }
+    __syncthreads();
+    // a pair is listed from its lower row: tiles wholly at or below the wave's rows list nothing
+    graph_tile<D, Q, MODE>(tile, tile_cr, t0, nt, t0 + nt > wave_lo + 1u, r2, q, qi, live, qc, qr, cnt, best, queue,
+                           fill, g);
+  }
+  if constexpr (!kMin) {
+    if (fill) pair_flush(queue, fill, g);
+  }
+#pragma unroll
+  for (int a = 0; a < Q; ++a) {
+    if (live[a]) {
+      const float dself = dist2_canon<D>(q[a], q[a]);   // (see pop_direct_kernel)
+      g.pops[qi[a]] = cnt[a] + 1u - ((dself < r2) ? 1u : 0u);
+      if (kMin && best[a] != ~0ull) atomicMin(g.best + qc[a], best[a]);
+    }
+  }
+}
+
+// generic n_cols: the layout of pop_generic_kernel, then [2][kGTile] comp / rank (min edge) or the wave's pair queue
+template <int MODE>
+__global__ __launch_bounds__(kGBlock) void graph_generic_kernel(const float* __restrict__ coords, uint32_t n_rows,
+                                                                uint32_t D, uint32_t i_from, uint32_t i_to, float r2,
+                                                                GraphOut g, const uint32_t* __restrict__ gate) {
+  constexpr bool kMin = MODE == kGraphMinEdge;
+  if (gate && gate[1] == 0) return;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* qs = smem;                          // [D][kGBlock]
+  float* tile = smem + (size_t)D * kGBlock;  // [kGTile][D]
+  uint32_t* tile_cr = reinterpret_cast<uint32_t*>(tile + (size_t)kGTile * D);
+  uint2* queue = reinterpret_cast<uint2*>(tile + (size_t)kGTile * D);
+  const uint32_t wave_lo = i_from + blockIdx.x * kGBlock;
+  const uint32_t qi = wave_lo + threadIdx.x;
+  const bool live = qi < i_to;
+  const uint32_t row = live ? qi : i_to - 1;
+  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = coords[(size_t)row * D + k];
+  const uint32_t qc = kMin ? g.comp[row] : 0u, qr = kMin ? g.rank[row] : 0u;
+  uint32_t cnt = 0, fill = 0;
+  unsigned long long best = ~0ull;
+  for (uint32_t t0 = 0; t0 < n_rows; t0 += kGTile) {
+    const uint32_t nt = min((uint32_t)kGTile, n_rows - t0);
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = coords[(size_t)t0 * D + e];
+    if (kMin && threadIdx.x < nt) {
+      tile_cr[threadIdx.x] = g.comp[t0 + threadIdx.x];
+      tile_cr[kGTile + threadIdx.x] = g.rank[t0 + threadIdx.x];
+    }
+    __syncthreads();
+    const bool emit = t0 + nt > wave_lo + 1u;
+    for (uint32_t r = 0; r < nt; ++r) {
+      const uint32_t j = t0 + r;
+      const float d = dist2_canon_rt(qs + threadIdx.x, kGBlock, tile + r * D, 1, (int)D);
+      const bool hit = d < r2;
+      cnt += hit ? 1u : 0u;
+      if constexpr (kMin) {
+        const uint32_t rr = tile_cr[kGTile + r];
+        const unsigned long long key = ((unsigned long long)max(qr, rr) << 32) | min(qr, rr);
+        best = (hit && tile_cr[r] != qc && key < best) ? key : best;
+      } else {
+        if (emit) pair_push(hit && live && j > qi, qi, j, queue, fill, g);
+      }
+    }
+  }
+  if constexpr (!kMin) {
+    if (fill) pair_flush(queue, fill, g);
+  }
+  if (live) {
+    const float dself = dist2_canon_rt(qs + threadIdx.x, kGBlock, qs + threadIdx.x, kGBlock, (int)D);
+    g.pops[qi] = cnt + 1u - ((dself < r2) ? 1u : 0u);
+    if (kMin && best != ~0ull) atomicMin(g.best + qc, best);
+  }
+}
+
+// -----------------------------------------------------------------------------------------
 // small helpers
 // -----------------------------------------------------------------------------------------
 __global__ void nn_init_kernel(uint32_t n_rows, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx,
@@ -431,6 +628,49 @@ const auto kPop4 = make_pop_table<4>(DSeq{});
 const auto kPop8 = make_pop_table<8>(DSeq{});
 const auto kNn = make_nn_table(DSeq{});
 
+using GraphLaunch = void (*)(const float*, uint32_t, uint32_t, uint32_t, float, const GraphOut&, const uint32_t*,
+                             hipStream_t);
+
+template <int D, int MODE>
+void graph_launch(const float* c, uint32_t n, uint32_t i_from, uint32_t i_to, float r2, const GraphOut& g,
+                  const uint32_t* gate, hipStream_t s) {
+  const uint32_t per_block = kBlock * Cfg<D>::Q;
+  const uint32_t grid = (i_to - i_from + per_block - 1) / per_block;
+  hipLaunchKernelGGL((graph_direct_kernel<D, MODE>), dim3(grid), dim3(kBlock), 0, s, c, n, i_from, i_to, r2, g, gate);
+}
+
+template <int MODE, int... Ds>
+constexpr auto make_graph_table(std::integer_sequence<int, Ds...>) {
+  return std::array<GraphLaunch, sizeof...(Ds)>{&graph_launch<Ds + 1, MODE>...};
+}
+
+const auto kGraphPairsTab = make_graph_table<kGraphPairs>(DSeq{});
+const auto kGraphMinEdgeTab = make_graph_table<kGraphMinEdge>(DSeq{});
+
+// one launch of the radius-graph kernels over query rows [i_from, i_to); false: n_cols unsupported
+template <int MODE>
+bool launch_graph(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from, uint32_t i_to, float r2,
+                  const GraphOut& g, const uint32_t* gate, hipStream_t stream) {
+  if (n_cols >= 1 && n_cols <= (uint32_t)kMaxColsTemplated) {
+    if (i_to > i_from)
+      (MODE == kGraphPairs ? kGraphPairsTab : kGraphMinEdgeTab)[n_cols - 1](d_coords, n_rows, i_from, i_to, r2, g,
+                                                                             gate, stream);
+    return true;
+  }
+  if (n_cols > (uint32_t)kMaxColsTemplated && n_cols <= (uint32_t)kMaxColsGeneric) {
+    if (i_to <= i_from) return true;
+    const uint32_t grid = (i_to - i_from + kGBlock - 1) / kGBlock;
+    const size_t smem = sizeof(float) * (size_t)n_cols * (kGBlock + kGTile) +
+                        (MODE == kGraphPairs ? sizeof(uint2) * kPairQueue : sizeof(uint32_t) * 2 * kGTile);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(graph_generic_kernel<MODE>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(graph_generic_kernel<MODE>, dim3(grid), dim3(kGBlock), smem, stream, d_coords, n_rows, n_cols,
+                       i_from, i_to, r2, g, gate);
+    return true;
+  }
+  return false;
+}
+
 }  // namespace
 
 bool launch_pop_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from,
@@ -474,6 +714,21 @@ bool launch_nn_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, c
     return true;
   }
   return false;
+}
+
+bool launch_pairs_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops,
+                         uint2* d_pairs, unsigned long long capacity, unsigned long long* d_count,
+                         const uint32_t* gate, hipStream_t stream) {
+  const GraphOut g{d_pops, d_pairs, d_pairs ? capacity : 0ull, d_count, nullptr, nullptr, nullptr};
+  return launch_graph<kGraphPairs>(d_coords, n_rows, n_cols, 0, n_rows, r2, g, gate, stream);
+}
+
+bool launch_min_edge_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2,
+                            const uint32_t* d_comp, const uint32_t* d_rank, uint32_t i_from, uint32_t i_to,
+                            unsigned long long* d_best, uint32_t* d_pops, const uint32_t* gate,
+                            hipStream_t stream) {
+  const GraphOut g{d_pops, nullptr, 0ull, nullptr, d_comp, d_rank, d_best};
+  return launch_graph<kGraphMinEdge>(d_coords, n_rows, n_cols, i_from, i_to, r2, g, gate, stream);
 }
 
 void launch_nn_init(uint32_t n_rows, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,

@@ -1177,8 +1177,7 @@ void launch_pop_pruned_segment(const float* d_coords, uint32_t n_rows, uint32_t 
                    max_radius2(rad2, n_rad), r == 0, comp_clean);
 }
 
-// positions of the sweep's spatial order -> frame ids, for the pairs actually written; a flagged
-// data set (the matrix-core kernel stood down) reports count = ~0
+// positions of the sweep's spatial order -> frame ids, for the pairs actually written
 __global__ void edges_to_frames_kernel(uint2* __restrict__ edges, const unsigned long long* __restrict__ count,
                                        unsigned long long capacity, const uint32_t* __restrict__ perm) {
   const unsigned long long n = *count < capacity ? *count : capacity;
@@ -1188,8 +1187,10 @@ __global__ void edges_to_frames_kernel(uint2* __restrict__ edges, const unsigned
     edges[k] = make_uint2(perm[e.x], perm[e.y]);
   }
 }
+// a flagged data set (the matrix-core kernel stood down; the count-only path summed the zeroed pops): the count
+// starts again at 0 for the gated direct kernel that follows (dc_direct.hip launch_pairs_direct)
 __global__ void edges_flag_kernel(const uint32_t* __restrict__ hdr, unsigned long long* __restrict__ count) {
-  if (hdr[1] != 0) *count = ~0ull;
+  if (hdr[1] != 0) *count = 0ull;
 }
 
 // per-frame values into the sweep's order (component ids, ranks)

@@ -51,7 +51,8 @@ void launch_pop_pruned(const float* d_coords, uint32_t n_rows, uint32_t n_cols, 
                        void* d_ws, hipStream_t stream, bool comp_clean = false);
 // pruned population sweep at squared radius r2 that also lists every unordered frame pair with
 // canonical d2 < r2 (frame ids; d_pairs may be nullptr to count only); needs mfma_prepare first.
-// *d_count: number of pairs found (> capacity: buffer too small), ~0 if the data was flagged.
+// *d_count: number of pairs found (> capacity: buffer too small); 0, and nothing written, if the data was flagged
+// (the gated launch_pairs_direct answers then).
 void launch_radius_pairs(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2,
                          uint32_t* d_pops, uint2* d_pairs, unsigned long long capacity,
                          unsigned long long* d_count, void* d_ws, hipStream_t stream);

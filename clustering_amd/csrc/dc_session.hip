@@ -674,9 +674,7 @@ int dc_hip_session_radius_pairs(dc_hip_session* s, float r2, uint32_t* pairs, si
   if (rc == DC_OK) {
     e = hipMemcpyAsync(count, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-    if (e == hipSuccess && *count == ~0ull) {
-      rc = failf(DC_ERR_INVALID_ARGUMENT, "radius pairs need finite coordinates");
-    } else if (e == hipSuccess && capacity) {
+    if (e == hipSuccess && capacity) {
       const size_t k = (size_t)std::min<unsigned long long>(*count, capacity);
       if (k) e = hipMemcpy(pairs, d_pairs, sizeof(uint32_t) * 2 * k, hipMemcpyDeviceToHost);
     }
@@ -736,7 +734,6 @@ int dc_hip_session_radius_forest(dc_hip_session* s, float r2, const uint32_t* ra
   uint32_t rounds = 0;
   // every round at least halves the number of components that still have a partner
   for (; rounds < 64; ++rounds) {
-    uint32_t flagged = 0;
     rc = on_every_device(s, [&](int g) -> int {
       DevState& d = s->dev[g];
       SESSION_HIP_TRY(hipMemcpyAsync(d.d_comp, comp.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, d.stream));
@@ -751,14 +748,7 @@ int dc_hip_session_radius_forest(dc_hip_session* s, float r2, const uint32_t* ra
     DevState& d0 = s->dev[0];
     SESSION_HIP_TRY(hipSetDevice(d0.device));
     SESSION_HIP_TRY(hipMemcpyAsync(best.data(), d0.d_words, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, d0.stream));
-    if (rounds == 0) {
-      uint32_t hdr[2] = {0, 0};
-      SESSION_HIP_TRY(hipMemcpyAsync(hdr, d0.d_ws, sizeof(hdr), hipMemcpyDeviceToHost, d0.stream));
-      SESSION_HIP_TRY(hipStreamSynchronize(d0.stream));
-      flagged = hdr[1];
-    }
     if ((rc = sync_all(s, "radius forest sweep")) != DC_OK) return rc;
-    if (flagged != 0) return failf(DC_ERR_INVALID_ARGUMENT, "the radius graph needs finite coordinates");
     size_t joined = 0;
     for (size_t c = 0; c < n; ++c) {
       if (best[c] == ~0ull) continue;

@@ -267,15 +267,18 @@ DC_API int dc_hip_sigma2_dev(const float* d_nn_d2, size_t n_rows, double* sigma2
 
 /* the radius graph that the reference's screening walks one frame at a time: replaces the O(n^2) scans
  * of high_density_neighborhood (density_clustering.cpp:292-332, called per frame from
- * density_clustering_common.cpp:97-121; CUDA: density_clustering_cuda.cu:396-594) by ONE pruned sweep
- * that lists every unordered frame pair {i, j}, i != j, whose canonical d2 is < r2 (strict, :319).
+ * density_clustering_common.cpp:97-121; CUDA: density_clustering_cuda.cu:396-594) by ONE sweep that
+ * lists every unordered frame pair {i, j}, i != j, whose canonical d2 is < r2 (strict, :319).  The
+ * pruned matrix-core sweep for n_cols <= 64; an exact direct sweep over all pairs for n_cols 65..400
+ * and for coordinates that are not finite (inf / NaN in a row: no partners, population 1, as in the
+ * reference), chosen on the device like the populations' fallback.
  *   r2       the squared distance itself (the reference passes max_dist = 4*sigma2, a float)
  *   d_pops   [n_rows] uint32 device, out: populations at that radius (1 + number of partners)
  *   d_pairs  [capacity][2] uint32 device, out: frame ids of the pairs, in no particular order, each
  *            pair once; may be NULL with capacity 0 to count only
  *   d_count  device uint64, out: number of pairs found -- if it exceeds capacity only the first
- *            `capacity` were written (call again with a larger buffer); ~0 if the coordinates are not
- *            finite (no pairs are produced then).  Needs n_cols <= 64 and a workspace as above. */
+ *            `capacity` were written (call again with a larger buffer).
+ * Needs a workspace as above for n_cols <= 64; for n_cols > 64 none (NULL / 0: dc_hip_workspace_bytes is 0). */
 DC_API int dc_hip_radius_pairs_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
                                    uint32_t* d_pops, uint32_t* d_pairs, size_t capacity,
                                    unsigned long long* d_count, void* d_workspace,
@@ -290,15 +293,17 @@ DC_API int dc_hip_radius_pairs_dev(const float* d_coords, size_t n_rows, size_t 
  *   d_best   [n_rows] uint64 device, out: d_best[id] = (max << 32 | min) of the lightest pair with
  *            canonical d2 < r2 that joins component id to another one, ~0 if there is none
  *   d_pops   [n_rows] uint32 device, out: populations at that radius
- * Needs n_cols <= 64, n_rows <= 2^24 and a workspace as above; with coordinates that are not finite
- * every d_best entry stays ~0 (dc_hip_radius_forest reports the error). */
+ * Needs n_rows <= 2^24, and a workspace as above for n_cols <= 64 (none for n_cols > 64).  Any column
+ * count up to 400 and coordinates that are not finite are served (the direct sweep, as for the pairs). */
 DC_API int dc_hip_radius_min_edge_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
                                       const uint32_t* d_comp, const uint32_t* d_rank,
                                       unsigned long long* d_best, uint32_t* d_pops, void* d_workspace,
                                       size_t workspace_bytes, void* stream);
 /* the same for one segment of a sharded run (n_segments > 0): only the pairs seen from the queries of
  * that segment enter d_best (every pair is seen from both of its ends, possibly by different segments);
- * the partial d_best arrays merge by an element-wise UNSIGNED minimum, the partial d_pops by summation. */
+ * the partial d_best arrays merge by an element-wise UNSIGNED minimum, the partial d_pops by summation.
+ * The segments are those of the pruned sweep's spatial order; for n_cols > 64 or non-finite data they
+ * are the reference's row blocks (density_clustering_cuda.cu:149,165-169) -- either is a partition. */
 DC_API int dc_hip_radius_min_edge_segment_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
                                               const uint32_t* d_comp, const uint32_t* d_rank,
                                               size_t segment, size_t n_segments,
