@@ -43,9 +43,14 @@ __host__ __device__ inline float scale32_pop(float M, float r2max, int K, int D)
   const double u = 5.9604644775390625e-8;
   const double cap = (r2max > 0.0f) ? (double)r2max : 0.0;
   const double eps1 = 1.25 * u * ((4.0 * K + 13.0) * (double)M + (0.25 * D + 18.0) * cap);   // band at scale 1
-  if (!(eps1 > 1.0e-76)) return 1.8446744e19f;                                               // (all rows equal, r = 0: 2^64)
+  if (!(eps1 > 1.0e-76)) return 0x1p63f;                                                     // (all rows equal, r = 0)
   const float c = (float)(sqrt((1.0 - 1.0 / 65536.0) / eps1) * (1.0 - 1.0 / 1048576.0));
-  return c < 1.8446744e19f ? c : 1.8446744e19f;   // (M <= 1e36 and r2 <= FLT_MAX keep c above 2^-56: no lower clamp needed)
+  // kept in [2^-60, 2^63] (a smaller c is always admissible: the band scales with S = c^2), so that S and S r2 stay finite
+  // for every finite r2 -- at 2^64, S overflowed for data of spread ~1e-17 and every pair read as inside.  Only r2max =
+  // +inf (a radius whose fl32 square overflows) takes the lower clamp; M <= 1e36 and finite r2 keep c above 2^-56.  In
+  // such a launch chunk every finite radius gets thr ~ -1: all its pairs fall in the band and take the exact re-check
+  // (pop32_fix), O(n^2) exact distances -- slow, and correct.
+  return fminf(fmaxf(c, 0x1p-60f), 0x1p63f);
 }
 
 // Spatial order of the fp32 population sweep (round 6): the frames by the cell of a G x G grid on columns 0 / 1 (their
@@ -183,7 +188,12 @@ __global__ __launch_bounds__(256, 2) void pop_mfma32_kernel(
   if (qt0 >= T) return;   // whole wave leaves; no barriers in this kernel
   // scaled units (the image was built with the same scale): inside <=> t < 0, outside <=> t >= 2, else band
   const float cs = scale32_pop(__uint_as_float(hdr[0]), r2max, 2 * S, (int)n_cols);
-  const float thr = (cs * cs) * r2 - 1.0f;
+  // (r2 = +inf: FLT_MAX, every finite pair inside, while a pad row's +inf norm still gives t = +inf, outside -- with +inf
+  //  here that t was inf - inf, whose NaN came out of the device with its sign bit set and counted as inside.  Only
+  //  overflow is capped: a NaN radius keeps thr NaN, no chain passes the tile test and the row gets 1 -- d2 < NaN holds
+  //  for no pair, the self pair included)
+  const float thr0 = (cs * cs) * r2 - 1.0f;
+  const float thr = (thr0 > FLT_MAX) ? FLT_MAX : thr0;
 
   float b[TQ][S];
   f32x2 nlo[TQ];

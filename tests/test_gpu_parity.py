@@ -220,7 +220,8 @@ def test_duplicates_and_offset_data(dens, oracle, variant):
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("scale,D", [(1e-12, 10), (1e-6, 3), (1e-3, 10), (1e4, 10), (1e8, 30), (3e17, 5)])
+@pytest.mark.parametrize("scale,D", [(1e-17, 10), (1e-17, 9), (1e-12, 10), (1e-6, 3), (1e-3, 10), (1e4, 10), (1e8, 30),
+                                     (3e17, 5)])
 def test_data_far_from_unit_scale(dens, oracle, scale, D, variant):
     """The fp16 operand images of the matrix-core sweeps carry a per-data-set power-of-two scale
     (scale_of in dc_mfma_kernels.hpp): results must not depend on the magnitude of the coordinates.
