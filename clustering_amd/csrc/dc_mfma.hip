@@ -1007,12 +1007,39 @@ static uint32_t data_cookie(const float* d_coords, uint32_t n_rows, uint32_t n_c
   return (0x5354A7u ^ (n_rows * 2654435761u) ^ (n_cols * 40503u) ^ (uint32_t)((uintptr_t)d_coords >> 4)) | 1u;
 }
 
-// DC_POP_CELL_FRAMES / DC_NN_CELL_FRAMES: measurement overrides of the frames per cell of the orderings
-static float cell_frames(bool nn) {
-  static const float v[2] = {[] { const char* e = getenv("DC_POP_CELL_FRAMES"); return (e && e[0]) ? (float)atof(e) : kPopCellFrames; }(),
-                             [] { const char* e = getenv("DC_NN_CELL_FRAMES"); return (e && e[0]) ? (float)atof(e) : kNnCellFrames; }()};
-  return v[nn ? 1 : 0];
+// the measurement and test switches of the matrix-core sweeps (dc_mfma.hpp SweepSwitches), read once
+const SweepSwitches& sweep_switches() {
+  static const SweepSwitches sw = [] {
+    auto env = [](const char* name) -> const char* {
+      const char* v = getenv(name);
+      return (v && v[0]) ? v : nullptr;
+    };
+    auto one_of_124 = [](const char* v, int dflt) {
+      const int k = v ? atoi(v) : dflt;
+      return (k == 1 || k == 2 || k == 4) ? k : dflt;
+    };
+    SweepSwitches w;
+    const char* v;
+    if ((v = env("DC_POP_SYM"))) w.pop_sym = v[0] != '0';
+    if ((v = env("DC_POP_SHARED"))) w.pop_shared = atoi(v);
+    if ((v = env("DC_NN_SHARED"))) w.nn_shared = atoi(v);
+    w.waves_per_group = one_of_124(env("DC_WAVES_PER_GROUP"), 0);
+    if ((v = env("DC_NN_COOP"))) w.nn_coop = atoi(v);
+    if ((v = env("DC_WAVE_TARGET"))) w.wave_target = (uint32_t)atoi(v);
+    if ((v = env("DC_SHARE_FLOOR"))) w.share_floor = (uint32_t)atoi(v);
+    if ((v = env("DC_POP_COMPONENTS"))) w.components = v[0] != '0';
+    w.pop_cell_frames = (v = env("DC_POP_CELL_FRAMES")) ? (float)atof(v) : kPopCellFrames;
+    w.nn_cell_frames = (v = env("DC_NN_CELL_FRAMES")) ? (float)atof(v) : kNnCellFrames;
+    if ((v = env("DC_NN_FE_BITS"))) w.nn_fe_bits = atoi(v);
+    w.mfma32_wpb = (uint32_t)one_of_124(env("DC_MFMA32_WPB"), 1);
+    if ((v = env("DC_MFMA32_CHUNKS"))) w.mfma32_chunks = (uint32_t)atoi(v);
+    return w;
+  }();
+  return sw;
 }
+
+// DC_POP_CELL_FRAMES / DC_NN_CELL_FRAMES: measurement overrides of the frames per cell of the orderings
+static float cell_frames(bool nn) { return nn ? sweep_switches().nn_cell_frames : sweep_switches().pop_cell_frames; }
 static float nn_cell_frames() { return cell_frames(true); }
 
 int mfma_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws,
@@ -1128,53 +1155,43 @@ void launch_pop_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, ui
 struct QuerySel {
   uint32_t i_from, i_to, segment, n_segments;
 };
-static int tq_of(uint32_t n_cols) { return nm_for((int)n_cols) <= 5 ? 4 : 2; }   // = tq_for<NM>
-static int tq_nn_of(uint32_t n_cols) { return nm_for((int)n_cols) <= 2 ? DC_NN_TQ_SMALL : tq_of(n_cols); }   // = tq_nn_for<NM>
-static int tq_pop_of(uint32_t n_cols) { return nm_for((int)n_cols) <= 2 ? 6 : tq_of(n_cols); }   // = tq_pop_for<NM>
-// query tiles per group of the population sweep that will run: the unit segments are dealt out in and the
-// query image is built for (pop_shared_kernel: the four waves of a workgroup form one group)
-static uint32_t pop_group_tiles(uint32_t n_rows, uint32_t n_cols, bool sink, int n_rad) {
-  if (!sink && pop_shared_wanted(n_rows, n_cols, n_rad)) return 4u * (uint32_t)tq_shared_of(n_cols, n_rad);
-  return (uint32_t)tq_pop_of(n_cols);
-}
-// radii per sweep: one (the folded-threshold sweeps), except the shared-operand sweep of wide rows: up to eight
-static bool pop_multi_radius(uint32_t n_rows, uint32_t n_cols, int n_rad) {
-  const int nm = nm_for((int)n_cols);
-  return n_rad > 1 && nm >= 3 && nm <= 8 && pop_shared_wanted(n_rows, n_cols, n_rad);
+static CallKind call_kind(const QuerySel& qs, uint32_t n_rows) {
+  return qs.n_segments > 0 ? kCallSegment : (qs.i_from == 0 && qs.i_to == n_rows) ? kCallAll : kCallRange;
 }
 
+// plan: plan_pop's for this call (dc_mfma_kernels.hpp) -- the padded orders are laid out for its groups
 // r2_scale: the largest squared radius the prepared images have to serve (the radii of the whole call)
 // comp_clean: the component region of the workspace has been zero-filled by this call already (mfma_prepare)
-static void pop_pruned_one(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const QuerySel& qs,
-                           const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
-                           const EdgeSink* sink, hipStream_t stream, float r2_scale, bool prep = true, bool comp_clean = false);
+static void pop_pruned_one(const PopPlan& plan, const float* d_coords, uint32_t n_rows, uint32_t n_cols,
+                           const QuerySel& qs, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
+                           const EdgeSink* sink, hipStream_t stream, float r2_scale, bool prep, bool comp_clean);
 
-void launch_pop_pruned(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from,
-                       uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
-                       hipStream_t stream, bool comp_clean) {
-  if (pop_multi_radius(n_rows, n_cols, n_rad)) {
-    pop_pruned_one(d_coords, n_rows, n_cols, QuerySel{i_from, i_to, 0, 0}, rad2, n_rad, d_pops, d_ws, nullptr, stream,
+// the populations of the queries qs: one sweep for all radii, or one per radius (nr == 1) on one preparation
+static void pop_pruned_sel(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const QuerySel& qs,
+                           const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws, hipStream_t stream,
+                           bool comp_clean) {
+  const PopPlan plan = plan_pop(n_rows, n_cols, n_rad, call_kind(qs, n_rows), kSinkNone, sweep_switches());
+  if (plan.nr > 1) {
+    pop_pruned_one(plan, d_coords, n_rows, n_cols, qs, rad2, n_rad, d_pops, d_ws, nullptr, stream,
                    max_radius2(rad2, n_rad), true, comp_clean);
     return;
   }
   for (int r = 0; r < n_rad; ++r)
-    pop_pruned_one(d_coords, n_rows, n_cols, QuerySel{i_from, i_to, 0, 0}, single_radius(rad2, r), 1,
-                   d_pops + (size_t)r * n_rows, d_ws, nullptr, stream, max_radius2(rad2, n_rad),
-                   r == 0, comp_clean);   // one preparation for all radii
+    pop_pruned_one(plan, d_coords, n_rows, n_cols, qs, single_radius(rad2, r), 1, d_pops + (size_t)r * n_rows, d_ws,
+                   nullptr, stream, max_radius2(rad2, n_rad), r == 0, comp_clean);
+}
+
+void launch_pop_pruned(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from,
+                       uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
+                       hipStream_t stream, bool comp_clean) {
+  pop_pruned_sel(d_coords, n_rows, n_cols, QuerySel{i_from, i_to, 0, 0}, rad2, n_rad, d_pops, d_ws, stream, comp_clean);
 }
 
 void launch_pop_pruned_segment(const float* d_coords, uint32_t n_rows, uint32_t n_cols,
                                uint32_t segment, uint32_t n_segments, const Rad2& rad2, int n_rad,
                                uint32_t* d_pops, void* d_ws, hipStream_t stream, bool comp_clean) {
-  if (pop_multi_radius(n_rows, n_cols, n_rad)) {
-    pop_pruned_one(d_coords, n_rows, n_cols, QuerySel{0, n_rows, segment, n_segments}, rad2, n_rad, d_pops, d_ws,
-                   nullptr, stream, max_radius2(rad2, n_rad), true, comp_clean);
-    return;
-  }
-  for (int r = 0; r < n_rad; ++r)
-    pop_pruned_one(d_coords, n_rows, n_cols, QuerySel{0, n_rows, segment, n_segments},
-                   single_radius(rad2, r), 1, d_pops + (size_t)r * n_rows, d_ws, nullptr, stream,
-                   max_radius2(rad2, n_rad), r == 0, comp_clean);
+  pop_pruned_sel(d_coords, n_rows, n_cols, QuerySel{0, n_rows, segment, n_segments}, rad2, n_rad, d_pops, d_ws, stream,
+                 comp_clean);
 }
 
 // positions of the sweep's spatial order -> frame ids, for the pairs actually written
@@ -1222,13 +1239,15 @@ void launch_radius_pairs(const float* d_coords, uint32_t n_rows, uint32_t n_cols
   (void)hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream);
   if (d_pairs && capacity) {
     const EdgeSink sink{d_pairs, d_count, capacity, nullptr, nullptr, nullptr};
-    pop_pruned_one(d_coords, n_rows, n_cols, QuerySel{0, n_rows, 0, 0}, one, 1, d_pops, d_ws, &sink, stream, r2, true, true);
+    pop_pruned_one(plan_pop(n_rows, n_cols, 1, kCallAll, kSinkPairs, sweep_switches()), d_coords, n_rows, n_cols,
+                   QuerySel{0, n_rows, 0, 0}, one, 1, d_pops, d_ws, &sink, stream, r2, true, true);
     hipLaunchKernelGGL(edges_to_frames_kernel, dim3(1024), dim3(256), 0, stream, d_pairs,
                        (const unsigned long long*)d_count, capacity,
                        (const uint32_t*)((char*)d_ws + L.off_perm_p));
   } else {
     // counting only: the plain population sweep knows the answer
-    pop_pruned_one(d_coords, n_rows, n_cols, QuerySel{0, n_rows, 0, 0}, one, 1, d_pops, d_ws, nullptr, stream, r2, true, true);
+    pop_pruned_one(plan_pop(n_rows, n_cols, 1, kCallAll, kSinkNone, sweep_switches()), d_coords, n_rows, n_cols,
+                   QuerySel{0, n_rows, 0, 0}, one, 1, d_pops, d_ws, nullptr, stream, r2, true, true);
     hipLaunchKernelGGL(pairs_from_pops_kernel, dim3(256), dim3(256), 0, stream, (const uint32_t*)d_pops,
                        n_rows, d_count);
     hipLaunchKernelGGL(halve_kernel, dim3(1), dim3(1), 0, stream, d_count);
@@ -1246,23 +1265,18 @@ void launch_radius_min_edge(const float* d_coords, uint32_t n_rows, uint32_t n_c
   (void)hipMemsetAsync(d_best, 0xFF, sizeof(unsigned long long) * n_rows, stream);
   // comp / rank arrive per FRAME; pop_pruned_one gathers them into the sweep's order
   const EdgeSink sink{nullptr, nullptr, 0, d_comp, d_rank, d_best};
-  pop_pruned_one(d_coords, n_rows, n_cols, QuerySel{0, n_rows, segment, n_segments}, one, 1, d_pops, d_ws,
-                 &sink, stream, r2, true, true);
+  const QuerySel qs{0, n_rows, segment, n_segments};
+  pop_pruned_one(plan_pop(n_rows, n_cols, 1, call_kind(qs, n_rows), kSinkMinEdge, sweep_switches()), d_coords, n_rows,
+                 n_cols, qs, one, 1, d_pops, d_ws, &sink, stream, r2, true, true);
 }
 
 uint32_t seg_block(uint32_t n_segments) { return n_segments <= 1u ? 1u : kSegBlockGroups; }
 
 // DC_POP_COMPONENTS=0: one component whatever the data looks like (measurements, tests)
-static bool components_off() {
-  static const bool off = [] {
-    const char* v = getenv("DC_POP_COMPONENTS");
-    return v && v[0] == '0';
-  }();
-  return off;
-}
+static bool components_off() { return !sweep_switches().components; }
 
-static void pop_pruned_one(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const QuerySel& qs,
-                           const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
+static void pop_pruned_one(const PopPlan& plan, const float* d_coords, uint32_t n_rows, uint32_t n_cols,
+                           const QuerySel& qs, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
                            const EdgeSink* sink_in, hipStream_t stream, float r2_scale, bool prep, bool comp_clean) {
   // prep == false: the orderings, images and boxes of the previous call (same coordinates, same query
   // selection) are still in the workspace -- the further radii of one populations call
@@ -1293,7 +1307,7 @@ static void pop_pruned_one(const float* d_coords, uint32_t n_rows, uint32_t n_co
   // The orders are PADDED: every component of the frames (dc_mfma_kernels.hpp "components") starts at a whole query
   // group; the sort's last pass writes its values straight to the padded positions (SortRemap: segment starts -> bases),
   // the pad positions in between keep the kInvalidFrame that order_meta_kernel's presets left there.
-  const uint32_t tq = pop_group_tiles(n_rows, n_cols, sink_in != nullptr, n_rad), group_rows = 32u * tq;
+  const uint32_t tq = plan.group_tiles, group_rows = 32u * tq;
   const uint32_t T_r = (n_rows + (uint32_t)kMaxComp * (group_rows - 1u) + 31u) / 32u;
   const uint32_t T_q = (n_q + (uint32_t)kMaxComp * (group_rows - 1u) + 31u) / 32u;
   const size_t tmp_bytes = sort_temp_bytes(n_rows + kOrderPadRows);
@@ -1313,11 +1327,7 @@ static void pop_pruned_one(const float* d_coords, uint32_t n_rows, uint32_t n_co
     sink = &sink_local;
   }
   // the counts by position of the one-radius symmetric per-wave sweep (the pq region): cleared by this call's preparation
-  const bool pos_clean = prep && sink_in == nullptr && n_rad == 1 && !pop_shared_wanted(n_rows, n_cols, n_rad) &&
-                         pop_sym_wanted(false, q_mode, q_seg, n_rows, n_rad) && tq <= 6u;
-  // the multi-radius symmetric sweep takes its thresholds off the accumulator in place, one MFMA per radius: the band of
-  // the scale has to pay for those steps (guard_shift; NR - 1 of them, NR = 4 or 8 radii per sweep)
-  const int shift_steps = (sink_in == nullptr && pop_multi_radius(n_rows, n_cols, n_rad)) ? (n_rad > 4 ? 7 : 3) : 0;
+  const bool pos_clean = prep && plan.pos_clean;
   if (prep) {
     // (round 5: the passes of dc_prep.hpp -- twelve launches for the thirty of rounds 3 - 4, same values)
     const uint32_t cookie = data_cookie(d_coords, n_rows, n_cols);
@@ -1339,7 +1349,7 @@ static void pop_pruned_one(const float* d_coords, uint32_t n_rows, uint32_t n_co
                        cnt_tab, 1, perm_p, tile_comp, 32u * T_r);
     // ... where the components start, the scale of the sweep (it follows the components' extents) ...
     hipLaunchKernelGGL(order_meta_kernel, dim3(1), dim3(1024), 0, stream, hdr, comp, (const uint32_t*)cnt_tab, kb_r, start_r, range_r,
-                       base_r, n_rows, group_rows, 1, fmaxf(r2_scale, 0.0f), n_cols, shift_steps);
+                       base_r, n_rows, group_rows, 1, fmaxf(r2_scale, 0.0f), n_cols, plan.shift_steps);
     // ... the sort, whose last pass moves every component to a whole query group of the padded order ...
     {
       const SortRemap remap{start_r, base_r, (uint32_t)kMaxComp, tile_comp};
@@ -1390,7 +1400,7 @@ static void pop_pruned_one(const float* d_coords, uint32_t n_rows, uint32_t n_co
 #define X(SV)                                                                                 \
   case SV:                                                                                    \
     if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                      \
-      pop_pruned_step_##SV(d_coords, n_rows, n_cols, d_ws, T_r, n_pos_q, q_mode, q_seg, rad2, n_rad, \
+      pop_pruned_step_##SV(plan, d_coords, n_rows, n_cols, d_ws, T_r, n_pos_q, q_mode, q_seg, rad2, n_rad, \
                            d_pops, sink, stream, pos_clean);                                  \
     break;
     DC_FOR_EACH_S(X)
@@ -1682,17 +1692,16 @@ static void nn_pruned_sel(const float* d_coords, uint32_t n_rows, uint32_t n_col
   }
   // (query tiles per group: a wave's, or with the shared-operand sweep the workgroup's; the orders are padded so that
   //  every component starts at a whole group -- see pop_pruned_one)
-  const uint32_t tq = nn_shared_wanted(n_rows, n_cols) ? 4u * (uint32_t)tq_of(n_cols) : (uint32_t)tq_nn_of(n_cols), group_rows = 32u * tq;
+  const NnPlan plan = plan_nn(n_rows, n_cols, sweep_switches());
+  const uint32_t tq = plan.group_tiles, group_rows = 32u * tq;
   const uint32_t T_r = (n_rows + (uint32_t)kMaxComp * (group_rows - 1u) + 31u) / 32u;
   const uint32_t T_q = (n_q + (uint32_t)kMaxComp * (group_rows - 1u) + 31u) / 32u;
   // ordering key: (cell number over all components, quantised free energy) in whole sort passes
   const unsigned fine_bits = cell_key_bits(n_rows, kNnCellFrames) + 1u;
   const unsigned key_bits = (fine_bits + 9u <= 24u) ? 24u : 32u;
   unsigned fe_bits = key_bits > fine_bits ? std::min(key_bits - fine_bits, 16u) : 0u;
-  {  // DC_NN_FE_BITS: measurements (0 = the frames of a cell in any order)
-    static const int forced = [] { const char* e = getenv("DC_NN_FE_BITS"); return (e && e[0]) ? atoi(e) : -1; }();
-    if (forced >= 0) fe_bits = std::min((unsigned)forced, fe_bits);
-  }
+  // DC_NN_FE_BITS: measurements (0 = the frames of a cell in any order)
+  if (sweep_switches().nn_fe_bits >= 0) fe_bits = std::min((unsigned)sweep_switches().nn_fe_bits, fe_bits);
   const float r_conn = -8.0f;   // components: connected over 8 cells of the ordering (no radius in this sweep)
   const uint32_t cookie = data_cookie(d_coords, n_rows, n_cols);
   uint32_t* start_r = comp + kCompStart, *start_q = comp + kCompStart + (kMaxComp + 1);
@@ -1760,7 +1769,7 @@ static void nn_pruned_sel(const float* d_coords, uint32_t n_rows, uint32_t n_col
 #define X(SV)                                                                                   \
   case SV:                                                                                      \
     if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                        \
-      nn_pruned_step_##SV(d_coords, n_rows, n_cols, d_fe, d_ws, T_r, n_pos_q, q_mode, q_seg, -1.0f, \
+      nn_pruned_step_##SV(plan, d_coords, n_rows, n_cols, d_fe, d_ws, T_r, n_pos_q, q_mode, q_seg, -1.0f, \
                           d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream);                        \
     break;
     DC_FOR_EACH_S(X)
@@ -1893,7 +1902,7 @@ __global__ void nn_block_unpack_kernel(const uint32_t* __restrict__ blocks /* [G
 }
 
 static uint32_t nn_group_rows(uint32_t n_rows, uint32_t n_cols) {
-  return 32u * (nn_shared_wanted(n_rows, n_cols) ? 4u * (uint32_t)tq_of(n_cols) : (uint32_t)tq_nn_of(n_cols));
+  return 32u * plan_nn(n_rows, n_cols, sweep_switches()).group_tiles;
 }
 // tiles of the neighbour sweep's padded order (every component starts at a whole query group)
 static uint32_t nn_order_tiles(uint32_t n_rows, uint32_t n_cols) {
@@ -1980,10 +1989,6 @@ void launch_nn_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, con
 
 // ---- DC_VARIANT_MFMA32: the fp32-input MFMA instance (dc_mfma32.hpp) ---------------------------------------------
 bool mfma32_supports(size_t n_cols) { return n_cols == 9 || n_cols == 10; }
-static uint32_t wpb32() {
-  static const uint32_t v = [] { const char* e = getenv("DC_MFMA32_WPB"); const int k = (e && e[0]) ? atoi(e) : 1; return (k == 1 || k == 2 || k == 4) ? (uint32_t)k : 1u; }();
-  return v;
-}
 
 void launch_pop_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
                        const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws, hipStream_t stream) {
@@ -2007,15 +2012,11 @@ void launch_pop_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, 
   for (int r = 0; r < n_rad; ++r) r2max = std::max(r2max, rad2.v[r]);
   hipLaunchKernelGGL(image32_kernel, dim3((32 * L.T + 255) / 256), dim3(256), 0, stream, d_coords, n_rows, n_cols, L.T,
                      (const float*)(p + kHdrMeans), (const uint32_t*)perm, (const uint32_t*)p, r2max, img, norms);
-#ifdef DC_MFMA32_TQ
-  constexpr int kTQ = DC_MFMA32_TQ;
-#else
   constexpr int kTQ = 8;
-#endif
   // (two waves per SIMD at eight query tiles per wave: 2 048 wave slots; DC_MFMA32_CHUNKS for measurements)
-  static const uint32_t env_chunks = [] { const char* v = getenv("DC_MFMA32_CHUNKS"); return (v && v[0]) ? (uint32_t)atoi(v) : 0u; }();
+  const uint32_t env_chunks = sweep_switches().mfma32_chunks;
   // (waves per workgroup: DC_MFMA32_WPB, measurements)
-  const uint32_t wpb = wpb32();
+  const uint32_t wpb = sweep_switches().mfma32_wpb;
   const uint32_t blocks = ((L.T + kTQ - 1) / kTQ + wpb - 1) / wpb;   // (all positions: the rows of a range are scattered over the order)
   const uint32_t chunks = env_chunks ? std::min(env_chunks, L.T) : chunks32(blocks * wpb, L.T, 2048u);
   const dim3 grid(blocks, chunks), block(64 * wpb);
@@ -2056,10 +2057,10 @@ void launch_nn_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, c
   hipLaunchKernelGGL(image32_kernel, grid_t, blk, 0, stream, d_coords, n_rows, n_cols, L.T, (const float*)(p + kHdrMeans),
                      (const uint32_t*)perm, (const uint32_t*)p, -1.0f, img_s, norms_s);
   constexpr int kTQ = 4;
-  static const uint32_t env_chunks = [] { const char* v = getenv("DC_MFMA32_CHUNKS"); return (v && v[0]) ? (uint32_t)atoi(v) : 0u; }();
+  const uint32_t env_chunks = sweep_switches().mfma32_chunks;
   // ONE wave per workgroup: a workgroup holds its wave slots until its last wave is done, and the waves of this sweep
   // differ in length (those that start from published bounds skip most of the candidate path)
-  const uint32_t wpb = wpb32();
+  const uint32_t wpb = sweep_switches().mfma32_wpb;
   const uint32_t blocks = (grid_for(i_from, i_to, kTQ) * 4u + wpb - 1) / wpb;
   const uint32_t chunks = env_chunks ? std::min(env_chunks, L.T) : chunks32(blocks * wpb, L.T, 2048u);
   unsigned long long* merge64 = (unsigned long long*)(p + L.off_merge64);

@@ -22,6 +22,58 @@ struct EdgeSink {
 };
 enum SinkMode { kSinkNone = 0, kSinkPairs = 1, kSinkMinEdge = 2 };
 
+// Measurement and test switches of the matrix-core sweeps, read from the environment once (sweep_switches(),
+// dc_mfma.hip); the defaults are the library's behaviour.  The forcing switches move the size thresholds of the planners
+// (plan_pop / plan_nn, dc_mfma_kernels.hpp) only within the forms each MFMA count is built for.
+struct SweepSwitches {
+  bool pop_sym = true;            // DC_POP_SYM=0: no symmetric population sweeps
+  int pop_shared = -1;            // DC_POP_SHARED=0 / 1: shared-operand population sweeps off / on where built
+  int nn_shared = -1;             // DC_NN_SHARED=0 / 1: the same for the neighbour sweep
+  int waves_per_group = 0;        // DC_WAVES_PER_GROUP=1 / 2 / 4: waves per workgroup of the per-wave sweeps
+  int nn_coop = -1;               // DC_NN_COOP=0 / 1: COOP neighbour workgroups never / from four shares on
+  uint32_t wave_target = 0;       // DC_WAVE_TARGET: waves a pruned launch aims at (0: the sweep's own)
+  uint32_t share_floor = 0;       // DC_SHARE_FLOOR: least reference tiles per share (0: the sweep's own)
+  bool components = true;         // DC_POP_COMPONENTS=0: one component whatever the data
+  float pop_cell_frames = 0.0f;   // DC_POP_CELL_FRAMES / DC_NN_CELL_FRAMES: frames per cell of the orderings (0: default)
+  float nn_cell_frames = 0.0f;
+  int nn_fe_bits = -1;            // DC_NN_FE_BITS: free-energy bits of the neighbour ordering's key (-1: default)
+  uint32_t mfma32_wpb = 1;        // DC_MFMA32_WPB=1 / 2 / 4: waves per workgroup of the fp32-MFMA instance
+  uint32_t mfma32_chunks = 0;     // DC_MFMA32_CHUNKS: its reference shares (0: chosen by size)
+};
+const SweepSwitches& sweep_switches();
+
+// The plan of one pruned sweep: which kernel form runs and how its query groups are cut.  The padded orders are laid
+// out for group_tiles; the kernel that runs must have the same groups, so both come from the plan.
+enum PopForm {
+  kPopWave,        // per-wave one-sided (pop_pruned_kernel)
+  kPopWaveSym,     // per-wave symmetric: every unordered pair once, counts by position
+  kPopPairs,       // per-wave, listing the pairs
+  kPopMinEdge,     // per-wave, lightest pair out of every component
+  kPopShared,      // reference operands shared through LDS, one-sided (pop_shared_kernel)
+  kPopSharedSym,   // ... symmetric
+  kPopMsym,        // several radii per sweep, symmetric (pop_msym_kernel)
+  kPopMulti,       // several radii per sweep, one-sided (pop_shared_kernel, row ranges)
+};
+enum NnForm {
+  kNnWave,     // per-wave (nn_pruned_kernel); COOP workgroups from coop_shares reference shares per group on
+  kNnShared,   // reference operands shared through LDS (nn_shared_kernel)
+};
+enum CallKind { kCallAll, kCallRange, kCallSegment };   // queries: all rows / a row range / one segment of a sharded run
+struct PopPlan {
+  PopForm form;
+  int nr;                  // radii per sweep: 1, 4 or 8
+  uint32_t tq;             // query tiles per wave (the kernel's TQ)
+  uint32_t group_tiles;    // query tiles per group (the unit of the padded orders and of the segments' deal)
+  uint32_t waves;          // waves per workgroup
+  int shift_steps;         // thresholds taken off the accumulator in place: the band of the scale pays for them
+  bool pos_clean;          // the preparation clears the counts by position (kPopWaveSym)
+};
+struct NnPlan {
+  NnForm form;
+  uint32_t tq, group_tiles, waves;
+  uint32_t coop_shares;    // kNnWave: reference shares per group from which the shares are the waves of one workgroup
+};
+
 // true if the MFMA kernels handle this n_cols
 bool mfma_supports(size_t n_cols);
 // bytes of device scratch (operand images, norms) for a problem size; 0 if unsupported

@@ -74,6 +74,7 @@
 #pragma once
 #include "dc_mfma.hpp"
 
+#include <assert.h>
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
@@ -2767,21 +2768,14 @@ __global__ void nn_merge_unpack_rows_kernel(const unsigned long long* __restrict
 // leave room for at two waves per SIMD; each reference fragment is fetched once per TQ chains.  Measured at
 // 300k rows: NM = 5 (D = 24) 5.6 / 6.2 ms with four tiles against 6.4 / 6.5 with two; NM = 6 (D = 30) 7.8 / 9.3 against
 // 7.1 / 7.4; NM = 7 (D = 32) 8.2 / 10.0 against 7.7 / 8.3; NM = 8 (D = 40) 11.0 / 11.4 against 8.8 / 10.0.
-template <int NM>
-constexpr int tq_for = (NM <= 5) ? 4 : 2;
+constexpr int tq_wave(int nm) { return nm <= 5 ? 4 : 2; }
 
 // the population sweep keeps less state per query tile: with two MFMAs per chain six tiles fit
 // (measured at C3: 23.6 ms against 25.1 ms with four; eight spill; the neighbour sweep loses at six)
-template <int NM>
-constexpr int tq_pop_for = (NM <= 2) ? 6 : tq_for<NM>;
+constexpr int tq_pop(int nm) { return nm <= 2 ? 6 : tq_wave(nm); }
 // the neighbour sweeps: six as well since the early-out (round 4: the chains are short, the per-tile work -- loads,
-// list, the one test -- is shared by six of them; C3 11.0 -> 10.7 ms, 256 registers, no spill.  DC_NN_TQ_SMALL=4:
-// measurements)
-#ifndef DC_NN_TQ_SMALL
-#define DC_NN_TQ_SMALL 6
-#endif
-template <int NM>
-constexpr int tq_nn_for = (NM <= 2) ? DC_NN_TQ_SMALL : tq_for<NM>;   // (dc_mfma.hip tq_nn_of)
+// list, the one test -- is shared by six of them; C3 11.0 -> 10.7 ms, 256 registers, no spill)
+constexpr int tq_nn(int nm) { return nm <= 2 ? 6 : tq_wave(nm); }
 // query tiles per wave of the full sweeps (double-buffered reference operands)
 template <int NM>
 constexpr int tq_full_for = (NM <= 4) ? 4 : (NM <= 8) ? 2 : 1;
@@ -2856,20 +2850,103 @@ constexpr uint32_t kPopShareFloor = 1024, kNnShareFloor = 900;     //  49152 / 1
                                                                    //  154 -> 132, 1M x 16 x 4 radii 91 -> 78, 600k x 40 19.2 -> 17.3 ms; the
                                                                    //  per-wave sweep of C3 is box-dependent at 196608 (11.76 -> 11.58 on one,
                                                                    //  12.1 -> 12.4 ms on another, 56 % more memory-side traffic): it stays)
+constexpr uint32_t kNnCoopWaves = 4;        // waves (shares) of one COOP workgroup
 // waves per workgroup of the per-wave sweeps (pop_pruned_kernel, nn_pruned_kernel; see nn_pruned_kernel): ONE while a
 // chain has at most two MFMAs -- no slot waits for the slowest wave of a workgroup (1M x 10: neighbours 16.1 -> 15.0 ms,
 // 1M x 3: 5.7 -> 5.3 / populations 6.3 -> 6.05 ms) -- and four beyond that: the four waves of a workgroup sit on one CU
 // and walk nearly the same reference tiles at nearly the same time, so three of them find the operands in its L1
 // (populations 600k x 12: 8.0 ms with four waves per workgroup, 10.4 ms with one; 300k x 40: 6.1 / 7.9 ms; the neighbour
 // sweep does not care).  DC_WAVES_PER_GROUP = 1 / 2 / 4 for measurements.
-inline uint32_t waves_per_group(int nm) {
-  static const int forced = [] {
-    const char* v = getenv("DC_WAVES_PER_GROUP");
-    const int k = (v && v[0]) ? atoi(v) : 0;
-    return (k == 1 || k == 2 || k == 4) ? k : 0;
-  }();
-  if (forced) return (uint32_t)forced;
+inline uint32_t waves_per_group(int nm, const SweepSwitches& sw) {
+  if (sw.waves_per_group) return (uint32_t)sw.waves_per_group;
   return nm <= 2 ? 1u : 4u;
+}
+
+// ---- the plans of the pruned sweeps -------------------------------------------------------------------------------
+// The forms each MFMA count is built for; dc_mfma_step.hip instantiates nothing else, and the planners return nothing
+// else: the per-wave sweeps for every count, the shared-operand sweeps with one radius for 5 - 8 MFMAs, with four or
+// eight radii for 3 - 8, the shared-operand neighbour sweep for 5 - 8.
+constexpr bool pop_form_built(PopForm f, int nm) {
+  return (f == kPopMsym || f == kPopMulti)        ? (nm >= 3 && nm <= 8)
+         : (f == kPopShared || f == kPopSharedSym) ? (nm >= 5 && nm <= 8)
+                                                   : (nm >= 1 && nm <= kMaxMfma);
+}
+constexpr bool nn_form_built(NnForm f, int nm) {
+  return f == kNnShared ? (nm >= 5 && nm <= 8) : (nm >= 1 && nm <= kMaxMfma);
+}
+inline bool image_beyond_caches(uint32_t n_rows, int nm) {   // operand image > 96 MiB
+  return (size_t)((n_rows + 31) / 32) * (size_t)nm * 1024 > ((size_t)96 << 20);
+}
+// the shared-operand population sweep for nr radii per sweep (dc_mfma_shared.hpp "Which calls take the shared-operand
+// sweep"): five or more MFMAs and an image beyond the caches, or enough radii per sweep
+inline bool pop_shared_rule(uint32_t n_rows, int nm, int nr, const SweepSwitches& sw) {
+  if (!pop_form_built(nr > 1 ? kPopMulti : kPopShared, nm) || n_rows + 32u * kPadTiles > kPopQueueMaxRows) return false;
+  if (sw.pop_shared >= 0) return sw.pop_shared != 0;
+  if (nm >= 5 && image_beyond_caches(n_rows, nm)) return true;
+  return n_rows >= 50000u && ((nm >= 3 && nr >= 3) || (nm >= 5 && nr >= 2));
+}
+// The plan of a pruned population launch of n_rad radii (at most kMaxRadiiPerLaunch) for the queries of `kind`; a sink
+// (pairs, min-edge) comes with one radius.  nr == 1: one sweep per radius.
+// The symmetric forms take all rows as queries in the reference order -- every query group, or the groups of one
+// segment of a sharded run (a group owns the same pairs of groups whichever rank runs it, so the ranks' counts are
+// PARTIAL counts of all rows and merge by summation like the one-sided ones) -- but not a row range, no pair sink, and
+// positions that fit the queue entries.  DC_POP_SYM = 0 turns them off (tests, measurements).
+// With one radius the shared-operand sweep is symmetric (5M x 30, all rows: 1 482 -> 932 ms; 1M x 30: 56.3 -> 35.8 ms);
+// with several, pop_msym_kernel is (dc_mfma_msym.hpp: the one-sided crediting of pop_shared_kernel took the eight radii
+// of C5's segment sweep from 797 to 2 062 ms).
+inline PopPlan plan_pop(uint32_t n_rows, uint32_t n_cols, int n_rad, CallKind kind, SinkMode sink,
+                        const SweepSwitches& sw) {
+  const int nm = nm_for((int)n_cols);
+  const bool sym = sw.pop_sym && kind != kCallRange && n_rows + 32u * kPadTiles <= kPopQueueMaxRows;
+  PopPlan p{};
+  if (sink == kSinkNone && n_rad > 1 && pop_shared_rule(n_rows, nm, n_rad, sw)) {
+    p.nr = n_rad <= 4 ? 4 : 8;
+    p.form = sym ? kPopMsym : kPopMulti;
+    p.tq = tq_shared(nm, p.nr);
+    p.group_tiles = 4 * p.tq;
+    p.waves = 4;
+    // the multi-radius symmetric sweep takes its thresholds off the accumulator in place, one MFMA per radius: the band
+    // of the scale pays for those NR - 1 steps (guard_shift; charged to the one-sided row-range sweep as well)
+    p.shift_steps = p.nr - 1;
+  } else if (sink == kSinkNone && pop_shared_rule(n_rows, nm, 1, sw)) {
+    p.nr = 1;
+    p.form = sym ? kPopSharedSym : kPopShared;
+    p.tq = tq_shared(nm, 1);
+    p.group_tiles = 4 * p.tq;
+    p.waves = 4;
+  } else {
+    p.nr = 1;
+    p.form = sink == kSinkMinEdge ? kPopMinEdge : sink == kSinkPairs ? kPopPairs : sym ? kPopWaveSym : kPopWave;
+    p.tq = tq_pop(nm);
+    p.group_tiles = p.tq;
+    p.waves = waves_per_group(nm, sw);
+    p.pos_clean = p.form == kPopWaveSym;   // (the counts by position live in the pq region: order_rows2_kernel clears it)
+  }
+  return p;
+}
+// The plan of a pruned neighbour sweep: the shared-operand form for an image beyond the caches (DC_NN_SHARED = 0 / 1
+// forces it off / on where built); its workgroup of four waves is one group of 4 * tq_wave tiles.  Many reference
+// shares per group (a rank of a sharded run: 34 at an eighth of C3) make the shares of a group the waves of ONE
+// workgroup that learn their thresholds together (nn_pruned_kernel<.., COOP>); DC_NN_COOP = 0 / 1 never / from
+// kNnCoopWaves shares on.
+inline NnPlan plan_nn(uint32_t n_rows, uint32_t n_cols, const SweepSwitches& sw) {
+  const int nm = nm_for((int)n_cols);
+  bool shared = nn_form_built(kNnShared, nm) && n_rows < (1u << 30);
+  if (shared) shared = sw.nn_shared >= 0 ? sw.nn_shared != 0 : image_beyond_caches(n_rows, nm);
+  NnPlan p{};
+  if (shared) {
+    p.form = kNnShared;
+    p.tq = tq_wave(nm);
+    p.group_tiles = 4 * p.tq;
+    p.waves = 4;
+  } else {
+    p.form = kNnWave;
+    p.tq = tq_nn(nm);
+    p.group_tiles = p.tq;
+    p.waves = waves_per_group(nm, sw);
+  }
+  p.coop_shares = sw.nn_coop < 0 ? kNnCoopMinShares : sw.nn_coop == 0 ? 0xFFFFFFFFu : kNnCoopWaves;
+  return p;
 }
 // Share floor of the per-wave population sweep by problem size: a share of 1 024 reference tiles is right from about
 // 400 000 rows on (C3), but it left a 100 000-row problem (C2: 3 500 tiles) with three shares = 1 500 waves for the
@@ -2882,10 +2959,9 @@ inline uint32_t pop_share_floor(uint32_t ref_tiles) {
 inline uint32_t pick_chunks(uint32_t tiles, int tq, uint32_t target, uint32_t ref_tiles,
                             uint32_t share_floor, size_t /*tile_bytes*/) {
   // DC_WAVE_TARGET / DC_SHARE_FLOOR: measurement overrides of the two tuning constants (both sweeps)
-  static const uint32_t env_target = [] { const char* v = getenv("DC_WAVE_TARGET"); return (v && v[0]) ? (uint32_t)atoi(v) : 0u; }();
-  static const uint32_t env_floor = [] { const char* v = getenv("DC_SHARE_FLOOR"); return (v && v[0]) ? (uint32_t)atoi(v) : 0u; }();
-  if (env_target) target = env_target;
-  if (env_floor) share_floor = env_floor;
+  const SweepSwitches& sw = sweep_switches();
+  if (sw.wave_target) target = sw.wave_target;
+  if (sw.share_floor) share_floor = sw.share_floor;
   const uint32_t waves = (tiles + tq - 1) / tq;
   uint32_t r = waves >= target ? 1u : (target + waves - 1) / waves;
   const uint32_t by_share = ref_tiles / share_floor;
@@ -2894,33 +2970,62 @@ inline uint32_t pick_chunks(uint32_t tiles, int tq, uint32_t target, uint32_t re
   return r < 1u ? 1u : r;
 }
 
-template <int S, int TQV>
-void nn_pruned_launch(const float* coords, uint32_t n_rows, uint32_t n_cols, const float* fe,
-                      const NnPrunedArgs& A, uint32_t T, const uint32_t* hdr,
-                      unsigned long long* chain_counter, uint32_t* nn_idx, float* nn_d2,
-                      uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
+// the main kernel of a sweep, bracketed for sweep_timer_read (kind 0: population, 1: neighbour)
+template <class F>
+void timed_launch(int kind, hipStream_t s, F&& launch) {
+  sweep_timer_mark(kind, true, s);
+  launch();
+  sweep_timer_mark(kind, false, s);
+}
+// around a neighbour sweep of n_chunks reference shares: the merge buffer of several shares and the boxes of every share
+// in front, the merged results back to the frames behind (group_tiles: query tiles per group)
+inline void nn_shares_begin(const NnPrunedArgs& A, uint32_t n_rows, uint32_t T, uint32_t n_chunks, hipStream_t s) {
+  if (n_chunks > 1)
+    hipLaunchKernelGGL(nn_merge_fill_kernel, dim3((2 * n_rows + 255) / 256), dim3(256), 0, s, A.merge64, n_rows);
+  hipLaunchKernelGGL(box_by_share_kernel, dim3((T + 255) / 256), dim3(256), 0, s, A.box_r, T, n_chunks, A.box_t);
+}
+inline void nn_shares_end(const NnPrunedArgs& A, uint32_t n_rows, uint32_t n_chunks, uint32_t group_tiles,
+                          uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
+  if (n_chunks <= 1) return;
+  if (A.full_range)
+    hipLaunchKernelGGL(nn_merge_unpack_rows_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s,
+                       (const unsigned long long*)A.merge64, A.invpos_r, n_rows, group_tiles, A.q_seg, nn_idx, nn_d2,
+                       hd_idx, hd_d2);
+  else
+    hipLaunchKernelGGL(nn_merge_unpack_kernel, dim3((A.n_q + 255) / 256), dim3(256), 0, s,
+                       (const unsigned long long*)A.merge64, A.perm_q, A.n_q, n_rows, group_tiles, A.q_seg, nn_idx,
+                       nn_d2, hd_idx, hd_d2);
+}
+
+template <int S>
+void nn_pruned_dispatch(const NnPlan& pl, const float* coords, uint32_t n_rows, uint32_t n_cols, const float* fe,
+                        const NnPrunedArgs& A, uint32_t T, const uint32_t* hdr,
+                        unsigned long long* chain_counter, uint32_t* nn_idx, float* nn_d2,
+                        uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
+  assert(nn_form_built(pl.form, S));
   if (A.n_q == 0) return;
   // T: tiles of the (padded) reference order; A.n_q: positions of the query order
   const CompView CV{A.tile_comp_q, A.comp + kCompRange, 32u * T, A.comp};
-  if (nn_shared_wanted(n_rows, n_cols)) {
-    // reference operands shared through LDS (dc_mfma_nn_shared.hpp): the workgroup's 4 * TQV tiles are one group
-    const uint32_t groups = seg_groups(((A.n_q + 31) / 32 + 4 * TQV - 1) / (4 * TQV), A.q_seg);
-    if (groups == 0) return;
-    const uint32_t n_chunks = pick_chunks(groups * 4 * TQV, TQV, kNnWaveTarget, T, kNnShareFloor, (size_t)S * 1024 + 128);
-    const size_t smem = (size_t)kRing * (S * 64 + kNnRingExtra) * 16 + sizeof(uint32_t) * 4 * (TQV * kQueueCap * 64 + TQV * 32);
-    if (n_chunks > 1)
-      hipLaunchKernelGGL(nn_merge_fill_kernel, dim3((2 * n_rows + 255) / 256), dim3(256), 0, s, A.merge64, n_rows);
-    hipLaunchKernelGGL(box_by_share_kernel, dim3((T + 255) / 256), dim3(256), 0, s, A.box_r, T, n_chunks, A.box_t);
-    {
-      sweep_timer_mark(1, true, s);
+  if (pl.form == kNnShared) {
+    if constexpr (nn_form_built(kNnShared, S)) {
+      // reference operands shared through LDS (dc_mfma_nn_shared.hpp): the workgroup's 4 * TQV tiles are one group
+      constexpr int TQV = tq_wave(S);
+      assert(pl.tq == (uint32_t)TQV);
+      const uint32_t groups = seg_groups(((A.n_q + 31) / 32 + 4 * TQV - 1) / (4 * TQV), A.q_seg);
+      if (groups == 0) return;
+      const uint32_t n_chunks = pick_chunks(groups * 4 * TQV, TQV, kNnWaveTarget, T, kNnShareFloor, (size_t)S * 1024 + 128);
+      const size_t smem = (size_t)kRing * (S * 64 + kNnRingExtra) * 16 + sizeof(uint32_t) * 4 * (TQV * kQueueCap * 64 + TQV * 32);
+      nn_shares_begin(A, n_rows, T, n_chunks, s);
       // (the MFMAs in front of the early-out test: the most this NM can need, or one fewer for its narrowest rows)
       constexpr int kNbMax = kNnCoarseMax<S>;
       constexpr int kNbMin = (S > 1) ? nn_coarse_for((16 * (S - 1) - kConstSlots) / kPieceGroups + 1) : kNbMax;
       auto launch = [&](auto nb_c) {
-        hipLaunchKernelGGL((nn_shared_kernel<S, TQV, decltype(nb_c)::value>), dim3(grid_x8(groups), n_chunks), dim3(256), smem, s, coords,
-                           n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.ferange_r, A.fe_c,
-                           A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg, A.full_range, A.cell2,
-                           hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
+        timed_launch(1, s, [&] {
+          hipLaunchKernelGGL((nn_shared_kernel<S, TQV, decltype(nb_c)::value>), dim3(grid_x8(groups), n_chunks), dim3(256), smem, s, coords,
+                             n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.ferange_r, A.fe_c,
+                             A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg, A.full_range, A.cell2,
+                             hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
+        });
       };
       if constexpr (kNbMin != kNbMax) {
         if (nn_coarse_for((int)n_cols) < kNbMax)
@@ -2930,110 +3035,43 @@ void nn_pruned_launch(const float* coords, uint32_t n_rows, uint32_t n_cols, con
       } else {
         launch(std::integral_constant<int, kNbMax>{});
       }
-      sweep_timer_mark(1, false, s);
+      nn_shares_end(A, n_rows, n_chunks, 4u * TQV, nn_idx, nn_d2, hd_idx, hd_d2, s);
     }
-    if (n_chunks > 1 && A.full_range)
-      hipLaunchKernelGGL(nn_merge_unpack_rows_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s,
-                         (const unsigned long long*)A.merge64, A.invpos_r, n_rows, (uint32_t)(4 * TQV), A.q_seg, nn_idx,
-                         nn_d2, hd_idx, hd_d2);
-    else if (n_chunks > 1)
-      hipLaunchKernelGGL(nn_merge_unpack_kernel, dim3((A.n_q + 255) / 256), dim3(256), 0, s,
-                         (const unsigned long long*)A.merge64, A.perm_q, A.n_q, n_rows, (uint32_t)(4 * TQV), A.q_seg, nn_idx,
-                         nn_d2, hd_idx, hd_d2);
     return;
   }
+  constexpr int TQV = tq_nn(S);
+  assert(pl.tq == (uint32_t)TQV);
   const uint32_t waves = seg_groups(((A.n_q + 31) / 32 + TQV - 1) / TQV, A.q_seg), tiles = waves * TQV;
   if (waves == 0) return;
   uint32_t n_chunks = pick_chunks(tiles, TQV, kNnWaveTargetPerWave, T, kNnShareFloor, (size_t)S * 1024 + 128);
-  // Many shares per group (a rank of a sharded run: 34 at an eighth of C3): the shares of a group as the waves of ONE
-  // workgroup that learn their thresholds together (nn_pruned_kernel<.., COOP>); DC_NN_COOP = 0 / 1 forces either form
-  static const int coop_env = [] { const char* v = getenv("DC_NN_COOP"); return (v && v[0]) ? atoi(v) : -1; }();
-  static const uint32_t kCoopWaves = [] { const char* v = getenv("DC_NN_COOP_WAVES"); const int k = (v && v[0]) ? atoi(v) : 4; return (k == 2 || k == 4 || k == 8) ? (uint32_t)k : 4u; }();
-  const bool coop = (coop_env >= 0) ? (coop_env != 0 && n_chunks >= kCoopWaves) : (n_chunks >= kNnCoopMinShares);
-  if (coop) {
-    n_chunks = (n_chunks + kCoopWaves - 1) / kCoopWaves * kCoopWaves;
-    const size_t smem_c = sizeof(uint32_t) * (kCoopWaves * (kListCap + 2 * kWaveQueue) + 8 * TQV * 32) +
+  if (n_chunks >= pl.coop_shares) {
+    // the shares of a group as the waves of ONE workgroup (plan_nn)
+    n_chunks = (n_chunks + kNnCoopWaves - 1) / kNnCoopWaves * kNnCoopWaves;
+    const size_t smem_c = sizeof(uint32_t) * (kNnCoopWaves * (kListCap + 2 * kWaveQueue) + 8 * TQV * 32) +
                           sizeof(float) * TQV * 32 * (size_t)n_cols;
-    hipLaunchKernelGGL(nn_merge_fill_kernel, dim3((2 * n_rows + 255) / 256), dim3(256), 0, s, A.merge64, n_rows);
-    hipLaunchKernelGGL(box_by_share_kernel, dim3((T + 255) / 256), dim3(256), 0, s, A.box_r, T, n_chunks, A.box_t);
-    sweep_timer_mark(1, true, s);
-    hipLaunchKernelGGL((nn_pruned_kernel<S, TQV, true>), dim3(grid_x8(waves), n_chunks / kCoopWaves), dim3(64 * kCoopWaves), smem_c, s,
-                       coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.ferange_r,
-                       A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
-                       A.full_range, A.cell2, hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
-    sweep_timer_mark(1, false, s);
-    if (A.full_range)
-      hipLaunchKernelGGL(nn_merge_unpack_rows_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s,
-                         (const unsigned long long*)A.merge64, A.invpos_r, n_rows, (uint32_t)TQV, A.q_seg,
-                         nn_idx, nn_d2, hd_idx, hd_d2);
-    else
-      hipLaunchKernelGGL(nn_merge_unpack_kernel, dim3((A.n_q + 255) / 256), dim3(256), 0, s,
-                         (const unsigned long long*)A.merge64, A.perm_q, A.n_q, n_rows, (uint32_t)TQV, A.q_seg,
-                         nn_idx, nn_d2, hd_idx, hd_d2);
-    return;
+    nn_shares_begin(A, n_rows, T, n_chunks, s);
+    timed_launch(1, s, [&] {
+      hipLaunchKernelGGL((nn_pruned_kernel<S, TQV, true>), dim3(grid_x8(waves), n_chunks / kNnCoopWaves), dim3(64 * kNnCoopWaves), smem_c, s,
+                         coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.ferange_r,
+                         A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
+                         A.full_range, A.cell2, hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
+    });
+  } else {
+    // query rows (original coordinates) + candidate queues, per wave
+    const uint32_t wpb = pl.waves;
+    const size_t smem = wpb * (sizeof(uint32_t) * kListCap + sizeof(float) * TQV * 32 * (size_t)n_cols +
+                               sizeof(uint32_t) * (TQV * kQueueCap * 64 + 2 * TQV * 32));
+    nn_shares_begin(A, n_rows, T, n_chunks, s);
+    timed_launch(1, s, [&] {
+      hipLaunchKernelGGL((nn_pruned_kernel<S, TQV>), dim3(grid_x8((waves + wpb - 1) / wpb), n_chunks), dim3(64 * wpb), smem, s,
+                         coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.ferange_r,
+                         A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
+                         A.full_range, A.cell2, hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
+    });
   }
-  // query rows (original coordinates) + candidate queues, per wave
-  const uint32_t wpb = waves_per_group(S);
-  const size_t smem = wpb * (sizeof(uint32_t) * kListCap + sizeof(float) * TQV * 32 * (size_t)n_cols +
-                             sizeof(uint32_t) * (TQV * kQueueCap * 64 + 2 * TQV * 32));
-  if (n_chunks > 1)
-    hipLaunchKernelGGL(nn_merge_fill_kernel, dim3((2 * n_rows + 255) / 256), dim3(256), 0, s,
-                       A.merge64, n_rows);
-  hipLaunchKernelGGL(box_by_share_kernel, dim3((T + 255) / 256), dim3(256), 0, s, A.box_r, T, n_chunks, A.box_t);
-  { sweep_timer_mark(1, true, s); hipLaunchKernelGGL((nn_pruned_kernel<S, TQV>), dim3(grid_x8((waves + wpb - 1) / wpb), n_chunks), dim3(64 * wpb), smem, s,
-                     coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.ferange_r,
-                     A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
-                     A.full_range, A.cell2, hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx,
-                     hd_d2, CV); sweep_timer_mark(1, false, s); }
-  if (n_chunks > 1 && A.full_range)
-    hipLaunchKernelGGL(nn_merge_unpack_rows_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s,
-                       (const unsigned long long*)A.merge64, A.invpos_r, n_rows, (uint32_t)TQV, A.q_seg,
-                       nn_idx, nn_d2, hd_idx, hd_d2);
-  else if (n_chunks > 1)
-    hipLaunchKernelGGL(nn_merge_unpack_kernel, dim3((A.n_q + 255) / 256), dim3(256), 0, s,
-                       (const unsigned long long*)A.merge64, A.perm_q, A.n_q, n_rows, (uint32_t)TQV, A.q_seg,
-                       nn_idx, nn_d2, hd_idx, hd_d2);
+  nn_shares_end(A, n_rows, n_chunks, (uint32_t)TQV, nn_idx, nn_d2, hd_idx, hd_d2, s);
 }
 
-template <int S>
-void nn_pruned_dispatch(const float* coords, uint32_t n_rows, uint32_t n_cols, const float* fe,
-                        const NnPrunedArgs& A, uint32_t T, const uint32_t* hdr,
-                        unsigned long long* chain_counter, uint32_t* nn_idx, float* nn_d2,
-                        uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
-  // (the shared-operand sweep keeps tq_for: its workgroup of four waves is one group of 4 * TQ tiles)
-  if (nn_shared_wanted(n_rows, n_cols))
-    nn_pruned_launch<S, tq_for<S>>(coords, n_rows, n_cols, fe, A, T, hdr, chain_counter, nn_idx, nn_d2, hd_idx, hd_d2, s);
-  else
-    nn_pruned_launch<S, tq_nn_for<S>>(coords, n_rows, n_cols, fe, A, T, hdr, chain_counter, nn_idx, nn_d2, hd_idx, hd_d2, s);
-}
-
-// pruned population sweep: queries = n_q spatially ordered rows (image/perm/boxes "q"), references =
-// all rows spatially ordered ("p"); full_range: the query set is every row -> the two orders coincide
-// Which calls take the symmetric sweep: all rows as queries in the reference order -- every query group, or the
-// groups of one segment of a sharded run (a group owns the same pairs of groups whichever rank runs it, so the
-// ranks' counts are PARTIAL counts of all rows and merge by summation like the one-sided ones) -- but not a row
-// range; one radius, no pair sink, positions that fit the queue entries.  DC_POP_SYM = 0 turns it off (tests,
-// measurements).
-inline bool pop_sym_wanted(bool sink, int q_mode, QSeg q_seg, uint32_t n_rows, int n_rad) {
-  static const bool off = [] {
-    const char* v = getenv("DC_POP_SYM");
-    return v && v[0] == '0';
-  }();
-  (void)q_seg;
-  return !off && !sink && q_mode == kQueryAll && n_rad == 1 && n_rows + 32u * kPadTiles <= kPopQueueMaxRows;
-}
-// the shared-operand sweeps in their symmetric form: with ONE radius (5M x 30, all rows: 1 482 -> 932 ms; 1M x 30:
-// 56.3 -> 35.8 ms).  With several radii per sweep the reference side costs one 128-byte atomic per reference tile,
-// wave and RADIUS into count arrays far larger than the L2 (C5: 8 x 20 MB): four radii at 1M x 16 still gain 9 %, but
-// the eight radii of C5's segment sweep went from 797 to 2 062 ms -- about 10^9 such atomics per second is what the
-// memory side takes.  DC_POP_SHARED_SYM = 0 / 1 / 2: never / one radius only (default) / always.
-inline bool pop_shared_sym_wanted(int nr) {
-  static const int mode = [] {
-    const char* v = getenv("DC_POP_SHARED_SYM");
-    return (v && v[0]) ? atoi(v) : 1;
-  }();
-  return mode >= 2 || (mode == 1 && nr == 1);
-}
 // counts by position in the sweep's order -> populations by frame (a flagged data set: the direct kernel writes)
 __global__ void pops_by_frame_kernel(const uint32_t* __restrict__ pops_pos, const uint32_t* __restrict__ perm,
                                      uint32_t n_rows, const uint32_t* __restrict__ hdr, uint32_t* __restrict__ pops) {
@@ -3042,20 +3080,18 @@ __global__ void pops_by_frame_kernel(const uint32_t* __restrict__ pops_pos, cons
   if (pos < n_rows && perm[pos] != kInvalidFrame) pops[perm[pos]] = pops_pos[pos];
 }
 
-template <int S, int NRV, int TQV>
-void pop_pruned_launch(const float* coords, uint32_t n_rows, uint32_t n_cols, const Ptrs& P,
-                       uint32_t T, uint32_t n_q, int q_mode, QSeg q_seg, const Rad2& rad2,
-                       int n_rad, uint32_t* pops, unsigned long long* chain_counter,
-                       const EdgeSink* sink, hipStream_t s, bool pos_clean = false) {
+// pruned population sweep: queries = n_q spatially ordered rows (image/perm/boxes "q"), references =
+// all rows spatially ordered ("p"); full_range: the query set is every row -> the two orders coincide.
+// The form, the radii per sweep and the query tiles are the plan's (plan_pop).
+template <int S>
+void pop_pruned_dispatch(const PopPlan& pl, const float* coords, uint32_t n_rows, uint32_t n_cols, const Ptrs& P,
+                         uint32_t T, uint32_t n_q, int q_mode, QSeg q_seg, const Rad2& rad2,
+                         int n_rad, uint32_t* pops, unsigned long long* chain_counter,
+                         const EdgeSink* sink, hipStream_t s, bool pos_clean) {
   // pos_clean: the counts by position of the one-radius symmetric per-wave sweep (the pq region) were cleared by the
   // preparation (order_rows2_kernel) -- no fill in front of the sweep
+  assert(pop_form_built(pl.form, S) && n_rad <= pl.nr);
   if (n_q == 0) return;
-  // the query groups of this launch: all of them, or one segment's share
-  const uint32_t waves = seg_groups(((n_q + 31) / 32 + TQV - 1) / TQV, q_seg), tiles = waves * TQV;
-  if (waves == 0) return;
-  const uint32_t wpb = waves_per_group(S);
-  const dim3 grid(grid_x8((waves + wpb - 1) / wpb), pick_chunks(tiles, TQV, kPopWaveTarget, T, pop_share_floor(T), (size_t)S * 1024 + 128)),
-      block(64 * wpb);
   // B form of the query rows: its own image for a row range, else the B form of the rows in the
   // reference order (img_q)
   const bool own = q_mode == kQueryOwnOrder;
@@ -3072,119 +3108,114 @@ void pop_pruned_launch(const float* coords, uint32_t n_rows, uint32_t n_cols, co
   const float* norms_q = own ? P.norms_q : P.norms_p;
   const uint32_t* perm_q = own ? P.perm_q : P.perm_p;
   const float4* box_q = own ? P.box_q : P.box_p;
-  // survivor list + query rows (original coordinates) + queues of deferred exact evaluations, per wave
-  const size_t smem = wpb * (sizeof(uint32_t) * kListCap + sizeof(float) * TQV * 32 * (size_t)n_cols +
-                             sizeof(uint32_t) * TQV * kQueueCap * 64);
-  if (!sink && pop_shared_wanted(n_rows, n_cols, n_rad)) {
-    // reference operands shared through LDS (dc_mfma_shared.hpp); NRV radii in this one sweep
-    constexpr int kTQS = tq_shared_for<S, NRV>;
-    const uint32_t groups = seg_groups(((n_q + 31) / 32 + 4 * kTQS - 1) / (4 * kTQS), q_seg);
+  // counts by position for the symmetric shared-operand forms: [radius][32 T] (pop_shared_kernel) or [tile][NR][32]
+  // (pop_msym_kernel), in the regions from norms_s to vals_in of the workspace (the population sweeps leave them alone
+  // once the orders are built)
+  uint32_t* pops_shared_pos = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(P.norms_s));
+  // reference operands shared through LDS (dc_mfma_shared.hpp, dc_mfma_msym.hpp); NR radii in one sweep
+  auto shared = [&](auto nr_c) {
+    constexpr int NR = decltype(nr_c)::value;
+    constexpr int TQ = tq_shared(S, NR);
+    assert(pl.tq == (uint32_t)TQ);
+    const uint32_t groups = seg_groups(((n_q + 31) / 32 + 4 * TQ - 1) / (4 * TQ), q_seg);
     if (groups == 0) return;
-    const dim3 grid_s(grid_x8(groups), pick_chunks(groups * 4 * kTQS, kTQS, kPopSharedWaveTarget, T, kPopShareFloor, (size_t)S * 1024 + 128));
-    const size_t smem_s = (size_t)kRing * kTileUnits<S> * 16 + sizeof(uint32_t) * 4 * shared_wave_words(kTQS, NRV);
-    if constexpr (NRV > 1 && kTQS == kMsTQ) {
-      if (pop_sym_wanted(false, q_mode, q_seg, n_rows, 1) && pop_msym_wanted()) {
-        // symmetric form for several radii (dc_mfma_msym.hpp): counts by position [tile][NRV][32] in the regions from
-        // norms_s to vals_in of the workspace (the population sweeps leave them alone once the orders are built)
-        uint32_t* pops_pos = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(P.norms_s));
-        (void)hipMemsetAsync(pops_pos, 0, sizeof(uint32_t) * 32 * (size_t)T * NRV, s);
+    const dim3 grid_s(grid_x8(groups), pick_chunks(groups * 4 * TQ, TQ, kPopSharedWaveTarget, T, kPopShareFloor, (size_t)S * 1024 + 128));
+    const size_t smem_s = (size_t)kRing * kTileUnits<S> * 16 + sizeof(uint32_t) * 4 * shared_wave_words(TQ, NR);
+    if constexpr (NR > 1) {
+      if (pl.form == kPopMsym) {
+        (void)hipMemsetAsync(pops_shared_pos, 0, sizeof(uint32_t) * 32 * (size_t)T * NR, s);
         // (two launches: the instance with the thresholds taken off the accumulator in place, and the one that subtracts on
         //  the vector unit -- each looks at the scale and the radii and the one they do not ask for returns at once)
-        sweep_timer_mark(0, true, s);
-        hipLaunchKernelGGL((pop_msym_kernel<S, NRV, true>), grid_s, dim3(256), (msym_smem<S, NRV>()), s, coords, n_rows, n_cols,
-                           P.img_p, P.norms_p, P.box_p, P.coords_p, T, img_q, norms_q, perm_q, box_q, n_q, q_seg, P.hdr,
-                           chain_counter, rad2, n_rad, CV, pops_pos);
-        hipLaunchKernelGGL((pop_msym_kernel<S, NRV, false>), grid_s, dim3(256), (msym_smem<S, NRV>()), s, coords, n_rows, n_cols,
-                           P.img_p, P.norms_p, P.box_p, P.coords_p, T, img_q, norms_q, perm_q, box_q, n_q, q_seg, P.hdr,
-                           chain_counter, rad2, n_rad, CV, pops_pos);
-        sweep_timer_mark(0, false, s);
-        cross(4u * kTQS, pops_pos, (size_t)NRV, 2);
-        hipLaunchKernelGGL((pops_by_frame_ms_kernel<NRV>), dim3((32 * T + 255) / 256), dim3(256), 0, s, (const uint32_t*)pops_pos,
-                           P.perm_p, 32u * T, n_rows, n_rad, P.hdr, pops);
+        timed_launch(0, s, [&] {
+          hipLaunchKernelGGL((pop_msym_kernel<S, NR, true>), grid_s, dim3(256), (msym_smem<S, NR>()), s, coords, n_rows, n_cols,
+                             P.img_p, P.norms_p, P.box_p, P.coords_p, T, img_q, norms_q, perm_q, box_q, n_q, q_seg, P.hdr,
+                             chain_counter, rad2, n_rad, CV, pops_shared_pos);
+          hipLaunchKernelGGL((pop_msym_kernel<S, NR, false>), grid_s, dim3(256), (msym_smem<S, NR>()), s, coords, n_rows, n_cols,
+                             P.img_p, P.norms_p, P.box_p, P.coords_p, T, img_q, norms_q, perm_q, box_q, n_q, q_seg, P.hdr,
+                             chain_counter, rad2, n_rad, CV, pops_shared_pos);
+        });
+        cross(4u * TQ, pops_shared_pos, (size_t)NR, 2);
+        hipLaunchKernelGGL((pops_by_frame_ms_kernel<NR>), dim3((32 * T + 255) / 256), dim3(256), 0, s,
+                           (const uint32_t*)pops_shared_pos, P.perm_p, 32u * T, n_rows, n_rad, P.hdr, pops);
+        return;
+      }
+    } else {
+      if (pl.form == kPopSharedSym) {
+        (void)hipMemsetAsync(pops_shared_pos, 0, sizeof(uint32_t) * 32 * (size_t)T, s);
+        timed_launch(0, s, [&] {
+          hipLaunchKernelGGL((pop_shared_kernel<S, TQ, 1, true>), grid_s, dim3(256), smem_s, s, coords, n_rows, n_cols,
+                             P.img_p, P.norms_p, P.box_p, P.coords_p, T, img_q, norms_q, perm_q, box_q, n_q, q_seg, P.hdr,
+                             chain_counter, rad2, n_rad, pops, own ? 0 : 1, CV, pops_shared_pos);
+        });
+        cross(4u * TQ, pops_shared_pos, (size_t)32 * T, 1);
+        hipLaunchKernelGGL(pops_by_frame_kernel, dim3((32 * T + 255) / 256), dim3(256), 0, s,
+                           (const uint32_t*)pops_shared_pos, P.perm_p, 32u * T, P.hdr, pops);
         return;
       }
     }
-    if (pop_sym_wanted(false, q_mode, q_seg, n_rows, 1) && pop_shared_sym_wanted(NRV)) {
-      // symmetric form: counts by position, one array of 32 T words per radius (the regions from norms_s to
-      // vals_in of the workspace: the population sweeps leave them alone once the orders are built)
-      uint32_t* pops_pos = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(P.norms_s));
-      (void)hipMemsetAsync(pops_pos, 0, sizeof(uint32_t) * 32 * (size_t)T * NRV, s);
-      { sweep_timer_mark(0, true, s); hipLaunchKernelGGL((pop_shared_kernel<S, kTQS, NRV, true>), grid_s, dim3(256), smem_s, s, coords, n_rows, n_cols,
-                         P.img_p, P.norms_p, P.box_p, P.coords_p, T, img_q, norms_q, perm_q, box_q, n_q, q_seg, P.hdr,
-                         chain_counter, rad2, n_rad, pops, own ? 0 : 1, CV, pops_pos); sweep_timer_mark(0, false, s); }
-      cross(4u * kTQS, pops_pos, (size_t)32 * T, 1);
-      for (int rr = 0; rr < n_rad; ++rr)
-        hipLaunchKernelGGL(pops_by_frame_kernel, dim3((32 * T + 255) / 256), dim3(256), 0, s,
-                           (const uint32_t*)(pops_pos + (size_t)rr * 32 * T), P.perm_p, 32u * T, P.hdr,
-                           pops + (size_t)rr * n_rows);
+    timed_launch(0, s, [&] {
+      hipLaunchKernelGGL((pop_shared_kernel<S, TQ, NR>), grid_s, dim3(256), smem_s, s, coords, n_rows, n_cols, P.img_p,
+                         P.norms_p, P.box_p, P.coords_p, T, img_q, norms_q, perm_q, box_q, n_q, q_seg, P.hdr,
+                         chain_counter, rad2, n_rad, pops, own ? 0 : 1, CV);
+    });
+    cross(4u * TQ, pops, (size_t)n_rows, 0);
+  };
+  switch (pl.form) {
+    case kPopMsym:
+    case kPopMulti:
+      if constexpr (pop_form_built(kPopMulti, S)) {
+        if (pl.nr == 4)
+          shared(std::integral_constant<int, 4>{});
+        else
+          shared(std::integral_constant<int, 8>{});
+      }
       return;
-    }
-    { sweep_timer_mark(0, true, s); hipLaunchKernelGGL((pop_shared_kernel<S, kTQS, NRV>), grid_s, dim3(256), smem_s, s, coords, n_rows, n_cols, P.img_p,
-                       P.norms_p, P.box_p, P.coords_p, T, img_q, norms_q, perm_q, box_q, n_q, q_seg, P.hdr,
-                       chain_counter, rad2, n_rad, pops, own ? 0 : 1, CV); sweep_timer_mark(0, false, s); }
-    cross(4u * kTQS, pops, (size_t)n_rows, 0);
-    return;
+    case kPopShared:
+    case kPopSharedSym:
+      if constexpr (pop_form_built(kPopShared, S)) shared(std::integral_constant<int, 1>{});
+      return;
+    default:
+      break;
   }
-  if constexpr (NRV == 1 && TQV <= 6) {
-    if (pop_sym_wanted(sink != nullptr, q_mode, q_seg, n_rows, n_rad)) {
+  // the per-wave sweeps, one radius
+  constexpr int TQ = tq_pop(S);
+  assert(pl.tq == (uint32_t)TQ);
+  // the query groups of this launch: all of them, or one segment's share
+  const uint32_t waves = seg_groups(((n_q + 31) / 32 + TQ - 1) / TQ, q_seg), tiles = waves * TQ;
+  if (waves == 0) return;
+  const uint32_t wpb = pl.waves;
+  const dim3 grid(grid_x8((waves + wpb - 1) / wpb), pick_chunks(tiles, TQ, kPopWaveTarget, T, pop_share_floor(T), (size_t)S * 1024 + 128)),
+      block(64 * wpb);
+  // survivor list + query rows (original coordinates) + queues of deferred exact evaluations, per wave
+  const size_t smem = wpb * (sizeof(uint32_t) * kListCap + sizeof(float) * TQ * 32 * (size_t)n_cols +
+                             sizeof(uint32_t) * TQ * kQueueCap * 64);
+  const EdgeSink no_sink{nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+  auto launch = [&](auto mode_c, auto sym_c, uint32_t* pops_pos) {
+    timed_launch(0, s, [&] {
+      hipLaunchKernelGGL((pop_pruned_kernel<S, 1, TQ, decltype(mode_c)::value, decltype(sym_c)::value>), grid, block, smem, s,
+                         coords, n_rows, n_cols, P.img_p, P.norms_p, P.perm_p, P.box_p, P.coords_p, T, img_q, norms_q,
+                         perm_q, box_q, n_q, q_seg, P.hdr, chain_counter, rad2, n_rad, pops, sink ? *sink : no_sink, CV,
+                         pops_pos);
+    });
+  };
+  switch (pl.form) {
+    case kPopWaveSym: {
       // symmetric sweep: counts by position (the pq region of the workspace: only the full neighbour sweep uses
       // it), then to the frames
       uint32_t* pops_pos = const_cast<uint32_t*>(P.pq);
       if (!pos_clean) (void)hipMemsetAsync(pops_pos, 0, sizeof(uint32_t) * 32 * (size_t)T, s);
-      { sweep_timer_mark(0, true, s); hipLaunchKernelGGL((pop_pruned_kernel<S, 1, TQV, kSinkNone, true>), grid, block, smem, s, coords, n_rows,
-                         n_cols, P.img_p, P.norms_p, P.perm_p, P.box_p, P.coords_p, T, img_q, norms_q,
-                         perm_q, box_q, n_q, q_seg, P.hdr, chain_counter, rad2, n_rad, pops,
-                         EdgeSink{nullptr, nullptr, 0, nullptr, nullptr, nullptr}, CV, pops_pos); sweep_timer_mark(0, false, s); }
-      cross((uint32_t)TQV, pops_pos, (size_t)32 * T, 1);
+      launch(std::integral_constant<int, kSinkNone>{}, std::true_type{}, pops_pos);
+      cross((uint32_t)TQ, pops_pos, (size_t)32 * T, 1);
       hipLaunchKernelGGL(pops_by_frame_kernel, dim3((32 * T + 255) / 256), dim3(256), 0, s, (const uint32_t*)pops_pos,
                          P.perm_p, 32u * T, P.hdr, pops);
       return;
     }
+    // radius-graph variants: all rows only (query positions = reference positions)
+    case kPopMinEdge: launch(std::integral_constant<int, kSinkMinEdge>{}, std::false_type{}, nullptr); break;
+    case kPopPairs: launch(std::integral_constant<int, kSinkPairs>{}, std::false_type{}, nullptr); break;
+    default: launch(std::integral_constant<int, kSinkNone>{}, std::false_type{}, nullptr); break;
   }
-  // radius-graph variants: all rows only (query positions = reference positions)
-  if (sink && sink->best)
-    { sweep_timer_mark(0, true, s); hipLaunchKernelGGL((pop_pruned_kernel<S, NRV, TQV, kSinkMinEdge>), grid, block, smem, s, coords,
-                       n_rows, n_cols, P.img_p, P.norms_p, P.perm_p, P.box_p, P.coords_p, T, img_q,
-                       norms_q, perm_q, box_q, n_q, q_seg, P.hdr, chain_counter, rad2, n_rad, pops, *sink, CV); sweep_timer_mark(0, false, s); }
-  else if (sink)
-    { sweep_timer_mark(0, true, s); hipLaunchKernelGGL((pop_pruned_kernel<S, NRV, TQV, kSinkPairs>), grid, block, smem, s, coords, n_rows,
-                       n_cols, P.img_p, P.norms_p, P.perm_p, P.box_p, P.coords_p, T, img_q, norms_q,
-                       perm_q, box_q, n_q, q_seg, P.hdr, chain_counter, rad2, n_rad, pops, *sink, CV); sweep_timer_mark(0, false, s); }
-  else
-    { sweep_timer_mark(0, true, s); hipLaunchKernelGGL((pop_pruned_kernel<S, NRV, TQV, kSinkNone>), grid, block, smem, s, coords, n_rows,
-                       n_cols, P.img_p, P.norms_p, P.perm_p, P.box_p, P.coords_p, T, img_q, norms_q,
-                       perm_q, box_q, n_q, q_seg, P.hdr, chain_counter, rad2, n_rad, pops,
-                       EdgeSink{nullptr, nullptr, 0, nullptr, nullptr, nullptr}, CV); sweep_timer_mark(0, false, s); }
-  cross((uint32_t)TQV, pops, (size_t)n_rows, 0);
-}
-
-template <int S, int NRV>
-void pop_pruned_tq(const float* coords, uint32_t n_rows, uint32_t n_cols, const Ptrs& P, uint32_t T,
-                   uint32_t n_q, int q_mode, QSeg q_seg, const Rad2& rad2, int n_rad,
-                   uint32_t* pops, unsigned long long* chain_counter, const EdgeSink* sink,
-                   hipStream_t s, bool pos_clean = false) {
-  pop_pruned_launch<S, NRV, tq_pop_for<S>>(coords, n_rows, n_cols, P, T, n_q, q_mode, q_seg, rad2,
-                                       n_rad, pops, chain_counter, sink, s, pos_clean);
-}
-
-template <int S>
-void pop_pruned_dispatch(const float* coords, uint32_t n_rows, uint32_t n_cols, const Ptrs& P,
-                         uint32_t T, uint32_t n_q, int q_mode, QSeg q_seg, const Rad2& rad2,
-                         int n_rad, uint32_t* pops, unsigned long long* chain_counter,
-                         const EdgeSink* sink, hipStream_t s, bool pos_clean = false) {
-  // one radius per sweep (dc_mfma.hip loops over the radii of a call) -- except the shared-operand sweep of wide
-  // rows, which takes up to eight (dc_mfma_shared.hpp; S >= 3 only: no instances for the narrow shapes)
-  if constexpr (S >= 3 && S <= 8) {
-    if (!sink && n_rad > 1 && pop_shared_wanted(n_rows, n_cols, n_rad)) {
-      if (n_rad <= 4)
-        pop_pruned_launch<S, 4, 2>(coords, n_rows, n_cols, P, T, n_q, q_mode, q_seg, rad2, n_rad, pops, chain_counter, sink, s);
-      else
-        pop_pruned_launch<S, 8, 2>(coords, n_rows, n_cols, P, T, n_q, q_mode, q_seg, rad2, n_rad, pops, chain_counter, sink, s);
-      return;
-    }
-  }
-  pop_pruned_tq<S, 1>(coords, n_rows, n_cols, P, T, n_q, q_mode, q_seg, rad2, n_rad, pops,
-                      chain_counter, sink, s, pos_clean);
+  cross((uint32_t)TQ, pops, (size_t)n_rows, 0);
 }
 
 template <int S>
@@ -3206,10 +3237,10 @@ void nn_dispatch(const float* coords, uint32_t n_rows, uint32_t n_cols, const Pt
   void pop_mfma_step_##SV(const float* coords, uint32_t n_rows, uint32_t n_cols, void* d_ws,     \
                           uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad,           \
                           uint32_t* pops, hipStream_t s);                                        \
-  void pop_pruned_step_##SV(const float* coords, uint32_t n_rows, uint32_t n_cols, void* d_ws,   \
-                            uint32_t T_ref, uint32_t n_q, int q_mode, QSeg q_seg, const Rad2& rad2, \
+  void pop_pruned_step_##SV(const PopPlan& plan, const float* coords, uint32_t n_rows, uint32_t n_cols, \
+                            void* d_ws, uint32_t T_ref, uint32_t n_q, int q_mode, QSeg q_seg, const Rad2& rad2, \
                             int n_rad, uint32_t* pops, const EdgeSink* sink, hipStream_t s, bool pos_clean); \
-  void nn_pruned_step_##SV(const float* coords, uint32_t n_rows, uint32_t n_cols, const float* fe, \
+  void nn_pruned_step_##SV(const NnPlan& plan, const float* coords, uint32_t n_rows, uint32_t n_cols, const float* fe, \
                            void* d_ws, uint32_t T_ref, uint32_t n_q, int q_mode, QSeg q_seg, float cell2, \
                            uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2,             \
                            hipStream_t s);                                                       \

@@ -23,10 +23,7 @@
 // population sweep"): groups of 4 * TQ = 8 tiles on a circle, a group meets its own tiles in both orders (query side
 // only) and the half of the other groups that lies ahead of it; the rule does not depend on the rank that runs a
 // group, so segments of a sharded run produce PARTIAL counts of all rows that merge by summation.
-#ifndef DC_MS_WIN
-#define DC_MS_WIN 3
-#endif
-constexpr int kMsWin = DC_MS_WIN;       // reference tiles per window: one barrier per window (LDS: two workgroups per CU at 3)
+constexpr int kMsWin = 3;               // reference tiles per window: one barrier per window (LDS: two workgroups per CU at 3)
 constexpr int kMsRing = 2 * kMsWin;     // operand slots: the window in use and the one in flight
 constexpr int kMsAccSlots = 2 * kMsWin; // accumulator slots: the window in use and the one being reduced
 constexpr int kMsTQ = 2;
@@ -165,11 +162,7 @@ __global__ __launch_bounds__(256, 2) void pop_msym_kernel(
   for (int rr = 1; rr < NR; ++rr) r2max = fmaxf(r2max, rad2.v[rr]);
   const float far2 = r2max * 1.0001f;   // boxes at least this far apart (squared) hold no pair inside
   // radii that hold nothing of a chain (see mr_chain_k): ascending radii only
-#ifdef DC_MS_ABL_NOSKIP
-  bool radii_ascending = false;
-#else
   bool radii_ascending = n_rad >= kMsSkip<NR>;
-#endif
 #pragma unroll
   for (int rr = 1; rr < NR; ++rr) radii_ascending &= (rr >= n_rad) || (P.dl.d[rr] >= P.dl.d[rr - 1]);
   // (rounded UP: fl(2 + d) may lie below 2 + d -- by up to 2^-5 at d ~ 2^19 -- and a chain whose minimum equals it would
@@ -231,9 +224,6 @@ __global__ __launch_bounds__(256, 2) void pop_msym_kernel(
       sh1[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)w1);
     }
   }
-#ifdef DC_MS_NO_INPLACE
-  inplace = false;
-#endif
   if (inplace != INPL) return;   // (the other instance's launch; before any barrier)
   const s16x8 ones_op = __builtin_bit_cast(s16x8, u32x4_t{0x3C003C00u & m32, 0x00003C00u & m32, 0u, 0u});
   auto shift_op = [&](int k) { return __builtin_bit_cast(s16x8, u32x4_t{sh0[k] & m32, sh1[k] & m32, 0u, 0u}); };
@@ -283,9 +273,7 @@ __global__ __launch_bounds__(256, 2) void pop_msym_kernel(
   uint32_t sb[NR][TQ];   // strings of the two chains on the current reference tile
   uint32_t next_par = 0;  // parity of the window after the current one
   auto flush = [&]() {
-#ifndef DC_MS_ABL_NOFLUSH
     pop_wave_flush_ms<NR>(queue, qn, jq_tab, fix_tab, TQ * 32, coords_r, coords_r, n_cols, rad2, lane, pops_pos, 4u * TQ, group);
-#endif
     qn = 0;
   };
   // the rest of an epilogue: query-side counts, band test, parking of the band pairs
@@ -423,11 +411,7 @@ __global__ __launch_bounds__(256, 2) void pop_msym_kernel(
     for (uint32_t j = 0; j < kMsUnits; ++j) {
       const uint32_t c2 = cnt2[j];
       const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane(t_unit[j]);
-#ifdef DC_MS_ABL_NOATOMIC
-      if (c2 == 0xFFFFFFFFu)
-#else
       if (have[j] && c2 != 0u && rr0[j] + (uint32_t)(lane >> 5) < (uint32_t)n_rad && 32u * t + (uint32_t)(lane & 31) < CV.n_pos)
-#endif
         atomicAdd(&pops_pos[(size_t)t * (NR * 32) + (size_t)(rr0[j] + (lane >> 5)) * 32 + (uint32_t)(lane & 31)], c2);
     }
   };
@@ -522,12 +506,10 @@ __global__ __launch_bounds__(256, 2) void pop_msym_kernel(
               if (tid == 0) flush_flag[par] = 0u;
             }
           }
-#ifndef DC_MS_ABL_NOREDUCE
           if (i >= (uint32_t)kMsWin) {
             const uint32_t j = i - kMsWin;
             reduce_window(j / kMsWin, [&](uint32_t k) { return entry_raw(j + k); }, (uint32_t)kMsWin, std::true_type{});
           }
-#endif
         }
         const uint32_t t_raw = entry_raw(i);   // (made a scalar behind the first epilogue: nothing before it needs the tile's number)
         const uint4* slot = ring + (i % kMsRing) * kUnits;
@@ -592,11 +574,7 @@ __global__ __launch_bounds__(256, 2) void pop_msym_kernel(
             });
             finish(std::integral_constant<int, 1>{}, e, t);
           }
-#ifndef DC_MS_ABL_NOCREDIT
           if ((t / (4u * TQ)) != group)   // (not the workgroup's own group)
-#else
-          if (t == 0xFFFFFFFFu)
-#endif
             credit((((i / kMsWin) & 1u) * kMsWin) + (i % kMsWin));
         }
       }
@@ -652,14 +630,6 @@ __global__ void pops_by_frame_ms_kernel(const uint32_t* __restrict__ pops_pos, c
   for (int rr = 0; rr < n_rad; ++rr) pops[(size_t)rr * n_rows + f] = pops_pos[ms_index<NR>(pos, rr)];
 }
 
-// DC_POP_MSYM = 0 keeps the one-sided multi-radius sweep (pop_shared_kernel<NM, 2, NR>; tests, measurements)
-inline bool pop_msym_wanted() {
-  static const bool off = [] {
-    const char* v = getenv("DC_POP_MSYM");
-    return v && v[0] == '0';
-  }();
-  return !off;
-}
 template <int NM, int NR>
 constexpr size_t msym_smem() {
   return (size_t)kMsRing * kTileUnits<NM> * 16 + (size_t)kMsAccSlots * NR * 64 * 8 + sizeof(uint32_t) * 4 * shared_wave_words(kMsTQ, NR);

@@ -31,34 +31,12 @@ __device__ __attribute__((noinline)) void nn_wave_flush_rows(const uint2* queue,
   }
 }
 
-// which shapes take the shared-operand neighbour sweep (DC_NN_SHARED = 0 / 1 forces it off / on)
-inline bool nn_shared_wanted(uint32_t n_rows, uint32_t n_cols) {
-  static const int forced = [] {
-    const char* v = getenv("DC_NN_SHARED");
-    return (v && v[0]) ? atoi(v) : -1;
-  }();
-  const int nm = nm_for((int)n_cols);
-  if (nm > 8 || n_rows >= (1u << 30)) return false;
-  if (forced >= 0) return forced != 0;
-  const size_t image = (size_t)((n_rows + 31) / 32) * (size_t)nm * 1024;
-  return nm >= 5 && image > ((size_t)96 << 20);
-}
-
 // NB: the MFMAs of a chain that run before the early-out test (dc_mfma_kernels.hpp "early-out of the pruned
 // neighbour sweep"): nn_coarse_for(n_cols); the fragments behind them are read from the ring only by the chains
 // that go on.
 // Only the NB coarse fragments of a tile go through the ring: 97 % of the chains stop after them, and the sweep ran at the
 // memory side's pace (C5: 0.56 TB per launch at 5.7 TB/s).  A chain that goes on loads its remaining fragments straight
-// from the image and waits for them -- one rank of C5 100 -> 87 ms.  (DC_NNS_GLOBAL_REST=0: the whole tile through the
-// ring, as before; measurements.)
-#ifndef DC_NNS_GLOBAL_REST
-#define DC_NNS_GLOBAL_REST 1
-#endif
-#if DC_NNS_GLOBAL_REST
-#define DC_NNS_RING_FRAGS NB
-#else
-#define DC_NNS_RING_FRAGS NM
-#endif
+// from the image and waits for them -- one rank of C5 100 -> 87 ms (the whole tile through the ring, as before).
 template <int NM, int TQ, int NB>
 __global__ __launch_bounds__(256, 2) void nn_shared_kernel(
     const float* __restrict__ coords, uint32_t n_rows, uint32_t n_cols,
@@ -312,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void nn_shared_kernel(
         const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_address(ring + slot_id * kUnits));
         const uint4* src = img_r + (size_t)t * (NM * 64) + lane;
 #pragma unroll
-        for (int m = 0; m < DC_NNS_RING_FRAGS; ++m) lds_dma16(src + m * 64, dst + (uint32_t)m * 1024u);
+        for (int m = 0; m < NB; ++m) lds_dma16(src + m * 64, dst + (uint32_t)m * 1024u);
         if (lane < 2) lds_dma4(reinterpret_cast<const float*>(ferange_r + t) + lane, dst + (uint32_t)NM * 1024u + 128u);
       };
       // the rest of an epilogue: free-energy classes, band test, parking of the candidates.
@@ -451,7 +429,6 @@ __global__ __launch_bounds__(256, 2) void nn_shared_kernel(
               f32x16 acc = mfma16(a[0], b[qi][0], c0);
 #pragma unroll
               for (int m = 1; m < NB; ++m) acc = mfma16(a[m], b[qi][m], acc);
-#if DC_NNS_GLOBAL_REST
               {
                 const uint4* rest = img_r + (size_t)t * (NM * 64) + lane;
                 s16x8 ar[NM - NB > 0 ? NM - NB : 1];
@@ -460,10 +437,6 @@ __global__ __launch_bounds__(256, 2) void nn_shared_kernel(
 #pragma unroll
                 for (int m = NB; m < NM; ++m) acc = mfma16(ar[m - NB], b[qi][m], acc);
               }
-#else
-#pragma unroll
-              for (int m = NB; m < NM; ++m) acc = mfma16(__builtin_bit_cast(s16x8, slot[m * 64 + lane]), b[qi][m], acc);
-#endif
               float tmin = INFINITY;
               tile_min<0, 16>(acc, tmin);
               finish(acc, qi_c, tmin, t, fr);

@@ -230,9 +230,6 @@ __global__ __launch_bounds__(256, 2) void pop_shared_kernel(
   bool symB = false;
   const uint32_t my_byte = ref_credit_byte(lane);
   auto credit = [&](uint32_t t) {
-#ifdef DC_ABL_SHARED_NOCREDIT
-    if (t != 0xFFFFFFFFu) return;
-#endif
 #pragma unroll
     for (int rr = 0; rr < NR; ++rr)
       if (rr < n_rad) ref_credit<TQ>(sb[rr], t, CV.n_pos, pops_pos + (size_t)rr * pos_stride, credit_stage[wib], my_byte, lane);
@@ -435,22 +432,6 @@ __global__ __launch_bounds__(256, 2) void pop_shared_kernel(
 // 2M x 20, 8 radii 1390 -> 1068 ms; 1M x 16, 8 radii 300 -> 222 ms, 4 radii 153 -> 127 ms; 600k x 12, 8 radii 90 -> 77 ms
 // (the distances are computed once; by the issue model the gain is (4*26 + 24*NM) R against 4*33 R + 24*NM cycles):
 // three or more MFMAs per chain and three or more radii, or five or more MFMAs and two radii.
-// DC_POP_SHARED = 0 / 1 forces it off / on (tests, measurements).
-template <int NM, int NR>
-constexpr int tq_shared_for = (NM <= 6 && NR == 1) ? 4 : 2;
-inline int nr_shared_of(int n_rad) { return n_rad <= 1 ? 1 : (n_rad <= 4 ? 4 : 8); }   // radii per sweep instance
-inline int tq_shared_of(uint32_t n_cols, int n_rad) {   // = tq_shared_for<NM, NR>
-  return (nm_for((int)n_cols) <= 6 && nr_shared_of(n_rad) == 1) ? 4 : 2;
-}
-inline bool pop_shared_wanted(uint32_t n_rows, uint32_t n_cols, int n_rad) {
-  static const int forced = [] {
-    const char* v = getenv("DC_POP_SHARED");
-    return (v && v[0]) ? atoi(v) : -1;
-  }();
-  const int nm = nm_for((int)n_cols);
-  if (n_rows + 32u * kPadTiles > kPopQueueMaxRows || nm > 8) return false;
-  if (forced >= 0) return forced != 0;
-  const size_t image = (size_t)((n_rows + 31) / 32) * (size_t)nm * 1024;
-  if (nm >= 5 && image > ((size_t)96 << 20)) return true;
-  return n_rows >= 50000u && ((nm >= 3 && n_rad >= 3) || (nm >= 5 && n_rad >= 2));
-}
+// The rule is plan_pop's (dc_mfma_kernels.hpp); DC_POP_SHARED = 0 / 1 forces it off / on where the form is built.
+// Query tiles per wave: four with one radius and at most six MFMAs per chain, else two.
+constexpr int tq_shared(int nm, int nr) { return (nm <= 6 && nr == 1) ? 4 : 2; }

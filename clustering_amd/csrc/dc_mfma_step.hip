@@ -19,18 +19,18 @@ void DC_CAT(pop_mfma_step_, DC_STEP)(const float* coords, uint32_t n_rows, uint3
                         pops, s);
 }
 
-void DC_CAT(pop_pruned_step_, DC_STEP)(const float* coords, uint32_t n_rows, uint32_t n_cols,
+void DC_CAT(pop_pruned_step_, DC_STEP)(const PopPlan& plan, const float* coords, uint32_t n_rows, uint32_t n_cols,
                                        void* d_ws, uint32_t T_ref, uint32_t n_q, int q_mode, QSeg q_seg,
                                        const Rad2& rad2, int n_rad, uint32_t* pops,
                                        const EdgeSink* sink, hipStream_t s, bool pos_clean) {
   const Layout L = make_layout(n_rows, n_cols);
   // evaluated-chain counter: header word 2..3 (8-byte aligned)
   // (T_ref: tiles of the padded reference order; n_q: positions of the query order)
-  pop_pruned_dispatch<DC_STEP>(coords, n_rows, n_cols, ws_ptrs(d_ws, L), T_ref, n_q, q_mode, q_seg,
+  pop_pruned_dispatch<DC_STEP>(plan, coords, n_rows, n_cols, ws_ptrs(d_ws, L), T_ref, n_q, q_mode, q_seg,
                                rad2, n_rad, pops, (unsigned long long*)((char*)d_ws + 8), sink, s, pos_clean);
 }
 
-void DC_CAT(nn_pruned_step_, DC_STEP)(const float* coords, uint32_t n_rows, uint32_t n_cols,
+void DC_CAT(nn_pruned_step_, DC_STEP)(const NnPlan& plan, const float* coords, uint32_t n_rows, uint32_t n_cols,
                                       const float* fe, void* d_ws, uint32_t T_ref, uint32_t n_q, int q_mode,
                                       QSeg q_seg, float cell2, uint32_t* nn_idx, float* nn_d2,
                                       uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
@@ -60,7 +60,7 @@ void DC_CAT(nn_pruned_step_, DC_STEP)(const float* coords, uint32_t n_rows, uint
   A.tile_comp_q = (const uint32_t*)(p + (own ? L.off_tile_comp_q : L.off_tile_comp));
   A.comp = (const uint32_t*)(p + L.off_comp);
   // (T_ref: tiles of the padded reference order; n_q: positions of the query order)
-  nn_pruned_dispatch<DC_STEP>(coords, n_rows, n_cols, fe, A, T_ref, (const uint32_t*)p,
+  nn_pruned_dispatch<DC_STEP>(plan, coords, n_rows, n_cols, fe, A, T_ref, (const uint32_t*)p,
                               (unsigned long long*)(p + 16), nn_idx, nn_d2, hd_idx, hd_d2, s);
 }
 

@@ -177,8 +177,9 @@ print("ok")
 
 
 def test_adjacent_components_in_the_shared_operand_sweeps():
-    """the same through pop_shared_kernel (one radius: symmetric; eight radii in one sweep; forced on for a small shape)"""
-    for extra in ({"DC_POP_SHARED": "1"}, {"DC_POP_SHARED": "1", "DC_POP_SHARED_SYM": "2"}):
+    """the same through the shared-operand sweeps (one radius: symmetric; eight radii in one sweep: pop_msym_kernel, and
+    pop_shared_kernel for the row range; forced on for a small shape)"""
+    for extra in ({"DC_POP_SHARED": "1"},):
         r = subprocess.run([sys.executable, "-c", _SHARED_ADJ_CHILD, ROOT], capture_output=True, text=True, timeout=900,
                            env=dict(os.environ, **extra))
         assert r.returncode == 0 and "ok" in r.stdout, (extra, r.stderr[-3000:])

@@ -629,14 +629,15 @@ def test_shared_operand_population_sweep():
     rows and large images, e.g. C5) forced on for small shapes of every kind -- all rows, a row range, the
     segments of a sharded run, duplicates, 1..8 MFMAs per chain, and (wide rows) up to eight radii per sweep --
     against the direct kernels AND against the oracle (all rows, the segment sums and the 4 / 8 / 17-radius sweeps of
-    every shape), bit for bit.  Three runs: the default (several radii in one SYMMETRIC sweep, pop_msym_kernel:
-    reference-side counts through lane-private LDS accumulators), the one-sided multi-radius sweep (DC_POP_MSYM=0) and
-    the round-2 symmetric form with its per-wave atomics (DC_POP_MSYM=0 DC_POP_SHARED_SYM=2)."""
+    every shape), bit for bit.  Several radii take one SYMMETRIC sweep (pop_msym_kernel: reference-side counts through
+    lane-private LDS accumulators) for all rows and segments, and the one-sided multi-radius sweep for a row range.
+    The shared-operand forms are built for 3 - 8 MFMAs per chain with several radii and 5 - 8 with one: the narrower
+    shapes take the per-wave sweeps, checked against the oracle the same way."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for extra in ({}, {"DC_POP_MSYM": "0"}, {"DC_POP_MSYM": "0", "DC_POP_SHARED_SYM": "2"}):
+    for extra in ({},):
         r = subprocess.run([sys.executable, "-c", SHARED_CHILD, root], capture_output=True, text=True, timeout=900,
                            env=dict(os.environ, DC_POP_SHARED="1", **extra))
         assert r.returncode == 0 and "ok" in r.stdout, (extra, r.stderr[-3000:])
@@ -737,7 +738,8 @@ def test_shared_operand_neighbour_sweep():
     """nn_shared_kernel (workgroup-wide rings and survivor lists, reference operands through an LDS ring; taken by
     itself only for wide rows and large images, e.g. C5) forced on for small shapes -- all rows, a row range, the
     segments of a sharded run, duplicates (ties), 1..8 MFMAs per chain, more than one reference share -- against
-    the direct kernels and (shapes up to 20 000 rows) against the oracle: indices and d2 bits."""
+    the direct kernels and (shapes up to 20 000 rows) against the oracle: indices and d2 bits.  The form is built for
+    5..8 MFMAs per chain; the narrower shapes take the per-wave sweep, checked the same way."""
     import os
     import subprocess
     import sys
@@ -797,11 +799,11 @@ def test_sweep_forms_agree():
     cases = [(1152, 10, [0.2]), (1344, 10, [0.3, 0.15]), (40000, 10, [0.2]), (9000, 3, [0.05]), (20000, 16, [0.4, 0.3, 0.5]),
              (12000, 30, [0.6])]
     envs = [{}, {"DC_POP_SYM": "0"}, {"DC_WAVES_PER_GROUP": "4"}, {"DC_WAVES_PER_GROUP": "1"},
-            {"DC_POP_SHARED": "1", "DC_POP_SHARED_SYM": "2"}, {"DC_POP_SHARED": "1", "DC_POP_SHARED_SYM": "0", "DC_NN_SHARED": "1"},
+            {"DC_POP_SHARED": "1"}, {"DC_POP_SHARED": "1", "DC_NN_SHARED": "1"},
             # round 6: the neighbour sweep's shares as the waves of one workgroup (COOP) -- forced on, with share floors that
-            # give these small shapes many reference shares -- in workgroups of 4, 2 and 8 waves
-            {"DC_NN_COOP": "1", "DC_SHARE_FLOOR": "16"}, {"DC_NN_COOP": "1", "DC_SHARE_FLOOR": "40", "DC_NN_COOP_WAVES": "2"},
-            {"DC_NN_COOP": "1", "DC_SHARE_FLOOR": "8", "DC_NN_COOP_WAVES": "8"}, {"DC_NN_COOP": "0", "DC_SHARE_FLOOR": "16"}]
+            # give these small shapes many reference shares
+            {"DC_NN_COOP": "1", "DC_SHARE_FLOOR": "16"}, {"DC_NN_COOP": "1", "DC_SHARE_FLOOR": "40"},
+            {"DC_NN_COOP": "1", "DC_SHARE_FLOOR": "8"}, {"DC_NN_COOP": "0", "DC_SHARE_FLOOR": "16"}]
     results = []
     for extra in envs:
         env = dict(os.environ, **extra)
