@@ -13,6 +13,9 @@ namespace dc {
 constexpr int kMaxColsTemplated = 32;   // n_cols with a register-resident kernel instance
 constexpr int kMaxColsGeneric = 400;    // n_cols the LDS-resident generic kernel can hold
 constexpr int kMaxRadiiPerLaunch = 8;   // radii swept per launch (more radii -> several launches)
+// widest row any entry point accepts: the kernels carry n_cols as uint32, and the wide sweep's chunk count and tail
+// columns (dc_wide.hip: up to V + 7 < n_cols + 8) must not wrap
+constexpr size_t kMaxColsAny = UINT32_MAX - 64;
 
 // squared radii of one launch, passed by value (kernarg segment -> SGPRs)
 struct Rad2 {
@@ -44,6 +47,20 @@ bool launch_min_edge_direct(const float* d_coords, uint32_t n_rows, uint32_t n_c
                             const uint32_t* d_comp, const uint32_t* d_rank, uint32_t i_from, uint32_t i_to,
                             unsigned long long* d_best, uint32_t* d_pops, const uint32_t* gate,
                             hipStream_t stream);
+
+// ---- launchers implemented in dc_wide.hip: the same products for n_cols > kMaxColsGeneric, with the columns streamed
+// through LDS in chunks (no upper limit on n_cols).  launch_*_direct hand such rows to them.
+void launch_pop_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                     const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, const uint32_t* gate, hipStream_t stream);
+void launch_nn_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, uint32_t i_from,
+                    uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
+                    const uint32_t* gate, hipStream_t stream);
+void launch_pairs_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops,
+                       uint2* d_pairs, unsigned long long capacity, unsigned long long* d_count, const uint32_t* gate,
+                       hipStream_t stream);
+void launch_min_edge_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, const uint32_t* d_comp,
+                          const uint32_t* d_rank, uint32_t i_from, uint32_t i_to, unsigned long long* d_best,
+                          uint32_t* d_pops, const uint32_t* gate, hipStream_t stream);
 
 // fills idx[i] = n_rows+1, d2[i] = FLT_MAX for all rows (density_clustering.cpp:242-245)
 void launch_nn_init(uint32_t n_rows, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
@@ -270,5 +287,47 @@ __device__ __forceinline__ float dist2_canon_rows(const float* x, const float* y
 }
 
 #endif   // DC_CANON_AVX
+
+// ---- the radius graph's outputs and the wave-private pair queue (dc_direct.hip, dc_wide.hip) ----------------------------
+constexpr uint32_t kPairQueue = 256;   // pairs a wave queues before it flushes (uint2 each)
+
+struct GraphOut {
+  uint32_t* pops;
+  uint2* pairs;                  // kGraphPairs: the list, slots < capacity written
+  unsigned long long capacity;
+  unsigned long long* count;     // kGraphPairs: total number of pairs (may exceed capacity)
+  const uint32_t* comp;          // kGraphMinEdge: component id and rank per frame, best per component id
+  const uint32_t* rank;
+  unsigned long long* best;
+};
+
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {   // set bits of m below this lane
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// the wave's queued pairs -> slots [base, base + fill) of the list; fill is wave-uniform
+__device__ __forceinline__ void pair_flush(const uint2* queue, uint32_t& fill, const GraphOut& g) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the queue writes of all lanes before their reads)
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const uint32_t lane = threadIdx.x & 63u;
+  unsigned long long base = 0;
+  if (lane == 0) base = atomicAdd(g.count, (unsigned long long)fill);
+  base = __shfl(base, 0, 64);
+  for (uint32_t k = lane; k < fill; k += 64)
+    if (base + k < g.capacity) g.pairs[base + k] = queue[k];
+  __builtin_amdgcn_wave_barrier();
+  fill = 0;
+}
+
+// one candidate pair per lane (emit: (i, j) is a pair); called by the whole wave
+__device__ __forceinline__ void pair_push(bool emit, uint32_t i, uint32_t j, uint2* queue, uint32_t& fill,
+                                          const GraphOut& g) {
+  const unsigned long long m = __ballot(emit);
+  if (m == 0) return;
+  if (fill + 64u > kPairQueue) pair_flush(queue, fill, g);
+  if (emit) queue[fill + lanes_below(m)] = make_uint2(i, j);
+  fill += (uint32_t)__popcll(m);
+}
 
 }  // namespace dc

@@ -300,47 +300,6 @@ __global__ __launch_bounds__(kGBlock) void nn_generic_kernel(
 //                  component, then one 64-bit atomicMin into best[comp[i]] (a Boruvka round)
 // -----------------------------------------------------------------------------------------
 enum GraphMode { kGraphPairs = 1, kGraphMinEdge = 2 };
-constexpr uint32_t kPairQueue = 256;   // pairs a wave queues before it flushes (uint2 each)
-
-struct GraphOut {
-  uint32_t* pops;
-  uint2* pairs;                  // kGraphPairs: the list, slots < capacity written
-  unsigned long long capacity;
-  unsigned long long* count;     // kGraphPairs: total number of pairs (may exceed capacity)
-  const uint32_t* comp;          // kGraphMinEdge: component id and rank per frame, best per component id
-  const uint32_t* rank;
-  unsigned long long* best;
-};
-
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {   // set bits of m below this lane
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// the wave's queued pairs -> slots [base, base + fill) of the list; fill is wave-uniform
-__device__ __forceinline__ void pair_flush(const uint2* queue, uint32_t& fill, const GraphOut& g) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the queue writes of all lanes before their reads)
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const uint32_t lane = threadIdx.x & 63u;
-  unsigned long long base = 0;
-  if (lane == 0) base = atomicAdd(g.count, (unsigned long long)fill);
-  base = __shfl(base, 0, 64);
-  for (uint32_t k = lane; k < fill; k += 64)
-    if (base + k < g.capacity) g.pairs[base + k] = queue[k];
-  __builtin_amdgcn_wave_barrier();
-  fill = 0;
-}
-
-// one candidate pair per lane (emit: (i, j) is a pair); called by the whole wave
-__device__ __forceinline__ void pair_push(bool emit, uint32_t i, uint32_t j, uint2* queue, uint32_t& fill,
-                                          const GraphOut& g) {
-  const unsigned long long m = __ballot(emit);
-  if (m == 0) return;
-  if (fill + 64u > kPairQueue) pair_flush(queue, fill, g);
-  if (emit) queue[fill + lanes_below(m)] = make_uint2(i, j);
-  fill += (uint32_t)__popcll(m);
-}
-
 template <int D, int Q, int MODE>
 __device__ __forceinline__ void graph_tile(const float* tile, const uint32_t* tile_cr, uint32_t t0, uint32_t nt,
                                            bool emit, float r2, const float (&q)[Q][D], const uint32_t (&qi)[Q],
@@ -692,6 +651,10 @@ bool launch_pop_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, 
                        n_rows, n_cols, i_from, i_to, rad2, n_rad, d_pops, gate);
     return true;
   }
+  if (n_cols > (uint32_t)kMaxColsGeneric) {
+    launch_pop_wide(d_coords, n_rows, n_cols, i_from, i_to, rad2, n_rad, d_pops, gate, stream);
+    return true;
+  }
   return false;
 }
 
@@ -713,12 +676,20 @@ bool launch_nn_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, c
                        n_rows, n_cols, d_fe, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, gate);
     return true;
   }
+  if (n_cols > (uint32_t)kMaxColsGeneric) {
+    launch_nn_wide(d_coords, n_rows, n_cols, d_fe, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, gate, stream);
+    return true;
+  }
   return false;
 }
 
 bool launch_pairs_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops,
                          uint2* d_pairs, unsigned long long capacity, unsigned long long* d_count,
                          const uint32_t* gate, hipStream_t stream) {
+  if (n_cols > (uint32_t)kMaxColsGeneric) {
+    launch_pairs_wide(d_coords, n_rows, n_cols, r2, d_pops, d_pairs, capacity, d_count, gate, stream);
+    return true;
+  }
   const GraphOut g{d_pops, d_pairs, d_pairs ? capacity : 0ull, d_count, nullptr, nullptr, nullptr};
   return launch_graph<kGraphPairs>(d_coords, n_rows, n_cols, 0, n_rows, r2, g, gate, stream);
 }
@@ -727,6 +698,10 @@ bool launch_min_edge_direct(const float* d_coords, uint32_t n_rows, uint32_t n_c
                             const uint32_t* d_comp, const uint32_t* d_rank, uint32_t i_from, uint32_t i_to,
                             unsigned long long* d_best, uint32_t* d_pops, const uint32_t* gate,
                             hipStream_t stream) {
+  if (n_cols > (uint32_t)kMaxColsGeneric) {
+    launch_min_edge_wide(d_coords, n_rows, n_cols, r2, d_comp, d_rank, i_from, i_to, d_best, d_pops, gate, stream);
+    return true;
+  }
   const GraphOut g{d_pops, nullptr, 0ull, nullptr, d_comp, d_rank, d_best};
   return launch_graph<kGraphMinEdge>(d_coords, n_rows, n_cols, i_from, i_to, r2, g, gate, stream);
 }

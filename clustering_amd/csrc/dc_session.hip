@@ -314,8 +314,7 @@ int dc_hip_session_open(const float* coords, size_t n_rows, size_t n_cols, const
   *out = nullptr;
   if (!coords && n_rows) return failf(DC_ERR_INVALID_ARGUMENT, "null coords");
   if (n_cols == 0) return failf(DC_ERR_INVALID_ARGUMENT, "n_cols must be >= 1");
-  if (n_cols > (size_t)dc::kMaxColsGeneric)
-    return failf(DC_ERR_INVALID_ARGUMENT, "n_cols=%zu not supported (max %d)", n_cols, dc::kMaxColsGeneric);
+  if (n_cols > dc::kMaxColsAny) return failf(DC_ERR_TOO_LARGE, "n_cols=%zu: at most %zu columns", n_cols, dc::kMaxColsAny);
   if (n_rows + 1 > (size_t)UINT32_MAX) return failf(DC_ERR_TOO_LARGE, "n_rows=%zu: frame ids must fit uint32", n_rows);
   const int avail = dc_hip_device_count();
   if (avail < 0) return avail;

@@ -239,7 +239,7 @@ def last_sweep_ms(kind, device):
 def radius_pairs(coords, r2, capacity=None):
     """All unordered frame pairs with canonical d2 < r2 (the radius graph of the reference's screening,
     density_clustering.cpp:292-332) -> (pairs int64 [n_pairs, 2] on the device, pops int32 [n_rows]).
-    One counting sweep sizes the buffer unless a capacity is given.  Any n_cols up to 400; rows with inf / NaN
+    One counting sweep sizes the buffer unless a capacity is given.  Any n_cols; rows with inf / NaN
     have no partners (population 1), like in the reference."""
     n_rows, n_cols = _check_coords(coords)
     dev = coords.device
@@ -268,7 +268,7 @@ def radius_min_edge(coords, r2, comp, rank, segment=0, n_segments=0):
     """One Boruvka round on the radius graph (dc_hip_radius_min_edge[_segment]_dev): comp, rank int32
     CUDA [n_rows] -> (best int64 [n_rows]: (max rank << 32 | min rank) of the lightest pair leaving
     component id, -1 (all ones) if none; pops int32 [n_rows]).  n_segments > 0: what the queries of one
-    segment of a sharded run see (partials merge by unsigned minimum / summation).  Any n_cols up to 400 and
+    segment of a sharded run see (partials merge by unsigned minimum / summation).  Any n_cols and
     non-finite coordinates, like radius_pairs."""
     n_rows, n_cols = _check_coords(coords)
     dev = coords.device
@@ -288,7 +288,7 @@ def radius_min_edge(coords, r2, comp, rank, segment=0, n_segments=0):
 def radius_forest(coords_host, r2, rank, device=0):
     """Bottleneck spanning forest of the radius graph (dc_hip_radius_forest).  coords_host: float32
     numpy [n_rows, n_cols]; rank: permutation of 0..n_rows-1 -> (edges uint32 numpy [n_edges, 2] of
-    frame ids, number of sweeps).  Any n_cols up to 400 and non-finite coordinates, like radius_pairs."""
+    frame ids, number of sweeps).  Any n_cols and non-finite coordinates, like radius_pairs."""
     coords_host = np.ascontiguousarray(coords_host, dtype=np.float32)
     n_rows, n_cols = coords_host.shape
     rank = np.ascontiguousarray(rank, dtype=np.uint32)

@@ -55,7 +55,7 @@ typedef enum dc_status {
   DC_ERR_INVALID_ARGUMENT = -1,
   DC_ERR_NO_DEVICE = -2,      /* reference: "no CUDA-compatible GPUs found", cuda.cu:37-40 */
   DC_ERR_HIP = -3,            /* a HIP runtime call failed; see dc_hip_last_error() */
-  DC_ERR_TOO_LARGE = -4,      /* n_rows + 1 does not fit the uint32 index type */
+  DC_ERR_TOO_LARGE = -4,      /* n_rows + 1 does not fit the uint32 index type, or n_cols > 2^32 - 65 */
   DC_ERR_WORKSPACE = -5       /* workspace missing or too small */
 } dc_status;
 
@@ -269,7 +269,7 @@ DC_API int dc_hip_sigma2_dev(const float* d_nn_d2, size_t n_rows, double* sigma2
  * of high_density_neighborhood (density_clustering.cpp:292-332, called per frame from
  * density_clustering_common.cpp:97-121; CUDA: density_clustering_cuda.cu:396-594) by ONE sweep that
  * lists every unordered frame pair {i, j}, i != j, whose canonical d2 is < r2 (strict, :319).  The
- * pruned matrix-core sweep for n_cols <= 64; an exact direct sweep over all pairs for n_cols 65..400
+ * pruned matrix-core sweep for n_cols <= 64; an exact direct sweep over all pairs for any wider rows
  * and for coordinates that are not finite (inf / NaN in a row: no partners, population 1, as in the
  * reference), chosen on the device like the populations' fallback.
  *   r2       the squared distance itself (the reference passes max_dist = 4*sigma2, a float)
@@ -294,7 +294,7 @@ DC_API int dc_hip_radius_pairs_dev(const float* d_coords, size_t n_rows, size_t 
  *            canonical d2 < r2 that joins component id to another one, ~0 if there is none
  *   d_pops   [n_rows] uint32 device, out: populations at that radius
  * Needs n_rows <= 2^24, and a workspace as above for n_cols <= 64 (none for n_cols > 64).  Any column
- * count up to 400 and coordinates that are not finite are served (the direct sweep, as for the pairs). */
+ * count and coordinates that are not finite are served (the direct sweep, as for the pairs). */
 DC_API int dc_hip_radius_min_edge_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
                                       const uint32_t* d_comp, const uint32_t* d_rank,
                                       unsigned long long* d_best, uint32_t* d_pops, void* d_workspace,
