@@ -321,7 +321,9 @@ DC_API int dc_hip_populations(const float* coords, size_t n_rows, size_t n_cols,
                               size_t n_radii, size_t i_from, size_t i_to, int device, uint32_t* pops);
 
 /* replaces nearest_neighbors_per_gpu(coords, n_rows, n_cols, free_energy, i_from, i_to, i_gpu)
- * (density_clustering_cuda.cu:184-191).  All outputs HOST [n_rows]. */
+ * (density_clustering_cuda.cu:184-191).  All outputs HOST [n_rows].  Free energies may be any floats: "lower" is
+ * the IEEE comparison fe[j] < fe[i], so a NaN is never lower and a NaN frame has no lower neighbour, and -0.0 is not
+ * lower than +0.0. */
 DC_API int dc_hip_nearest_neighbors(const float* coords, size_t n_rows, size_t n_cols, const float* fe,
                                     size_t i_from, size_t i_to, int device, uint32_t* nn_idx,
                                     float* nn_d2, uint32_t* hd_idx, float* hd_d2);
@@ -400,7 +402,8 @@ DC_API int dc_hip_session_populations(dc_hip_session* session, const float* radi
 DC_API int dc_hip_session_free_energies(dc_hip_session* session, size_t radius_index, float* fe,
                                         uint32_t* max_pop);
 /* free energies from the caller instead (-D re-use, density_clustering.cpp:600-611; and the reference's
- * nearest_neighbors(coords, ..., free_energy) signature).  fe: HOST [n_rows]. */
+ * nearest_neighbors(coords, ..., free_energy) signature).  fe: HOST [n_rows], any floats, compared as
+ * dc_hip_nearest_neighbors does (IEEE fe[j] < fe[i]: NaN is never lower, -0.0 not lower than +0.0). */
 DC_API int dc_hip_session_set_free_energies(dc_hip_session* session, const float* fe);
 /* CUDA::nearest_neighbors (density_clustering_cuda.cu:286-328) from the resident free energies, and
  * compute_sigma2 (density_clustering.cpp:334-343: double sum in frame order).  All outputs HOST

@@ -42,6 +42,10 @@ def fmt_g(x):
     return "%g" % float(np.float32(x))
 
 
+def bits_of(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
 def test_cli_single_radius_full_path(tmp_path, oracle):
     c = write_coords(tmp_path / "coords", gaussian_blobs(3000, 5, seed=42))
     r = subprocess.run([CLI, "density", "-f", str(tmp_path / "coords"), "-r", "0.1", "-p", str(tmp_path / "pop"),
@@ -342,3 +346,27 @@ def test_cli_refuses_malformed_coordinate_files(tmp_path):
                        capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     assert data_lines(tmp_path / "pop") == ["2", "3", "2"]     # d2 = 8, 8, 32 against r2 = 9
+
+
+def test_cli_free_energy_input_of_any_origin(tmp_path, oracle):
+    """-D with a hand-written file (not one this program wrote): negative values, exponent notation of either case, 9
+    significant digits, a leading '+', exact ties.  The -b output equals the oracle run on the float32 values the file
+    parses to."""
+    c = write_coords(tmp_path / "coords", gaussian_blobs(1500, 5, seed=46))
+    rng = np.random.default_rng(46)
+    fe = (rng.normal(0.0, 1.0, len(c)) * 10.0 ** rng.integers(-3, 4, len(c))).astype(np.float32)
+    fe[rng.integers(0, len(c), 100)] = fe[rng.integers(0, len(c), 100)]          # ties
+    fe[:4] = [-0.0, 0.0, -1.5e-7, 12345.6789]
+    fmts = ["%.9g", "%.8e", "%.8E", "%+.8e"]
+    with open(tmp_path / "fe_in", "w") as f:
+        f.write("# hand-written free energies\n")
+        for i, v in enumerate(fe):
+            f.write(fmts[i % 4] % float(v) + "\n")
+    parsed = np.array([float(l) for l in data_lines(tmp_path / "fe_in")], dtype=np.float64).astype(np.float32)
+    assert (parsed < 0).sum() > 500 and (bits_of(parsed) == bits_of(fe)).all()   # (9 digits: every float32 round-trips)
+    r = subprocess.run([CLI, "density", "-f", str(tmp_path / "coords"), "-D", str(tmp_path / "fe_in"),
+                        "-b", str(tmp_path / "nn")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    nn = oracle.nearest_neighbors(c, parsed)
+    want = ["%d %s %d %s" % (nn[0][i], fmt_g(nn[1][i]), nn[2][i], fmt_g(nn[3][i])) for i in range(len(c))]
+    assert data_lines(tmp_path / "nn") == want

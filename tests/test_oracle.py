@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import fe_families
 import refmath
 from clustering_amd.synth import gaussian_blobs
 
@@ -231,3 +232,29 @@ def test_screening_restatement_known_answers(oracle):
     micro = so.assign_low_density(first, nn[2], fe)
     assert list(micro) == [1, 1, 1, 2, 2, 2]
     assert list(so.sorted_names(np.array([7, 7, 7, 3, 3, 9], dtype=np.uint64))) == [1, 1, 1, 2, 2, 3]
+
+
+@pytest.mark.parametrize("family", sorted(fe_families.FAMILIES))
+@pytest.mark.parametrize("n_rows,D", [(300, 3), (257, 10), (64, 30), (33, 2), (2, 5), (1, 4)])
+def test_oracle_vs_numpy_emulation_free_energies_of_any_origin(oracle, family, n_rows, D):
+    """The referee of tests/test_gpu_free_energy_inputs.py on exactly its inputs: free energies that do not come from
+    populations (tests/fe_families.py: continuous, ties one ulp apart, +-0, spans that overflow, subnormals, +-inf,
+    NaN, ...).  fe[j] < fe[i] is an IEEE comparison in both: NaN is never lower and a NaN frame has no lower neighbour,
+    -0.0 is not lower than +0.0.  Indices equal, d2 bit-equal."""
+    c = gaussian_blobs(n_rows, D, seed=900 + n_rows + D)
+    if n_rows >= 64:
+        c[5] = c[17]                 # an exact tie in d2
+    pops = refmath.populations(c, [0.2 if D <= 10 else 0.08 * np.sqrt(2.0 * D)])[0]
+    fe = fe_families.make(family, c, pops, seed=D)
+    got = oracle.nearest_neighbors(c, fe)
+    exp = refmath.nearest_neighbors(c, fe)
+    assert (got[0] == exp[0]).all() and (got[2] == exp[2]).all()
+    assert (bits(got[1]) == bits(exp[1])).all() and (bits(got[3]) == bits(exp[3])).all()
+    if family == "nan":
+        assert (got[2][np.isnan(fe)] == n_rows + 1).all() and (bits(got[3][np.isnan(fe)]) == bits(FLT_MAX)).all()
+        assert not np.isnan(fe[got[2][got[2] <= n_rows].astype(np.int64)]).any()
+    if family in ("constant", "constant_3_5"):
+        assert (got[2] == n_rows + 1).all()
+    if family == "signed_zero":
+        hd = got[2] <= n_rows
+        assert (fe[got[2][hd].astype(np.int64)] < fe[hd]).all()   # (a -0.0 frame is never the lower neighbour of +0.0)
