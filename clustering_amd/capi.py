@@ -39,6 +39,8 @@ SYMBOLS = (
     "dc_hip_session_counters", "dc_hip_session_populations", "dc_hip_session_free_energies",
     "dc_hip_session_set_free_energies", "dc_hip_session_nearest_neighbors", "dc_hip_session_radius_pairs",
     "dc_hip_session_radius_forest",
+    "dc_hip_cross_workspace_bytes", "dc_hip_populations_cross_dev", "dc_hip_nearest_neighbors_cross_dev",
+    "dc_hip_free_energies_scaled_dev", "dc_hip_populations_cross", "dc_hip_nearest_neighbors_cross",
 )
 
 
@@ -153,6 +155,20 @@ def _load():
     lib.dc_hip_session_radius_pairs.argtypes = [vp, C.c_float, vp, sz, C.POINTER(C.c_uint64)]
     lib.dc_hip_session_radius_forest.restype = i32
     lib.dc_hip_session_radius_forest.argtypes = [vp, C.c_float, vp, vp, C.POINTER(sz), C.POINTER(C.c_uint32)]
+    lib.dc_hip_cross_workspace_bytes.restype = sz
+    lib.dc_hip_cross_workspace_bytes.argtypes = [sz, sz, sz]
+    lib.dc_hip_populations_cross_dev.restype = i32
+    lib.dc_hip_populations_cross_dev.argtypes = [vp, sz, vp, sz, sz, C.POINTER(C.c_float), sz, sz, sz, vp, vp, sz,
+                                                 i32, vp]
+    lib.dc_hip_nearest_neighbors_cross_dev.restype = i32
+    lib.dc_hip_nearest_neighbors_cross_dev.argtypes = [vp, sz, vp, sz, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz,
+                                                       i32, vp]
+    lib.dc_hip_free_energies_scaled_dev.restype = i32
+    lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
+    lib.dc_hip_populations_cross.restype = i32
+    lib.dc_hip_populations_cross.argtypes = [vp, sz, vp, sz, sz, vp, sz, sz, sz, i32, vp]
+    lib.dc_hip_nearest_neighbors_cross.restype = i32
+    lib.dc_hip_nearest_neighbors_cross.argtypes = [vp, sz, vp, sz, sz, vp, vp, sz, sz, i32, vp, vp, vp, vp]
     return lib
 
 

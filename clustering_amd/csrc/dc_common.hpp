@@ -48,6 +48,17 @@ bool launch_min_edge_direct(const float* d_coords, uint32_t n_rows, uint32_t n_c
                             unsigned long long* d_best, uint32_t* d_pops, const uint32_t* gate,
                             hipStream_t stream);
 
+// cross sweeps (dc_hip_*_cross_dev): query rows [i_from, i_to) of d_query [n_q][n_cols] against all n_ref rows of d_ref,
+// any n_cols >= 1.  pops [n_rad][n_q] (radius-major, this launch's radii); no self term.  nn / hd: "none" = (n_ref + 1,
+// FLT_MAX); d_fe_q == nullptr: nn only (d_fe_r, d_hd_* unused).  gate as above.
+void launch_pop_cross_direct(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
+                             uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops,
+                             const uint32_t* gate, hipStream_t stream);
+void launch_nn_cross_direct(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                            const float* d_fe_q, const float* d_fe_r, uint32_t i_from, uint32_t i_to,
+                            uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
+                            const uint32_t* gate, hipStream_t stream);
+
 // ---- launchers implemented in dc_wide.hip: the same products for n_cols > kMaxColsGeneric, with the columns streamed
 // through LDS in chunks (no upper limit on n_cols).  launch_*_direct hand such rows to them.
 void launch_pop_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
@@ -58,6 +69,12 @@ void launch_nn_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, con
 void launch_pairs_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops,
                        uint2* d_pairs, unsigned long long capacity, unsigned long long* d_count, const uint32_t* gate,
                        hipStream_t stream);
+void launch_pop_cross_wide(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
+                           uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops,
+                           const uint32_t* gate, hipStream_t stream);
+void launch_nn_cross_wide(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols, const float* d_fe_q,
+                          const float* d_fe_r, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+                          uint32_t* d_hd_idx, float* d_hd_d2, const uint32_t* gate, hipStream_t stream);
 void launch_min_edge_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, const uint32_t* d_comp,
                           const uint32_t* d_rank, uint32_t i_from, uint32_t i_to, unsigned long long* d_best,
                           uint32_t* d_pops, const uint32_t* gate, hipStream_t stream);
@@ -66,6 +83,9 @@ void launch_min_edge_wide(const float* d_coords, uint32_t n_rows, uint32_t n_col
 void launch_nn_init(uint32_t n_rows, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                     float* d_hd_d2, hipStream_t stream);
 
+// cross sweeps: idx = n_ref + 1, d2 = FLT_MAX for all n_q rows (d_hd_idx == nullptr: nn only)
+void launch_nn_init_cross(uint32_t n_q, uint32_t n_ref, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                          float* d_hd_d2, hipStream_t stream);
 // fe[i] = table[pops[i]]
 void launch_fe_gather(const uint32_t* d_pops, uint32_t n_rows, const float* d_table, float* d_fe,
                       hipStream_t stream);
@@ -78,8 +98,10 @@ void launch_nn_unpack(const unsigned long long* d_words, uint32_t n_rows, uint32
                       uint32_t* d_hd_idx, float* d_hd_d2, hipStream_t stream);
 // fe of every row with the device's double log; rows whose value sits within 64 ulp(double) of a float
 // rounding boundary go to d_flag_list as (row, pop) pairs (d_flag_count may exceed flag_cap)
+// fixed_max != 0: the maximum the free energies are scaled by, instead of max(pops)
 void launch_fe_log(const uint32_t* d_pops, uint32_t n_rows, uint32_t* d_state, uint32_t slot, float* d_fe,
-                   uint32_t* d_flag_list, uint32_t flag_cap, double tol_rel, hipStream_t stream);
+                   uint32_t* d_flag_list, uint32_t flag_cap, double tol_rel, hipStream_t stream,
+                   uint32_t fixed_max = 0);
 constexpr uint32_t kFeStateWords = 8;   // device state of the free-energy pass in front of its list of flagged rows
 
 // ---- canonical squared distance ------------------------------------------------------------------------------------

@@ -289,6 +289,182 @@ __global__ __launch_bounds__(kGBlock) void nn_generic_kernel(
 }
 
 // -----------------------------------------------------------------------------------------
+// cross sweeps: query rows of one array against every row of another (dc_hip_*_cross_dev).  The
+// shapes and the arithmetic of the kernels above; no pair is left out and nothing is added:
+//   pops[r][q] = #{ j < n_ref : d2(Q_q, R_j) < rad2[r] }
+//   nn[q]      = lexicographic min of (d2, j) over all j;  hd[q]: the same over fe_r[j] < fe_q[q]
+// "none" is (n_ref + 1, FLT_MAX).  fe_q == nullptr: neighbours only (hd is not written).
+// -----------------------------------------------------------------------------------------
+template <int D, int NR>
+__global__ __launch_bounds__(kBlock) void pop_cross_direct_kernel(
+    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_q, uint32_t n_ref,
+    uint32_t i_from, uint32_t i_to, Rad2 rad2, int n_rad, uint32_t* __restrict__ pops,
+    const uint32_t* __restrict__ gate) {
+  constexpr int S = Cfg<D>::S, Q = Cfg<D>::Q;
+  if (gate && gate[1] == 0) return;
+  __shared__ __attribute__((aligned(16))) float tile[kTile * S];
+  const uint32_t qbase = i_from + blockIdx.x * (kBlock * Q);
+  float q[Q][D];
+  uint32_t qi[Q], cnt[Q][NR];
+#pragma unroll
+  for (int a = 0; a < Q; ++a) {
+    qi[a] = qbase + a * kBlock + threadIdx.x;
+    const uint32_t row = qi[a] < i_to ? qi[a] : i_to - 1;   // clamp: result discarded
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[a][k] = qcoords[(size_t)row * D + k];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) cnt[a][r] = 0;
+  }
+  for (uint32_t t0 = 0; t0 < n_ref; t0 += kTile) {
+    const uint32_t nt = min((uint32_t)kTile, n_ref - t0);
+    __syncthreads();
+    stage_tile<D>(rcoords, t0, nt, tile);
+    __syncthreads();
+#pragma unroll 2
+    for (uint32_t r = 0; r < nt; ++r) {
+      float ref[D];
+      load_ref<D>(tile, r, ref);
+#pragma unroll
+      for (int a = 0; a < Q; ++a) {
+        const float d = dist2_canon<D>(q[a], ref);
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) cnt[a][rr] += (d < rad2.v[rr]) ? 1u : 0u;
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < Q; ++a)
+    if (qi[a] < i_to) {
+#pragma unroll
+      for (int rr = 0; rr < NR; ++rr)
+        if (rr < n_rad) pops[(size_t)rr * n_q + qi[a]] = cnt[a][rr];
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void nn_cross_direct_kernel(
+    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_ref,
+    const float* __restrict__ fe_q, const float* __restrict__ fe_r, uint32_t i_from, uint32_t i_to,
+    uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx,
+    float* __restrict__ hd_d2, const uint32_t* __restrict__ gate) {
+  constexpr int S = Cfg<D>::S, Q = Cfg<D>::Q;
+  if (gate && gate[1] == 0) return;
+  __shared__ __attribute__((aligned(16))) float tile[kTile * S];
+  __shared__ float tile_fe[kTile];
+  const uint32_t qbase = i_from + blockIdx.x * (kBlock * Q);
+  float q[Q][D], qfe[Q], best[Q], bhd[Q];
+  uint32_t qi[Q], bj[Q], bjhd[Q];
+#pragma unroll
+  for (int a = 0; a < Q; ++a) {
+    qi[a] = qbase + a * kBlock + threadIdx.x;
+    const uint32_t row = qi[a] < i_to ? qi[a] : i_to - 1;
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[a][k] = qcoords[(size_t)row * D + k];
+    qfe[a] = fe_q ? fe_q[row] : -INFINITY;   // (no free energies: nothing is lower)
+    best[a] = FLT_MAX;
+    bhd[a] = FLT_MAX;
+    bj[a] = n_ref + 1;
+    bjhd[a] = n_ref + 1;
+  }
+  const uint32_t no_qi[Q] = {};   // (nn_tile without its diagonal test never reads them)
+  for (uint32_t t0 = 0; t0 < n_ref; t0 += kTile) {
+    const uint32_t nt = min((uint32_t)kTile, n_ref - t0);
+    __syncthreads();
+    stage_tile<D>(rcoords, t0, nt, tile);
+    if (threadIdx.x < nt) tile_fe[threadIdx.x] = fe_q ? fe_r[t0 + threadIdx.x] : 0.0f;
+    __syncthreads();
+    nn_tile<D, Q, false>(tile, tile_fe, t0, nt, q, no_qi, qfe, best, bj, bhd, bjhd);
+  }
+#pragma unroll
+  for (int a = 0; a < Q; ++a) {
+    if (qi[a] < i_to) {
+      nn_idx[qi[a]] = bj[a];
+      nn_d2[qi[a]] = best[a];
+      if (fe_q) {
+        hd_idx[qi[a]] = bjhd[a];
+        hd_d2[qi[a]] = bhd[a];
+      }
+    }
+  }
+}
+
+// generic n_cols (33..kMaxColsGeneric): the LDS layout of pop_generic_kernel / nn_generic_kernel
+__global__ __launch_bounds__(kGBlock) void pop_cross_generic_kernel(
+    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_q, uint32_t n_ref,
+    uint32_t D, uint32_t i_from, uint32_t i_to, Rad2 rad2, int n_rad, uint32_t* __restrict__ pops,
+    const uint32_t* __restrict__ gate) {
+  if (gate && gate[1] == 0) return;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* qs = smem;                          // [D][kGBlock]
+  float* tile = smem + (size_t)D * kGBlock;  // [kGTile][D]
+  const uint32_t qi = i_from + blockIdx.x * kGBlock + threadIdx.x;
+  const uint32_t row = qi < i_to ? qi : i_to - 1;
+  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = qcoords[(size_t)row * D + k];
+  uint32_t cnt[kMaxRadiiPerLaunch];
+#pragma unroll
+  for (int r = 0; r < kMaxRadiiPerLaunch; ++r) cnt[r] = 0;
+  for (uint32_t t0 = 0; t0 < n_ref; t0 += kGTile) {
+    const uint32_t nt = min((uint32_t)kGTile, n_ref - t0);
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = rcoords[(size_t)t0 * D + e];
+    __syncthreads();
+    for (uint32_t r = 0; r < nt; ++r) {
+      const float d = dist2_canon_rt(qs + threadIdx.x, kGBlock, tile + r * D, 1, (int)D);
+#pragma unroll
+      for (int rr = 0; rr < kMaxRadiiPerLaunch; ++rr) cnt[rr] += (d < rad2.v[rr]) ? 1u : 0u;
+    }
+  }
+  if (qi < i_to) {
+#pragma unroll
+    for (int rr = 0; rr < kMaxRadiiPerLaunch; ++rr)
+      if (rr < n_rad) pops[(size_t)rr * n_q + qi] = cnt[rr];
+  }
+}
+
+__global__ __launch_bounds__(kGBlock) void nn_cross_generic_kernel(
+    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_ref, uint32_t D,
+    const float* __restrict__ fe_q, const float* __restrict__ fe_r, uint32_t i_from, uint32_t i_to,
+    uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx,
+    float* __restrict__ hd_d2, const uint32_t* __restrict__ gate) {
+  if (gate && gate[1] == 0) return;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* qs = smem;
+  float* tile = smem + (size_t)D * kGBlock;
+  float* tile_fe = tile + (size_t)kGTile * D;
+  const uint32_t qi = i_from + blockIdx.x * kGBlock + threadIdx.x;
+  const uint32_t row = qi < i_to ? qi : i_to - 1;
+  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = qcoords[(size_t)row * D + k];
+  const float qfe = fe_q ? fe_q[row] : -INFINITY;
+  float best = FLT_MAX, bhd = FLT_MAX;
+  uint32_t bj = n_ref + 1, bjhd = n_ref + 1;
+  for (uint32_t t0 = 0; t0 < n_ref; t0 += kGTile) {
+    const uint32_t nt = min((uint32_t)kGTile, n_ref - t0);
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = rcoords[(size_t)t0 * D + e];
+    if (threadIdx.x < nt) tile_fe[threadIdx.x] = fe_q ? fe_r[t0 + threadIdx.x] : 0.0f;
+    __syncthreads();
+    for (uint32_t r = 0; r < nt; ++r) {
+      const uint32_t j = t0 + r;
+      const float d = dist2_canon_rt(qs + threadIdx.x, kGBlock, tile + r * D, 1, (int)D);
+      const bool lt = d < best;
+      const bool lh = (tile_fe[r] < qfe) && (d < bhd);
+      best = lt ? d : best;
+      bj = lt ? j : bj;
+      bhd = lh ? d : bhd;
+      bjhd = lh ? j : bjhd;
+    }
+  }
+  if (qi < i_to) {
+    nn_idx[qi] = bj;
+    nn_d2[qi] = best;
+    if (fe_q) {
+      hd_idx[qi] = bjhd;
+      hd_d2[qi] = bhd;
+    }
+  }
+}
+
+// -----------------------------------------------------------------------------------------
 // radius graph (canonical d2 < r2, the graph of the reference's screening, density_clustering.cpp:
 // 292-332) for every n_cols the sweeps above accept: the two products of the matrix-core sweep's
 // sinks (dc_mfma.hpp EdgeSink), for n_cols > 64 and for data the operand-image pass flagged.
@@ -458,6 +634,20 @@ __global__ void nn_init_kernel(uint32_t n_rows, uint32_t* nn_idx, float* nn_d2, 
   }
 }
 
+// cross sweeps: every query row starts at "none" = (n_ref + 1, FLT_MAX); hd may be absent (nn only)
+__global__ void nn_init_cross_kernel(uint32_t n_q, uint32_t none, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx,
+                                     float* hd_d2) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_q) {
+    nn_idx[i] = none;
+    nn_d2[i] = FLT_MAX;
+    if (hd_idx) {
+      hd_idx[i] = none;
+      hd_d2[i] = FLT_MAX;
+    }
+  }
+}
+
 __global__ void fe_gather_kernel(const uint32_t* __restrict__ pops, uint32_t n_rows,
                                  const float* __restrict__ table, float* __restrict__ fe) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -587,6 +777,44 @@ const auto kPop4 = make_pop_table<4>(DSeq{});
 const auto kPop8 = make_pop_table<8>(DSeq{});
 const auto kNn = make_nn_table(DSeq{});
 
+using PopCrossLaunch = void (*)(const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, const Rad2&, int,
+                                uint32_t*, const uint32_t*, hipStream_t);
+using NnCrossLaunch = void (*)(const float*, const float*, uint32_t, const float*, const float*, uint32_t, uint32_t,
+                               uint32_t*, float*, uint32_t*, float*, const uint32_t*, hipStream_t);
+
+template <int D, int NR>
+void pop_cross_launch(const float* qc, const float* rc, uint32_t n_q, uint32_t n_ref, uint32_t i_from, uint32_t i_to,
+                      const Rad2& rad2, int n_rad, uint32_t* pops, const uint32_t* gate, hipStream_t s) {
+  const uint32_t per_block = kBlock * Cfg<D>::Q;
+  const uint32_t grid = (i_to - i_from + per_block - 1) / per_block;
+  hipLaunchKernelGGL((pop_cross_direct_kernel<D, NR>), dim3(grid), dim3(kBlock), 0, s, qc, rc, n_q, n_ref, i_from, i_to,
+                     rad2, n_rad, pops, gate);
+}
+
+template <int D>
+void nn_cross_launch(const float* qc, const float* rc, uint32_t n_ref, const float* fe_q, const float* fe_r,
+                     uint32_t i_from, uint32_t i_to, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2,
+                     const uint32_t* gate, hipStream_t s) {
+  const uint32_t per_block = kBlock * Cfg<D>::Q;
+  const uint32_t grid = (i_to - i_from + per_block - 1) / per_block;
+  hipLaunchKernelGGL((nn_cross_direct_kernel<D>), dim3(grid), dim3(kBlock), 0, s, qc, rc, n_ref, fe_q, fe_r, i_from,
+                     i_to, nn_idx, nn_d2, hd_idx, hd_d2, gate);
+}
+
+template <int NR, int... Ds>
+constexpr auto make_pop_cross_table(std::integer_sequence<int, Ds...>) {
+  return std::array<PopCrossLaunch, sizeof...(Ds)>{&pop_cross_launch<Ds + 1, NR>...};
+}
+template <int... Ds>
+constexpr auto make_nn_cross_table(std::integer_sequence<int, Ds...>) {
+  return std::array<NnCrossLaunch, sizeof...(Ds)>{&nn_cross_launch<Ds + 1>...};
+}
+
+const auto kPopCross1 = make_pop_cross_table<1>(DSeq{});
+const auto kPopCross4 = make_pop_cross_table<4>(DSeq{});
+const auto kPopCross8 = make_pop_cross_table<8>(DSeq{});
+const auto kNnCross = make_nn_cross_table(DSeq{});
+
 using GraphLaunch = void (*)(const float*, uint32_t, uint32_t, uint32_t, float, const GraphOut&, const uint32_t*,
                              hipStream_t);
 
@@ -683,6 +911,46 @@ bool launch_nn_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, c
   return false;
 }
 
+void launch_pop_cross_direct(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
+                             uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops,
+                             const uint32_t* gate, hipStream_t stream) {
+  if (i_to <= i_from || n_rad <= 0 || n_ref == 0) return;
+  if (n_cols <= (uint32_t)kMaxColsTemplated) {
+    const auto& tab = (n_rad == 1) ? kPopCross1 : (n_rad <= 4 ? kPopCross4 : kPopCross8);
+    tab[n_cols - 1](d_query, d_ref, n_q, n_ref, i_from, i_to, rad2, n_rad, d_pops, gate, stream);
+  } else if (n_cols <= (uint32_t)kMaxColsGeneric) {
+    const uint32_t grid = (i_to - i_from + kGBlock - 1) / kGBlock;
+    const size_t smem = sizeof(float) * (size_t)n_cols * (kGBlock + kGTile);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pop_cross_generic_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(pop_cross_generic_kernel, dim3(grid), dim3(kGBlock), smem, stream, d_query, d_ref, n_q, n_ref,
+                       n_cols, i_from, i_to, rad2, n_rad, d_pops, gate);
+  } else {
+    launch_pop_cross_wide(d_query, d_ref, n_q, n_ref, n_cols, i_from, i_to, rad2, n_rad, d_pops, gate, stream);
+  }
+}
+
+void launch_nn_cross_direct(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                            const float* d_fe_q, const float* d_fe_r, uint32_t i_from, uint32_t i_to,
+                            uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
+                            const uint32_t* gate, hipStream_t stream) {
+  if (i_to <= i_from || n_ref == 0) return;
+  if (n_cols <= (uint32_t)kMaxColsTemplated) {
+    kNnCross[n_cols - 1](d_query, d_ref, n_ref, d_fe_q, d_fe_r, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2,
+                         gate, stream);
+  } else if (n_cols <= (uint32_t)kMaxColsGeneric) {
+    const uint32_t grid = (i_to - i_from + kGBlock - 1) / kGBlock;
+    const size_t smem = sizeof(float) * ((size_t)n_cols * (kGBlock + kGTile) + kGTile);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nn_cross_generic_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(nn_cross_generic_kernel, dim3(grid), dim3(kGBlock), smem, stream, d_query, d_ref, n_ref, n_cols,
+                       d_fe_q, d_fe_r, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, gate);
+  } else {
+    launch_nn_cross_wide(d_query, d_ref, n_ref, n_cols, d_fe_q, d_fe_r, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx,
+                         d_hd_d2, gate, stream);
+  }
+}
+
 bool launch_pairs_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops,
                          uint2* d_pairs, unsigned long long capacity, unsigned long long* d_count,
                          const uint32_t* gate, hipStream_t stream) {
@@ -713,6 +981,13 @@ void launch_nn_init(uint32_t n_rows, uint32_t* d_nn_idx, float* d_nn_d2, uint32_
                      d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
 }
 
+void launch_nn_init_cross(uint32_t n_q, uint32_t n_ref, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                          float* d_hd_d2, hipStream_t stream) {
+  if (n_q == 0) return;
+  hipLaunchKernelGGL(nn_init_cross_kernel, dim3((n_q + 255) / 256), dim3(256), 0, stream, n_q, n_ref + 1, d_nn_idx,
+                     d_nn_d2, d_hd_idx, d_hd_d2);
+}
+
 void launch_fe_gather(const uint32_t* d_pops, uint32_t n_rows, const float* d_table, float* d_fe,
                       hipStream_t stream) {
   if (n_rows == 0) return;
@@ -722,10 +997,13 @@ void launch_fe_gather(const uint32_t* d_pops, uint32_t n_rows, const float* d_ta
 
 // (the call's slot of the state is zero on entry: see fe_log_kernel)
 void launch_fe_log(const uint32_t* d_pops, uint32_t n_rows, uint32_t* d_state, uint32_t slot, float* d_fe, uint32_t* d_flag_list,
-                   uint32_t flag_cap, double tol_rel, hipStream_t stream) {
+                   uint32_t flag_cap, double tol_rel, hipStream_t stream, uint32_t fixed_max) {
   if (n_rows == 0) return;
   const uint32_t grid = min((n_rows + 1023u) / 1024u, 256u);
-  hipLaunchKernelGGL(max_u32_kernel, dim3(grid), dim3(256), 0, stream, d_pops, n_rows, d_state + 2u * slot);
+  if (fixed_max)   // (the scale of another population array: dc_hip_free_energies_scaled_dev)
+    (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_state + 2u * slot), (int)fixed_max, 1, stream);
+  else
+    hipLaunchKernelGGL(max_u32_kernel, dim3(grid), dim3(256), 0, stream, d_pops, n_rows, d_state + 2u * slot);
   hipLaunchKernelGGL(fe_log_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, stream, d_pops, n_rows, d_state, slot, d_fe,
                      (uint2*)d_flag_list, flag_cap, tol_rel);
 }

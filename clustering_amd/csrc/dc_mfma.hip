@@ -373,6 +373,26 @@ __global__ void fe_rank_kernel(const float* __restrict__ fe, const float* __rest
 }
 
 
+// cross sweeps: pq[q] = #{ p < n_ref : fe_s[p] < fe_q[q] } -- fe_rank_kernel for queries of another array
+__global__ void fe_rank_cross_kernel(const float* __restrict__ fe_q, uint32_t n_q, const float* __restrict__ fe_s,
+                                     uint32_t n_ref, uint32_t* __restrict__ pq) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_q) return;
+  const float f = fe_q[i];
+  uint32_t lo = 0, hi = n_ref;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (fe_s[mid] < f) lo = mid + 1; else hi = mid;
+  }
+  pq[i] = lo;
+}
+
+// perm[p] = p for the n real positions, kInvalidFrame for the pad positions up to n_pos
+__global__ void iota_kernel(uint32_t* __restrict__ perm, uint32_t n, uint32_t n_pos) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n_pos) perm[p] = p < n ? p : kInvalidFrame;
+}
+
 // Upper bound, known on the host, of the bits a cell key needs: the grid has about K = n / frames_per_cell cells
 // (auto_cell), at most 4002 per dimension; (x + 1)(y + 1) with x y <= K and x, y <= 4001 is at most
 // K + 4001 + K / 4001 + 1.  The radix sort (dc_sort.hip) costs one pass (~25 us at 10^6 frames) per 8 key bits: C3's population
@@ -1985,6 +2005,165 @@ void launch_nn_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, con
     default:
       break;
   }
+}
+
+// ---- cross sweeps: query rows of Q against every row of R (dc_hip_*_cross_dev) -------------------------------------
+// Workspace: the header (statistics and scale, as for the self sweeps), the A form + norms of R (natural order for the
+// populations, ordered by free energy for the neighbours), the B form + norms of Q, and the free-energy ordering of R
+// with its radix-sort scratch.
+struct CrossLayout {
+  uint32_t T_q, T_r, NM;
+  size_t off_img_r, off_norm_r, off_img_q, off_norm_q, off_fe_s, off_perm, off_invpos, off_pq, off_keys_in,
+      off_keys_out, off_vals_in, off_sort, total;
+};
+
+static CrossLayout make_cross_layout(size_t n_q, size_t n_ref, size_t n_cols) {
+  CrossLayout L;
+  L.T_q = (uint32_t)((n_q + 31) / 32);
+  L.T_r = (uint32_t)((n_ref + 31) / 32);
+  L.NM = (uint32_t)nm_for((int)n_cols);
+  const size_t rows_r = align256(sizeof(float) * 32 * (size_t)L.T_r);
+  L.off_img_r = kHdrBytes;
+  L.off_norm_r = align256(L.off_img_r + (size_t)16 * 64 * L.T_r * L.NM);
+  L.off_img_q = L.off_norm_r + rows_r;
+  L.off_norm_q = align256(L.off_img_q + (size_t)16 * 64 * L.T_q * L.NM);
+  L.off_fe_s = L.off_norm_q + align256(sizeof(float) * 32 * (size_t)L.T_q);
+  L.off_perm = L.off_fe_s + rows_r;
+  L.off_invpos = L.off_perm + rows_r;
+  L.off_pq = L.off_invpos + rows_r;
+  L.off_keys_in = L.off_pq + align256(sizeof(uint32_t) * (size_t)n_q);
+  L.off_keys_out = L.off_keys_in + rows_r;
+  L.off_vals_in = L.off_keys_out + rows_r;
+  L.off_sort = L.off_vals_in + rows_r;
+  L.total = L.off_sort + align256(sort_temp_bytes(n_ref));
+  return L;
+}
+
+size_t cross_workspace_bytes(size_t n_q, size_t n_ref, size_t n_cols) {
+  if (!mfma_supports(n_cols)) return 0;
+  return make_cross_layout(n_q, n_ref, n_cols).total;
+}
+
+// The statistics of Q and R TOGETHER: column sums of both sets (colsum_kernel adds into the header), one mean over
+// n_q + n_ref rows, then max |x - m|^2, the non-finite / overflow flag and the extents of both sets (rowstats_kernel
+// keeps them with atomicMax / atomicOr).  Every image of the call is built around this origin and at the scale that
+// M = max over BOTH sets gives: a band sized on one set alone would not cover pairs whose other end lies farther out.
+static int cross_prepare(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                         void* d_ws, hipStream_t stream) {
+  char* p = (char*)d_ws;
+  if (hipMemsetAsync(p, 0, kHdrBytes, stream) != hipSuccess) return -1;
+  const float* sets[2] = {d_query, d_ref};
+  const uint32_t rows[2] = {n_q, n_ref};
+  for (int k = 0; k < 2; ++k) {
+    const uint32_t blocks = (uint32_t)std::min<size_t>(512, ((size_t)rows[k] * n_cols + 255) / 256);
+    hipLaunchKernelGGL(colsum_kernel, dim3(blocks), dim3(256), 0, stream, sets[k], rows[k], n_cols,
+                       (double*)(p + kHdrSums));
+  }
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, stream, (const double*)(p + kHdrSums), n_q + n_ref, n_cols,
+                     (float*)(p + kHdrMeans));
+  for (int k = 0; k < 2; ++k)
+    hipLaunchKernelGGL(rowstats_kernel, dim3(std::min<uint32_t>((rows[k] + 255) / 256, 512u)), dim3(256), 0, stream,
+                       sets[k], rows[k], n_cols, (const float*)(p + kHdrMeans), (uint32_t*)p, 0u);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+static CrossArgs cross_args(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, void* d_ws,
+                            const CrossLayout& L, bool with_pq) {
+  char* p = (char*)d_ws;
+  CrossArgs X;
+  X.qcoords = d_query;
+  X.rcoords = d_ref;
+  X.n_q = n_q;
+  X.n_ref = n_ref;
+  X.T_q = L.T_q;
+  X.T_r = L.T_r;
+  X.img_r = (const uint4*)(p + L.off_img_r);
+  X.norms_r = (const float*)(p + L.off_norm_r);
+  X.img_q = (const uint4*)(p + L.off_img_q);
+  X.norms_q = (const float*)(p + L.off_norm_q);
+  X.perm_r = (const uint32_t*)(p + L.off_perm);
+  X.pq = with_pq ? (const uint32_t*)(p + L.off_pq) : nullptr;
+  X.hdr = (const uint32_t*)p;
+  return X;
+}
+
+// image of one set (A form of R through perm, or in natural order; B form of Q) with its norms
+static void cross_image(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t NM, uint32_t T,
+                        const uint32_t* perm, int b_form, void* img, void* norms, void* d_ws, hipStream_t stream) {
+  char* p = (char*)d_ws;
+  const dim3 grid((uint32_t)(((size_t)T * NM * 64 + 255) / 256));
+  hipLaunchKernelGGL(image_kernel, grid, dim3(256), image_smem(n_cols), stream, d_coords, n_rows, n_rows, n_cols, NM, T,
+                     (const float*)(p + kHdrMeans), perm, b_form, (uint4*)img, (float*)norms, (const uint32_t*)p);
+}
+
+int launch_pop_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                          uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
+                          hipStream_t stream) {
+  const CrossLayout L = make_cross_layout(n_q, n_ref, n_cols);
+  char* p = (char*)d_ws;
+  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
+  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)d_ws, max_radius2(rad2, n_rad), n_cols);
+  cross_image(d_ref, n_ref, n_cols, L.NM, L.T_r, nullptr, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
+  cross_image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
+  const CrossArgs X = cross_args(d_query, n_q, d_ref, n_ref, d_ws, L, false);
+  for (int r = 0; r < n_rad; ++r) {
+    const Rad2 one = single_radius(rad2, r);
+    uint32_t* out = d_pops + (size_t)r * n_q;
+    switch (nm_for((int)n_cols)) {
+#define X_(SV)                                                                                  \
+  case SV:                                                                                      \
+    if ((DC_STEP_MASK >> (SV - 1)) & 1u) pop_cross_step_##SV(X, n_cols, i_from, i_to, one, out, stream); \
+    break;
+      DC_FOR_EACH_S(X_)
+#undef X_
+      default:
+        break;
+    }
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_nn_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                         const float* d_fe_q, const float* d_fe_r, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx,
+                         float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t stream) {
+  const CrossLayout L = make_cross_layout(n_q, n_ref, n_cols);
+  char* p = (char*)d_ws;
+  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
+  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)p, -1.0f, n_cols);   // the neighbour scale
+  uint32_t* perm = (uint32_t*)(p + L.off_perm);
+  const dim3 blk(256), grid_r((n_ref + 255) / 256), grid_t((32 * L.T_r + 255) / 256);
+  if (d_fe_q) {
+    // the references ordered by free energy (a NaN raises the flag: the direct kernel answers), and per query the
+    // number of references with strictly lower free energy -- its candidates for nn_hd are a prefix of that order
+    uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
+    uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
+    hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>(grid_r.x, 1024u)), blk, 0, stream, d_fe_r, n_ref, keys_in,
+                       vals_in, (uint32_t*)p);
+    if (sort_pairs_u32(keys_in, (uint32_t*)(p + L.off_keys_out), vals_in, perm, n_ref, p + L.off_sort,
+                       sort_temp_bytes(n_ref), stream) != 0)
+      return -3;
+    hipLaunchKernelGGL(fe_scatter_kernel, grid_t, blk, 0, stream, perm, d_fe_r, n_ref, L.T_r,
+                       (uint32_t*)(p + L.off_invpos), (float*)(p + L.off_fe_s));
+    hipLaunchKernelGGL(fe_rank_cross_kernel, dim3((n_q + 255) / 256), blk, 0, stream, d_fe_q, n_q,
+                       (const float*)(p + L.off_fe_s), n_ref, (uint32_t*)(p + L.off_pq));
+  } else {
+    hipLaunchKernelGGL(iota_kernel, grid_t, blk, 0, stream, perm, n_ref, 32 * L.T_r);   // natural order
+  }
+  cross_image(d_ref, n_ref, n_cols, L.NM, L.T_r, perm, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
+  cross_image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
+  const CrossArgs X = cross_args(d_query, n_q, d_ref, n_ref, d_ws, L, d_fe_q != nullptr);
+  switch (nm_for((int)n_cols)) {
+#define X_(SV)                                                                                   \
+  case SV:                                                                                       \
+    if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                         \
+      nn_cross_step_##SV(X, n_cols, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream);  \
+    break;
+    DC_FOR_EACH_S(X_)
+#undef X_
+    default:
+      break;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // ---- DC_VARIANT_MFMA32: the fp32-input MFMA instance (dc_mfma32.hpp) ---------------------------------------------

@@ -59,6 +59,20 @@ enum NnForm {
   kNnShared,   // reference operands shared through LDS (nn_shared_kernel)
 };
 enum CallKind { kCallAll, kCallRange, kCallSegment };   // queries: all rows / a row range / one segment of a sharded run
+// operands of one cross sweep (dc_mfma_kernels.hpp pop_cross_mfma_kernel / nn_cross_mfma_kernel)
+struct CrossArgs {
+  const float* qcoords;   // [n_q][n_cols]
+  const float* rcoords;   // [n_ref][n_cols]
+  uint32_t n_q, n_ref, T_q, T_r;
+  const uint4* img_r;     // A form of R: natural order (populations) or ordered by free energy (neighbours)
+  const float* norms_r;
+  const uint4* img_q;     // B form of Q, natural order
+  const float* norms_q;
+  const uint32_t* perm_r; // neighbours: sorted position -> reference frame
+  const uint32_t* pq;     // neighbours: per query, references with strictly lower free energy (nullptr: nn only)
+  const uint32_t* hdr;
+};
+
 struct PopPlan {
   PopForm form;
   int nr;                  // radii per sweep: 1, 4 or 8
@@ -165,6 +179,18 @@ void launch_nn_pruned_segment(const float* d_coords, uint32_t n_rows, uint32_t n
 void launch_nn_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe,
                     uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
                     uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t stream);
+
+// cross sweeps (dc_hip_*_cross_dev), n_cols <= 64, every pair: the query rows [i_from, i_to) of d_query [n_q] against
+// all n_ref >= 1 rows of d_ref, one origin and one scale over both sets.  Each call computes the statistics of both sets
+// into the header first (the gated direct kernel reads its flag); pops [n_rad][n_q]; d_fe_q == nullptr: nn only.
+// Return 0, or a negative code when a launch failed.
+size_t cross_workspace_bytes(size_t n_q, size_t n_ref, size_t n_cols);
+int launch_pop_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                          uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
+                          hipStream_t stream);
+int launch_nn_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                         const float* d_fe_q, const float* d_fe_r, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx,
+                         float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t stream);
 
 // The rows of one segment of a sharded neighbour sweep compacted into a dense block [4][nn_block_rows] (nn_idx,
 // nn_d2 bits, hd_idx, hd_d2 bits by local position), and the gathered blocks of all segments back to the four

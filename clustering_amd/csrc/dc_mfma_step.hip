@@ -72,5 +72,15 @@ void DC_CAT(nn_mfma_step_, DC_STEP)(const float* coords, uint32_t n_rows, uint32
                        hd_idx, hd_d2, s);
 }
 
+void DC_CAT(pop_cross_step_, DC_STEP)(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                                      const Rad2& rad2, uint32_t* pops, hipStream_t s) {
+  pop_cross_dispatch<DC_STEP>(X, n_cols, i_from, i_to, rad2, pops, s);
+}
+
+void DC_CAT(nn_cross_step_, DC_STEP)(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                                     uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
+  nn_cross_dispatch<DC_STEP>(X, n_cols, i_from, i_to, nn_idx, nn_d2, hd_idx, hd_d2, s);
+}
+
 }  // namespace dc
 

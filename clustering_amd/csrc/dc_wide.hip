@@ -64,6 +64,12 @@ struct WideArgs {
   uint32_t* hd_idx;
   float* hd_d2;
   GraphOut g;   // g.pops: pops of radius 0 ([n_rad][n_rows] radius-major for kWidePop)
+  // cross sweeps (pop / nn): query rows from qcoords, no pair left out, no self term; pops [n_rad][n_q]; fe = the
+  // reference's free energies, fe_q the queries' (nullptr: nn only).  Self sweeps: qcoords = coords, cross = 0.
+  const float* qcoords;
+  const float* fe_q;
+  uint32_t n_q;
+  int cross;
 };
 
 // what one lane stages of a chunk: kWLoads pieces of 4 columns, and 4 tail columns of one row
@@ -72,7 +78,8 @@ struct Stage {
   f4 t;
 };
 
-__device__ __forceinline__ void stage_load(const float* __restrict__ coords, uint32_t n_rows, uint32_t D, uint32_t V,
+__device__ __forceinline__ void stage_load(const float* __restrict__ coords, const float* __restrict__ qcoords,
+                                           uint32_t n_rows, uint32_t D, uint32_t V,
                                            uint32_t qend, uint32_t qbase, uint32_t t0, uint32_t c0, bool last,
                                            Stage& st) {
 #pragma unroll
@@ -80,13 +87,14 @@ __device__ __forceinline__ void stage_load(const float* __restrict__ coords, uin
     const uint32_t e = threadIdx.x + kWBlock * m, row = e >> 3, col = c0 + 4u * (e & 7u);
     const uint32_t grow = row < kWRows ? qbase + row : t0 + (row - kWRows);
     const bool ok = (row < kWRows ? grow < qend : grow < n_rows) && col < V;   // (V % 4 == 0: all 4 or none)
-    st.v[m] = ok ? f4(*reinterpret_cast<const f4_row*>(coords + (size_t)grow * D + col)) : f4(0.0f);
+    const float* src = row < kWRows ? qcoords : coords;
+    st.v[m] = ok ? f4(*reinterpret_cast<const f4_row*>(src + (size_t)grow * D + col)) : f4(0.0f);
   }
   if (last && threadIdx.x < 2 * kWStage) {
     const uint32_t row = threadIdx.x >> 1, k0 = V + 4u * (threadIdx.x & 1u);
     const uint32_t grow = row < kWRows ? qbase + row : t0 + (row - kWRows);
     const bool ok = row < kWRows ? grow < qend : grow < n_rows;
-    const float* src = coords + (size_t)grow * D;
+    const float* src = (row < kWRows ? qcoords : coords) + (size_t)grow * D;
 #pragma unroll
     for (int k = 0; k < 4; ++k) st.t[k] = (ok && k0 + k < D) ? src[k0 + k] : 0.0f;
   }
@@ -207,7 +215,7 @@ __global__ __launch_bounds__(kWBlock) void wide_kernel(const float* __restrict__
     qi[a] = qbase + qrow + 4u * a;
     live[a] = qi[a] < qend;
     const uint32_t row = live[a] ? qi[a] : i_to - 1;   // clamp: result discarded
-    qfe[a] = MODE == kWideNn ? w.fe[row] : 0.0f;
+    qfe[a] = MODE != kWideNn ? 0.0f : !w.cross ? w.fe[row] : w.fe_q ? w.fe_q[row] : -INFINITY;
     qc[a] = MODE == kWideMinEdge ? w.g.comp[row] : 0u;
     qr[a] = MODE == kWideMinEdge ? w.g.rank[row] : 0u;
   }
@@ -230,7 +238,7 @@ __global__ __launch_bounds__(kWBlock) void wide_kernel(const float* __restrict__
   uint32_t fill = 0;
 
   Stage st;
-  stage_load(coords, n_rows, D, V, qend, qbase, 0u, 0u, n_chunks == 1, st);
+  stage_load(coords, w.qcoords, n_rows, D, V, qend, qbase, 0u, 0u, n_chunks == 1, st);
   stage_store(buf[0], st, n_chunks == 1);
   __syncthreads();
   uint32_t t0 = 0, c = 0, cur = 0;   // tile, chunk of the tile, LDS buffer
@@ -238,7 +246,7 @@ __global__ __launch_bounds__(kWBlock) void wide_kernel(const float* __restrict__
     const bool last = c + 1 == n_chunks;
     const uint32_t nt0 = last ? t0 + kWRef : t0, nc = last ? 0u : c + 1;   // the next step
     const bool more = nt0 < n_rows;
-    if (more) stage_load(coords, n_rows, D, V, qend, qbase, nt0, nc * kWChunk, nc + 1 == n_chunks, st);
+    if (more) stage_load(coords, w.qcoords, n_rows, D, V, qend, qbase, nt0, nc * kWChunk, nc + 1 == n_chunks, st);
     const WideBuf& b = buf[cur];
     chunk_accumulate(b, qrow, tr, acc);
     if (last) {
@@ -252,7 +260,7 @@ __global__ __launch_bounds__(kWBlock) void wide_kernel(const float* __restrict__
         rj[cc] = t0 + tr + 16u * cc;
         rok[cc] = rj[cc] < n_rows;
         const uint32_t j = rok[cc] ? rj[cc] : 0u;
-        rfe[cc] = MODE == kWideNn ? w.fe[j] : 0.0f;
+        rfe[cc] = (MODE == kWideNn && w.fe) ? w.fe[j] : 0.0f;
         rc[cc] = MODE == kWideMinEdge ? w.g.comp[j] : 0u;
         rr[cc] = MODE == kWideMinEdge ? w.g.rank[j] : 0u;
       }
@@ -265,7 +273,7 @@ __global__ __launch_bounds__(kWBlock) void wide_kernel(const float* __restrict__
           const f4 rt0 = b.tail[kWRows + tr + 16 * cc][0], rt1 = b.tail[kWRows + tr + 16 * cc][1];
           const float d = finish_pair(acc[a][cc], qt0, qt1, rt0, rt1, rem);
           const uint32_t j = rj[cc];
-          const bool ok = rok[cc] && j != qi[a];
+          const bool ok = rok[cc] && (w.cross || j != qi[a]);
           if constexpr (kCount) {
 #pragma unroll
             for (int r = 0; r < NR; ++r) cnt[a][r] += (ok && d < w.rad2.v[r]) ? 1u : 0u;
@@ -317,12 +325,14 @@ __global__ __launch_bounds__(kWBlock) void wide_kernel(const float* __restrict__
     if constexpr (MODE == kWidePop) {
 #pragma unroll
       for (int r = 0; r < NR; ++r)
-        if (r < w.n_rad) w.g.pops[(size_t)r * n_rows + qi[a]] = cnt[a][r] + 1u;
+        if (r < w.n_rad) w.g.pops[(size_t)r * (w.cross ? w.n_q : n_rows) + qi[a]] = cnt[a][r] + (w.cross ? 0u : 1u);
     } else if constexpr (MODE == kWideNn) {
       w.nn_idx[qi[a]] = (uint32_t)best[a];
       w.nn_d2[qi[a]] = __uint_as_float((uint32_t)(best[a] >> 32));
-      w.hd_idx[qi[a]] = (uint32_t)bhd[a];
-      w.hd_d2[qi[a]] = __uint_as_float((uint32_t)(bhd[a] >> 32));
+      if (!w.cross || w.fe_q) {
+        w.hd_idx[qi[a]] = (uint32_t)bhd[a];
+        w.hd_d2[qi[a]] = __uint_as_float((uint32_t)(bhd[a] >> 32));
+      }
     } else {
       w.g.pops[qi[a]] = cnt[a][0] + 1u;
       if (MODE == kWideMinEdge && best[a] != ~0ull) atomicMin(w.g.best + qc[a], best[a]);
@@ -331,9 +341,10 @@ __global__ __launch_bounds__(kWBlock) void wide_kernel(const float* __restrict__
 }
 
 template <int MODE, int NR>
-void wide_launch(const float* c, uint32_t n, uint32_t D, uint32_t i_from, uint32_t i_to, const WideArgs& w,
+void wide_launch(const float* c, uint32_t n, uint32_t D, uint32_t i_from, uint32_t i_to, WideArgs w,
                  const uint32_t* gate, hipStream_t s) {
   if (i_to <= i_from) return;
+  if (!w.cross) w.qcoords = c;
   const uint32_t grid = (i_to - i_from + kWRows - 1) / kWRows;
   hipLaunchKernelGGL((wide_kernel<MODE, NR>), dim3(grid), dim3(kWBlock), 0, s, c, n, D, i_from, i_to, w, gate);
 }
@@ -365,6 +376,39 @@ void launch_nn_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, con
   w.hd_idx = d_hd_idx;
   w.hd_d2 = d_hd_d2;
   wide_launch<kWideNn, 1>(d_coords, n_rows, n_cols, i_from, i_to, w, gate, stream);
+}
+
+void launch_pop_cross_wide(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
+                           uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops,
+                           const uint32_t* gate, hipStream_t stream) {
+  WideArgs w{};
+  w.rad2 = rad2;
+  w.n_rad = n_rad;
+  w.g.pops = d_pops;
+  w.qcoords = d_query;
+  w.n_q = n_q;
+  w.cross = 1;
+  if (n_rad == 1)
+    wide_launch<kWidePop, 1>(d_ref, n_ref, n_cols, i_from, i_to, w, gate, stream);
+  else if (n_rad <= 4)
+    wide_launch<kWidePop, 4>(d_ref, n_ref, n_cols, i_from, i_to, w, gate, stream);
+  else
+    wide_launch<kWidePop, 8>(d_ref, n_ref, n_cols, i_from, i_to, w, gate, stream);
+}
+
+void launch_nn_cross_wide(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols, const float* d_fe_q,
+                          const float* d_fe_r, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+                          uint32_t* d_hd_idx, float* d_hd_d2, const uint32_t* gate, hipStream_t stream) {
+  WideArgs w{};
+  w.fe = d_fe_q ? d_fe_r : nullptr;
+  w.fe_q = d_fe_q;
+  w.nn_idx = d_nn_idx;
+  w.nn_d2 = d_nn_d2;
+  w.hd_idx = d_hd_idx;
+  w.hd_d2 = d_hd_d2;
+  w.qcoords = d_query;
+  w.cross = 1;
+  wide_launch<kWideNn, 1>(d_ref, n_ref, n_cols, i_from, i_to, w, gate, stream);
 }
 
 void launch_pairs_wide(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops,

@@ -182,6 +182,126 @@ def nearest_neighbors_partial(coords, fe, i_from=0, i_to=None, variant="auto", s
     return nn_idx, nn_d2, hd_idx, hd_d2
 
 
+# ---- cross sweeps: new frames against a reference trajectory (include/dc_density.h "cross sweeps") ----------------
+class _CrossWorkspace(Workspace):
+    def get(self, n_q, n_ref, n_cols):
+        need = int(capi.lib.dc_hip_cross_workspace_bytes(n_q, n_ref, n_cols))
+        if need == 0:
+            return C.c_void_p(0), 0
+        if self.buf is None or self.buf.numel() < need:
+            self.buf = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return _dev(self.buf), int(self.buf.numel())
+
+
+_cross_workspaces = {}
+
+
+def _cross_workspace(device):
+    key = str(device)
+    if key not in _cross_workspaces:
+        _cross_workspaces[key] = _CrossWorkspace(device)
+    return _cross_workspaces[key]
+
+
+def _check_pair(queries, reference):
+    n_q, n_cols = _check_coords(queries)
+    n_ref, n_cols_r = _check_coords(reference)
+    if n_cols != n_cols_r or queries.device != reference.device:
+        raise ValueError("queries and reference need the same n_cols and the same device")
+    return n_q, n_ref, n_cols
+
+
+def calculate_populations_against(queries, reference, radii, i_from=0, i_to=None, variant="auto", out=None):
+    """Populations of the query frames in the reference trajectory (dc_hip_populations_cross_dev):
+    pops[r][q] = #{ j : d2(Q_q, R_j) < r^2 } -- no self term, so a copy of reference frame j gets pop_R(j).
+    queries [n_q, n_cols], reference [n_ref, n_cols]: float32 CUDA tensors; radii in any order.
+    -> torch.int32 [n_radii, n_q] in the order of ``radii``, zero outside [i_from, i_to)."""
+    n_q, n_ref, n_cols = _check_pair(queries, reference)
+    i_to = n_q if i_to is None else i_to
+    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    if out is None:
+        out = torch.empty((rad.size, n_q), dtype=torch.int32, device=queries.device)
+    assert out.shape == (rad.size, n_q) and out.dtype == torch.int32 and out.is_contiguous()
+    rad_call, dst, order = _ascending(rad, out)
+    with torch.cuda.device(queries.device):
+        ws, ws_bytes = _cross_workspace(queries.device).get(n_q, n_ref, n_cols)
+        rc = capi.lib.dc_hip_populations_cross_dev(
+            _dev(queries), n_q, _dev(reference), n_ref, n_cols, rad_call.ctypes.data_as(C.POINTER(C.c_float)),
+            rad.size, i_from, i_to, _dev(dst), ws, ws_bytes, capi.VARIANTS[variant], _stream_ptr())
+    capi.check(rc, "dc_hip_populations_cross_dev")
+    if order is not None:
+        out[order] = dst
+    return out
+
+
+def calculate_free_energies_against(pops, max_pop):
+    """Free energies on another population array's scale (dc_hip_free_energies_scaled_dev):
+    fe = (float)-log((double)((float)pop * (1.0f / max_pop))).  pops: int32 CUDA [n]; pop 0 -> +inf,
+    pop > max_pop -> negative."""
+    assert pops.is_cuda and pops.dtype == torch.int32 and pops.dim() == 1 and pops.is_contiguous()
+    fe = torch.empty(pops.shape[0], dtype=torch.float32, device=pops.device)
+    with torch.cuda.device(pops.device):
+        rc = capi.lib.dc_hip_free_energies_scaled_dev(_dev(pops), pops.shape[0], int(max_pop), _dev(fe), _stream_ptr())
+    capi.check(rc, "dc_hip_free_energies_scaled_dev")
+    return fe
+
+
+def nearest_reference(queries, reference, fe_query=None, fe_ref=None, i_from=0, i_to=None, variant="auto"):
+    """Nearest reference frame of every query, and nearest reference frame of strictly lower free energy
+    (dc_hip_nearest_neighbors_cross_dev).  -> (nn_idx int32, nn_d2 float32, hd_idx, hd_d2), each [n_q]; "none" is
+    (n_ref + 1, FLT_MAX).  Without free energies hd_idx / hd_d2 are None."""
+    n_q, n_ref, n_cols = _check_pair(queries, reference)
+    i_to = n_q if i_to is None else i_to
+    with_fe = fe_query is not None
+    if with_fe:
+        assert fe_ref is not None
+        for f, n in ((fe_query, n_q), (fe_ref, n_ref)):
+            assert f.is_cuda and f.dtype == torch.float32 and f.shape == (n,) and f.is_contiguous()
+    dev = queries.device
+    nn_idx = torch.empty(n_q, dtype=torch.int32, device=dev)
+    nn_d2 = torch.empty(n_q, dtype=torch.float32, device=dev)
+    hd_idx = torch.empty(n_q, dtype=torch.int32, device=dev) if with_fe else None
+    hd_d2 = torch.empty(n_q, dtype=torch.float32, device=dev) if with_fe else None
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _cross_workspace(dev).get(n_q, n_ref, n_cols)
+        rc = capi.lib.dc_hip_nearest_neighbors_cross_dev(
+            _dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
+            _dev(fe_ref) if with_fe else None, i_from, i_to, _dev(nn_idx), _dev(nn_d2),
+            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None, ws, ws_bytes,
+            capi.VARIANTS[variant], _stream_ptr())
+    capi.check(rc, "dc_hip_nearest_neighbors_cross_dev")
+    return nn_idx, nn_d2, hd_idx, hd_d2
+
+
+def assign_frames(queries, reference, radius, ref_states, variant="auto"):
+    """Assign new frames to the states of an already clustered reference trajectory, end to end:
+      1. the reference's own populations at ``radius`` (self sweep), their maximum and the reference free energies;
+      2. the query populations in the reference and the query free energies on the reference's scale;
+      3. nearest reference frame and nearest reference frame of lower free energy;
+      4. the state of each query: ref_states[hd] if hd exists, else ref_states[nn], else 0 (unassigned, as in the
+         reference's density_clustering.cpp:345-360).
+    ref_states: int array-like [n_ref].  -> dict of CUDA tensors (states int32 [n_q] among them)."""
+    n_q, n_ref, n_cols = _check_pair(queries, reference)
+    dev = queries.device
+    states_r = torch.as_tensor(np.ascontiguousarray(ref_states, dtype=np.int32), device=dev)
+    assert states_r.shape == (n_ref,)
+    pops_ref = calculate_populations_partial(reference, [radius], variant=variant)[0].contiguous()
+    max_pop = int(pops_ref.max().item()) if n_ref else 0
+    fe_ref = calculate_free_energies(pops_ref)
+    pops_q = calculate_populations_against(queries, reference, [radius], variant=variant)[0].contiguous()
+    fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
+        torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
+    nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference(queries, reference, fe_q, fe_ref, variant=variant)
+    none = n_ref + 1
+    states = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    if n_ref:
+        pick = torch.where(hd_idx != none, hd_idx, nn_idx)
+        ok = pick != none
+        states[ok] = states_r[pick[ok].long()]
+    return {"states": states, "pops_ref": pops_ref, "max_pop": max_pop, "fe_ref": fe_ref, "pops": pops_q, "fe": fe_q,
+            "nn_idx": nn_idx, "nn_d2": nn_d2, "hd_idx": hd_idx, "hd_d2": hd_d2}
+
+
 def evaluated_tiles(device):
     """(pop_tiles, nn_tiles): 32x32 frame-pair tiles evaluated by the last pruned sweeps on this device's
     workspace.  The header is rebuilt by every sweep, so read it right after the sweep of interest

@@ -311,6 +311,54 @@ DC_API int dc_hip_radius_min_edge_segment_dev(const float* d_coords, size_t n_ro
                                               void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * cross sweeps: new frames measured against a reference trajectory (no counterpart in the reference, whose
+ * sweeps are all self-sweeps; the same arithmetic and decision rules as those)
+ * -------------------------------------------------------------------------------------
+ * Inputs: d_query [n_query][n_cols] and d_ref [n_ref][n_cols], float32 row-major, the same n_cols >= 1 (any width);
+ * d_query == d_ref is allowed.  Only the query rows [i_from, i_to) are answered.  d2(q, j) is the canonical squared
+ * distance of this build's summation order; it is bitwise symmetric in its two rows.
+ *   pop_r[q] = #{ j in [0, n_ref) : d2(Q_q, R_j) < fl32(r*r) }    -- NO self term
+ *       [n_radii][n_query] in the order of the radii argument, 0 outside the row range.  With Q bit-identical to R,
+ *       r > 0 and finite rows this equals the self-sweep populations exactly (the self pair supplies the "+1"): a
+ *       copy of reference frame j gets exactly pop_R(j).
+ *   nn[q]    = lexicographic minimum of (d2, j) over ALL j (no exclusion: a duplicate gives d2 = 0), among the
+ *              candidates with d2 < FLT_MAX (the reference's strict test against its initial value)
+ *   nn_hd[q] = the same over { j : fe_ref[j] < fe_query[q] } (IEEE comparison: a NaN is never lower and has no lower
+ *              neighbour, -0.0 is not lower than +0.0).  With Q = R[S] and fe_query = fe_ref[S] it equals the
+ *              self-sweep nn_hd of the rows S bit for bit (a frame is not lower than itself).
+ *   no candidate: (n_ref + 1, FLT_MAX); rows outside the range hold that value too.
+ * A non-finite row (inf / NaN in Q or in R) has no partners: it adds 0 to every population and is never a neighbour.
+ * Sizes: n_ref + 1 and n_query must fit uint32 (else DC_ERR_TOO_LARGE).
+ * Variants: DC_VARIANT_AUTO (the matrix-core sweep for n_cols <= 64 and finite data -- chosen on the device, like the
+ * self sweeps' fallback -- the direct kernels otherwise), DC_VARIANT_DIRECT, DC_VARIANT_MFMA (n_cols <= 64 only; every
+ * pair, one origin and one scale over Q and R together).  DC_VARIANT_MFMA_PRUNED, DC_VARIANT_MFMA32 and
+ * DC_FLAG_STATS_VALID are refused (DC_ERR_INVALID_ARGUMENT).  Results are the same for every variant. */
+
+/* bytes of scratch the cross sweeps need (0 when n_cols > 64: the direct kernels need none) */
+DC_API size_t dc_hip_cross_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols);
+
+/* populations of the query rows against the reference frames.  radii HOST [n_radii]; d_pops [n_radii][n_query]
+ * device, fully overwritten. */
+DC_API int dc_hip_populations_cross_dev(const float* d_query, size_t n_query, const float* d_ref, size_t n_ref,
+                                        size_t n_cols, const float* radii, size_t n_radii, size_t i_from, size_t i_to,
+                                        uint32_t* d_pops, void* d_ws, size_t ws_bytes, int variant, void* stream);
+
+/* nearest reference frame, and nearest reference frame of strictly lower free energy.  d_fe_query [n_query],
+ * d_fe_ref [n_ref] device; d_fe_query == NULL: nn only (d_fe_ref, d_hd_idx, d_hd_d2 may be NULL and are not written).
+ * Outputs [n_query] device. */
+DC_API int dc_hip_nearest_neighbors_cross_dev(const float* d_query, size_t n_query, const float* d_ref, size_t n_ref,
+                                              size_t n_cols, const float* d_fe_query, const float* d_fe_ref,
+                                              size_t i_from, size_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+                                              uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
+                                              int variant, void* stream);
+
+/* free energies on ANOTHER array's scale: fe[i] = (float)-log((double)((float)pop[i] * (1.0f / (float)max_pop))),
+ * with the device log + host-libm referee of dc_hip_free_energies_dev.  pop = 0 gives +inf, pop > max_pop a negative
+ * value; max_pop = 0 is DC_ERR_INVALID_ARGUMENT.  Synchronises the stream. */
+DC_API int dc_hip_free_energies_scaled_dev(const uint32_t* d_pops, size_t n, uint32_t max_pop, float* d_fe,
+                                           void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * host-pointer entry points (mirror the reference's per-GPU host functions)
  * ------------------------------------------------------------------------------------- */
 
@@ -327,6 +375,16 @@ DC_API int dc_hip_populations(const float* coords, size_t n_rows, size_t n_cols,
 DC_API int dc_hip_nearest_neighbors(const float* coords, size_t n_rows, size_t n_cols, const float* fe,
                                     size_t i_from, size_t i_to, int device, uint32_t* nn_idx,
                                     float* nn_d2, uint32_t* hd_idx, float* hd_d2);
+
+/* host-pointer forms of the cross sweeps (synchronous, one device, DC_VARIANT_AUTO).  pops HOST [n_radii][n_query];
+ * neighbour outputs HOST [n_query]; fe_query == NULL: nn only. */
+DC_API int dc_hip_populations_cross(const float* query, size_t n_query, const float* ref, size_t n_ref, size_t n_cols,
+                                    const float* radii, size_t n_radii, size_t i_from, size_t i_to, int device,
+                                    uint32_t* pops);
+DC_API int dc_hip_nearest_neighbors_cross(const float* query, size_t n_query, const float* ref, size_t n_ref,
+                                          size_t n_cols, const float* fe_query, const float* fe_ref, size_t i_from,
+                                          size_t i_to, int device, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx,
+                                          float* hd_d2);
 
 /* host-pointer form of dc_hip_radius_pairs_dev.  pairs: HOST [capacity][2]; *count: pairs found (if
  * larger than capacity, call again with a buffer of that size). */
