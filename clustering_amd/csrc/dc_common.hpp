@@ -22,18 +22,26 @@ struct Rad2 {
   float v[kMaxRadiiPerLaunch];
 };
 
+// what a sweep measures: rows of one array against the same array, without the self pair (kSelf: the query
+// array is the reference array, n_q == n_ref), or query rows against every row of a reference array (kAgainst:
+// dc_hip_*_cross_dev).  An explicit mode, never decided by comparing pointers: a sweep against a reference that happens
+// to be the query array itself still counts every pair.
+enum SweepMode { kSelf = 0, kAgainst = 1 };
+
 // ---- launchers implemented in dc_direct.hip -------------------------------------------
-// pops: [n_radii_total][n_rows] radius-major; this launch fills radius rows
-// r_first .. r_first+n_rad-1 for query rows [i_from, i_to).  Returns false if n_cols is unsupported.
+// Query rows [i_from, i_to) of d_query [n_q][n_cols] against the n_ref rows of d_ref, any n_cols >= 1 (rows wider
+// than kMaxColsGeneric go to the wide launchers).  pops: [n_radii_total][n_q] radius-major; this launch fills radius
+// rows r_first .. r_first+n_rad-1.  nn / hd: "none" = (n_ref + 1, FLT_MAX); kAgainst with d_fe_q == nullptr: nn only
+// (d_fe_r, d_hd_* unused).  Return false if n_cols is unsupported.
 // gate: optional device pointer to the MFMA workspace header; when given, the kernel runs only if
 // gate[1] != 0 (the operand-image pass flagged data the MFMA kernels must not touch).
-bool launch_pop_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from,
-                       uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row,
-                       const uint32_t* gate, hipStream_t stream);
+bool launch_pop_direct(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
+                       uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row,
+                       SweepMode mode, const uint32_t* gate, hipStream_t stream);
 
-bool launch_nn_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe,
-                      uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
-                      uint32_t* d_hd_idx, float* d_hd_d2, const uint32_t* gate, hipStream_t stream);
+bool launch_nn_direct(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols, const float* d_fe_q,
+                      const float* d_fe_r, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+                      uint32_t* d_hd_idx, float* d_hd_d2, SweepMode mode, const uint32_t* gate, hipStream_t stream);
 
 // The radius graph (canonical d2 < r2) without the matrix-core sweep: n_cols > 64, or flagged data behind the gate.
 // pairs: pops[i] for all rows, every unordered pair {i, j} once as (i, j) with i < j; *d_count (zeroed by the caller)
@@ -47,17 +55,6 @@ bool launch_min_edge_direct(const float* d_coords, uint32_t n_rows, uint32_t n_c
                             const uint32_t* d_comp, const uint32_t* d_rank, uint32_t i_from, uint32_t i_to,
                             unsigned long long* d_best, uint32_t* d_pops, const uint32_t* gate,
                             hipStream_t stream);
-
-// cross sweeps (dc_hip_*_cross_dev): query rows [i_from, i_to) of d_query [n_q][n_cols] against all n_ref rows of d_ref,
-// any n_cols >= 1.  pops [n_rad][n_q] (radius-major, this launch's radii); no self term.  nn / hd: "none" = (n_ref + 1,
-// FLT_MAX); d_fe_q == nullptr: nn only (d_fe_r, d_hd_* unused).  gate as above.
-void launch_pop_cross_direct(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
-                             uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops,
-                             const uint32_t* gate, hipStream_t stream);
-void launch_nn_cross_direct(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
-                            const float* d_fe_q, const float* d_fe_r, uint32_t i_from, uint32_t i_to,
-                            uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
-                            const uint32_t* gate, hipStream_t stream);
 
 // ---- launchers implemented in dc_wide.hip: the same products for n_cols > kMaxColsGeneric, with the columns streamed
 // through LDS in chunks (no upper limit on n_cols).  launch_*_direct hand such rows to them.
@@ -79,13 +76,10 @@ void launch_min_edge_wide(const float* d_coords, uint32_t n_rows, uint32_t n_col
                           const uint32_t* d_rank, uint32_t i_from, uint32_t i_to, unsigned long long* d_best,
                           uint32_t* d_pops, const uint32_t* gate, hipStream_t stream);
 
-// fills idx[i] = n_rows+1, d2[i] = FLT_MAX for all rows (density_clustering.cpp:242-245)
-void launch_nn_init(uint32_t n_rows, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+// fills idx[i] = n_ref + 1, d2[i] = FLT_MAX for all n_q rows (density_clustering.cpp:242-245; d_hd_idx == nullptr:
+// nn only)
+void launch_nn_init(uint32_t n_q, uint32_t n_ref, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                     float* d_hd_d2, hipStream_t stream);
-
-// cross sweeps: idx = n_ref + 1, d2 = FLT_MAX for all n_q rows (d_hd_idx == nullptr: nn only)
-void launch_nn_init_cross(uint32_t n_q, uint32_t n_ref, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
-                          float* d_hd_d2, hipStream_t stream);
 // fe[i] = table[pops[i]]
 void launch_fe_gather(const uint32_t* d_pops, uint32_t n_rows, const float* d_table, float* d_fe,
                       hipStream_t stream);

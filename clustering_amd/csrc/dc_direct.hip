@@ -63,16 +63,22 @@ __device__ __forceinline__ void load_ref(const float* tile, uint32_t r, float (&
 }
 
 // -----------------------------------------------------------------------------------------
-// population count: pops[r][i] = 1 + #{ j != i : d2(i,j) < rad2[r] }
+// The query rows [i_from, i_to) of qcoords [n_q][D] against every row of rcoords [n_ref][D].  M decides
+// the rest:
+//   kSelf (qcoords == rcoords, n_q == n_ref): the reference's sweep, which leaves out the self pair:
+//     pops[r][i] = 1 + #{ j != i : d2(i,j) < rad2[r] };  nn / hd over j != i
+//   kAgainst: nothing is left out and nothing is added (dc_hip_*_cross_dev):
+//     pops[r][q] = #{ j < n_ref : d2(Q_q, R_j) < rad2[r] };  nn / hd over every j;  fe_q == nullptr: nn only
+// "none" is (n_ref + 1, FLT_MAX) in both.
 // -----------------------------------------------------------------------------------------
-template <int D, int NR>
-__global__ __launch_bounds__(kBlock) void pop_direct_kernel(const float* __restrict__ coords,
-                                                            uint32_t n_rows, uint32_t i_from,
-                                                            uint32_t i_to, Rad2 rad2, int n_rad,
-                                                            uint32_t* __restrict__ pops,
-                                                            const uint32_t* __restrict__ gate) {
+template <int D, int NR, SweepMode M>
+__global__ __launch_bounds__(kBlock) void pop_direct_kernel(
+    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_q, uint32_t n_ref,
+    uint32_t i_from, uint32_t i_to, Rad2 rad2, int n_rad, uint32_t* __restrict__ pops,
+    const uint32_t* __restrict__ gate) {
   constexpr int S = Cfg<D>::S, Q = Cfg<D>::Q;
   if (gate && gate[1] == 0) return;
+  if constexpr (M == kSelf) rcoords = qcoords, n_q = n_ref;   // (one array: the registers of the reference's loop)
   __shared__ __attribute__((aligned(16))) float tile[kTile * S];
   const uint32_t qbase = i_from + blockIdx.x * (kBlock * Q);
 
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void pop_direct_kernel(const float* __restr
     qi[a] = qbase + a * kBlock + threadIdx.x;
     const uint32_t row = qi[a] < i_to ? qi[a] : i_to - 1;   // clamp: result discarded
 #pragma unroll
-    for (int k = 0; k < D; ++k) q[a][k] = coords[(size_t)row * D + k];
+    for (int k = 0; k < D; ++k) q[a][k] = qcoords[(size_t)row * D + k];
   }
   uint32_t cnt[Q][NR];
 #pragma unroll
@@ -91,10 +97,10 @@ __global__ __launch_bounds__(kBlock) void pop_direct_kernel(const float* __restr
 #pragma unroll
     for (int r = 0; r < NR; ++r) cnt[a][r] = 0;
 
-  for (uint32_t t0 = 0; t0 < n_rows; t0 += kTile) {
-    const uint32_t nt = min((uint32_t)kTile, n_rows - t0);
+  for (uint32_t t0 = 0; t0 < n_ref; t0 += kTile) {
+    const uint32_t nt = min((uint32_t)kTile, n_ref - t0);
     __syncthreads();
-    stage_tile<D>(coords, t0, nt, tile);
+    stage_tile<D>(rcoords, t0, nt, tile);
     __syncthreads();
 #pragma unroll 2
     for (uint32_t r = 0; r < nt; ++r) {
@@ -108,16 +114,17 @@ __global__ __launch_bounds__(kBlock) void pop_direct_kernel(const float* __restr
       }
     }
   }
-  // The sweep counted the self pair iff d2(i,i) < rad2 (d2(i,i) is +0, or NaN for non-finite
+  // A self sweep counted the self pair iff d2(i,i) < rad2 (d2(i,i) is +0, or NaN for non-finite
   // rows); the reference never evaluates it and starts every population at 1 (:132-134).
 #pragma unroll
   for (int a = 0; a < Q; ++a) {
     if (qi[a] < i_to) {
-      const float dself = dist2_canon<D>(q[a], q[a]);
+      const float dself = (M == kSelf) ? dist2_canon<D>(q[a], q[a]) : 0.0f;
 #pragma unroll
       for (int rr = 0; rr < NR; ++rr)
         if (rr < n_rad)   // an instance with NR slots also serves fewer radii (unused slots = -1)
-          pops[(size_t)rr * n_rows + qi[a]] = cnt[a][rr] + 1u - ((dself < rad2.v[rr]) ? 1u : 0u);
+          pops[(size_t)rr * n_q + qi[a]] =
+              (M == kSelf) ? cnt[a][rr] + 1u - ((dself < rad2.v[rr]) ? 1u : 0u) : cnt[a][rr];
     }
   }
 }
@@ -155,17 +162,20 @@ __device__ __forceinline__ void nn_tile(const float* tile, const float* tile_fe,
   }
 }
 
-template <int D>
+template <int D, SweepMode M>
 __global__ __launch_bounds__(kBlock) void nn_direct_kernel(
-    const float* __restrict__ coords, uint32_t n_rows, const float* __restrict__ fe,
-    uint32_t i_from, uint32_t i_to, uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2,
-    uint32_t* __restrict__ hd_idx, float* __restrict__ hd_d2, const uint32_t* __restrict__ gate) {
+    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_ref,
+    const float* __restrict__ fe_q, const float* __restrict__ fe_r, uint32_t i_from, uint32_t i_to,
+    uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx,
+    float* __restrict__ hd_d2, const uint32_t* __restrict__ gate) {
   constexpr int S = Cfg<D>::S, Q = Cfg<D>::Q;
   if (gate && gate[1] == 0) return;
   __shared__ __attribute__((aligned(16))) float tile[kTile * S];
   __shared__ float tile_fe[kTile];
   const uint32_t qbase = i_from + blockIdx.x * (kBlock * Q);
   const uint32_t qend = min(qbase + kBlock * Q, i_to);   // this workgroup's rows: [qbase, qend)
+  if constexpr (M == kSelf) rcoords = qcoords, fe_r = fe_q;
+  const bool with_fe = (M == kSelf) || fe_q;            // (a self sweep always has free energies)
 
   float q[Q][D], qfe[Q], best[Q], bhd[Q];
   uint32_t qi[Q], bj[Q], bjhd[Q];
@@ -174,22 +184,22 @@ __global__ __launch_bounds__(kBlock) void nn_direct_kernel(
     qi[a] = qbase + a * kBlock + threadIdx.x;
     const uint32_t row = qi[a] < i_to ? qi[a] : i_to - 1;
 #pragma unroll
-    for (int k = 0; k < D; ++k) q[a][k] = coords[(size_t)row * D + k];
-    qfe[a] = fe[row];
+    for (int k = 0; k < D; ++k) q[a][k] = qcoords[(size_t)row * D + k];
+    qfe[a] = with_fe ? fe_q[row] : -INFINITY;   // (no free energies: nothing is lower)
     best[a] = FLT_MAX;       // :257-260
     bhd[a] = FLT_MAX;
-    bj[a] = n_rows + 1;
-    bjhd[a] = n_rows + 1;
+    bj[a] = n_ref + 1;
+    bjhd[a] = n_ref + 1;
   }
 
-  for (uint32_t t0 = 0; t0 < n_rows; t0 += kTile) {
-    const uint32_t nt = min((uint32_t)kTile, n_rows - t0);
+  for (uint32_t t0 = 0; t0 < n_ref; t0 += kTile) {
+    const uint32_t nt = min((uint32_t)kTile, n_ref - t0);
     __syncthreads();
-    stage_tile<D>(coords, t0, nt, tile);
-    if (threadIdx.x < nt) tile_fe[threadIdx.x] = fe[t0 + threadIdx.x];
+    stage_tile<D>(rcoords, t0, nt, tile);
+    if (threadIdx.x < nt) tile_fe[threadIdx.x] = with_fe ? fe_r[t0 + threadIdx.x] : 0.0f;
     __syncthreads();
     // only tiles that overlap this workgroup's own rows can contain a self pair
-    if (t0 < qend && t0 + nt > qbase)
+    if (M == kSelf && t0 < qend && t0 + nt > qbase)
       nn_tile<D, Q, true>(tile, tile_fe, t0, nt, q, qi, qfe, best, bj, bhd, bjhd);
     else
       nn_tile<D, Q, false>(tile, tile_fe, t0, nt, q, qi, qfe, best, bj, bhd, bjhd);
@@ -199,38 +209,40 @@ __global__ __launch_bounds__(kBlock) void nn_direct_kernel(
     if (qi[a] < i_to) {
       nn_idx[qi[a]] = bj[a];
       nn_d2[qi[a]] = best[a];
-      hd_idx[qi[a]] = bjhd[a];
-      hd_d2[qi[a]] = bhd[a];
+      if (with_fe) {
+        hd_idx[qi[a]] = bjhd[a];
+        hd_d2[qi[a]] = bhd[a];
+      }
     }
   }
 }
 
 // -----------------------------------------------------------------------------------------
 // generic n_cols (33..kMaxColsGeneric): query rows live in LDS, lane-major ([k][lane], no bank
-// conflicts); 64 lanes per workgroup, 32 reference rows per tile.  Same arithmetic.
+// conflicts); 64 lanes per workgroup, 32 reference rows per tile.  Same arithmetic, same modes.
 // -----------------------------------------------------------------------------------------
 constexpr int kGBlock = 64, kGTile = 32;
 
-__global__ __launch_bounds__(kGBlock) void pop_generic_kernel(const float* __restrict__ coords,
-                                                              uint32_t n_rows, uint32_t D,
-                                                              uint32_t i_from, uint32_t i_to,
-                                                              Rad2 rad2, int n_rad,
-                                                              uint32_t* __restrict__ pops,
-                                                              const uint32_t* __restrict__ gate) {
+template <SweepMode M>
+__global__ __launch_bounds__(kGBlock) void pop_generic_kernel(
+    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_q, uint32_t n_ref,
+    uint32_t D, uint32_t i_from, uint32_t i_to, Rad2 rad2, int n_rad, uint32_t* __restrict__ pops,
+    const uint32_t* __restrict__ gate) {
   if (gate && gate[1] == 0) return;
+  if constexpr (M == kSelf) rcoords = qcoords, n_q = n_ref;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* qs = smem;                        // [D][kGBlock]
   float* tile = smem + (size_t)D * kGBlock;  // [kGTile][D]
   const uint32_t qi = i_from + blockIdx.x * kGBlock + threadIdx.x;
   const uint32_t row = qi < i_to ? qi : i_to - 1;
-  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = coords[(size_t)row * D + k];
+  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = qcoords[(size_t)row * D + k];
   uint32_t cnt[kMaxRadiiPerLaunch];
 #pragma unroll
   for (int r = 0; r < kMaxRadiiPerLaunch; ++r) cnt[r] = 0;
-  for (uint32_t t0 = 0; t0 < n_rows; t0 += kGTile) {
-    const uint32_t nt = min((uint32_t)kGTile, n_rows - t0);
+  for (uint32_t t0 = 0; t0 < n_ref; t0 += kGTile) {
+    const uint32_t nt = min((uint32_t)kGTile, n_ref - t0);
     __syncthreads();
-    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = coords[(size_t)t0 * D + e];
+    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = rcoords[(size_t)t0 * D + e];
     __syncthreads();
     for (uint32_t r = 0; r < nt; ++r) {
       const float d = dist2_canon_rt(qs + threadIdx.x, kGBlock, tile + r * D, 1, (int)D);
@@ -239,39 +251,44 @@ __global__ __launch_bounds__(kGBlock) void pop_generic_kernel(const float* __res
     }
   }
   if (qi < i_to) {
-    const float dself = dist2_canon_rt(qs + threadIdx.x, kGBlock, qs + threadIdx.x, kGBlock, (int)D);
+    const float dself =
+        (M == kSelf) ? dist2_canon_rt(qs + threadIdx.x, kGBlock, qs + threadIdx.x, kGBlock, (int)D) : 0.0f;
 #pragma unroll
     for (int rr = 0; rr < kMaxRadiiPerLaunch; ++rr)
       if (rr < n_rad)
-        pops[(size_t)rr * n_rows + qi] = cnt[rr] + 1u - ((dself < rad2.v[rr]) ? 1u : 0u);
+        pops[(size_t)rr * n_q + qi] = (M == kSelf) ? cnt[rr] + 1u - ((dself < rad2.v[rr]) ? 1u : 0u) : cnt[rr];
   }
 }
 
+template <SweepMode M>
 __global__ __launch_bounds__(kGBlock) void nn_generic_kernel(
-    const float* __restrict__ coords, uint32_t n_rows, uint32_t D, const float* __restrict__ fe,
-    uint32_t i_from, uint32_t i_to, uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2,
-    uint32_t* __restrict__ hd_idx, float* __restrict__ hd_d2, const uint32_t* __restrict__ gate) {
+    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_ref, uint32_t D,
+    const float* __restrict__ fe_q, const float* __restrict__ fe_r, uint32_t i_from, uint32_t i_to,
+    uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx,
+    float* __restrict__ hd_d2, const uint32_t* __restrict__ gate) {
   if (gate && gate[1] == 0) return;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* qs = smem;
   float* tile = smem + (size_t)D * kGBlock;
   float* tile_fe = tile + (size_t)kGTile * D;
+  if constexpr (M == kSelf) rcoords = qcoords, fe_r = fe_q;
+  const bool with_fe = (M == kSelf) || fe_q;
   const uint32_t qi = i_from + blockIdx.x * kGBlock + threadIdx.x;
   const uint32_t row = qi < i_to ? qi : i_to - 1;
-  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = coords[(size_t)row * D + k];
-  const float qfe = fe[row];
+  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = qcoords[(size_t)row * D + k];
+  const float qfe = with_fe ? fe_q[row] : -INFINITY;
   float best = FLT_MAX, bhd = FLT_MAX;
-  uint32_t bj = n_rows + 1, bjhd = n_rows + 1;
-  for (uint32_t t0 = 0; t0 < n_rows; t0 += kGTile) {
-    const uint32_t nt = min((uint32_t)kGTile, n_rows - t0);
+  uint32_t bj = n_ref + 1, bjhd = n_ref + 1;
+  for (uint32_t t0 = 0; t0 < n_ref; t0 += kGTile) {
+    const uint32_t nt = min((uint32_t)kGTile, n_ref - t0);
     __syncthreads();
-    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = coords[(size_t)t0 * D + e];
-    if (threadIdx.x < nt) tile_fe[threadIdx.x] = fe[t0 + threadIdx.x];
+    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = rcoords[(size_t)t0 * D + e];
+    if (threadIdx.x < nt) tile_fe[threadIdx.x] = with_fe ? fe_r[t0 + threadIdx.x] : 0.0f;
     __syncthreads();
     for (uint32_t r = 0; r < nt; ++r) {
       const uint32_t j = t0 + r;
       const float d = dist2_canon_rt(qs + threadIdx.x, kGBlock, tile + r * D, 1, (int)D);
-      const bool other = (j != qi);
+      const bool other = (M != kSelf) || (j != qi);
       const bool lt = other && (d < best);
       const bool lh = other && (tile_fe[r] < qfe) && (d < bhd);
       best = lt ? d : best;
@@ -283,181 +300,7 @@ __global__ __launch_bounds__(kGBlock) void nn_generic_kernel(
   if (qi < i_to) {
     nn_idx[qi] = bj;
     nn_d2[qi] = best;
-    hd_idx[qi] = bjhd;
-    hd_d2[qi] = bhd;
-  }
-}
-
-// -----------------------------------------------------------------------------------------
-// cross sweeps: query rows of one array against every row of another (dc_hip_*_cross_dev).  The
-// shapes and the arithmetic of the kernels above; no pair is left out and nothing is added:
-//   pops[r][q] = #{ j < n_ref : d2(Q_q, R_j) < rad2[r] }
-//   nn[q]      = lexicographic min of (d2, j) over all j;  hd[q]: the same over fe_r[j] < fe_q[q]
-// "none" is (n_ref + 1, FLT_MAX).  fe_q == nullptr: neighbours only (hd is not written).
-// -----------------------------------------------------------------------------------------
-template <int D, int NR>
-__global__ __launch_bounds__(kBlock) void pop_cross_direct_kernel(
-    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_q, uint32_t n_ref,
-    uint32_t i_from, uint32_t i_to, Rad2 rad2, int n_rad, uint32_t* __restrict__ pops,
-    const uint32_t* __restrict__ gate) {
-  constexpr int S = Cfg<D>::S, Q = Cfg<D>::Q;
-  if (gate && gate[1] == 0) return;
-  __shared__ __attribute__((aligned(16))) float tile[kTile * S];
-  const uint32_t qbase = i_from + blockIdx.x * (kBlock * Q);
-  float q[Q][D];
-  uint32_t qi[Q], cnt[Q][NR];
-#pragma unroll
-  for (int a = 0; a < Q; ++a) {
-    qi[a] = qbase + a * kBlock + threadIdx.x;
-    const uint32_t row = qi[a] < i_to ? qi[a] : i_to - 1;   // clamp: result discarded
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[a][k] = qcoords[(size_t)row * D + k];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) cnt[a][r] = 0;
-  }
-  for (uint32_t t0 = 0; t0 < n_ref; t0 += kTile) {
-    const uint32_t nt = min((uint32_t)kTile, n_ref - t0);
-    __syncthreads();
-    stage_tile<D>(rcoords, t0, nt, tile);
-    __syncthreads();
-#pragma unroll 2
-    for (uint32_t r = 0; r < nt; ++r) {
-      float ref[D];
-      load_ref<D>(tile, r, ref);
-#pragma unroll
-      for (int a = 0; a < Q; ++a) {
-        const float d = dist2_canon<D>(q[a], ref);
-#pragma unroll
-        for (int rr = 0; rr < NR; ++rr) cnt[a][rr] += (d < rad2.v[rr]) ? 1u : 0u;
-      }
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < Q; ++a)
-    if (qi[a] < i_to) {
-#pragma unroll
-      for (int rr = 0; rr < NR; ++rr)
-        if (rr < n_rad) pops[(size_t)rr * n_q + qi[a]] = cnt[a][rr];
-    }
-}
-
-template <int D>
-__global__ __launch_bounds__(kBlock) void nn_cross_direct_kernel(
-    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_ref,
-    const float* __restrict__ fe_q, const float* __restrict__ fe_r, uint32_t i_from, uint32_t i_to,
-    uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx,
-    float* __restrict__ hd_d2, const uint32_t* __restrict__ gate) {
-  constexpr int S = Cfg<D>::S, Q = Cfg<D>::Q;
-  if (gate && gate[1] == 0) return;
-  __shared__ __attribute__((aligned(16))) float tile[kTile * S];
-  __shared__ float tile_fe[kTile];
-  const uint32_t qbase = i_from + blockIdx.x * (kBlock * Q);
-  float q[Q][D], qfe[Q], best[Q], bhd[Q];
-  uint32_t qi[Q], bj[Q], bjhd[Q];
-#pragma unroll
-  for (int a = 0; a < Q; ++a) {
-    qi[a] = qbase + a * kBlock + threadIdx.x;
-    const uint32_t row = qi[a] < i_to ? qi[a] : i_to - 1;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[a][k] = qcoords[(size_t)row * D + k];
-    qfe[a] = fe_q ? fe_q[row] : -INFINITY;   // (no free energies: nothing is lower)
-    best[a] = FLT_MAX;
-    bhd[a] = FLT_MAX;
-    bj[a] = n_ref + 1;
-    bjhd[a] = n_ref + 1;
-  }
-  const uint32_t no_qi[Q] = {};   // (nn_tile without its diagonal test never reads them)
-  for (uint32_t t0 = 0; t0 < n_ref; t0 += kTile) {
-    const uint32_t nt = min((uint32_t)kTile, n_ref - t0);
-    __syncthreads();
-    stage_tile<D>(rcoords, t0, nt, tile);
-    if (threadIdx.x < nt) tile_fe[threadIdx.x] = fe_q ? fe_r[t0 + threadIdx.x] : 0.0f;
-    __syncthreads();
-    nn_tile<D, Q, false>(tile, tile_fe, t0, nt, q, no_qi, qfe, best, bj, bhd, bjhd);
-  }
-#pragma unroll
-  for (int a = 0; a < Q; ++a) {
-    if (qi[a] < i_to) {
-      nn_idx[qi[a]] = bj[a];
-      nn_d2[qi[a]] = best[a];
-      if (fe_q) {
-        hd_idx[qi[a]] = bjhd[a];
-        hd_d2[qi[a]] = bhd[a];
-      }
-    }
-  }
-}
-
-// generic n_cols (33..kMaxColsGeneric): the LDS layout of pop_generic_kernel / nn_generic_kernel
-__global__ __launch_bounds__(kGBlock) void pop_cross_generic_kernel(
-    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_q, uint32_t n_ref,
-    uint32_t D, uint32_t i_from, uint32_t i_to, Rad2 rad2, int n_rad, uint32_t* __restrict__ pops,
-    const uint32_t* __restrict__ gate) {
-  if (gate && gate[1] == 0) return;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* qs = smem;                          // [D][kGBlock]
-  float* tile = smem + (size_t)D * kGBlock;  // [kGTile][D]
-  const uint32_t qi = i_from + blockIdx.x * kGBlock + threadIdx.x;
-  const uint32_t row = qi < i_to ? qi : i_to - 1;
-  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = qcoords[(size_t)row * D + k];
-  uint32_t cnt[kMaxRadiiPerLaunch];
-#pragma unroll
-  for (int r = 0; r < kMaxRadiiPerLaunch; ++r) cnt[r] = 0;
-  for (uint32_t t0 = 0; t0 < n_ref; t0 += kGTile) {
-    const uint32_t nt = min((uint32_t)kGTile, n_ref - t0);
-    __syncthreads();
-    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = rcoords[(size_t)t0 * D + e];
-    __syncthreads();
-    for (uint32_t r = 0; r < nt; ++r) {
-      const float d = dist2_canon_rt(qs + threadIdx.x, kGBlock, tile + r * D, 1, (int)D);
-#pragma unroll
-      for (int rr = 0; rr < kMaxRadiiPerLaunch; ++rr) cnt[rr] += (d < rad2.v[rr]) ? 1u : 0u;
-    }
-  }
-  if (qi < i_to) {
-#pragma unroll
-    for (int rr = 0; rr < kMaxRadiiPerLaunch; ++rr)
-      if (rr < n_rad) pops[(size_t)rr * n_q + qi] = cnt[rr];
-  }
-}
-
-__global__ __launch_bounds__(kGBlock) void nn_cross_generic_kernel(
-    const float* __restrict__ qcoords, const float* __restrict__ rcoords, uint32_t n_ref, uint32_t D,
-    const float* __restrict__ fe_q, const float* __restrict__ fe_r, uint32_t i_from, uint32_t i_to,
-    uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx,
-    float* __restrict__ hd_d2, const uint32_t* __restrict__ gate) {
-  if (gate && gate[1] == 0) return;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* qs = smem;
-  float* tile = smem + (size_t)D * kGBlock;
-  float* tile_fe = tile + (size_t)kGTile * D;
-  const uint32_t qi = i_from + blockIdx.x * kGBlock + threadIdx.x;
-  const uint32_t row = qi < i_to ? qi : i_to - 1;
-  for (uint32_t k = 0; k < D; ++k) qs[k * kGBlock + threadIdx.x] = qcoords[(size_t)row * D + k];
-  const float qfe = fe_q ? fe_q[row] : -INFINITY;
-  float best = FLT_MAX, bhd = FLT_MAX;
-  uint32_t bj = n_ref + 1, bjhd = n_ref + 1;
-  for (uint32_t t0 = 0; t0 < n_ref; t0 += kGTile) {
-    const uint32_t nt = min((uint32_t)kGTile, n_ref - t0);
-    __syncthreads();
-    for (uint32_t e = threadIdx.x; e < nt * D; e += kGBlock) tile[e] = rcoords[(size_t)t0 * D + e];
-    if (threadIdx.x < nt) tile_fe[threadIdx.x] = fe_q ? fe_r[t0 + threadIdx.x] : 0.0f;
-    __syncthreads();
-    for (uint32_t r = 0; r < nt; ++r) {
-      const uint32_t j = t0 + r;
-      const float d = dist2_canon_rt(qs + threadIdx.x, kGBlock, tile + r * D, 1, (int)D);
-      const bool lt = d < best;
-      const bool lh = (tile_fe[r] < qfe) && (d < bhd);
-      best = lt ? d : best;
-      bj = lt ? j : bj;
-      bhd = lh ? d : bhd;
-      bjhd = lh ? j : bjhd;
-    }
-  }
-  if (qi < i_to) {
-    nn_idx[qi] = bj;
-    nn_d2[qi] = best;
-    if (fe_q) {
+    if (with_fe) {
       hd_idx[qi] = bjhd;
       hd_d2[qi] = bhd;
     }
@@ -623,20 +466,9 @@ __global__ __launch_bounds__(kGBlock) void graph_generic_kernel(const float* __r
 // -----------------------------------------------------------------------------------------
 // small helpers
 // -----------------------------------------------------------------------------------------
-__global__ void nn_init_kernel(uint32_t n_rows, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx,
+// every query row starts at "none" = (none, FLT_MAX) (density_clustering.cpp:242-245); hd may be absent (nn only)
+__global__ void nn_init_kernel(uint32_t n_q, uint32_t none, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx,
                                float* hd_d2) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_rows) {
-    nn_idx[i] = n_rows + 1;
-    hd_idx[i] = n_rows + 1;
-    nn_d2[i] = FLT_MAX;
-    hd_d2[i] = FLT_MAX;
-  }
-}
-
-// cross sweeps: every query row starts at "none" = (n_ref + 1, FLT_MAX); hd may be absent (nn only)
-__global__ void nn_init_cross_kernel(uint32_t n_q, uint32_t none, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx,
-                                     float* hd_d2) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_q) {
     nn_idx[i] = none;
@@ -738,82 +570,44 @@ __global__ void max_u32_kernel(const uint32_t* __restrict__ v, uint32_t n, uint3
 }
 
 // ---- dispatch tables over n_cols ---------------------------------------------------------
-using PopLaunch = void (*)(const float*, uint32_t, uint32_t, uint32_t, const Rad2&, int, uint32_t*,
-                           const uint32_t*, hipStream_t);
-using NnLaunch = void (*)(const float*, uint32_t, const float*, uint32_t, uint32_t, uint32_t*,
-                          float*, uint32_t*, float*, const uint32_t*, hipStream_t);
+using PopLaunch = void (*)(const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, const Rad2&, int,
+                           uint32_t*, const uint32_t*, hipStream_t);
+using NnLaunch = void (*)(const float*, const float*, uint32_t, const float*, const float*, uint32_t, uint32_t,
+                          uint32_t*, float*, uint32_t*, float*, const uint32_t*, hipStream_t);
 
-template <int D, int NR>
-void pop_launch(const float* c, uint32_t n, uint32_t i_from, uint32_t i_to, const Rad2& rad2,
-                int n_rad, uint32_t* pops, const uint32_t* gate, hipStream_t s) {
+template <int D, int NR, SweepMode M>
+void pop_launch(const float* qc, const float* rc, uint32_t n_q, uint32_t n_ref, uint32_t i_from, uint32_t i_to,
+                const Rad2& rad2, int n_rad, uint32_t* pops, const uint32_t* gate, hipStream_t s) {
   const uint32_t per_block = kBlock * Cfg<D>::Q;
   const uint32_t grid = (i_to - i_from + per_block - 1) / per_block;
-  hipLaunchKernelGGL((pop_direct_kernel<D, NR>), dim3(grid), dim3(kBlock), 0, s, c, n, i_from,
-                     i_to, rad2, n_rad, pops, gate);
-}
-
-template <int D>
-void nn_launch(const float* c, uint32_t n, const float* fe, uint32_t i_from, uint32_t i_to,
-               uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2, const uint32_t* gate,
-               hipStream_t s) {
-  const uint32_t per_block = kBlock * Cfg<D>::Q;
-  const uint32_t grid = (i_to - i_from + per_block - 1) / per_block;
-  hipLaunchKernelGGL((nn_direct_kernel<D>), dim3(grid), dim3(kBlock), 0, s, c, n, fe, i_from, i_to,
-                     nn_idx, nn_d2, hd_idx, hd_d2, gate);
-}
-
-template <int NR, int... Ds>
-constexpr auto make_pop_table(std::integer_sequence<int, Ds...>) {
-  return std::array<PopLaunch, sizeof...(Ds)>{&pop_launch<Ds + 1, NR>...};
-}
-template <int... Ds>
-constexpr auto make_nn_table(std::integer_sequence<int, Ds...>) {
-  return std::array<NnLaunch, sizeof...(Ds)>{&nn_launch<Ds + 1>...};
-}
-
-using DSeq = std::make_integer_sequence<int, kMaxColsTemplated>;
-const auto kPop1 = make_pop_table<1>(DSeq{});
-const auto kPop4 = make_pop_table<4>(DSeq{});
-const auto kPop8 = make_pop_table<8>(DSeq{});
-const auto kNn = make_nn_table(DSeq{});
-
-using PopCrossLaunch = void (*)(const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, const Rad2&, int,
-                                uint32_t*, const uint32_t*, hipStream_t);
-using NnCrossLaunch = void (*)(const float*, const float*, uint32_t, const float*, const float*, uint32_t, uint32_t,
-                               uint32_t*, float*, uint32_t*, float*, const uint32_t*, hipStream_t);
-
-template <int D, int NR>
-void pop_cross_launch(const float* qc, const float* rc, uint32_t n_q, uint32_t n_ref, uint32_t i_from, uint32_t i_to,
-                      const Rad2& rad2, int n_rad, uint32_t* pops, const uint32_t* gate, hipStream_t s) {
-  const uint32_t per_block = kBlock * Cfg<D>::Q;
-  const uint32_t grid = (i_to - i_from + per_block - 1) / per_block;
-  hipLaunchKernelGGL((pop_cross_direct_kernel<D, NR>), dim3(grid), dim3(kBlock), 0, s, qc, rc, n_q, n_ref, i_from, i_to,
+  hipLaunchKernelGGL((pop_direct_kernel<D, NR, M>), dim3(grid), dim3(kBlock), 0, s, qc, rc, n_q, n_ref, i_from, i_to,
                      rad2, n_rad, pops, gate);
 }
 
-template <int D>
-void nn_cross_launch(const float* qc, const float* rc, uint32_t n_ref, const float* fe_q, const float* fe_r,
-                     uint32_t i_from, uint32_t i_to, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2,
-                     const uint32_t* gate, hipStream_t s) {
+template <int D, SweepMode M>
+void nn_launch(const float* qc, const float* rc, uint32_t n_ref, const float* fe_q, const float* fe_r,
+               uint32_t i_from, uint32_t i_to, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2,
+               const uint32_t* gate, hipStream_t s) {
   const uint32_t per_block = kBlock * Cfg<D>::Q;
   const uint32_t grid = (i_to - i_from + per_block - 1) / per_block;
-  hipLaunchKernelGGL((nn_cross_direct_kernel<D>), dim3(grid), dim3(kBlock), 0, s, qc, rc, n_ref, fe_q, fe_r, i_from,
+  hipLaunchKernelGGL((nn_direct_kernel<D, M>), dim3(grid), dim3(kBlock), 0, s, qc, rc, n_ref, fe_q, fe_r, i_from,
                      i_to, nn_idx, nn_d2, hd_idx, hd_d2, gate);
 }
 
-template <int NR, int... Ds>
-constexpr auto make_pop_cross_table(std::integer_sequence<int, Ds...>) {
-  return std::array<PopCrossLaunch, sizeof...(Ds)>{&pop_cross_launch<Ds + 1, NR>...};
+template <int NR, SweepMode M, int... Ds>
+constexpr auto make_pop_table(std::integer_sequence<int, Ds...>) {
+  return std::array<PopLaunch, sizeof...(Ds)>{&pop_launch<Ds + 1, NR, M>...};
 }
-template <int... Ds>
-constexpr auto make_nn_cross_table(std::integer_sequence<int, Ds...>) {
-  return std::array<NnCrossLaunch, sizeof...(Ds)>{&nn_cross_launch<Ds + 1>...};
+template <SweepMode M, int... Ds>
+constexpr auto make_nn_table(std::integer_sequence<int, Ds...>) {
+  return std::array<NnLaunch, sizeof...(Ds)>{&nn_launch<Ds + 1, M>...};
 }
 
-const auto kPopCross1 = make_pop_cross_table<1>(DSeq{});
-const auto kPopCross4 = make_pop_cross_table<4>(DSeq{});
-const auto kPopCross8 = make_pop_cross_table<8>(DSeq{});
-const auto kNnCross = make_nn_cross_table(DSeq{});
+using DSeq = std::make_integer_sequence<int, kMaxColsTemplated>;
+template <int NR, SweepMode M>
+const auto kPop = make_pop_table<NR, M>(DSeq{});
+template <SweepMode M>
+const auto kNn = make_nn_table<M>(DSeq{});
 
 using GraphLaunch = void (*)(const float*, uint32_t, uint32_t, uint32_t, float, const GraphOut&, const uint32_t*,
                              hipStream_t);
@@ -858,97 +652,70 @@ bool launch_graph(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint3
   return false;
 }
 
-}  // namespace
-
-bool launch_pop_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from,
-                       uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops,
-                       const uint32_t* gate, hipStream_t stream) {
-  if (i_to <= i_from || n_rad <= 0) return true;
-  if (n_cols >= 1 && n_cols <= (uint32_t)kMaxColsTemplated) {
-    // instances exist for 1, 4 and 8 radius slots; unused slots hold -1 ("d < -1" is never true)
-    const auto& tab = (n_rad == 1) ? kPop1 : (n_rad <= 4 ? kPop4 : kPop8);
-    tab[n_cols - 1](d_coords, n_rows, i_from, i_to, rad2, n_rad, d_pops, gate, stream);
-    return true;
-  }
-  if (n_cols > (uint32_t)kMaxColsTemplated && n_cols <= (uint32_t)kMaxColsGeneric) {
-    const uint32_t grid = (i_to - i_from + kGBlock - 1) / kGBlock;
-    const size_t smem = sizeof(float) * (size_t)n_cols * (kGBlock + kGTile);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pop_generic_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(pop_generic_kernel, dim3(grid), dim3(kGBlock), smem, stream, d_coords,
-                       n_rows, n_cols, i_from, i_to, rad2, n_rad, d_pops, gate);
-    return true;
-  }
-  if (n_cols > (uint32_t)kMaxColsGeneric) {
-    launch_pop_wide(d_coords, n_rows, n_cols, i_from, i_to, rad2, n_rad, d_pops, gate, stream);
-    return true;
-  }
-  return false;
-}
-
-bool launch_nn_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe,
-                      uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
-                      uint32_t* d_hd_idx, float* d_hd_d2, const uint32_t* gate, hipStream_t stream) {
-  if (i_to <= i_from) return true;
-  if (n_cols >= 1 && n_cols <= (uint32_t)kMaxColsTemplated) {
-    kNn[n_cols - 1](d_coords, n_rows, d_fe, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2,
-                    gate, stream);
-    return true;
-  }
-  if (n_cols > (uint32_t)kMaxColsTemplated && n_cols <= (uint32_t)kMaxColsGeneric) {
-    const uint32_t grid = (i_to - i_from + kGBlock - 1) / kGBlock;
-    const size_t smem = sizeof(float) * ((size_t)n_cols * (kGBlock + kGTile) + kGTile);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nn_generic_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(nn_generic_kernel, dim3(grid), dim3(kGBlock), smem, stream, d_coords,
-                       n_rows, n_cols, d_fe, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, gate);
-    return true;
-  }
-  if (n_cols > (uint32_t)kMaxColsGeneric) {
-    launch_nn_wide(d_coords, n_rows, n_cols, d_fe, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, gate, stream);
-    return true;
-  }
-  return false;
-}
-
-void launch_pop_cross_direct(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
-                             uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops,
-                             const uint32_t* gate, hipStream_t stream) {
-  if (i_to <= i_from || n_rad <= 0 || n_ref == 0) return;
+template <SweepMode M>
+void pop_direct(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
+                uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops, const uint32_t* gate,
+                hipStream_t stream) {
   if (n_cols <= (uint32_t)kMaxColsTemplated) {
-    const auto& tab = (n_rad == 1) ? kPopCross1 : (n_rad <= 4 ? kPopCross4 : kPopCross8);
+    // instances exist for 1, 4 and 8 radius slots; unused slots hold -1 ("d < -1" is never true)
+    const auto& tab = (n_rad == 1) ? kPop<1, M> : (n_rad <= 4 ? kPop<4, M> : kPop<8, M>);
     tab[n_cols - 1](d_query, d_ref, n_q, n_ref, i_from, i_to, rad2, n_rad, d_pops, gate, stream);
   } else if (n_cols <= (uint32_t)kMaxColsGeneric) {
     const uint32_t grid = (i_to - i_from + kGBlock - 1) / kGBlock;
     const size_t smem = sizeof(float) * (size_t)n_cols * (kGBlock + kGTile);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pop_cross_generic_kernel),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pop_generic_kernel<M>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(pop_cross_generic_kernel, dim3(grid), dim3(kGBlock), smem, stream, d_query, d_ref, n_q, n_ref,
+    hipLaunchKernelGGL(pop_generic_kernel<M>, dim3(grid), dim3(kGBlock), smem, stream, d_query, d_ref, n_q, n_ref,
                        n_cols, i_from, i_to, rad2, n_rad, d_pops, gate);
+  } else if (M == kSelf) {
+    launch_pop_wide(d_query, n_q, n_cols, i_from, i_to, rad2, n_rad, d_pops, gate, stream);
   } else {
     launch_pop_cross_wide(d_query, d_ref, n_q, n_ref, n_cols, i_from, i_to, rad2, n_rad, d_pops, gate, stream);
   }
 }
 
-void launch_nn_cross_direct(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
-                            const float* d_fe_q, const float* d_fe_r, uint32_t i_from, uint32_t i_to,
-                            uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
-                            const uint32_t* gate, hipStream_t stream) {
-  if (i_to <= i_from || n_ref == 0) return;
+template <SweepMode M>
+void nn_direct(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols, const float* d_fe_q,
+               const float* d_fe_r, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+               uint32_t* d_hd_idx, float* d_hd_d2, const uint32_t* gate, hipStream_t stream) {
   if (n_cols <= (uint32_t)kMaxColsTemplated) {
-    kNnCross[n_cols - 1](d_query, d_ref, n_ref, d_fe_q, d_fe_r, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2,
-                         gate, stream);
+    kNn<M>[n_cols - 1](d_query, d_ref, n_ref, d_fe_q, d_fe_r, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2,
+                       gate, stream);
   } else if (n_cols <= (uint32_t)kMaxColsGeneric) {
     const uint32_t grid = (i_to - i_from + kGBlock - 1) / kGBlock;
     const size_t smem = sizeof(float) * ((size_t)n_cols * (kGBlock + kGTile) + kGTile);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nn_cross_generic_kernel),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nn_generic_kernel<M>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(nn_cross_generic_kernel, dim3(grid), dim3(kGBlock), smem, stream, d_query, d_ref, n_ref, n_cols,
+    hipLaunchKernelGGL(nn_generic_kernel<M>, dim3(grid), dim3(kGBlock), smem, stream, d_query, d_ref, n_ref, n_cols,
                        d_fe_q, d_fe_r, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, gate);
+  } else if (M == kSelf) {
+    launch_nn_wide(d_query, n_ref, n_cols, d_fe_q, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, gate, stream);
   } else {
     launch_nn_cross_wide(d_query, d_ref, n_ref, n_cols, d_fe_q, d_fe_r, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx,
                          d_hd_d2, gate, stream);
   }
+}
+
+}  // namespace
+
+bool launch_pop_direct(const float* d_query, const float* d_ref, uint32_t n_q, uint32_t n_ref, uint32_t n_cols,
+                       uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops, SweepMode mode,
+                       const uint32_t* gate, hipStream_t stream) {
+  if (i_to <= i_from || n_rad <= 0 || n_ref == 0) return true;
+  if (n_cols == 0) return false;
+  (mode == kSelf ? pop_direct<kSelf> : pop_direct<kAgainst>)(d_query, d_ref, n_q, n_ref, n_cols, i_from, i_to, rad2,
+                                                             n_rad, d_pops, gate, stream);
+  return true;
+}
+
+bool launch_nn_direct(const float* d_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols, const float* d_fe_q,
+                      const float* d_fe_r, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+                      uint32_t* d_hd_idx, float* d_hd_d2, SweepMode mode, const uint32_t* gate, hipStream_t stream) {
+  if (i_to <= i_from || n_ref == 0) return true;
+  if (n_cols == 0) return false;
+  (mode == kSelf ? nn_direct<kSelf> : nn_direct<kAgainst>)(d_query, d_ref, n_ref, n_cols, d_fe_q, d_fe_r, i_from,
+                                                           i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, gate, stream);
+  return true;
 }
 
 bool launch_pairs_direct(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops,
@@ -974,18 +741,11 @@ bool launch_min_edge_direct(const float* d_coords, uint32_t n_rows, uint32_t n_c
   return launch_graph<kGraphMinEdge>(d_coords, n_rows, n_cols, i_from, i_to, r2, g, gate, stream);
 }
 
-void launch_nn_init(uint32_t n_rows, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+void launch_nn_init(uint32_t n_q, uint32_t n_ref, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                     float* d_hd_d2, hipStream_t stream) {
-  if (n_rows == 0) return;
-  hipLaunchKernelGGL(nn_init_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, stream, n_rows,
-                     d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
-}
-
-void launch_nn_init_cross(uint32_t n_q, uint32_t n_ref, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
-                          float* d_hd_d2, hipStream_t stream) {
   if (n_q == 0) return;
-  hipLaunchKernelGGL(nn_init_cross_kernel, dim3((n_q + 255) / 256), dim3(256), 0, stream, n_q, n_ref + 1, d_nn_idx,
-                     d_nn_d2, d_hd_idx, d_hd_d2);
+  hipLaunchKernelGGL(nn_init_kernel, dim3((n_q + 255) / 256), dim3(256), 0, stream, n_q, n_ref + 1, d_nn_idx, d_nn_d2,
+                     d_hd_idx, d_hd_d2);
 }
 
 void launch_fe_gather(const uint32_t* d_pops, uint32_t n_rows, const float* d_table, float* d_fe,

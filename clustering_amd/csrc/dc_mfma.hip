@@ -358,28 +358,13 @@ __global__ void fe_scatter_kernel(const uint32_t* __restrict__ perm, const float
   }
 }
 
-// pq[i] = #{ p : fe_s[p] < fe[i] }  (float comparison, exactly the reference's "fe[j] < fe[i]")
-__global__ void fe_rank_kernel(const float* __restrict__ fe, const float* __restrict__ fe_s,
-                               uint32_t n_rows, uint32_t* __restrict__ pq) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_rows) return;
-  const float f = fe[i];
-  uint32_t lo = 0, hi = n_rows;   // first position whose value is not < f
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (fe_s[mid] < f) lo = mid + 1; else hi = mid;
-  }
-  pq[i] = lo;
-}
-
-
-// cross sweeps: pq[q] = #{ p < n_ref : fe_s[p] < fe_q[q] } -- fe_rank_kernel for queries of another array
-__global__ void fe_rank_cross_kernel(const float* __restrict__ fe_q, uint32_t n_q, const float* __restrict__ fe_s,
-                                     uint32_t n_ref, uint32_t* __restrict__ pq) {
+// pq[q] = #{ p < n_ref : fe_s[p] < fe_q[q] }  (float comparison, exactly the reference's "fe[j] < fe[i]")
+__global__ void fe_rank_kernel(const float* __restrict__ fe_q, uint32_t n_q, const float* __restrict__ fe_s,
+                               uint32_t n_ref, uint32_t* __restrict__ pq) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_q) return;
   const float f = fe_q[i];
-  uint32_t lo = 0, hi = n_ref;
+  uint32_t lo = 0, hi = n_ref;   // first position whose value is not < f
   while (lo < hi) {
     const uint32_t mid = (lo + hi) >> 1;
     if (fe_s[mid] < f) lo = mid + 1; else hi = mid;
@@ -1131,43 +1116,94 @@ static float max_radius2(const Rad2& rad2, int n_rad) {
   for (int r = 0; r < n_rad; ++r) m = std::max(m, rad2.v[r]);
   return m;
 }
-// operand images of the frames in natural order (the full sweeps): A form + norms and / or B form
-static void natural_images(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, bool a_form,
-                           bool b_form, hipStream_t stream) {
-  const Layout L = make_layout(n_rows, n_cols);
+// One unpruned sweep per radius (see single_radius) and the neighbour sweep, through the translation unit of the call's
+// MFMA count (dc_mfma_step.hip)
+static void pop_mfma_steps(const SweepArgs& X, SweepMode mode, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                           const Rad2& rad2, int n_rad, uint32_t* d_pops, hipStream_t stream) {
+  for (int r = 0; r < n_rad; ++r) {
+    const Rad2 one = single_radius(rad2, r);
+    uint32_t* out = d_pops + (size_t)r * X.n_q;
+    switch (nm_for((int)n_cols)) {
+#define X_(SV)                                                                                          \
+  case SV:                                                                                              \
+    if ((DC_STEP_MASK >> (SV - 1)) & 1u) pop_mfma_step_##SV(X, mode, n_cols, i_from, i_to, one, out, stream); \
+    break;
+      DC_FOR_EACH_S(X_)
+#undef X_
+      default:
+        break;
+    }
+  }
+}
+
+static void nn_mfma_steps(const SweepArgs& X, SweepMode mode, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                          uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, hipStream_t stream) {
+  switch (nm_for((int)n_cols)) {
+#define X_(SV)                                                                                      \
+  case SV:                                                                                          \
+    if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                            \
+      nn_mfma_step_##SV(X, mode, n_cols, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream); \
+    break;
+    DC_FOR_EACH_S(X_)
+#undef X_
+    default:
+      break;
+  }
+}
+
+// operand image of n_rows frames (A form, b_form == 0, in the order of perm or natural; B form, b_form == 1) and their
+// norms (norms == nullptr: not written)
+static void image(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t NM, uint32_t T, const uint32_t* perm,
+                  int b_form, void* img, void* norms, void* d_ws, hipStream_t stream) {
   char* p = (char*)d_ws;
-  const dim3 grid_img((uint32_t)(((size_t)L.T * L.NM * 64 + 255) / 256));
-  if (a_form)
-    hipLaunchKernelGGL(image_kernel, grid_img, dim3(256), image_smem(n_cols), stream, d_coords, n_rows, n_rows, n_cols,
-                       L.NM, L.T, (const float*)(p + kHdrMeans), (const uint32_t*)nullptr, 0,
-                       (uint4*)(p + L.off_img), (float*)(p + L.off_norm), (const uint32_t*)p);
-  if (b_form)
-    hipLaunchKernelGGL(image_kernel, grid_img, dim3(256), image_smem(n_cols), stream, d_coords, n_rows, n_rows, n_cols,
-                       L.NM, L.T, (const float*)(p + kHdrMeans), (const uint32_t*)nullptr, 1,
-                       (uint4*)(p + L.off_img_b), a_form ? (float*)nullptr : (float*)(p + L.off_norm),
-                       (const uint32_t*)p);
+  const dim3 grid((uint32_t)(((size_t)T * NM * 64 + 255) / 256));
+  hipLaunchKernelGGL(image_kernel, grid, dim3(256), image_smem(n_cols), stream, d_coords, n_rows, n_rows, n_cols, NM, T,
+                     (const float*)(p + kHdrMeans), perm, b_form, (uint4*)img, (float*)norms, (const uint32_t*)p);
+}
+
+// Where ordering the references by free energy leaves its results: perm (sorted position -> reference), invpos, fe_s,
+// per query pq, and the sort's scratch
+struct FeOrder {
+  uint32_t *keys_in, *keys_out, *vals_in, *perm, *invpos, *pq;
+  float* fe_s;
+  void* sort_tmp;
+};
+
+// The references of a neighbour sweep ordered by free energy (a NaN raises the flag: the direct kernel answers), per
+// query the number of references with strictly lower free energy -- its candidates for nn_hd are a prefix of that
+// order -- and the A-form image + norms of the references in that order.  d_fe_q == nullptr (nn only): natural order.
+// Returns non-zero when the sort failed.
+static int order_by_fe(const float* d_ref, uint32_t n_ref, uint32_t n_cols, uint32_t NM, uint32_t T_r,
+                       const float* d_fe_r, const float* d_fe_q, uint32_t n_q, const FeOrder& B, void* img,
+                       void* norms, void* d_ws, hipStream_t stream) {
+  const dim3 blk(256), grid_r((n_ref + 255) / 256), grid_t((32 * T_r + 255) / 256);
+  if (d_fe_q) {
+    hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>(grid_r.x, 1024u)), blk, 0, stream, d_fe_r, n_ref,
+                       B.keys_in, B.vals_in, (uint32_t*)d_ws);
+    if (sort_pairs_u32(B.keys_in, B.keys_out, B.vals_in, B.perm, n_ref, B.sort_tmp, sort_temp_bytes(n_ref), stream) != 0)
+      return -3;
+    hipLaunchKernelGGL(fe_scatter_kernel, grid_t, blk, 0, stream, B.perm, d_fe_r, n_ref, T_r, B.invpos, B.fe_s);
+    hipLaunchKernelGGL(fe_rank_kernel, dim3((n_q + 255) / 256), blk, 0, stream, d_fe_q, n_q, (const float*)B.fe_s,
+                       n_ref, B.pq);
+  } else {
+    hipLaunchKernelGGL(iota_kernel, grid_t, blk, 0, stream, B.perm, n_ref, 32 * T_r);
+  }
+  image(d_ref, n_ref, n_cols, NM, T_r, B.perm, 0, img, norms, d_ws, stream);
+  return 0;
 }
 
 void launch_pop_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from,
                      uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
                      hipStream_t stream) {
+  const Layout L = make_layout(n_rows, n_cols);
+  char* p = (char*)d_ws;
   hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)d_ws, max_radius2(rad2, n_rad), n_cols);
-  natural_images(d_coords, n_rows, n_cols, d_ws, true, true, stream);
-  for (int r = 0; r < n_rad; ++r) {
-    const Rad2 one = single_radius(rad2, r);
-    uint32_t* out = d_pops + (size_t)r * n_rows;
-    switch (nm_for((int)n_cols)) {
-#define X(SV)                                                                                   \
-  case SV:                                                                                      \
-    if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                        \
-      pop_mfma_step_##SV(d_coords, n_rows, n_cols, d_ws, i_from, i_to, one, 1, out, stream);     \
-    break;
-      DC_FOR_EACH_S(X)
-#undef X
-      default:
-        break;
-    }
-  }
+  image(d_coords, n_rows, n_cols, L.NM, L.T, nullptr, 0, p + L.off_img, p + L.off_norm, d_ws, stream);
+  image(d_coords, n_rows, n_cols, L.NM, L.T, nullptr, 1, p + L.off_img_b, nullptr, d_ws, stream);
+  const SweepArgs X{d_coords, d_coords, n_rows, n_rows, L.T, L.T, (const uint4*)(p + L.off_img),
+                    (const float*)(p + L.off_norm), (const uint4*)(p + L.off_img_b), (const float*)(p + L.off_norm),
+                    nullptr, nullptr, nullptr, (const uint32_t*)p};
+  pop_mfma_steps(X, kSelf, n_cols, i_from, i_to, rad2, n_rad, d_pops, stream);
 }
 
 // rows answered by a pruned sweep: the row range [i_from, i_to), or -- n_segments > 0 -- segment
@@ -1973,38 +2009,18 @@ void launch_nn_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, con
   // order the reference frames by free energy and build their operand image
   const Layout L = make_layout(n_rows, n_cols);
   char* p = (char*)d_ws;
-  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
-  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
-  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
-  uint32_t* perm = (uint32_t*)(p + L.off_perm);
-  const dim3 blk(256), grid_n((n_rows + 255) / 256), grid_t((32 * L.T + 255) / 256);
-  auto grid_img = [&](uint32_t tiles) { return dim3((uint32_t)(((size_t)tiles * L.NM * 64 + 255) / 256)); };
   hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)p, -1.0f, n_cols);   // the neighbour scale
-  natural_images(d_coords, n_rows, n_cols, d_ws, false, true, stream);   // queries: B form + norms
-  hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>(grid_n.x, 1024u)), blk, 0, stream, d_fe, n_rows, keys_in, vals_in,
-                     (uint32_t*)p);
-  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm, n_rows, p + L.fixed_end,
-                     sort_temp_bytes(n_rows), stream) != 0)
+  image(d_coords, n_rows, n_cols, L.NM, L.T, nullptr, 1, p + L.off_img_b, p + L.off_norm, d_ws, stream);   // queries
+  const FeOrder B{(uint32_t*)(p + L.off_keys_in), (uint32_t*)(p + L.off_keys_out), (uint32_t*)(p + L.off_vals_in),
+                  (uint32_t*)(p + L.off_perm),    (uint32_t*)(p + L.off_invpos),   (uint32_t*)(p + L.off_pq),
+                  (float*)(p + L.off_fe_s),       p + L.fixed_end};
+  if (order_by_fe(d_coords, n_rows, n_cols, L.NM, L.T, d_fe, d_fe, n_rows, B, p + L.off_img_s, p + L.off_norm_s, d_ws,
+                  stream) != 0)
     return;
-  hipLaunchKernelGGL(fe_scatter_kernel, grid_t, blk, 0, stream, perm, d_fe, n_rows, L.T,
-                     (uint32_t*)(p + L.off_invpos), (float*)(p + L.off_fe_s));
-  hipLaunchKernelGGL(fe_rank_kernel, grid_n, blk, 0, stream, d_fe, (const float*)(p + L.off_fe_s),
-                     n_rows, (uint32_t*)(p + L.off_pq));
-  hipLaunchKernelGGL(image_kernel, grid_img(L.T), blk, image_smem(n_cols), stream, d_coords, n_rows, n_rows, n_cols,
-                     L.NM, L.T, (const float*)(p + kHdrMeans), (const uint32_t*)perm, 0,
-                     (uint4*)(p + L.off_img_s), (float*)(p + L.off_norm_s), (const uint32_t*)p);
-  switch (nm_for((int)n_cols)) {
-#define X(SV)                                                                                \
-  case SV:                                                                                   \
-    if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                     \
-      nn_mfma_step_##SV(d_coords, n_rows, n_cols, d_ws, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, \
-                        d_hd_d2, stream);                                                    \
-    break;
-    DC_FOR_EACH_S(X)
-#undef X
-    default:
-      break;
-  }
+  const SweepArgs X{d_coords, d_coords, n_rows, n_rows, L.T, L.T, (const uint4*)(p + L.off_img_s),
+                    (const float*)(p + L.off_norm_s), (const uint4*)(p + L.off_img_b), (const float*)(p + L.off_norm),
+                    B.perm, B.invpos, B.pq, (const uint32_t*)p};
+  nn_mfma_steps(X, kSelf, n_cols, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream);
 }
 
 // ---- cross sweeps: query rows of Q against every row of R (dc_hip_*_cross_dev) -------------------------------------
@@ -2067,33 +2083,13 @@ static int cross_prepare(const float* d_query, uint32_t n_q, const float* d_ref,
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-static CrossArgs cross_args(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, void* d_ws,
-                            const CrossLayout& L, bool with_pq) {
+static SweepArgs against_args(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, void* d_ws,
+                              const CrossLayout& L, bool with_pq) {
   char* p = (char*)d_ws;
-  CrossArgs X;
-  X.qcoords = d_query;
-  X.rcoords = d_ref;
-  X.n_q = n_q;
-  X.n_ref = n_ref;
-  X.T_q = L.T_q;
-  X.T_r = L.T_r;
-  X.img_r = (const uint4*)(p + L.off_img_r);
-  X.norms_r = (const float*)(p + L.off_norm_r);
-  X.img_q = (const uint4*)(p + L.off_img_q);
-  X.norms_q = (const float*)(p + L.off_norm_q);
-  X.perm_r = (const uint32_t*)(p + L.off_perm);
-  X.pq = with_pq ? (const uint32_t*)(p + L.off_pq) : nullptr;
-  X.hdr = (const uint32_t*)p;
-  return X;
-}
-
-// image of one set (A form of R through perm, or in natural order; B form of Q) with its norms
-static void cross_image(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t NM, uint32_t T,
-                        const uint32_t* perm, int b_form, void* img, void* norms, void* d_ws, hipStream_t stream) {
-  char* p = (char*)d_ws;
-  const dim3 grid((uint32_t)(((size_t)T * NM * 64 + 255) / 256));
-  hipLaunchKernelGGL(image_kernel, grid, dim3(256), image_smem(n_cols), stream, d_coords, n_rows, n_rows, n_cols, NM, T,
-                     (const float*)(p + kHdrMeans), perm, b_form, (uint4*)img, (float*)norms, (const uint32_t*)p);
+  return SweepArgs{d_query, d_ref, n_q, n_ref, L.T_q, L.T_r, (const uint4*)(p + L.off_img_r),
+                   (const float*)(p + L.off_norm_r), (const uint4*)(p + L.off_img_q), (const float*)(p + L.off_norm_q),
+                   (const uint32_t*)(p + L.off_perm), nullptr, with_pq ? (const uint32_t*)(p + L.off_pq) : nullptr,
+                   (const uint32_t*)p};
 }
 
 int launch_pop_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
@@ -2103,23 +2099,10 @@ int launch_pop_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref
   char* p = (char*)d_ws;
   if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
   hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)d_ws, max_radius2(rad2, n_rad), n_cols);
-  cross_image(d_ref, n_ref, n_cols, L.NM, L.T_r, nullptr, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
-  cross_image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
-  const CrossArgs X = cross_args(d_query, n_q, d_ref, n_ref, d_ws, L, false);
-  for (int r = 0; r < n_rad; ++r) {
-    const Rad2 one = single_radius(rad2, r);
-    uint32_t* out = d_pops + (size_t)r * n_q;
-    switch (nm_for((int)n_cols)) {
-#define X_(SV)                                                                                  \
-  case SV:                                                                                      \
-    if ((DC_STEP_MASK >> (SV - 1)) & 1u) pop_cross_step_##SV(X, n_cols, i_from, i_to, one, out, stream); \
-    break;
-      DC_FOR_EACH_S(X_)
-#undef X_
-      default:
-        break;
-    }
-  }
+  image(d_ref, n_ref, n_cols, L.NM, L.T_r, nullptr, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
+  image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
+  pop_mfma_steps(against_args(d_query, n_q, d_ref, n_ref, d_ws, L, false), kAgainst, n_cols, i_from, i_to, rad2, n_rad,
+                 d_pops, stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2130,39 +2113,15 @@ int launch_nn_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref,
   char* p = (char*)d_ws;
   if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
   hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)p, -1.0f, n_cols);   // the neighbour scale
-  uint32_t* perm = (uint32_t*)(p + L.off_perm);
-  const dim3 blk(256), grid_r((n_ref + 255) / 256), grid_t((32 * L.T_r + 255) / 256);
-  if (d_fe_q) {
-    // the references ordered by free energy (a NaN raises the flag: the direct kernel answers), and per query the
-    // number of references with strictly lower free energy -- its candidates for nn_hd are a prefix of that order
-    uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
-    uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
-    hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>(grid_r.x, 1024u)), blk, 0, stream, d_fe_r, n_ref, keys_in,
-                       vals_in, (uint32_t*)p);
-    if (sort_pairs_u32(keys_in, (uint32_t*)(p + L.off_keys_out), vals_in, perm, n_ref, p + L.off_sort,
-                       sort_temp_bytes(n_ref), stream) != 0)
-      return -3;
-    hipLaunchKernelGGL(fe_scatter_kernel, grid_t, blk, 0, stream, perm, d_fe_r, n_ref, L.T_r,
-                       (uint32_t*)(p + L.off_invpos), (float*)(p + L.off_fe_s));
-    hipLaunchKernelGGL(fe_rank_cross_kernel, dim3((n_q + 255) / 256), blk, 0, stream, d_fe_q, n_q,
-                       (const float*)(p + L.off_fe_s), n_ref, (uint32_t*)(p + L.off_pq));
-  } else {
-    hipLaunchKernelGGL(iota_kernel, grid_t, blk, 0, stream, perm, n_ref, 32 * L.T_r);   // natural order
-  }
-  cross_image(d_ref, n_ref, n_cols, L.NM, L.T_r, perm, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
-  cross_image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
-  const CrossArgs X = cross_args(d_query, n_q, d_ref, n_ref, d_ws, L, d_fe_q != nullptr);
-  switch (nm_for((int)n_cols)) {
-#define X_(SV)                                                                                   \
-  case SV:                                                                                       \
-    if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                         \
-      nn_cross_step_##SV(X, n_cols, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream);  \
-    break;
-    DC_FOR_EACH_S(X_)
-#undef X_
-    default:
-      break;
-  }
+  const FeOrder B{(uint32_t*)(p + L.off_keys_in), (uint32_t*)(p + L.off_keys_out), (uint32_t*)(p + L.off_vals_in),
+                  (uint32_t*)(p + L.off_perm),    (uint32_t*)(p + L.off_invpos),   (uint32_t*)(p + L.off_pq),
+                  (float*)(p + L.off_fe_s),       p + L.off_sort};
+  if (int rc = order_by_fe(d_ref, n_ref, n_cols, L.NM, L.T_r, d_fe_r, d_fe_q, n_q, B, p + L.off_img_r,
+                           p + L.off_norm_r, d_ws, stream))
+    return rc;
+  image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
+  nn_mfma_steps(against_args(d_query, n_q, d_ref, n_ref, d_ws, L, d_fe_q != nullptr), kAgainst, n_cols, i_from, i_to,
+                d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2231,7 +2190,7 @@ void launch_nn_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, c
   if (sort_pairs_u32(keys_in, keys_out, vals_in, perm, n_rows, p + L.fixed_end, sort_temp_bytes(n_rows), stream) != 0) return;
   hipLaunchKernelGGL(fe_scatter_kernel, grid_t, blk, 0, stream, perm, d_fe, n_rows, L.T, (uint32_t*)(p + L.off_invpos),
                      (float*)(p + L.off_fe_s));
-  hipLaunchKernelGGL(fe_rank_kernel, grid_n, blk, 0, stream, d_fe, (const float*)(p + L.off_fe_s), n_rows,
+  hipLaunchKernelGGL(fe_rank_kernel, grid_n, blk, 0, stream, d_fe, n_rows, (const float*)(p + L.off_fe_s), n_rows,
                      (uint32_t*)(p + L.off_pq));
   hipLaunchKernelGGL(image32_kernel, grid_t, blk, 0, stream, d_coords, n_rows, n_cols, L.T, (const float*)(p + kHdrMeans),
                      (const uint32_t*)perm, (const uint32_t*)p, -1.0f, img_s, norms_s);

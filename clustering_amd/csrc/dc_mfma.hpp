@@ -59,17 +59,19 @@ enum NnForm {
   kNnShared,   // reference operands shared through LDS (nn_shared_kernel)
 };
 enum CallKind { kCallAll, kCallRange, kCallSegment };   // queries: all rows / a row range / one segment of a sharded run
-// operands of one cross sweep (dc_mfma_kernels.hpp pop_cross_mfma_kernel / nn_cross_mfma_kernel)
-struct CrossArgs {
-  const float* qcoords;   // [n_q][n_cols]
-  const float* rcoords;   // [n_ref][n_cols]
+// operands of one unpruned matrix-core sweep (dc_mfma_kernels.hpp pop_mfma_kernel / nn_mfma_kernel): the query rows
+// of Q against every row of R.  A self sweep passes the same frames on both sides (T_q == T_r).
+struct SweepArgs {
+  const float* qcoords;     // [n_q][n_cols]
+  const float* rcoords;     // [n_ref][n_cols]
   uint32_t n_q, n_ref, T_q, T_r;
-  const uint4* img_r;     // A form of R: natural order (populations) or ordered by free energy (neighbours)
+  const uint4* img_r;       // A form of R: natural order (populations) or ordered by free energy (neighbours)
   const float* norms_r;
-  const uint4* img_q;     // B form of Q, natural order
+  const uint4* img_q;       // B form of Q, natural order
   const float* norms_q;
-  const uint32_t* perm_r; // neighbours: sorted position -> reference frame
-  const uint32_t* pq;     // neighbours: per query, references with strictly lower free energy (nullptr: nn only)
+  const uint32_t* perm;     // neighbours: sorted position -> reference frame
+  const uint32_t* invpos;   // self neighbour sweeps: frame -> sorted position
+  const uint32_t* pq;       // neighbours: per query, references with strictly lower free energy (nullptr: nn only)
   const uint32_t* hdr;
 };
 

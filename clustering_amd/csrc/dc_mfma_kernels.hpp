@@ -671,11 +671,30 @@ __device__ __forceinline__ uint32_t tile_row(uint32_t t, int r, int h) {
   return 32u * t + (uint32_t)((r & 3) + 8 * (r >> 2) + 4 * h);
 }
 
-// canonical d2 of two rows of the ORIGINAL coordinate matrix (the only arithmetic that decides)
-__device__ __attribute__((noinline)) float exact_d2(const float* __restrict__ coords,
-                                                   uint32_t n_cols, uint32_t jq, uint32_t i) {
-  return dist2_canon_rt(coords + (size_t)jq * n_cols, 1, coords + (size_t)i * n_cols, 1,
-                        (int)n_cols);
+// The rows an exact re-check reads: one coordinate matrix that holds the query and the reference rows (self
+// sweeps, the pruned sweeps), or a query matrix and a reference matrix (sweeps against a reference).
+struct QueryRef {
+  const float* q;
+  const float* r;
+};
+__device__ __forceinline__ const float* query_row(const float* c, uint32_t j, uint32_t n) { return c + (size_t)j * n; }
+__device__ __forceinline__ const float* ref_row(const float* c, uint32_t i, uint32_t n) { return c + (size_t)i * n; }
+__device__ __forceinline__ const float* query_row(QueryRef c, uint32_t j, uint32_t n) { return c.q + (size_t)j * n; }
+__device__ __forceinline__ const float* ref_row(QueryRef c, uint32_t i, uint32_t n) { return c.r + (size_t)i * n; }
+
+// the rows of an unpruned sweep's re-check
+template <SweepMode M>
+__device__ __forceinline__ auto exact_rows(const SweepArgs& X) {
+  if constexpr (M == kSelf)
+    return X.qcoords;
+  else
+    return QueryRef{X.qcoords, X.rcoords};
+}
+
+// canonical d2 of query row jq and reference row i of the ORIGINAL coordinates (the only arithmetic that decides)
+template <class Rows>
+__device__ __attribute__((noinline)) float exact_d2(Rows rows, uint32_t n_cols, uint32_t jq, uint32_t i) {
+  return dist2_canon_rt(query_row(rows, jq, n_cols), 1, ref_row(rows, i, n_cols), 1, (int)n_cols);
 }
 
 // minimum of elements [R0, R1) of an accumulator tile (v_min3_f32: two elements per instruction)
@@ -776,9 +795,8 @@ struct PopDelta {
 // rare: exact re-check of the band pairs of one accumulator tile.  Everything by value and a
 // returned delta, so that neither the accumulators nor the per-query state ever get an address
 // (an escaping reference would park them in scratch for the whole hot loop).
-template <int NR>
-__device__ __attribute__((noinline)) PopDelta<NR> pop_fix(const float* __restrict__ coords,
-                                                          const uint32_t* __restrict__ perm,
+template <int NR, class Rows>
+__device__ __attribute__((noinline)) PopDelta<NR> pop_fix(Rows coords, const uint32_t* __restrict__ perm,
                                                           uint32_t n_rows, uint32_t n_cols,
                                                           Rad2 rad2, PopDeltas<NR> dl, f32x16 acc,
                                                           uint32_t wbits, uint32_t jq, uint32_t t,
@@ -841,19 +859,21 @@ __device__ __forceinline__ PopSetup<NR> pop_setup(const uint32_t* __restrict__ h
   return P;
 }
 
-template <int NM, int NR, int TQ>
-__global__ __launch_bounds__(256, 2) void pop_mfma_kernel(
-    const float* __restrict__ coords, uint32_t n_rows, uint32_t n_cols,
-    const uint4* __restrict__ img, const uint4* __restrict__ img_b,
-    const float* __restrict__ norms, const uint32_t* __restrict__ hdr, uint32_t T, uint32_t i_from,
-    uint32_t i_to, Rad2 rad2, int n_rad, uint32_t* __restrict__ pops) {
-  if (hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
+// The query rows [i_from, i_to) of X against every reference row, every tile pair evaluated.  kSelf: Q = R, the
+// reference's populations (the self pair taken out, 1 added); kAgainst: every pair counts, nothing is added.
+template <int NM, int NR, int TQ, SweepMode M>
+__global__ __launch_bounds__(256, 2) void pop_mfma_kernel(SweepArgs X, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                                                          Rad2 rad2, int n_rad, uint32_t* __restrict__ pops) {
+  if (X.hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
   const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
   const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6);
   const uint32_t qt0 = i_from / 32 + wave * TQ;
   if (qt0 * 32 >= i_to) return;   // whole wave leaves; no barriers in this kernel
+  // (a self sweep: one array, one tile count, one set of norms -- the registers of the reference's loop)
+  if constexpr (M == kSelf) X.rcoords = X.qcoords, X.n_q = X.n_ref, X.T_q = X.T_r, X.norms_q = X.norms_r;
+  const uint32_t T = X.T_r;
 
-  const PopSetup<NR> P = pop_setup<NR>(hdr, rad2, n_cols);
+  const PopSetup<NR> P = pop_setup<NR>(X.hdr, rad2, n_cols);
 
   s16x8 b[TQ][NM];
   PopQ<NR> q[TQ];
@@ -863,18 +883,18 @@ __global__ __launch_bounds__(256, 2) void pop_mfma_kernel(
   for (int qt = 0; qt < TQ; ++qt) {
     const uint32_t tile = qt0 + qt;
     jq[qt] = tile * 32 + c;
-    const bool live = (tile < T) && (jq[qt] >= i_from) && (jq[qt] < i_to);
+    const bool live = (tile < X.T_q) && (jq[qt] >= i_from) && (jq[qt] < i_to);
     livemask[qt] = __builtin_amdgcn_ballot_w64(live);
-    const uint32_t tl = tile < T ? tile : T - 1;
-    const float cq = live ? norms[tl * 32 + c] - P.rad2e.v[0] : dead_const(P.sc);
-    load_query<NM>(img_b, tl, lane, h, cq, P.sc, b[qt]);
+    const uint32_t tl = tile < X.T_q ? tile : X.T_q - 1;
+    const float cq = live ? X.norms_q[tl * 32 + c] - P.rad2e.v[0] : dead_const(P.sc);
+    load_query<NM>(X.img_q, tl, lane, h, cq, P.sc, b[qt]);
 #pragma unroll
     for (int rr = 0; rr < NR; ++rr) q[qt].cnt[rr] = 0;
   }
 
   s16x8 a0[NM], a1[NM];
   float4 n0[4], n1[4];
-  load_tile<NM>(img, norms, 0, lane, h, a0, n0);
+  load_tile<NM>(X.img_r, X.norms_r, 0, lane, h, a0, n0);
 
   // the rest of an epilogue: counts, band test, rare exact path
   auto finish = [&](const f32x16& acc, auto qi_c, const PopAcc<NR>& e, uint32_t t) {
@@ -886,7 +906,7 @@ __global__ __launch_bounds__(256, 2) void pop_mfma_kernel(
     for (int rr = 0; rr < NR; ++rr) band |= band_of(e.bits[rr]);
     if (__builtin_expect((__builtin_amdgcn_ballot_w64(band != 0) & livemask[qi]) != 0, 0)) {
       const PopDelta<NR> dl =
-          pop_fix<NR>(coords, nullptr, n_rows, n_cols, rad2, P.dl, acc, P.wbits, jq[qi], t, h);
+          pop_fix<NR>(exact_rows<M>(X), nullptr, X.n_ref, n_cols, rad2, P.dl, acc, P.wbits, jq[qi], t, h);
 #pragma unroll
       for (int rr = 0; rr < NR; ++rr) q[qi].cnt[rr] += ((livemask[qi] >> lane) & 1) ? dl.d[rr] : 0u;
     }
@@ -924,10 +944,10 @@ __global__ __launch_bounds__(256, 2) void pop_mfma_kernel(
   };
 
   for (uint32_t t = 0; t < T; t += 2) {
-    load_tile<NM>(img, norms, (t + 1 < T) ? t + 1 : t, lane, h, a1, n1);
+    load_tile<NM>(X.img_r, X.norms_r, (t + 1 < T) ? t + 1 : t, lane, h, a1, n1);
     tile_body(a0, n0, t);
     if (t + 1 < T) {
-      load_tile<NM>(img, norms, (t + 2 < T) ? t + 2 : t + 1, lane, h, a0, n0);
+      load_tile<NM>(X.img_r, X.norms_r, (t + 2 < T) ? t + 2 : t + 1, lane, h, a0, n0);
       tile_body(a1, n1, t + 1);
     }
   }
@@ -945,9 +965,13 @@ __global__ __launch_bounds__(256, 2) void pop_mfma_kernel(
     for (int rr = 0; rr < NR; ++rr) {
       const uint32_t total = q[qt].cnt[rr] + (uint32_t)__shfl_xor((int)q[qt].cnt[rr], 32, 64);
       if (h == 0 && live && rr < n_rad) {
-        // the sweep met the self pair and counted it iff d2(i,i) < rad2; the reference starts at 1
-        const float dself = exact_d2(coords, n_cols, jq[qt], jq[qt]);
-        pops[(size_t)rr * n_rows + jq[qt]] = total + 1u - ((dself < rad2.v[rr]) ? 1u : 0u);
+        if constexpr (M == kSelf) {
+          // the sweep met the self pair and counted it iff d2(i,i) < rad2; the reference starts at 1
+          const float dself = exact_d2(X.qcoords, n_cols, jq[qt], jq[qt]);
+          pops[(size_t)rr * X.n_q + jq[qt]] = total + 1u - ((dself < rad2.v[rr]) ? 1u : 0u);
+        } else {
+          pops[(size_t)rr * X.n_q + jq[qt]] = total;
+        }
       }
     }
   }
@@ -1703,8 +1727,8 @@ __device__ __attribute__((noinline)) NnMin nn_special(f32x16 acc, uint32_t t, in
 
 // rare: exact evaluation of the candidates of one accumulator tile (values within the band of the
 // running minimum), merged lexicographically on (d2, frame id)
-__device__ __attribute__((noinline)) NnBest nn_fix(const float* __restrict__ coords,
-                                                   const uint32_t* __restrict__ perm,
+template <class Rows>
+__device__ __attribute__((noinline)) NnBest nn_fix(Rows coords, const uint32_t* __restrict__ perm,
                                                    uint32_t n_rows, uint32_t n_cols, f32x16 acc,
                                                    float bn, float bh, NnBest best, uint32_t jq,
                                                    uint32_t spos, uint32_t pq, uint32_t t, int h) {
@@ -1791,24 +1815,24 @@ __device__ __forceinline__ void nn_chain_coarse(const s16x8 (&a)[NA], const s16x
 __host__ __device__ constexpr int nn_coarse_for(int n_cols) { return (n_cols + kConstSlots + 15) / 16; }
 template <int NM>
 constexpr int kNnCoarseMax = nn_coarse_for((16 * NM - kConstSlots) / kPieceGroups);
-template <int NM, int TQ>
-__global__ __launch_bounds__(256, 2) void nn_mfma_kernel(
-    const float* __restrict__ coords, uint32_t n_rows, uint32_t n_cols,
-    const uint4* __restrict__ img_b, const float* __restrict__ norms,
-    const uint4* __restrict__ img_s, const float* __restrict__ norms_s,
-    const uint32_t* __restrict__ perm, const uint32_t* __restrict__ invpos,
-    const uint32_t* __restrict__ pq_of, const uint32_t* __restrict__ hdr, uint32_t T,
-    uint32_t i_from, uint32_t i_to, uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2,
-    uint32_t* __restrict__ hd_idx, float* __restrict__ hd_d2) {
-  if (hdr[1] != 0) return;
+// The query rows [i_from, i_to) of X against every reference row (ordered by free energy through X.perm).  kSelf:
+// Q = R, the query itself is left out (X.invpos gives its position); kAgainst: no reference row is the query, and
+// X.pq == nullptr asks for nn only.
+template <int NM, int TQ, SweepMode M>
+__global__ __launch_bounds__(256, 2) void nn_mfma_kernel(SweepArgs X, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                                                         uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2,
+                                                         uint32_t* __restrict__ hd_idx, float* __restrict__ hd_d2) {
+  if (X.hdr[1] != 0) return;
   const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
   const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6);
   const uint32_t qt0 = i_from / 32 + wave * TQ;
   if (qt0 * 32 >= i_to) return;
+  if constexpr (M == kSelf) X.rcoords = X.qcoords, X.n_q = X.n_ref, X.T_q = X.T_r;
+  const uint32_t T = X.T_r, n_ref = X.n_ref;
 
   // (scaled units, like the accumulators and the running minima taken from them)
-  const Scale sc = load_scale(hdr);   // (the neighbour scale: scale_kernel ran before the images were built)
-  const GuardBand gb = guard_band(__uint_as_float(hdr[0]) * sc.s2, 0.0f, (int)n_cols, sc);
+  const Scale sc = load_scale(X.hdr);   // (the neighbour scale: scale_kernel ran before the images were built)
+  const GuardBand gb = guard_band(__uint_as_float(X.hdr[0]) * sc.s2, 0.0f, (int)n_cols, sc);
 
   s16x8 b[TQ][NM];
   NnQ q[TQ];
@@ -1818,14 +1842,20 @@ __global__ __launch_bounds__(256, 2) void nn_mfma_kernel(
   for (int qt = 0; qt < TQ; ++qt) {
     const uint32_t tile = qt0 + qt;
     jq[qt] = tile * 32 + c;
-    const bool live = (tile < T) && (jq[qt] >= i_from) && (jq[qt] < i_to);
+    const bool live = (tile < X.T_q) && (jq[qt] >= i_from) && (jq[qt] < i_to);
     livemask[qt] = __builtin_amdgcn_ballot_w64(live);
-    const uint32_t tl = tile < T ? tile : T - 1;
-    load_query<NM>(img_b, tl, lane, h, live ? norms[tl * 32 + c] : dead_const(sc), sc, b[qt]);
-    const uint32_t jl = live ? jq[qt] : (n_rows - 1);
-    q[qt].pq = live ? pq_of[jl] : 0u;
-    q[qt].spos = live ? invpos[jl] : 0xFFFFFFFFu;
-    q[qt].t_self = live ? (q[qt].spos >> 5) : 0xFFFFFFFFu;
+    const uint32_t tl = tile < X.T_q ? tile : X.T_q - 1;
+    load_query<NM>(X.img_q, tl, lane, h, live ? X.norms_q[tl * 32 + c] : dead_const(sc), sc, b[qt]);
+    if constexpr (M == kSelf) {
+      const uint32_t jl = live ? jq[qt] : (X.n_q - 1);
+      q[qt].pq = live ? X.pq[jl] : 0u;
+      q[qt].spos = live ? X.invpos[jl] : 0xFFFFFFFFu;
+      q[qt].t_self = live ? (q[qt].spos >> 5) : 0xFFFFFFFFu;
+    } else {
+      q[qt].pq = (live && X.pq) ? X.pq[jq[qt]] : 0u;
+      q[qt].spos = 0xFFFFFFFFu;   // (no reference row is the query itself)
+      q[qt].t_self = 0xFFFFFFFFu;
+    }
     q[qt].t_full = q[qt].pq >> 5;
     q[qt].t_part = (q[qt].pq & 31u) ? (q[qt].pq >> 5) : 0xFFFFFFFFu;
     // idle lanes start at -inf: they can never trigger the exact path and never change
@@ -1833,20 +1863,20 @@ __global__ __launch_bounds__(256, 2) void nn_mfma_kernel(
     q[qt].m_hd = live ? INFINITY : -INFINITY;
     q[qt].bd_nn = FLT_MAX;
     q[qt].bd_hd = FLT_MAX;
-    q[qt].bj_nn = n_rows + 1;
-    q[qt].bj_hd = n_rows + 1;
+    q[qt].bj_nn = n_ref + 1;
+    q[qt].bj_hd = n_ref + 1;
   }
 
   s16x8 a0[NM], a1[NM];
   float4 n0[4], n1[4];
-  load_tile<NM>(img_s, norms_s, 0, lane, h, a0, n0);
+  load_tile<NM>(X.img_r, X.norms_r, 0, lane, h, a0, n0);
 
   // the rest of an epilogue: minima of the special tiles, band test against the running minima, rare
   // exact path.  Bitwise logic on purpose (no short-circuit control flow in the hot path).
   auto finish = [&](const f32x16& acc, auto qi_c, float tmin, uint32_t t) {
     constexpr int qi = decltype(qi_c)::value;
     NnQ& Q = q[qi];
-    const bool special = (t == Q.t_self) | (t == Q.t_part);
+    const bool special = (M == kSelf && t == Q.t_self) | (t == Q.t_part);
     float hmin = (t < Q.t_full) ? tmin : INFINITY;
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(special) != 0, 0)) {
       const NnMin g = nn_special(acc, t, h, Q.spos, Q.pq);   // valid for every lane, just slower
@@ -1859,7 +1889,7 @@ __global__ __launch_bounds__(256, 2) void nn_mfma_kernel(
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(trig) != 0, 0)) {
       const bool live = (livemask[qi] >> lane) & 1;
       NnBest best{Q.bd_nn, Q.bd_hd, Q.bj_nn, Q.bj_hd};
-      best = nn_fix(coords, perm, n_rows, n_cols, acc, bn, bh, best, jq[qi], Q.spos, Q.pq, t, h);
+      best = nn_fix(exact_rows<M>(X), X.perm, n_ref, n_cols, acc, bn, bh, best, jq[qi], Q.spos, Q.pq, t, h);
       Q.bd_nn = live ? best.bd_nn : Q.bd_nn;
       Q.bj_nn = live ? best.bj_nn : Q.bj_nn;
       Q.bd_hd = live ? best.bd_hd : Q.bd_hd;
@@ -1898,10 +1928,10 @@ __global__ __launch_bounds__(256, 2) void nn_mfma_kernel(
   };
 
   for (uint32_t t = 0; t < T; t += 2) {
-    load_tile<NM>(img_s, norms_s, (t + 1 < T) ? t + 1 : t, lane, h, a1, n1);
+    load_tile<NM>(X.img_r, X.norms_r, (t + 1 < T) ? t + 1 : t, lane, h, a1, n1);
     tile_body(a0, n0, t);
     if (t + 1 < T) {
-      load_tile<NM>(img_s, norms_s, (t + 2 < T) ? t + 2 : t + 1, lane, h, a0, n0);
+      load_tile<NM>(X.img_r, X.norms_r, (t + 2 < T) ? t + 2 : t + 1, lane, h, a0, n0);
       tile_body(a1, n1, t + 1);
     }
   }
@@ -1917,15 +1947,17 @@ __global__ __launch_bounds__(256, 2) void nn_mfma_kernel(
     // merge the two half-waves (disjoint reference rows of the same query)
     float od = __shfl_xor(Q.bd_nn, 32, 64);
     uint32_t oj = (uint32_t)__shfl_xor((int)Q.bj_nn, 32, 64);
-    lexi_update(oj <= n_rows, Q.bd_nn, Q.bj_nn, od, oj, n_rows);
+    lexi_update(oj <= n_ref, Q.bd_nn, Q.bj_nn, od, oj, n_ref);
     od = __shfl_xor(Q.bd_hd, 32, 64);
     oj = (uint32_t)__shfl_xor((int)Q.bj_hd, 32, 64);
-    lexi_update(oj <= n_rows, Q.bd_hd, Q.bj_hd, od, oj, n_rows);
+    lexi_update(oj <= n_ref, Q.bd_hd, Q.bj_hd, od, oj, n_ref);
     if (h == 0 && ((livemask[qt] >> lane) & 1)) {
       nn_idx[jq[qt]] = Q.bj_nn;
       nn_d2[jq[qt]] = Q.bd_nn;
-      hd_idx[jq[qt]] = Q.bj_hd;
-      hd_d2[jq[qt]] = Q.bd_hd;
+      if (M == kSelf || X.pq) {
+        hd_idx[jq[qt]] = Q.bj_hd;
+        hd_d2[jq[qt]] = Q.bd_hd;
+      }
     }
   }
 }
@@ -2786,15 +2818,15 @@ inline uint32_t grid_for(uint32_t i_from, uint32_t i_to, int tq) {
   return (waves + 3) / 4;
 }
 
-template <int S>
-void pop_dispatch(const float* coords, uint32_t n_rows, uint32_t n_cols, const Ptrs& P, uint32_t T,
-                  uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* pops,
+template <int S, SweepMode M>
+void pop_dispatch(const SweepArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to, const Rad2& rad2, uint32_t* pops,
                   hipStream_t s) {
   constexpr int kTQ = tq_full_for<S>;
   const dim3 grid(grid_for(i_from, i_to, kTQ)), block(256);
   // one radius per sweep (dc_mfma.hip loops over the radii of a call)
-  { sweep_timer_mark(0, true, s); hipLaunchKernelGGL((pop_mfma_kernel<S, 1, kTQ>), grid, block, 0, s, coords, n_rows, n_cols, P.img,
-                     P.img_b, P.norms, P.hdr, T, i_from, i_to, rad2, n_rad, pops); sweep_timer_mark(0, false, s); }
+  sweep_timer_mark(0, true, s);
+  hipLaunchKernelGGL((pop_mfma_kernel<S, 1, kTQ, M>), grid, block, 0, s, X, n_cols, i_from, i_to, rad2, 1, pops);
+  sweep_timer_mark(0, false, s);
 }
 
 // tile boxes regrouped by reference share: share c holds the tiles c, c + n, c + 2n, ... at
@@ -3218,343 +3250,14 @@ void pop_pruned_dispatch(const PopPlan& pl, const float* coords, uint32_t n_rows
   cross((uint32_t)TQ, pops, (size_t)n_rows, 0);
 }
 
-template <int S>
-void nn_dispatch(const float* coords, uint32_t n_rows, uint32_t n_cols, const Ptrs& P, uint32_t T,
-                 uint32_t i_from, uint32_t i_to, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx,
-                 float* hd_d2, hipStream_t s) {
-  constexpr int kTQnn = tq_full_for<S>;
-  const dim3 grid(grid_for(i_from, i_to, kTQnn)), block(256);
-  { sweep_timer_mark(1, true, s); hipLaunchKernelGGL((nn_mfma_kernel<S, kTQnn>), grid, block, 0, s, coords, n_rows, n_cols, P.img_b,
-                     P.norms, P.img_s, P.norms_s, P.perm, P.invpos, P.pq, P.hdr, T, i_from, i_to, nn_idx,
-                     nn_d2, hd_idx, hd_d2); sweep_timer_mark(1, false, s); }
-}
-
-// =============================================================================================
-// cross sweeps: the query rows of one array Q against every row of a reference array R
-// (dc_hip_populations_cross_dev / dc_hip_nearest_neighbors_cross_dev).  pop_mfma_kernel and nn_mfma_kernel with
-//   - two operand images: the A form + norms of R (T_r tiles), the B form + norms of Q (query tiles);
-//   - two coordinate arrays for the canonical re-check (exact_d2_cross);
-//   - no self pair: nothing is subtracted from the counts, no element is masked as "the query itself".
-// Both images are built around ONE origin and ONE scale: the column means over Q and R together and M = max |x - m|^2
-// over both sets (dc_mfma.hip cross_prepare), so the guard band bounds every pair, whichever set lies farther out.
-// =============================================================================================
-__device__ __attribute__((noinline)) float exact_d2_cross(const float* __restrict__ qcoords,
-                                                         const float* __restrict__ rcoords, uint32_t n_cols,
-                                                         uint32_t jq, uint32_t i) {
-  return dist2_canon_rt(qcoords + (size_t)jq * n_cols, 1, rcoords + (size_t)i * n_cols, 1, (int)n_cols);
-}
-
-// pop_fix with the query row in qcoords and the reference rows in rcoords (natural order, n_ref rows)
-template <int NR>
-__device__ __attribute__((noinline)) PopDelta<NR> pop_fix_cross(const float* __restrict__ qcoords,
-                                                                const float* __restrict__ rcoords, uint32_t n_ref,
-                                                                uint32_t n_cols, Rad2 rad2, PopDeltas<NR> dl,
-                                                                f32x16 acc, uint32_t wbits, uint32_t jq, uint32_t t,
-                                                                int h) {
-  PopDelta<NR> out;
-#pragma unroll
-  for (int rr = 0; rr < NR; ++rr) out.d[rr] = 0;
-  uint32_t m = 0;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    bool any = false;
-#pragma unroll
-    for (int rr = 0; rr < NR; ++rr) any = any | (__float_as_uint(rr == 0 ? acc[r] : acc[r] - dl.d[rr]) < wbits);
-    m |= (any & (tile_row(t, r, h) < n_ref)) ? (1u << r) : 0u;
-  }
-  while (__builtin_amdgcn_ballot_w64(m != 0) != 0) {
-    if (m != 0) {
-      const int r = __builtin_ctz(m);
-      const float d2c = exact_d2_cross(qcoords, rcoords, n_cols, jq, tile_row(t, r, h));
-      float av = acc[0];
-#pragma unroll
-      for (int k = 1; k < 16; ++k) av = (r == k) ? acc[k] : av;
-#pragma unroll
-      for (int rr = 0; rr < NR; ++rr)
-        if (__float_as_uint(rr == 0 ? av : av - dl.d[rr]) < wbits) out.d[rr] += (d2c < rad2.v[rr]) ? 1u : 0u;
-      m &= m - 1;
-    }
-  }
-  return out;
-}
-
-template <int NM, int NR, int TQ>
-__global__ __launch_bounds__(256, 2) void pop_cross_mfma_kernel(CrossArgs X, uint32_t n_cols, uint32_t i_from,
-                                                                uint32_t i_to, Rad2 rad2, int n_rad,
-                                                                uint32_t* __restrict__ pops) {
-  if (X.hdr[1] != 0) return;   // non-finite / overflow-prone rows in Q or R: the gated direct kernel runs instead
-  const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
-  const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint32_t qt0 = i_from / 32 + wave * TQ;
-  if (qt0 * 32 >= i_to) return;
-  const uint32_t T = X.T_r;
-  const PopSetup<NR> P = pop_setup<NR>(X.hdr, rad2, n_cols);
-
-  s16x8 b[TQ][NM];
-  PopQ<NR> q[TQ];
-  uint32_t jq[TQ];
-  uint64_t livemask[TQ];
-#pragma unroll
-  for (int qt = 0; qt < TQ; ++qt) {
-    const uint32_t tile = qt0 + qt;
-    jq[qt] = tile * 32 + c;
-    const bool live = (tile < X.T_q) && (jq[qt] >= i_from) && (jq[qt] < i_to);
-    livemask[qt] = __builtin_amdgcn_ballot_w64(live);
-    const uint32_t tl = tile < X.T_q ? tile : X.T_q - 1;
-    const float cq = live ? X.norms_q[tl * 32 + c] - P.rad2e.v[0] : dead_const(P.sc);
-    load_query<NM>(X.img_q, tl, lane, h, cq, P.sc, b[qt]);
-#pragma unroll
-    for (int rr = 0; rr < NR; ++rr) q[qt].cnt[rr] = 0;
-  }
-
-  s16x8 a0[NM], a1[NM];
-  float4 n0[4], n1[4];
-  load_tile<NM>(X.img_r, X.norms_r, 0, lane, h, a0, n0);
-
-  auto finish = [&](const f32x16& acc, auto qi_c, const PopAcc<NR>& e, uint32_t t) {
-    constexpr int qi = decltype(qi_c)::value;
-#pragma unroll
-    for (int rr = 0; rr < NR; ++rr) q[qi].cnt[rr] += __builtin_popcount(inside_of(e.bits[rr]));
-    uint32_t band = 0;
-#pragma unroll
-    for (int rr = 0; rr < NR; ++rr) band |= band_of(e.bits[rr]);
-    if (__builtin_expect((__builtin_amdgcn_ballot_w64(band != 0) & livemask[qi]) != 0, 0)) {
-      const PopDelta<NR> dl =
-          pop_fix_cross<NR>(X.qcoords, X.rcoords, X.n_ref, n_cols, rad2, P.dl, acc, P.wbits, jq[qi], t, h);
-#pragma unroll
-      for (int rr = 0; rr < NR; ++rr) q[qi].cnt[rr] += ((livemask[qi] >> lane) & 1) ? dl.d[rr] : 0u;
-    }
-  };
-
-  f32x16 accA, accB;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) accB[r] = INFINITY;
-  uint32_t tB = 0;
-  auto tile_body = [&](const s16x8 (&a)[NM], const float4 (&nv)[4], uint32_t t) {
-    const f32x16 c0 = frag16(nv);
-    if constexpr (TQ == 1) {
-      PopAcc<NR> e;
-      pop_epi_begin<NR>(e);
-      pop_chain<NM, NR>(a, b[0], c0, accA, accB, P.dl, e);
-      finish(accB, std::integral_constant<int, 0>{}, e, tB);
-      accB = accA;
-    } else {
-      constexpr_for_pairs<TQ>([&](auto qt_c) {
-        constexpr int qt = decltype(qt_c)::value;
-        constexpr int qb = (qt == 0) ? TQ - 1 : qt - 1;
-        PopAcc<NR> e;
-        pop_epi_begin<NR>(e);
-        pop_chain<NM, NR>(a, b[qt], c0, accA, accB, P.dl, e);
-        finish(accB, std::integral_constant<int, qb>{}, e, (qt == 0) ? tB : t);
-        pop_epi_begin<NR>(e);
-        pop_chain<NM, NR>(a, b[qt + 1], c0, accB, accA, P.dl, e);
-        finish(accA, std::integral_constant<int, qt>{}, e, t);
-      });
-    }
-    keep_alive(c0);
-    tB = t;
-  };
-
-  for (uint32_t t = 0; t < T; t += 2) {
-    load_tile<NM>(X.img_r, X.norms_r, (t + 1 < T) ? t + 1 : t, lane, h, a1, n1);
-    tile_body(a0, n0, t);
-    if (t + 1 < T) {
-      load_tile<NM>(X.img_r, X.norms_r, (t + 2 < T) ? t + 2 : t + 1, lane, h, a0, n0);
-      tile_body(a1, n1, t + 1);
-    }
-  }
-  {
-    PopAcc<NR> e;
-    pop_epi_begin<NR>(e);
-    pop_epi<NR, 0, 16>(accB, P.dl, e);
-    finish(accB, std::integral_constant<int, TQ - 1>{}, e, tB);
-  }
-
-#pragma unroll
-  for (int qt = 0; qt < TQ; ++qt) {
-    const bool live = (livemask[qt] >> lane) & 1;
-#pragma unroll
-    for (int rr = 0; rr < NR; ++rr) {
-      const uint32_t total = q[qt].cnt[rr] + (uint32_t)__shfl_xor((int)q[qt].cnt[rr], 32, 64);
-      if (h == 0 && live && rr < n_rad) pops[(size_t)rr * X.n_q + jq[qt]] = total;   // (no self pair to take out)
-    }
-  }
-}
-
-// nn_fix with the query row in qcoords and the references (ordered by free energy through perm_r) in rcoords; no
-// element is the query itself
-__device__ __attribute__((noinline)) NnBest nn_fix_cross(const CrossArgs& X, uint32_t n_cols, f32x16 acc, float bn,
-                                                         float bh, NnBest best, uint32_t jq, uint32_t pq, uint32_t t,
-                                                         int h) {
-  uint32_t mn = 0, mh = 0;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const uint32_t pos = tile_row(t, r, h);
-    const bool real = pos < X.n_ref;
-    mn |= (real & (acc[r] < bn)) ? (1u << r) : 0u;
-    mh |= (real & (pos < pq) & (acc[r] < bh)) ? (1u << r) : 0u;
-  }
-  uint32_t m = mn | mh;
-  while (__builtin_amdgcn_ballot_w64(m != 0) != 0) {
-    if (m != 0) {
-      const int r = __builtin_ctz(m);
-      const uint32_t j = X.perm_r[tile_row(t, r, h)];
-      const float d2c = exact_d2_cross(X.qcoords, X.rcoords, n_cols, jq, j);
-      lexi_update((mn >> r) & 1u, best.bd_nn, best.bj_nn, d2c, j, X.n_ref);
-      lexi_update((mh >> r) & 1u, best.bd_hd, best.bj_hd, d2c, j, X.n_ref);
-      m &= m - 1;
-    }
-  }
-  return best;
-}
-
-template <int NM, int TQ>
-__global__ __launch_bounds__(256, 2) void nn_cross_mfma_kernel(CrossArgs X, uint32_t n_cols, uint32_t i_from,
-                                                               uint32_t i_to, uint32_t* __restrict__ nn_idx,
-                                                               float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx,
-                                                               float* __restrict__ hd_d2) {
-  if (X.hdr[1] != 0) return;
-  const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
-  const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint32_t qt0 = i_from / 32 + wave * TQ;
-  if (qt0 * 32 >= i_to) return;
-  const uint32_t T = X.T_r, n_ref = X.n_ref;
-  const Scale sc = load_scale(X.hdr);
-  const GuardBand gb = guard_band(__uint_as_float(X.hdr[0]) * sc.s2, 0.0f, (int)n_cols, sc);
-
-  s16x8 b[TQ][NM];
-  NnQ q[TQ];
-  uint32_t jq[TQ];
-  uint64_t livemask[TQ];
-#pragma unroll
-  for (int qt = 0; qt < TQ; ++qt) {
-    const uint32_t tile = qt0 + qt;
-    jq[qt] = tile * 32 + c;
-    const bool live = (tile < X.T_q) && (jq[qt] >= i_from) && (jq[qt] < i_to);
-    livemask[qt] = __builtin_amdgcn_ballot_w64(live);
-    const uint32_t tl = tile < X.T_q ? tile : X.T_q - 1;
-    load_query<NM>(X.img_q, tl, lane, h, live ? X.norms_q[tl * 32 + c] : dead_const(sc), sc, b[qt]);
-    q[qt].pq = (live && X.pq) ? X.pq[jq[qt]] : 0u;
-    q[qt].spos = 0xFFFFFFFFu;   // (no reference row is the query itself)
-    q[qt].t_self = 0xFFFFFFFFu;
-    q[qt].t_full = q[qt].pq >> 5;
-    q[qt].t_part = (q[qt].pq & 31u) ? (q[qt].pq >> 5) : 0xFFFFFFFFu;
-    q[qt].m_nn = live ? INFINITY : -INFINITY;
-    q[qt].m_hd = live ? INFINITY : -INFINITY;
-    q[qt].bd_nn = FLT_MAX;
-    q[qt].bd_hd = FLT_MAX;
-    q[qt].bj_nn = n_ref + 1;
-    q[qt].bj_hd = n_ref + 1;
-  }
-
-  s16x8 a0[NM], a1[NM];
-  float4 n0[4], n1[4];
-  load_tile<NM>(X.img_r, X.norms_r, 0, lane, h, a0, n0);
-
-  auto finish = [&](const f32x16& acc, auto qi_c, float tmin, uint32_t t) {
-    constexpr int qi = decltype(qi_c)::value;
-    NnQ& Q = q[qi];
-    float hmin = (t < Q.t_full) ? tmin : INFINITY;
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(t == Q.t_part) != 0, 0)) {
-      const NnMin g = nn_special(acc, t, h, 0xFFFFFFFFu, Q.pq);
-      tmin = g.tmin;
-      hmin = g.hmin;
-    }
-    const float new_nn = fminf(Q.m_nn, tmin), new_hd = fminf(Q.m_hd, hmin);
-    const float bn = nn_band(gb, new_nn), bh = nn_band(gb, new_hd);
-    const bool trig = (tmin < bn) | (hmin < bh);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(trig) != 0, 0)) {
-      const bool live = (livemask[qi] >> lane) & 1;
-      NnBest best{Q.bd_nn, Q.bd_hd, Q.bj_nn, Q.bj_hd};
-      best = nn_fix_cross(X, n_cols, acc, bn, bh, best, jq[qi], Q.pq, t, h);
-      Q.bd_nn = live ? best.bd_nn : Q.bd_nn;
-      Q.bj_nn = live ? best.bj_nn : Q.bj_nn;
-      Q.bd_hd = live ? best.bd_hd : Q.bd_hd;
-      Q.bj_hd = live ? best.bj_hd : Q.bj_hd;
-    }
-    Q.m_nn = new_nn;
-    Q.m_hd = new_hd;
-  };
-
-  f32x16 accA, accB;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) accB[r] = INFINITY;
-  uint32_t tB = 0;
-  auto tile_body = [&](const s16x8 (&a)[NM], const float4 (&nv)[4], uint32_t t) {
-    const f32x16 c0 = frag16(nv);
-    if constexpr (TQ == 1) {
-      float tmin = INFINITY;
-      nn_chain<NM>(a, b[0], c0, accA, accB, tmin);
-      finish(accB, std::integral_constant<int, 0>{}, tmin, tB);
-      accB = accA;
-    } else {
-      constexpr_for_pairs<TQ>([&](auto qt_c) {
-        constexpr int qt = decltype(qt_c)::value;
-        constexpr int qb = (qt == 0) ? TQ - 1 : qt - 1;
-        float tmin = INFINITY;
-        nn_chain<NM>(a, b[qt], c0, accA, accB, tmin);
-        finish(accB, std::integral_constant<int, qb>{}, tmin, (qt == 0) ? tB : t);
-        tmin = INFINITY;
-        nn_chain<NM>(a, b[qt + 1], c0, accB, accA, tmin);
-        finish(accA, std::integral_constant<int, qt>{}, tmin, t);
-      });
-    }
-    keep_alive(c0);
-    tB = t;
-  };
-
-  for (uint32_t t = 0; t < T; t += 2) {
-    load_tile<NM>(X.img_r, X.norms_r, (t + 1 < T) ? t + 1 : t, lane, h, a1, n1);
-    tile_body(a0, n0, t);
-    if (t + 1 < T) {
-      load_tile<NM>(X.img_r, X.norms_r, (t + 2 < T) ? t + 2 : t + 1, lane, h, a0, n0);
-      tile_body(a1, n1, t + 1);
-    }
-  }
-  {
-    float tmin = INFINITY;
-    tile_min<0, 16>(accB, tmin);
-    finish(accB, std::integral_constant<int, TQ - 1>{}, tmin, tB);
-  }
-
-#pragma unroll
-  for (int qt = 0; qt < TQ; ++qt) {
-    NnQ& Q = q[qt];
-    float od = __shfl_xor(Q.bd_nn, 32, 64);
-    uint32_t oj = (uint32_t)__shfl_xor((int)Q.bj_nn, 32, 64);
-    lexi_update(oj <= n_ref, Q.bd_nn, Q.bj_nn, od, oj, n_ref);
-    od = __shfl_xor(Q.bd_hd, 32, 64);
-    oj = (uint32_t)__shfl_xor((int)Q.bj_hd, 32, 64);
-    lexi_update(oj <= n_ref, Q.bd_hd, Q.bj_hd, od, oj, n_ref);
-    if (h == 0 && ((livemask[qt] >> lane) & 1)) {
-      nn_idx[jq[qt]] = Q.bj_nn;
-      nn_d2[jq[qt]] = Q.bd_nn;
-      if (X.pq) {
-        hd_idx[jq[qt]] = Q.bj_hd;
-        hd_d2[jq[qt]] = Q.bd_hd;
-      }
-    }
-  }
-}
-
-template <int S>
-void pop_cross_dispatch(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to, const Rad2& rad2,
-                        uint32_t* pops, hipStream_t s) {
-  constexpr int kTQ = tq_full_for<S>;
-  const dim3 grid(grid_for(i_from, i_to, kTQ)), block(256);
-  sweep_timer_mark(0, true, s);
-  hipLaunchKernelGGL((pop_cross_mfma_kernel<S, 1, kTQ>), grid, block, 0, s, X, n_cols, i_from, i_to, rad2, 1, pops);
-  sweep_timer_mark(0, false, s);
-}
-
-template <int S>
-void nn_cross_dispatch(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to, uint32_t* nn_idx,
-                       float* nn_d2, uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
+template <int S, SweepMode M>
+void nn_dispatch(const SweepArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to, uint32_t* nn_idx, float* nn_d2,
+                 uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
   constexpr int kTQnn = tq_full_for<S>;
   const dim3 grid(grid_for(i_from, i_to, kTQnn)), block(256);
   sweep_timer_mark(1, true, s);
-  hipLaunchKernelGGL((nn_cross_mfma_kernel<S, kTQnn>), grid, block, 0, s, X, n_cols, i_from, i_to, nn_idx, nn_d2,
-                     hd_idx, hd_d2);
+  hipLaunchKernelGGL((nn_mfma_kernel<S, kTQnn, M>), grid, block, 0, s, X, n_cols, i_from, i_to, nn_idx, nn_d2, hd_idx,
+                     hd_d2);
   sweep_timer_mark(1, false, s);
 }
 
@@ -3563,9 +3266,8 @@ void nn_cross_dispatch(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uin
 // one translation unit per MFMA count NM = nm_for(n_cols) (dc_mfma_step.hip, -DDC_STEP=n) so the
 // instances build in parallel; dc_mfma.hip switches over them.
 #define DC_DECLARE_STEP(SV)                                                                      \
-  void pop_mfma_step_##SV(const float* coords, uint32_t n_rows, uint32_t n_cols, void* d_ws,     \
-                          uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad,           \
-                          uint32_t* pops, hipStream_t s);                                        \
+  void pop_mfma_step_##SV(const SweepArgs& X, SweepMode mode, uint32_t n_cols, uint32_t i_from,  \
+                          uint32_t i_to, const Rad2& rad2, uint32_t* pops, hipStream_t s);       \
   void pop_pruned_step_##SV(const PopPlan& plan, const float* coords, uint32_t n_rows, uint32_t n_cols, \
                             void* d_ws, uint32_t T_ref, uint32_t n_q, int q_mode, QSeg q_seg, const Rad2& rad2, \
                             int n_rad, uint32_t* pops, const EdgeSink* sink, hipStream_t s, bool pos_clean); \
@@ -3573,12 +3275,8 @@ void nn_cross_dispatch(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uin
                            void* d_ws, uint32_t T_ref, uint32_t n_q, int q_mode, QSeg q_seg, float cell2, \
                            uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2,             \
                            hipStream_t s);                                                       \
-  void nn_mfma_step_##SV(const float* coords, uint32_t n_rows, uint32_t n_cols, void* d_ws,      \
-                         uint32_t i_from, uint32_t i_to, uint32_t* nn_idx, float* nn_d2,         \
-                         uint32_t* hd_idx, float* hd_d2, hipStream_t s);                         \
-  void pop_cross_step_##SV(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to,  \
-                           const Rad2& rad2, uint32_t* pops, hipStream_t s);                     \
-  void nn_cross_step_##SV(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to,   \
-                          uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2, hipStream_t s);
+  void nn_mfma_step_##SV(const SweepArgs& X, SweepMode mode, uint32_t n_cols, uint32_t i_from,   \
+                         uint32_t i_to, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx,        \
+                         float* hd_d2, hipStream_t s);
 
 }  // namespace dc

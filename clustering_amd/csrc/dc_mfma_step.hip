@@ -11,12 +11,10 @@
 
 namespace dc {
 
-void DC_CAT(pop_mfma_step_, DC_STEP)(const float* coords, uint32_t n_rows, uint32_t n_cols,
-                                     void* d_ws, uint32_t i_from, uint32_t i_to, const Rad2& rad2,
-                                     int n_rad, uint32_t* pops, hipStream_t s) {
-  const Layout L = make_layout(n_rows, n_cols);
-  pop_dispatch<DC_STEP>(coords, n_rows, n_cols, ws_ptrs(d_ws, L), L.T, i_from, i_to, rad2, n_rad,
-                        pops, s);
+void DC_CAT(pop_mfma_step_, DC_STEP)(const SweepArgs& X, SweepMode mode, uint32_t n_cols, uint32_t i_from,
+                                     uint32_t i_to, const Rad2& rad2, uint32_t* pops, hipStream_t s) {
+  (mode == kSelf ? pop_dispatch<DC_STEP, kSelf> : pop_dispatch<DC_STEP, kAgainst>)(X, n_cols, i_from, i_to, rad2, pops,
+                                                                                   s);
 }
 
 void DC_CAT(pop_pruned_step_, DC_STEP)(const PopPlan& plan, const float* coords, uint32_t n_rows, uint32_t n_cols,
@@ -64,22 +62,11 @@ void DC_CAT(nn_pruned_step_, DC_STEP)(const NnPlan& plan, const float* coords, u
                               (unsigned long long*)(p + 16), nn_idx, nn_d2, hd_idx, hd_d2, s);
 }
 
-void DC_CAT(nn_mfma_step_, DC_STEP)(const float* coords, uint32_t n_rows, uint32_t n_cols,
-                                    void* d_ws, uint32_t i_from, uint32_t i_to, uint32_t* nn_idx,
-                                    float* nn_d2, uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
-  const Layout L = make_layout(n_rows, n_cols);
-  nn_dispatch<DC_STEP>(coords, n_rows, n_cols, ws_ptrs(d_ws, L), L.T, i_from, i_to, nn_idx, nn_d2,
-                       hd_idx, hd_d2, s);
-}
-
-void DC_CAT(pop_cross_step_, DC_STEP)(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
-                                      const Rad2& rad2, uint32_t* pops, hipStream_t s) {
-  pop_cross_dispatch<DC_STEP>(X, n_cols, i_from, i_to, rad2, pops, s);
-}
-
-void DC_CAT(nn_cross_step_, DC_STEP)(const CrossArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
-                                     uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
-  nn_cross_dispatch<DC_STEP>(X, n_cols, i_from, i_to, nn_idx, nn_d2, hd_idx, hd_d2, s);
+void DC_CAT(nn_mfma_step_, DC_STEP)(const SweepArgs& X, SweepMode mode, uint32_t n_cols, uint32_t i_from,
+                                    uint32_t i_to, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2,
+                                    hipStream_t s) {
+  (mode == kSelf ? nn_dispatch<DC_STEP, kSelf> : nn_dispatch<DC_STEP, kAgainst>)(X, n_cols, i_from, i_to, nn_idx, nn_d2,
+                                                                                 hd_idx, hd_d2, s);
 }
 
 }  // namespace dc

@@ -32,15 +32,25 @@ def _dev(t):
     return C.c_void_p(t.data_ptr())
 
 
-class Workspace:
-    """Device scratch for the sweeps (MFMA operand images); grown on demand, reused across calls."""
+def _self_bytes(n_rows, n_cols, n_radii=1):
+    return capi.lib.dc_hip_workspace_bytes(n_rows, n_cols, n_radii)
 
-    def __init__(self, device):
+
+def _cross_bytes(n_q, n_ref, n_cols):
+    return capi.lib.dc_hip_cross_workspace_bytes(n_q, n_ref, n_cols)
+
+
+class Workspace:
+    """Device scratch of one kind of sweep (MFMA operand images); grown on demand, reused across calls.
+    ``size`` is the library's byte count for a call's shape: get(*shape) asks it and returns (pointer, bytes)."""
+
+    def __init__(self, device, size=_self_bytes):
         self.device = device
+        self.size = size
         self.buf = None
 
-    def get(self, n_rows, n_cols, n_radii=1):
-        need = int(capi.lib.dc_hip_workspace_bytes(n_rows, n_cols, n_radii))
+    def get(self, *shape):
+        need = int(self.size(*shape))
         if need == 0:
             return C.c_void_p(0), 0
         if self.buf is None or self.buf.numel() < need:
@@ -48,14 +58,23 @@ class Workspace:
         return _dev(self.buf), int(self.buf.numel())
 
 
-_workspaces = {}
+_workspaces = {}        # self sweeps, per device
+_cross_workspaces = {}  # sweeps against a reference, per device
+
+
+def _cached(cache, device, size):
+    key = str(device)
+    if key not in cache:
+        cache[key] = Workspace(device, size)
+    return cache[key]
 
 
 def _workspace(device):
-    key = str(device)
-    if key not in _workspaces:
-        _workspaces[key] = Workspace(device)
-    return _workspaces[key]
+    return _cached(_workspaces, device, _self_bytes)
+
+
+def _cross_workspace(device):
+    return _cached(_cross_workspaces, device, _cross_bytes)
 
 
 def _variant(variant, stats_valid):
@@ -183,26 +202,6 @@ def nearest_neighbors_partial(coords, fe, i_from=0, i_to=None, variant="auto", s
 
 
 # ---- cross sweeps: new frames against a reference trajectory (include/dc_density.h "cross sweeps") ----------------
-class _CrossWorkspace(Workspace):
-    def get(self, n_q, n_ref, n_cols):
-        need = int(capi.lib.dc_hip_cross_workspace_bytes(n_q, n_ref, n_cols))
-        if need == 0:
-            return C.c_void_p(0), 0
-        if self.buf is None or self.buf.numel() < need:
-            self.buf = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return _dev(self.buf), int(self.buf.numel())
-
-
-_cross_workspaces = {}
-
-
-def _cross_workspace(device):
-    key = str(device)
-    if key not in _cross_workspaces:
-        _cross_workspaces[key] = _CrossWorkspace(device)
-    return _cross_workspaces[key]
-
-
 def _check_pair(queries, reference):
     n_q, n_cols = _check_coords(queries)
     n_ref, n_cols_r = _check_coords(reference)

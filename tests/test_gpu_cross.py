@@ -167,6 +167,30 @@ def test_query_equals_reference_gives_the_self_populations(dens, oracle):
         assert (host(got).astype(np.uint64) == want).all(), v
 
 
+@pytest.mark.parametrize("D", [10, 33, 401])
+def test_same_buffer_on_both_sides_keeps_the_self_pair(dens, probe, D):
+    """Against a reference that is the query buffer itself, every pair counts, the self pair included: radius 0 gives
+    0 (a self sweep gives 1), and each frame's nearest reference is its lowest-index exact copy at d2 = 0 (a self sweep
+    gives another frame).  Nothing may decide the mode by comparing the two pointers."""
+    n = 777 if D <= 64 else 300
+    c = gaussian_blobs(n, D, seed=D + 17)
+    rng = np.random.default_rng(D)
+    c[rng.integers(0, n, n // 8)] = c[rng.integers(0, n, n // 8)]   # exact copies, before and after their originals
+    d2 = block_d2(probe, c, c)
+    radii = [0.0, radius(D), 0.5 * radius(D)]
+    pops_exp = expect_pops(d2, radii)
+    assert (pops_exp[0] == 0).all()
+    fe = rng.normal(size=n).astype(np.float32)
+    nn_exp = expect_nn(d2, fe, fe)
+    assert (nn_exp[1] == 0).all() and (nn_exp[0] <= np.arange(n)).all()
+    t, f = gpu(c), gpu(fe)
+    for v in variants(D):
+        pops = dens.calculate_populations_against(t, t, radii, variant=v)
+        assert (host(pops) == pops_exp).all(), (D, v)
+        same_nn(dens.nearest_reference(t, t, f, f, variant=v), nn_exp, (D, v))
+        same_nn(dens.nearest_reference(t, t, variant=v), nn_exp[:2], (D, v, "nn only"))
+
+
 @pytest.mark.parametrize("family", sorted(fe_families.FAMILIES))
 def test_copies_of_reference_frames(dens, oracle, family):
     """Q = R[S]: the populations are the self populations of S, the free energies against R's maximum are fe_R[S] bit
