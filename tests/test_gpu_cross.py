@@ -3,18 +3,16 @@ clustering_amd.density.calculate_populations_against / nearest_reference / assig
 the CPU referees: the [n_q, n_r] block of the probe's pairwise d2 matrix (the reference's own loop shape) for
 populations and neighbours, the oracle's populations of the union for large runs, the oracle's self sweeps for the
 properties a cross sweep must share with them, and Python's math.log (the host libm) for the free energies."""
-import math
-
 import numpy as np
 import pytest
 
 import fe_families
+from crossref import (FLT_MAX, F32, bits, block_d2, expect_nn, expect_pops, fe_of, gpu, host, radius,
+                      same_nn, sets, variants)
 from clustering_amd.synth import gaussian_blobs
 
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-FLT_MAX = np.finfo(np.float32).max
 WIDTHS = [1, 2, 3, 4, 5, 9, 10, 16, 30, 33, 64, 65, 100, 401]
 
 
@@ -38,94 +36,6 @@ def oracle():
     from clustering_amd import capi
     from oracle.oracle import Oracle
     return Oracle(order=capi.CANON_ORDER)
-
-
-def variants(D):
-    return ("auto", "direct", "mfma") if D <= 64 else ("auto", "direct")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def gpu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def block_d2(probe, Q, R):
-    """canonical d2 of every (query, reference) pair: the [n_q, n_r] block of the probe's matrix of the union"""
-    n_q = len(Q)
-    return probe.pairwise_d2(np.vstack([Q, R]))[:n_q, n_q:]
-
-
-def expect_pops(d2, radii, i_from=0, i_to=None):
-    i_to = d2.shape[0] if i_to is None else i_to
-    out = np.zeros((len(radii), d2.shape[0]), dtype=np.int64)
-    for k, r in enumerate(radii):
-        r2 = F32(r) * F32(r)
-        out[k, i_from:i_to] = (d2[i_from:i_to] < r2).sum(axis=1)
-    return out
-
-
-def lexi_min(d2, allowed):
-    """per row the lexicographic minimum of (d2, j) over allowed candidates with d2 < FLT_MAX -> (idx, d2)"""
-    n_q, n_r = d2.shape
-    ok = allowed & (d2 < FLT_MAX)
-    v = np.where(ok, d2, np.inf)
-    m = v.min(axis=1) if n_r else np.full(n_q, np.inf)
-    has = np.isfinite(m)
-    idx = np.where(has, np.argmax(ok & (v == m[:, None]), axis=1) if n_r else 0, n_r + 1).astype(np.int64)
-    return idx, np.where(has, m, FLT_MAX).astype(np.float32)
-
-
-def expect_nn(d2, fe_q=None, fe_r=None, i_from=0, i_to=None):
-    n_q, n_r = d2.shape
-    i_to = n_q if i_to is None else i_to
-    nn_i, nn_d = lexi_min(d2, np.ones_like(d2, dtype=bool))
-    out = [nn_i, nn_d]
-    if fe_q is not None:
-        with np.errstate(invalid="ignore"):
-            out += list(lexi_min(d2, fe_r[None, :] < fe_q[:, None]))
-    rows = np.zeros(n_q, dtype=bool)
-    rows[i_from:i_to] = True
-    for k in range(0, len(out), 2):
-        out[k] = np.where(rows, out[k], n_r + 1)
-        out[k + 1] = np.where(rows, out[k + 1], FLT_MAX).astype(np.float32)
-    return out
-
-
-def same_nn(got, exp, what):
-    g = [host(t) for t in got if t is not None]
-    assert len(g) == len(exp), what
-    for k in range(0, len(exp), 2):
-        assert (g[k].astype(np.int64) == exp[k]).all(), (what, "idx", k, np.flatnonzero(g[k] != exp[k])[:5])
-        assert (bits(g[k + 1]) == bits(exp[k + 1])).all(), (what, "d2", k)
-
-
-def sets(D, n_q, n_r, seed):
-    """queries and references from the same blobs, with exact duplicates between and within the sets"""
-    c = gaussian_blobs(n_q + n_r, D, seed=seed)
-    rng = np.random.default_rng(seed)
-    Q, R = c[:n_q].copy(), c[n_q:].copy()
-    if n_q >= 8 and n_r >= 8:
-        Q[rng.integers(0, n_q, n_q // 8)] = R[rng.integers(0, n_r, n_q // 8)]
-        R[rng.integers(0, n_r, n_r // 16)] = R[rng.integers(0, n_r, n_r // 16)]
-    return Q, R
-
-
-def radius(D):
-    return 0.2 if D <= 10 else float(0.08 * np.sqrt(2.0 * D))
-
-
-def fe_of(pops, max_pop):
-    """the free energies of the reference's formula, with the host libm"""
-    rec = F32(1.0) / F32(max_pop)
-    return np.array([F32(-math.log(float(F32(F32(p) * rec)))) if p else F32(np.inf) for p in pops], dtype=np.float32)
 
 
 # ---- parity ---------------------------------------------------------------------------------------------------------

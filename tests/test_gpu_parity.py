@@ -820,8 +820,9 @@ def test_sweep_forms_agree():
 @pytest.mark.gpu
 def test_degenerate_inputs_pruned_equals_direct(dens):
     """Inputs at the edges of the scale rule of the matrix-core sweeps -- all rows identical (M = 0: every pair in the
-    band), two far points with a tiny radius, a radius beyond everything / of 1e-30 / infinite, coordinates of 1e15 and
-    1e-15, a constant and a huge column, lattices (exact ties), n = 1 and 2, 64 columns: pruned sweeps = direct kernels."""
+    band), two far points with a tiny radius, a radius beyond everything / of 1e-30 / infinite / NaN / of 1e20 (whose fp32
+    square is inf), coordinates of 1e15 and 1e-15, a constant and a huge column, lattices (exact ties), n = 1 and 2, 64
+    columns: the pruned and the unpruned matrix-core sweeps = direct kernels."""
     import torch
     rng = np.random.default_rng(5)
     n, d = 5000, 10
@@ -838,6 +839,9 @@ def test_degenerate_inputs_pruned_equals_direct(dens):
                                                      rng.normal(size=(n, 1)) * 1e6], 1), [3.0, 1e6]),
         ("radius 1e-30", rng.normal(size=(n, d)), [1e-30, 3.0]),
         ("radius inf", rng.normal(size=(300, 3)), [float("inf")]),
+        ("radius NaN", rng.normal(size=(n, d)), [float("nan")]),
+        ("radius 1e20", rng.normal(size=(700, 5)), [1e20]),
+        ("NaN and 1e20 among others", rng.normal(size=(n, d)), [3.0, float("nan"), 1e20, 0.5]),
         ("n = 1", rng.normal(size=(1, 7)), [1.0]),
         ("n = 2 identical", np.ones((2, 40)), [0.0, 1.0]),
         ("64 columns", rng.normal(size=(3000, 64)), [8.0, 11.0, 12.5]),
@@ -845,13 +849,14 @@ def test_degenerate_inputs_pruned_equals_direct(dens):
     ]
     for name, c, radii in cases:
         ct = torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)).cuda()
-        a = dens.calculate_populations_partial(ct, radii, variant="pruned")
         b = dens.calculate_populations_partial(ct, radii, variant="direct")
-        assert bool((a == b).all()), name
         fe = dens.calculate_free_energies(b[0].contiguous())
-        for p, q in zip(dens.nearest_neighbors_partial(ct, fe, variant="pruned"),
-                        dens.nearest_neighbors_partial(ct, fe, variant="direct")):
-            assert bool((p.view(torch.int32) == q.view(torch.int32)).all()), name
+        nn = dens.nearest_neighbors_partial(ct, fe, variant="direct")
+        for v in ("pruned", "mfma"):
+            a = dens.calculate_populations_partial(ct, radii, variant=v)
+            assert bool((a == b).all()), (name, v)
+            for p, q in zip(dens.nearest_neighbors_partial(ct, fe, variant=v), nn):
+                assert bool((p.view(torch.int32) == q.view(torch.int32)).all()), (name, v)
 
 
 @pytest.mark.gpu
