@@ -272,7 +272,8 @@ DC_API int dc_hip_sigma2_dev(const float* d_nn_d2, size_t n_rows, double* sigma2
  * pruned matrix-core sweep for n_cols <= 64; an exact direct sweep over all pairs for any wider rows
  * and for coordinates that are not finite (inf / NaN in a row: no partners, population 1, as in the
  * reference), chosen on the device like the populations' fallback.
- *   r2       the squared distance itself (the reference passes max_dist = 4*sigma2, a float)
+ *   r2       the squared distance itself (the reference passes max_dist = 4*sigma2, a float); a NaN, like 0 or a
+ *            negative value, holds no pair
  *   d_pops   [n_rows] uint32 device, out: populations at that radius (1 + number of partners)
  *   d_pairs  [capacity][2] uint32 device, out: frame ids of the pairs, in no particular order, each
  *            pair once; may be NULL with capacity 0 to count only
@@ -293,7 +294,8 @@ DC_API int dc_hip_radius_pairs_dev(const float* d_coords, size_t n_rows, size_t 
  *   d_best   [n_rows] uint64 device, out: d_best[id] = (max << 32 | min) of the lightest pair with
  *            canonical d2 < r2 that joins component id to another one, ~0 if there is none
  *   d_pops   [n_rows] uint32 device, out: populations at that radius
- * Needs n_rows <= 2^24, and a workspace as above for n_cols <= 64 (none for n_cols > 64).  Any column
+ * Needs n_rows <= 2^24 - 32768 (the sweep's queue holds 24-bit positions of the padded spatial order; more rows are
+ * DC_ERR_INVALID_ARGUMENT), and a workspace as above for n_cols <= 64 (none for n_cols > 64).  Any column
  * count and coordinates that are not finite are served (the direct sweep, as for the pairs). */
 DC_API int dc_hip_radius_min_edge_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
                                       const uint32_t* d_comp, const uint32_t* d_rank,

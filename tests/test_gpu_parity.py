@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from clustering_amd.synth import gaussian_blobs
+from graphref import components as _components
 
 pytestmark = pytest.mark.gpu
 
@@ -383,21 +384,6 @@ def test_radius_pairs_match_brute_force(dens, n_rows, n_cols, r2):
         deg[a] += 1
         deg[b] += 1
     assert (pops.cpu().numpy().astype(np.int64) == deg).all()
-
-
-def _components(n, pairs):
-    parent = list(range(n))
-
-    def find(x):
-        while parent[x] != x:
-            parent[x] = parent[parent[x]]
-            x = parent[x]
-        return x
-    for a, b in pairs:
-        ra, rb = find(int(a)), find(int(b))
-        if ra != rb:
-            parent[max(ra, rb)] = min(ra, rb)
-    return np.array([find(i) for i in range(n)])
 
 
 @pytest.mark.gpu

@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 
 from clustering_amd.synth import gaussian_blobs
+from graphref import ALL_ONES, brute_pairs, components, degrees, keys, min_edge_brute, raw_pairs
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "clustering_amd", "bin", "clustering")
-ALL_ONES = np.iinfo(np.uint64).max
 
 
 @pytest.fixture(scope="module")
@@ -59,43 +59,6 @@ def with_non_finite(c):
     c[400, 0] = np.nan
     c[401, D - 1] = -np.inf
     return c
-
-
-def brute_pairs(probe, c, r2):
-    """[n_pairs, 2] int64, i < j, sorted: every pair with canonical d2 < r2 (the reference's loop, d2(i,j) = d2(j,i))"""
-    d2 = probe.pairwise_d2(c)
-    ii, jj = np.nonzero(np.triu(d2 < np.float32(r2), k=1))
-    return np.stack([ii, jj], axis=1).astype(np.int64)
-
-
-def keys(pairs, n):
-    p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    return np.minimum(p[:, 0], p[:, 1]) * n + np.maximum(p[:, 0], p[:, 1])
-
-
-def degrees(pairs, n):
-    deg = np.ones(n, dtype=np.int64)
-    np.add.at(deg, pairs[:, 0], 1)
-    np.add.at(deg, pairs[:, 1], 1)
-    return deg
-
-
-def raw_pairs(dens, ct, r2, capacity):
-    """one dc_hip_radius_pairs_dev call -> (count, pairs int32 numpy [capacity, 2] or None, pops)"""
-    import torch
-    from clustering_amd import capi
-    n, d = ct.shape
-    pops = torch.zeros(n, dtype=torch.int32, device=ct.device)
-    count = torch.zeros(1, dtype=torch.int64, device=ct.device)
-    pairs = torch.full((capacity, 2), -1, dtype=torch.int32, device=ct.device) if capacity else None
-    ws, ws_bytes = dens._workspace(ct.device).get(n, d, 1)
-    with torch.cuda.device(ct.device):
-        rc = capi.lib.dc_hip_radius_pairs_dev(dens._dev(ct), n, d, float(r2), dens._dev(pops),
-                                              dens._dev(pairs) if pairs is not None else None, capacity,
-                                              dens._dev(count), ws, ws_bytes, dens._stream_ptr())
-    capi.check(rc, "dc_hip_radius_pairs_dev")
-    torch.cuda.synchronize()
-    return int(count.item()), (pairs.cpu().numpy() if pairs is not None else None), pops.cpu().numpy()
 
 
 def check_pair_list(dens, canon_probe, canon_oracle, c, r, r2):
@@ -147,19 +110,6 @@ def test_radius_pairs_non_finite_rows(dens, canon_probe, canon_oracle, n_cols):
     assert (pops.cpu().numpy()[bad] == 1).all()
 
 
-def min_edge_brute(pairs, comp, rank, n):
-    want = np.full(n, ALL_ONES, dtype=np.uint64)
-    a, b = pairs[:, 0], pairs[:, 1]
-    cross = comp[a] != comp[b]
-    a, b = a[cross], b[cross]
-    hi = np.maximum(rank[a], rank[b]).astype(np.uint64)
-    lo = np.minimum(rank[a], rank[b]).astype(np.uint64)
-    key = (hi << np.uint64(32)) | lo
-    np.minimum.at(want, comp[a], key)
-    np.minimum.at(want, comp[b], key)
-    return want
-
-
 @pytest.mark.parametrize("n_cols,non_finite", [(70, False), (10, True)])
 def test_min_edge_round_wide_and_flagged(dens, canon_probe, n_cols, non_finite):
     import torch
@@ -191,21 +141,6 @@ def test_min_edge_round_wide_and_flagged(dens, canon_probe, n_cols, non_finite):
         acc_b = np.minimum(acc_b, b.cpu().numpy().view(np.uint64))
         acc_p += p.cpu().numpy().astype(np.int64)
     assert (acc_b == got).all() and (acc_p == degrees(pairs, n)).all()
-
-
-def components(n, pairs):
-    parent = np.arange(n)
-
-    def find(x):
-        while parent[x] != x:
-            parent[x] = parent[parent[x]]
-            x = parent[x]
-        return x
-    for a, b in pairs:
-        ra, rb = find(int(a)), find(int(b))
-        if ra != rb:
-            parent[max(ra, rb)] = min(ra, rb)
-    return np.array([find(i) for i in range(n)])
 
 
 @pytest.mark.parametrize("n_rows,n_cols,non_finite", [(1500, 70, False), (1200, 100, False), (2000, 10, True)])
