@@ -73,6 +73,7 @@
 //   norms  [32T]               |y'|^2 (double accumulate, rounded once); +inf for the pad rows
 #pragma once
 #include "dc_mfma.hpp"
+#include "dc_credit.hpp"
 
 #include <assert.h>
 #include <float.h>
@@ -668,7 +669,7 @@ __device__ __forceinline__ float dead_const(const Scale& sc) { return ldexpf(655
 
 // row of reference tile t held by register r of a lane in half h
 __device__ __forceinline__ uint32_t tile_row(uint32_t t, int r, int h) {
-  return 32u * t + (uint32_t)((r & 3) + 8 * (r >> 2) + 4 * h);
+  return 32u * t + tile_row_local(r, h);
 }
 
 // The rows an exact re-check reads: one coordinate matrix that holds the query and the reference rows (self
@@ -1120,13 +1121,16 @@ __device__ __attribute__((noinline)) void pop_wave_flush_rows(const uint32_t* qu
 // the TQ chains of the wave's query tiles together (they meet the same 32 reference rows):
 //   in-lane     the sign bits of three strings add up bit-sliced (xor3 / majority: two v_bitop3) into 2-bit fields,
 //               the fields of the groups of three are added in 4-bit slots (even / odd elements apart);
-//   lanes       one step of the lane reduction fits the 4-bit slots (<= 12), then the slots are spread to bytes
-//               (four words, <= 192 = TQ * 32) for the remaining steps: row_shr 2, 4, 8 and row_bcast15 into the
-//               odd rows -- lanes 31 / 63 end up with the sums over the queries of their half;
-//   rows        those two lanes leave their 16 bytes in LDS, lane i < 32 picks the byte of row i and adds it to
-//               the row's count with one 128-byte atomic per tile.
-// ~50 VALU instructions per reference tile, i.e. 8 per chain at TQ = 6 -- against the 21 + 2 MFMAs of the second
-// chain they replace.
+//   lanes       a halving butterfly (dc_credit.hpp: the network, its levels and bounds, and the element each lane ends up
+//               with): the two words change places across the DPP rows of a half-wave (c ^ 16) and add to one word of
+//               4-bit slots (<= 12); its even and odd slots widen to bytes, are added across c ^ 8 and every lane keeps
+//               the set its bank names (<= 24); from there a lane carries one word of four bytes, so the last three
+//               levels (c ^ 1, c ^ 2, c ^ 4) are one v_add_u32_dpp each (<= 192 = TQ * 32);
+//   rows        16 lanes of a half-wave take one byte each and add it to the count of the row it belongs to, straight
+//               from the registers: one atomic per tile, nothing staged in LDS, no wave barrier.
+// (The multi-radius sweep's window reducer, dc_mfma_msym.hpp, keeps the earlier form -- a full-width DPP tree whose row-end
+// lanes stage their bytes in LDS, dpp_take / ref_credit_byte below: its lanes are LDS accumulators of two radii, not the
+// queries of one, and it has no register to spare.)
 template <int CTRL, int ROW_MASK = 0xF>
 __device__ __forceinline__ uint32_t dpp_take(uint32_t v) {   // v of the source lane, 0 where there is none
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, ROW_MASK == 0xF);
@@ -1136,46 +1140,55 @@ __device__ __forceinline__ uint32_t ref_credit_byte(int lane) {
   const int i = lane & 31, hh = (i >> 2) & 1, r = (i & 3) + 4 * (i >> 3), f = 15 - r;
   return (uint32_t)(16 * hh + 4 * (f & 3) + (f >> 2));
 }
+// the exchanges of credit_network on the device
+struct CreditDpp {
+  __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) const {
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+  }
+  __device__ __forceinline__ uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) const {
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
+  }
+  __device__ __forceinline__ uint32_t pick_bits(uint32_t m, uint32_t a, uint32_t b) const {
+    return __builtin_amdgcn_bitop3_b32(a, b, m, 0xE4);
+  }
+  __device__ __forceinline__ void swap16(uint32_t& a, uint32_t& b) const {
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = r[0];
+    b = r[1];
+  }
+  template <int CTRL>
+  __device__ __forceinline__ uint32_t take(uint32_t v) const {   // (every lane of these controls has a source)
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
+  }
+  template <int BANKS>
+  __device__ __forceinline__ uint32_t pick(uint32_t u, uint32_t v) const {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)u, (int)v, 0xE4 /* quad_perm:[0,1,2,3] */, 0xF, BANKS, false);
+  }
+  __device__ __forceinline__ void level(int, uint32_t, int, uint32_t) const {}
+};
 template <int TQ>
 __device__ __forceinline__ void ref_credit(const uint32_t (&sb)[TQ], uint32_t t, uint32_t n_rows,
-                                           uint32_t* __restrict__ pops_pos, uint32_t* stage /* 8 words of LDS */,
-                                           uint32_t my_byte, int lane) {
-  static_assert(TQ <= 6, "4-bit slots hold the sums of two groups of three strings over two lanes");
+                                           uint32_t* __restrict__ pops_pos, int lane) {
   {  // nothing inside in the whole tile (tiles at the edge of the pruning radius): nothing to credit
     uint32_t any = 0;
 #pragma unroll
     for (int q = 0; q < TQ; ++q) any |= sb[q];
     if (__builtin_amdgcn_ballot_w64((any & kSignBits) != 0u) == 0) return;
   }
-  uint32_t A = 0, B = 0;
-#pragma unroll
-  for (int g = 0; g < TQ; g += 3) {
-    const uint32_t a = sb[g], b = (g + 1 < TQ) ? sb[g + 1] : 0u, c = (g + 2 < TQ) ? sb[g + 2] : 0u;
-    const uint32_t lo = a ^ b ^ c, hi = (a & b) | (a & c) | (b & c);   // valid at the sign positions (odd bits)
-    const uint32_t x = ((lo >> 1) & 0x55555555u) | (hi & kSignBits);   // element r: 0..3 at bits 31-2r, 30-2r
-    A += x & 0x33333333u;
-    B += (x >> 2) & 0x33333333u;
-  }
-  A += dpp_take<0x111>(A);   // row_shr:1
-  B += dpp_take<0x111>(B);
-  uint32_t W[4] = {A & 0x0F0F0F0Fu, B & 0x0F0F0F0Fu, (A >> 4) & 0x0F0F0F0Fu, (B >> 4) & 0x0F0F0F0Fu};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    W[e] += dpp_take<0x112>(W[e]);         // row_shr:2
-    W[e] += dpp_take<0x114>(W[e]);         // row_shr:4
-    W[e] += dpp_take<0x118>(W[e]);         // row_shr:8
-    W[e] += dpp_take<0x142, 0xA>(W[e]);    // row_bcast15 into rows 1 and 3: lanes 31 / 63 hold their half's sums
-  }
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) u32x4 LdsU4;
-  typedef __attribute__((address_space(3))) unsigned char LdsU8;
-  if ((lane & 31) == 31) ((LdsU4*)stage)[lane >> 5] = u32x4{W[0], W[1], W[2], W[3]};
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (one wave: its LDS operations execute in order)
-  __builtin_amdgcn_wave_barrier();
-  const uint32_t cnt = ((const volatile LdsU8*)stage)[my_byte];
-  __builtin_amdgcn_wave_barrier();
-  const uint32_t row = 32u * t + (uint32_t)lane;
-  if (lane < 32 && cnt != 0u && row < n_rows) atomicAdd(&pops_pos[row], cnt);
+  uint32_t A, B;
+  credit_slots<TQ>(sb, A, B, CreditDpp{});
+  const uint32_t w = credit_network(A, B, CreditDpp{});
+  const uint32_t cnt = __builtin_amdgcn_ubfe(w, credit_lane_shift(lane), 8u);
+  const uint32_t row = 32u * t + credit_lane_row(lane);
+  if (credit_lane_active(lane) && cnt != 0u && row < n_rows) atomicAdd(&pops_pos[row], cnt);
+}
+// (the signature of the staged form, which the device probe tests/cpp/test_mfma_model.hip still calls: the LDS stage and
+// the byte index are not used any more)
+template <int TQ>
+__device__ __forceinline__ void ref_credit(const uint32_t (&sb)[TQ], uint32_t t, uint32_t n_rows,
+                                           uint32_t* __restrict__ pops_pos, uint32_t* /* stage */, uint32_t /* my_byte */,
+                                           int lane) {
+  ref_credit<TQ>(sb, t, n_rows, pops_pos, lane);
 }
 
 __device__ __forceinline__ float box_gap2(const float4& a, const float4& b) {
@@ -1238,7 +1251,6 @@ __global__ __launch_bounds__(256, 2) void pop_pruned_kernel(
     const uint32_t* __restrict__ hdr, unsigned long long* __restrict__ chain_counter, Rad2 rad2,
     int n_rad, uint32_t* __restrict__ pops, EdgeSink sink, CompView CV, uint32_t* __restrict__ pops_pos = nullptr) {
   static_assert(!SYM || (MODE == kSinkNone && NR == 1), "the symmetric sweep is the plain one-radius sweep");
-  __shared__ uint32_t credit_stage[4][8];
   // dynamic LDS, per wave of the workgroup (one wave, see nn_pruned_kernel): the survivor list of a scan round
   // [kListCap], then [TQ*32][n_cols] query rows (original coordinates), then the queues of deferred exact
   // evaluations [TQ][kQueueCap][64]
@@ -1354,7 +1366,6 @@ __global__ __launch_bounds__(256, 2) void pop_pruned_kernel(
   const uint32_t n_groups = (TQT + TQ - 1) / TQ;
   uint32_t sb[TQ];
   bool symB = false;
-  const uint32_t my_byte = ref_credit_byte(lane);
   auto flush_wave = [&]() {
     if constexpr (SYM)
       pop_wave_flush_rows(queues, qn, qrows, fix_tab, coords_r, n_cols, rad2.v[0], lane, pops_pos, (uint32_t)TQ, wave);
@@ -1571,7 +1582,7 @@ __global__ __launch_bounds__(256, 2) void pop_pruned_kernel(
         finish(accB, std::integral_constant<int, qb>{}, e, (qt == 0) ? tB : t);
         if constexpr (SYM && qt == 0) {   // the strings of tile tB are complete now
           if (pendB) park_tile(tB);
-          if (symB) ref_credit<TQ>(sb, tB, CV.n_pos, pops_pos, credit_stage[wib], my_byte, lane);
+          if (symB) ref_credit<TQ>(sb, tB, CV.n_pos, pops_pos, lane);
         }
         pop_epi_begin<NR>(e);
         if constexpr (qt + 2 == TQ)   // last chain of the tile
@@ -1622,7 +1633,7 @@ __global__ __launch_bounds__(256, 2) void pop_pruned_kernel(
       finish(accB, std::integral_constant<int, TQ - 1>{}, e, tB);
       if constexpr (SYM) {
         if (pendB) park_tile(tB);
-        if (symB) ref_credit<TQ>(sb, tB, CV.n_pos, pops_pos, credit_stage[wib], my_byte, lane);
+        if (symB) ref_credit<TQ>(sb, tB, CV.n_pos, pops_pos, lane);
         symB = false;
         pendB = false;
       }

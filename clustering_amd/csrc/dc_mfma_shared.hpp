@@ -140,7 +140,6 @@ __global__ __launch_bounds__(256, 2) void pop_shared_kernel(
   static_assert(TQ % 2 == 0, "accumulator ping-pong needs an even number of query tiles");
   static_assert(NR >= 1 && NR <= 8 && TQ * 32 <= 256, "queue entries: 8 radius flags, 8 bits of query index");
   __shared__ uint32_t lists[4][kShareSub];
-  __shared__ uint32_t credit_stage[4][8];
   __shared__ uint32_t list_cnt[4];
   __shared__ float4 wave_box[4];
   // dynamic LDS: operand ring [kRing][kTileUnits] x 16 B, then per wave the compact queue of deferred exact
@@ -228,11 +227,10 @@ __global__ __launch_bounds__(256, 2) void pop_shared_kernel(
   const uint32_t pos_stride = 32u * T;
   uint32_t sb[NR][TQ];
   bool symB = false;
-  const uint32_t my_byte = ref_credit_byte(lane);
   auto credit = [&](uint32_t t) {
 #pragma unroll
     for (int rr = 0; rr < NR; ++rr)
-      if (rr < n_rad) ref_credit<TQ>(sb[rr], t, CV.n_pos, pops_pos + (size_t)rr * pos_stride, credit_stage[wib], my_byte, lane);
+      if (rr < n_rad) ref_credit<TQ>(sb[rr], t, CV.n_pos, pops_pos + (size_t)rr * pos_stride, lane);
   };
   const float* q_rows = q_in_ref_order ? coords_r : coords;
   auto flush = [&]() {
