@@ -18,7 +18,7 @@ if CANON_ORDER not in _CANON_DIRS:
     raise ImportError(f"DC_CANON_ORDER={CANON_ORDER!r}: expected 'sse2' (the reference's default build), 'avx' or 'fma'")
 LIB_PATH = os.environ.get("DC_LIB_PATH") or os.path.join(_HERE, _CANON_DIRS[CANON_ORDER], "libdcdensity.so")
 
-DC_OK = 0
+DC_OK, DC_ERR_INVALID_ARGUMENT, DC_ERR_HIP = 0, -1, -3
 ABI_VERSION = 5               # include/dc_density.h: DC_HIP_ABI_VERSION this binding was written against
 FLAG_STATS_VALID = 0x100      # DC_FLAG_STATS_VALID
 VARIANT_AUTO, VARIANT_DIRECT, VARIANT_MFMA, VARIANT_MFMA_PRUNED = 0, 1, 2, 3
@@ -45,7 +45,9 @@ SYMBOLS = (
 
 
 class DensityLibraryError(RuntimeError):
-    pass
+    """status: the C ABI's return code (0 where the error did not come from a call); detail: dc_hip_last_error()"""
+    status = 0
+    detail = ""
 
 
 def _load():
@@ -178,7 +180,9 @@ lib = _load()
 def check(rc, what=""):
     if rc != DC_OK:
         msg = lib.dc_hip_last_error().decode("utf-8", "replace")
-        raise DensityLibraryError(f"{what or 'dc_hip call'} failed (status {rc}): {msg}")
+        err = DensityLibraryError(f"{what or 'dc_hip call'} failed (status {rc}): {msg}")
+        err.status, err.detail = int(rc), msg
+        raise err
 
 
 def device_count():

@@ -438,6 +438,8 @@ int dc_hip_session_open(const float* coords, size_t n_rows, size_t n_cols, const
     else if (s->host_merge)
       snprintf(line, sizeof(line), "%d devices: partial results merge THROUGH THE HOST over PCIe, not RCCL (%s)", n_devices,
                s->merge_note.empty() ? "no reason recorded" : s->merge_note.c_str());
+    else if (!s->merge_note.empty())   // (DC_SESSION_FORCE_RCCL=1 on one device, and no communicator)
+      snprintf(line, sizeof(line), "one device: nothing to merge (RCCL was asked for and is not used: %s)", s->merge_note.c_str());
     else
       snprintf(line, sizeof(line), "one device: nothing to merge");
     s->merge_line = line;
@@ -535,7 +537,7 @@ int dc_hip_session_free_energies(dc_hip_session* s, size_t radius_index, float* 
 
 int dc_hip_session_set_free_energies(dc_hip_session* s, const float* fe) {
   DeviceGuard guard;
-  if (!s || !fe) return failf(DC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!s || (!fe && s->n_rows)) return failf(DC_ERR_INVALID_ARGUMENT, "null argument");   // (no rows: nothing to read, like every other entry point)
   if (s->n_rows == 0) return DC_OK;
   const size_t n = s->n_rows;
   int rc = on_every_device(s, [&](int g) -> int {

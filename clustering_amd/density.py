@@ -595,12 +595,15 @@ class Session:
                    "dc_hip_session_populations")
         return out
 
-    def free_energies(self, radius_index=0, fetch=True):
+    def free_energies(self, radius_index=0, fetch=True, max_pop=False):
+        """-> fe float32 [n_rows] (None unless fetch); max_pop=True: (fe, the largest resident population of that radius)"""
         out = np.empty(self.n_rows, dtype=np.float32) if fetch else None
+        mx = C.c_uint32(0)
         capi.check(capi.lib.dc_hip_session_free_energies(self._h, radius_index,
-                                                         out.ctypes.data_as(C.c_void_p) if fetch else None, None),
+                                                         out.ctypes.data_as(C.c_void_p) if fetch else None,
+                                                         C.byref(mx) if max_pop else None),
                    "dc_hip_session_free_energies")
-        return out
+        return (out, int(mx.value)) if max_pop else out
 
     def set_free_energies(self, fe):
         f = np.ascontiguousarray(fe, dtype=np.float32)
@@ -608,17 +611,26 @@ class Session:
         capi.check(capi.lib.dc_hip_session_set_free_energies(self._h, f.ctypes.data_as(C.c_void_p)),
                    "dc_hip_session_set_free_energies")
 
-    def nearest_neighbors(self):
-        """-> (nn_idx u32, nn_d2 f32, hd_idx u32, hd_d2 f32, sigma2)"""
+    def nearest_neighbors(self, nn_idx=True, nn_d2=True, hd_idx=True, hd_d2=True, sigma2=True):
+        """-> (nn_idx u32, nn_d2 f32, hd_idx u32, hd_d2 f32, sigma2); an output switched off goes to the library as NULL
+        (the result then only stays resident) and comes back as None"""
         n = self.n_rows
-        nn_idx, hd_idx = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
-        nn_d2, hd_d2 = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.float32)
+        want = (nn_idx, nn_d2, hd_idx, hd_d2)
+        out = [np.empty(n, dtype=t) if w else None for w, t in zip(want, (np.uint32, np.float32, np.uint32, np.float32))]
         s2 = C.c_double(0.0)
         capi.check(capi.lib.dc_hip_session_nearest_neighbors(
-            self._h, nn_idx.ctypes.data_as(C.c_void_p), nn_d2.ctypes.data_as(C.c_void_p),
-            hd_idx.ctypes.data_as(C.c_void_p), hd_d2.ctypes.data_as(C.c_void_p), C.byref(s2)),
-            "dc_hip_session_nearest_neighbors")
-        return nn_idx, nn_d2, hd_idx, hd_d2, s2.value
+            self._h, *[a.ctypes.data_as(C.c_void_p) if a is not None else None for a in out],
+            C.byref(s2) if sigma2 else None), "dc_hip_session_nearest_neighbors")
+        return out[0], out[1], out[2], out[3], (s2.value if sigma2 else None)
+
+    def radius_pairs(self, r2, capacity):
+        """dc_hip_session_radius_pairs -> (count of all pairs with d2 < r2, uint32 [min(count, capacity), 2]: the pairs
+        written); overwrites the resident populations of device 0"""
+        pairs = np.empty((max(capacity, 1), 2), dtype=np.uint32)
+        count = C.c_uint64(0)
+        capi.check(capi.lib.dc_hip_session_radius_pairs(self._h, float(r2), pairs.ctypes.data_as(C.c_void_p) if capacity else None,
+                                                        capacity, C.byref(count)), "dc_hip_session_radius_pairs")
+        return int(count.value), pairs[:min(int(count.value), capacity)].copy()
 
     def radius_forest(self, r2, rank):
         rank = np.ascontiguousarray(rank, dtype=np.uint32)

@@ -463,7 +463,8 @@ DC_API int dc_hip_session_free_energies(dc_hip_session* session, size_t radius_i
                                         uint32_t* max_pop);
 /* free energies from the caller instead (-D re-use, density_clustering.cpp:600-611; and the reference's
  * nearest_neighbors(coords, ..., free_energy) signature).  fe: HOST [n_rows], any floats, compared as
- * dc_hip_nearest_neighbors does (IEEE fe[j] < fe[i]: NaN is never lower, -0.0 not lower than +0.0). */
+ * dc_hip_nearest_neighbors does (IEEE fe[j] < fe[i]: NaN is never lower, -0.0 not lower than +0.0).  A session of
+ * 0 rows takes fe == NULL, as every other entry point takes its arrays of no rows. */
 DC_API int dc_hip_session_set_free_energies(dc_hip_session* session, const float* fe);
 /* CUDA::nearest_neighbors (density_clustering_cuda.cu:286-328) from the resident free energies, and
  * compute_sigma2 (density_clustering.cpp:334-343: double sum in frame order).  All outputs HOST
