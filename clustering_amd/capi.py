@@ -22,8 +22,9 @@ DC_OK, DC_ERR_INVALID_ARGUMENT, DC_ERR_HIP = 0, -1, -3
 ABI_VERSION = 5               # include/dc_density.h: DC_HIP_ABI_VERSION this binding was written against
 FLAG_STATS_VALID = 0x100      # DC_FLAG_STATS_VALID
 VARIANT_AUTO, VARIANT_DIRECT, VARIANT_MFMA, VARIANT_MFMA_PRUNED = 0, 1, 2, 3
+VARIANT_CROSS_PRUNED = 5      # dc_hip_populations_cross_dev only
 VARIANTS = {"auto": VARIANT_AUTO, "direct": VARIANT_DIRECT, "mfma": VARIANT_MFMA,
-            "pruned": VARIANT_MFMA_PRUNED, "mfma32": 4}
+            "pruned": VARIANT_MFMA_PRUNED, "mfma32": 4, "cross_pruned": VARIANT_CROSS_PRUNED}
 
 # every symbol include/dc_density.h declares (tests/test_capi_symbols.py checks the header against this)
 SYMBOLS = (
@@ -41,6 +42,7 @@ SYMBOLS = (
     "dc_hip_session_radius_forest",
     "dc_hip_cross_workspace_bytes", "dc_hip_populations_cross_dev", "dc_hip_nearest_neighbors_cross_dev",
     "dc_hip_free_energies_scaled_dev", "dc_hip_populations_cross", "dc_hip_nearest_neighbors_cross",
+    "dc_hip_cross_workspace_bytes_for",
 )
 
 
@@ -159,6 +161,8 @@ def _load():
     lib.dc_hip_session_radius_forest.argtypes = [vp, C.c_float, vp, vp, C.POINTER(sz), C.POINTER(C.c_uint32)]
     lib.dc_hip_cross_workspace_bytes.restype = sz
     lib.dc_hip_cross_workspace_bytes.argtypes = [sz, sz, sz]
+    lib.dc_hip_cross_workspace_bytes_for.restype = sz
+    lib.dc_hip_cross_workspace_bytes_for.argtypes = [sz, sz, sz, i32]
     lib.dc_hip_populations_cross_dev.restype = i32
     lib.dc_hip_populations_cross_dev.argtypes = [vp, sz, vp, sz, sz, C.POINTER(C.c_float), sz, sz, sz, vp, vp, sz,
                                                  i32, vp]

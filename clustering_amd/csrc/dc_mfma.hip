@@ -1,6 +1,7 @@
 // dc_mfma.hip -- host side of the MFMA variants: workspace layout, operand-image kernels and the
 // switch over the per-K-step translation units (kernels: dc_mfma_kernels.hpp).
 #include "dc_mfma_kernels.hpp"
+#include "dc_against.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -2103,6 +2104,96 @@ int launch_pop_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref
   image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
   pop_mfma_steps(against_args(d_query, n_q, d_ref, n_ref, d_ws, L, false), kAgainst, n_cols, i_from, i_to, rad2, n_rad,
                  d_pops, stream);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---- DC_VARIANT_CROSS_PRUNED: the population sweep against a reference with tile-pair pruning (dc_against.hip) -------
+// Workspace: the every-pair layout with more behind it.  The images and norms of both sets and R's permutation live
+// where that layout has them (here they hold the two CELL orders); behind its end follow R's tile boxes and its rows
+// in cell order (the exact path), the permutation and boxes of the query rows [i_from, i_to), and sort buffers sized
+// for the longer of the two sets.  So the every-pair sweep, which answers where this one cannot, fits the same
+// workspace by construction.
+struct AgainstLayout {
+  uint32_t T_q, T_r, NM;
+  size_t off_img_r, off_norm_r, off_perm_r, off_box_r, off_coords_r, off_img_q, off_norm_q, off_perm_q, off_box_q,
+      off_keys_in, off_keys_out, off_vals_in, off_sort, total;
+};
+static AgainstLayout make_against_layout(size_t n_q, size_t n_ref, size_t n_cols) {
+  const CrossLayout C = make_cross_layout(n_q, n_ref, n_cols);
+  AgainstLayout L;
+  L.T_q = C.T_q;
+  L.T_r = C.T_r;
+  L.NM = C.NM;
+  const size_t rows_q = align256(sizeof(float) * 32 * (size_t)L.T_q);
+  const size_t rows_s = std::max(align256(sizeof(float) * 32 * (size_t)L.T_r), rows_q);
+  L.off_img_r = C.off_img_r;
+  L.off_norm_r = C.off_norm_r;
+  L.off_img_q = C.off_img_q;
+  L.off_norm_q = C.off_norm_q;
+  L.off_perm_r = C.off_perm;
+  L.off_box_r = C.total;
+  L.off_coords_r = align256(L.off_box_r + sizeof(float) * 4 * (size_t)L.T_r);
+  L.off_perm_q = align256(L.off_coords_r + sizeof(float) * 32 * (size_t)L.T_r * n_cols);
+  L.off_box_q = L.off_perm_q + rows_q;
+  L.off_keys_in = align256(L.off_box_q + sizeof(float) * 4 * (size_t)L.T_q);
+  L.off_keys_out = L.off_keys_in + rows_s;
+  L.off_vals_in = L.off_keys_out + rows_s;
+  L.off_sort = L.off_vals_in + rows_s;
+  L.total = L.off_sort + align256(sort_temp_bytes(std::max(n_q, n_ref)));
+  return L;
+}
+
+// The queue of band pairs holds 24-bit reference positions (kPopQueuePosBits): a longer reference order takes the
+// every-pair sweep, as the self sweeps leave their queue path there.
+bool cross_pruned_takes(size_t n_ref, size_t n_cols) {
+  return mfma_supports(n_cols) && ((n_ref + 31) / 32) * 32 <= (size_t)kPopQueueMaxRows;
+}
+
+size_t cross_pruned_workspace_bytes(size_t n_q, size_t n_ref, size_t n_cols) {
+  if (!mfma_supports(n_cols)) return 0;
+  return make_against_layout(n_q, n_ref, n_cols).total;
+}
+
+int launch_pop_cross_pruned(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                            uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
+                            hipStream_t stream) {
+  if (!cross_pruned_takes(n_ref, n_cols))
+    return launch_pop_cross_mfma(d_query, n_q, d_ref, n_ref, n_cols, i_from, i_to, rad2, n_rad, d_pops, d_ws, stream);
+  const uint32_t n_sel = i_to - i_from;
+  const AgainstLayout L = make_against_layout(n_sel, n_ref, n_cols);   // (no larger than the layout of all n_q rows)
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
+  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
+  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
+  uint32_t* perm_r = (uint32_t*)(p + L.off_perm_r);
+  uint32_t* perm_q = (uint32_t*)(p + L.off_perm_q);
+  // one origin and one scale for both sets, exactly as the every-pair sweep
+  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
+  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, hdr, max_radius2(rad2, n_rad), n_cols);
+  const unsigned key_bits = cell_key_bits(n_ref, kPopCellFrames);
+  const size_t tmp_bytes = sort_temp_bytes(std::max(n_sel, n_ref));
+  const dim3 blk(256);
+  // R: keys of the one grid, the order, its rows, boxes, A form and norms
+  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_r + 255) / 256, 1024u)), blk, 0, stream, d_ref, n_cols,
+                     (const uint32_t*)hdr, n_ref, cell_frames(false), 0u, n_ref, keys_in, vals_in, perm_r, 32u * L.T_r);
+  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_r, n_ref, p + L.off_sort, tmp_bytes, stream, key_bits)) return -3;
+  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * L.T_r + 255) / 256), blk, 0, stream, d_ref, n_cols,
+                     (const uint32_t*)perm_r, L.T_r, (float*)(p + L.off_coords_r), (float4*)(p + L.off_box_r));
+  image(d_ref, 32u * L.T_r, n_cols, L.NM, L.T_r, perm_r, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
+  // Q: only the rows of the call, by the same key; B form, norms, boxes
+  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_q + 255) / 256, 1024u)), blk, 0, stream, d_query, n_cols,
+                     (const uint32_t*)hdr, n_ref, cell_frames(false), i_from, i_to, keys_in, vals_in, perm_q, 32u * L.T_q);
+  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_q, n_sel, p + L.off_sort, tmp_bytes, stream, key_bits)) return -3;
+  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * L.T_q + 255) / 256), blk, 0, stream, d_query, n_cols,
+                     (const uint32_t*)perm_q, L.T_q, (float*)nullptr, (float4*)(p + L.off_box_q));
+  image(d_query, 32u * L.T_q, n_cols, L.NM, L.T_q, perm_q, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
+  const AgainstArgs A{d_query, (const uint4*)(p + L.off_img_r), (const float*)(p + L.off_norm_r),
+                      (const float4*)(p + L.off_box_r), (const float*)(p + L.off_coords_r), (const uint4*)(p + L.off_img_q),
+                      (const float*)(p + L.off_norm_q), perm_q, (const float4*)(p + L.off_box_q), L.T_r, L.T_q, n_q,
+                      (const uint32_t*)hdr, (unsigned long long*)(p + 8)};
+  // one radius at a time on the one preparation, whose scale serves the largest
+  for (int r = 0; r < n_rad; ++r) pop_against_sweep(A, n_cols, single_radius(rad2, r), d_pops + (size_t)r * n_q, stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

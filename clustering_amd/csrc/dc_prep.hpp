@@ -716,3 +716,82 @@ __global__ __launch_bounds__(256) void order_rows2_kernel(
                        norms_b ? norms_b + (size_t)tile * 32u : nullptr, lane);
   }
 }
+
+// ---- the orders of a pruned sweep AGAINST a reference (DC_VARIANT_CROSS_PRUNED; sweep: dc_against.hip) --------------
+// ONE cell grid on columns 0/1 for both sets, over the bounding box of Q and R together (header words 8..11 after
+// cross_prepare), no components: a query may lie between the reference's clusters, so both sets keep the one origin
+// of cross_prepare.  The cell edge gives about frames_per_cell of the REFERENCE's n_ref frames per cell of that box
+// (auto_cell) -- the reference is what a query group scans; at most 4001 cells per dimension, numbered column by
+// column in serpentine order, so that consecutive cells are neighbours.
+struct AgainstGrid {
+  float lo0, lo1, cell;
+  uint32_t ny;
+};
+__device__ __forceinline__ AgainstGrid against_grid(const uint32_t* __restrict__ hdr, uint32_t n_ref, float frames_per_cell) {
+  AgainstGrid g;
+  g.lo0 = fkey_inv(~hdr[8]);
+  g.lo1 = fkey_inv(~hdr[10]);
+  float e1 = fkey_inv(hdr[11]) - g.lo1, e0 = fkey_inv(hdr[9]) - g.lo0;
+  if (!(fabsf(g.lo0) <= FLT_MAX)) g.lo0 = 0.0f;
+  if (!(fabsf(g.lo1) <= FLT_MAX)) g.lo1 = 0.0f;
+  if (!(e0 >= 0.0f) || !(e0 <= FLT_MAX)) e0 = 0.0f;
+  if (!(e1 >= 0.0f) || !(e1 <= FLT_MAX)) e1 = 0.0f;
+  g.cell = fmaxf(auto_cell(hdr, n_ref, frames_per_cell), fmaxf(e0, e1) / 4000.0f);
+  if (!(g.cell > 0.0f) || !(g.cell <= FLT_MAX)) g.cell = 1.0f;   // (every row on one point of the plane: one cell)
+  g.ny = (uint32_t)fminf(e1 / g.cell, 4000.0f) + 1u;
+  return g;
+}
+// keys and values of the rows [i_from, i_to) of one set, and the presets of its order of n_pos positions: every
+// position kInvalidFrame (the sort writes the i_to - i_from real entries over the first of them)
+__global__ __launch_bounds__(256) void against_key_kernel(const float* __restrict__ coords, uint32_t D,
+                                                          const uint32_t* __restrict__ hdr, uint32_t n_ref,
+                                                          float frames_per_cell, uint32_t i_from, uint32_t i_to,
+                                                          uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                          uint32_t* __restrict__ perm, uint32_t n_pos) {
+  const AgainstGrid g = against_grid(hdr, n_ref, frames_per_cell);
+  const uint32_t n_items = max(i_to - i_from, n_pos);
+  for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n_items; j += gridDim.x * 256u) {
+    if (j < n_pos) perm[j] = kInvalidFrame;
+    const uint32_t i = i_from + j;
+    if (i >= i_to) continue;
+    const float x = coords[(size_t)i * D], y = (D > 1) ? coords[(size_t)i * D + 1] : 0.0f;
+    uint32_t key = 0;
+    if (fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX) {   // (a non-finite row: the data is flagged, the sweep stands down)
+      const uint32_t bx = (uint32_t)fminf(fmaxf((x - g.lo0) / g.cell, 0.0f), 4000.0f);
+      const uint32_t by = min((uint32_t)fminf(fmaxf((y - g.lo1) / g.cell, 0.0f), 4000.0f), g.ny - 1u);
+      key = bx * g.ny + ((bx & 1u) ? g.ny - 1u - by : by);
+    }
+    keys[j] = key;
+    vals[j] = i;
+  }
+}
+// the rows of an order gathered by frame (coords_o != nullptr: the exact path reads them without a look-up) and the
+// box of every tile in the (col 0, col 1) plane; a pad position holds zeros and widens no box, an all-pad tile gets
+// the empty box (+inf, -inf, ..): infinitely far from everything
+__global__ __launch_bounds__(256) void against_rows_kernel(const float* __restrict__ coords, uint32_t D,
+                                                           const uint32_t* __restrict__ perm, uint32_t T,
+                                                           float* __restrict__ coords_o, float4* __restrict__ boxes) {
+  const uint32_t n_pos = 32u * T;
+  const uint32_t pos = blockIdx.x * 256u + threadIdx.x;
+  if (coords_o) {
+    const size_t base = (size_t)blockIdx.x * 256u * D, total = (size_t)n_pos * D;
+    for (uint32_t e = threadIdx.x; e < 256u * D && base + e < total; e += 256u) {
+      const uint32_t p = blockIdx.x * 256u + e / D, k = e - (e / D) * D;
+      const uint32_t i = perm[p];
+      coords_o[base + e] = (i != kInvalidFrame) ? coords[(size_t)i * D + k] : 0.0f;
+    }
+  }
+  const uint32_t frame = (pos < n_pos) ? perm[pos] : kInvalidFrame;
+  const bool live = frame != kInvalidFrame;
+  const float x = live ? coords[(size_t)frame * D] : 0.0f, y = (live && D > 1) ? coords[(size_t)frame * D + 1] : 0.0f;
+  float lo0 = live ? x : INFINITY, hi0 = live ? x : -INFINITY;
+  float lo1 = live ? y : INFINITY, hi1 = live ? y : -INFINITY;
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) {
+    lo0 = fminf(lo0, __shfl_xor(lo0, off, 64));
+    hi0 = fmaxf(hi0, __shfl_xor(hi0, off, 64));
+    lo1 = fminf(lo1, __shfl_xor(lo1, off, 64));
+    hi1 = fmaxf(hi1, __shfl_xor(hi1, off, 64));
+  }
+  if ((pos & 31u) == 0 && pos < n_pos) boxes[pos >> 5] = make_float4(lo0, hi0, lo1, hi1);
+}

@@ -40,6 +40,10 @@ def _cross_bytes(n_q, n_ref, n_cols):
     return capi.lib.dc_hip_cross_workspace_bytes(n_q, n_ref, n_cols)
 
 
+def _cross_pruned_bytes(n_q, n_ref, n_cols):
+    return capi.lib.dc_hip_cross_workspace_bytes_for(n_q, n_ref, n_cols, capi.VARIANT_CROSS_PRUNED)
+
+
 class Workspace:
     """Device scratch of one kind of sweep (MFMA operand images); grown on demand, reused across calls.
     ``size`` is the library's byte count for a call's shape: get(*shape) asks it and returns (pointer, bytes)."""
@@ -60,6 +64,7 @@ class Workspace:
 
 _workspaces = {}        # self sweeps, per device
 _cross_workspaces = {}  # sweeps against a reference, per device
+_cross_pruned_workspaces = {}  # ... of variant="cross_pruned" (the larger layout of its two orders), per device
 
 
 def _cached(cache, device, size):
@@ -75,6 +80,10 @@ def _workspace(device):
 
 def _cross_workspace(device):
     return _cached(_cross_workspaces, device, _cross_bytes)
+
+
+def _cross_pruned_workspace(device):
+    return _cached(_cross_pruned_workspaces, device, _cross_pruned_bytes)
 
 
 def _variant(variant, stats_valid):
@@ -214,7 +223,9 @@ def calculate_populations_against(queries, reference, radii, i_from=0, i_to=None
     """Populations of the query frames in the reference trajectory (dc_hip_populations_cross_dev):
     pops[r][q] = #{ j : d2(Q_q, R_j) < r^2 } -- no self term, so a copy of reference frame j gets pop_R(j).
     queries [n_q, n_cols], reference [n_ref, n_cols]: float32 CUDA tensors; radii in any order.
-    -> torch.int32 [n_radii, n_q] in the order of ``radii``, zero outside [i_from, i_to)."""
+    -> torch.int32 [n_radii, n_q] in the order of ``radii``, zero outside [i_from, i_to).
+    variant="cross_pruned" (n_cols <= 64): the matrix-core sweep with tile-pair pruning, in a workspace of its own
+    (evaluated_tiles_against reads its counters); the same results."""
     n_q, n_ref, n_cols = _check_pair(queries, reference)
     i_to = n_q if i_to is None else i_to
     rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
@@ -223,7 +234,8 @@ def calculate_populations_against(queries, reference, radii, i_from=0, i_to=None
     assert out.shape == (rad.size, n_q) and out.dtype == torch.int32 and out.is_contiguous()
     rad_call, dst, order = _ascending(rad, out)
     with torch.cuda.device(queries.device):
-        ws, ws_bytes = _cross_workspace(queries.device).get(n_q, n_ref, n_cols)
+        cache = _cross_pruned_workspace if variant == "cross_pruned" else _cross_workspace
+        ws, ws_bytes = cache(queries.device).get(n_q, n_ref, n_cols)
         rc = capi.lib.dc_hip_populations_cross_dev(
             _dev(queries), n_q, _dev(reference), n_ref, n_cols, rad_call.ctypes.data_as(C.POINTER(C.c_float)),
             rad.size, i_from, i_to, _dev(dst), ws, ws_bytes, capi.VARIANTS[variant], _stream_ptr())
@@ -279,15 +291,20 @@ def assign_frames(queries, reference, radius, ref_states, variant="auto"):
       3. nearest reference frame and nearest reference frame of lower free energy;
       4. the state of each query: ref_states[hd] if hd exists, else ref_states[nn], else 0 (unassigned, as in the
          reference's density_clustering.cpp:345-360).
-    ref_states: int array-like [n_ref].  -> dict of CUDA tensors (states int32 [n_q] among them)."""
+    ref_states: int array-like [n_ref].  -> dict of CUDA tensors (states int32 [n_q] among them).
+    variant="cross_pruned": step 2 runs the pruned sweep against the reference; the self sweep of step 1 and the
+    neighbours of step 3, which have no such variant, run on "auto"."""
     n_q, n_ref, n_cols = _check_pair(queries, reference)
+    pop_variant = variant
+    if variant == "cross_pruned":
+        variant = "auto"
     dev = queries.device
     states_r = torch.as_tensor(np.ascontiguousarray(ref_states, dtype=np.int32), device=dev)
     assert states_r.shape == (n_ref,)
     pops_ref = calculate_populations_partial(reference, [radius], variant=variant)[0].contiguous()
     max_pop = int(pops_ref.max().item()) if n_ref else 0
     fe_ref = calculate_free_energies(pops_ref)
-    pops_q = calculate_populations_against(queries, reference, [radius], variant=variant)[0].contiguous()
+    pops_q = calculate_populations_against(queries, reference, [radius], variant=pop_variant)[0].contiguous()
     fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
         torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
     nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference(queries, reference, fe_q, fe_ref, variant=variant)
@@ -313,6 +330,22 @@ def evaluated_tiles(device):
         rc = capi.lib.dc_hip_workspace_counters_dev(_dev(ws.buf), C.byref(a), C.byref(b), _stream_ptr())
     capi.check(rc, "dc_hip_workspace_counters_dev")
     return int(a.value), int(b.value)
+
+
+def evaluated_tiles_against(device):
+    """(pop_tiles, pop_mfma): 32x32 frame-pair tiles evaluated and MFMA instructions issued by the last
+    calculate_populations_against(..., variant="cross_pruned") on this device (all radii of the call together); the
+    counters of its workspace, read like evaluated_tiles.  (0, 0) after a call the pruned sweep did not answer."""
+    ws = _cross_pruned_workspace(device)
+    if ws.buf is None:
+        return 0, 0
+    a, b, m, n = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_workspace_counters_dev(_dev(ws.buf), C.byref(a), C.byref(b), _stream_ptr()),
+                   "dc_hip_workspace_counters_dev")
+        capi.check(capi.lib.dc_hip_workspace_mfma_counters_dev(_dev(ws.buf), C.byref(m), C.byref(n), _stream_ptr()),
+                   "dc_hip_workspace_mfma_counters_dev")
+    return int(a.value), int(m.value)
 
 
 def issued_mfmas(device):

@@ -68,9 +68,13 @@ typedef enum dc_variant {
   DC_VARIANT_MFMA_PRUNED = 3, /* the same on spatially ordered frames, skipping tile pairs farther apart than
                                  the radius (the GPU counterpart of the reference's box grid,
                                  density_clustering.cpp:41-89); identical results */
-  DC_VARIANT_MFMA32 = 4       /* the literal fp32-input MFMA (v_mfma_f32_32x32x2_f32) Gram form, every pair evaluated:
+  DC_VARIANT_MFMA32 = 4,      /* the literal fp32-input MFMA (v_mfma_f32_32x32x2_f32) Gram form, every pair evaluated:
                                  the instance BASELINE's "fraction of the fp32 MFMA roofline" is quoted on; n_cols
                                  9..10 only, one radius per sweep; identical results (classifier + band + re-check) */
+  DC_VARIANT_CROSS_PRUNED = 5 /* populations of new frames against a reference on the matrix cores with tile-pair
+                                 pruning: both sets ordered by the cells of one grid on columns 0/1, tile pairs at
+                                 least the largest radius apart skipped; n_cols <= 64; identical results.  ONLY
+                                 dc_hip_populations_cross_dev takes it: every other entry point refuses it */
 } dc_variant;
 /* may be OR-ed into the `variant` argument of the _dev sweeps: the column means, max |x - mean|^2, the
  * non-finite flag and the bounding box in this workspace's header were computed by an earlier sweep over
@@ -333,11 +337,23 @@ DC_API int dc_hip_radius_min_edge_segment_dev(const float* d_coords, size_t n_ro
  * Sizes: n_ref + 1 and n_query must fit uint32 (else DC_ERR_TOO_LARGE).
  * Variants: DC_VARIANT_AUTO (the matrix-core sweep for n_cols <= 64 and finite data -- chosen on the device, like the
  * self sweeps' fallback -- the direct kernels otherwise), DC_VARIANT_DIRECT, DC_VARIANT_MFMA (n_cols <= 64 only; every
- * pair, one origin and one scale over Q and R together).  DC_VARIANT_MFMA_PRUNED, DC_VARIANT_MFMA32 and
- * DC_FLAG_STATS_VALID are refused (DC_ERR_INVALID_ARGUMENT).  Results are the same for every variant. */
+ * pair, one origin and one scale over Q and R together), and -- dc_hip_populations_cross_dev only --
+ * DC_VARIANT_CROSS_PRUNED (n_cols <= 64 only: the same origin, scale and arithmetic on both sets ordered by one cell
+ * grid, tile pairs farther apart than the call's largest radius skipped; it needs the larger workspace of
+ * dc_hip_cross_workspace_bytes_for, and leaves its evaluated 32x32 tile pairs and issued MFMAs where
+ * dc_hip_workspace_counters_dev / dc_hip_workspace_mfma_counters_dev read them; a reference of more than 2^24 rows is
+ * answered by the every-pair sweep in the same workspace).  DC_VARIANT_MFMA_PRUNED, DC_VARIANT_MFMA32 and
+ * DC_FLAG_STATS_VALID are still refused (DC_ERR_INVALID_ARGUMENT): the self sweeps' pruned variant means components,
+ * a symmetric form and statistics kept across calls, none of which a rectangle has -- the pruned cross sweep is a
+ * sweep of its own and has a value of its own.  DC_VARIANT_AUTO chooses what it chose before that value existed.
+ * Results are the same for every variant. */
 
 /* bytes of scratch the cross sweeps need (0 when n_cols > 64: the direct kernels need none) */
 DC_API size_t dc_hip_cross_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols);
+/* ... for one variant: what dc_hip_cross_workspace_bytes returns for DC_VARIANT_AUTO / _DIRECT / _MFMA, the larger
+ * pruned layout for DC_VARIANT_CROSS_PRUNED (a smaller workspace: DC_ERR_WORKSPACE), 0 when n_cols > 64 and for a
+ * variant the cross sweeps refuse */
+DC_API size_t dc_hip_cross_workspace_bytes_for(size_t n_query, size_t n_ref, size_t n_cols, int variant);
 
 /* populations of the query rows against the reference frames.  radii HOST [n_radii]; d_pops [n_radii][n_query]
  * device, fully overwritten. */
