@@ -2,6 +2,7 @@
 // switch over the per-K-step translation units (kernels: dc_mfma_kernels.hpp).
 #include "dc_mfma_kernels.hpp"
 #include "dc_against.hpp"
+#include "dc_against_nn.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -2213,6 +2214,90 @@ int launch_nn_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref,
   image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
   nn_mfma_steps(against_args(d_query, n_q, d_ref, n_ref, d_ws, L, d_fe_q != nullptr), kAgainst, n_cols, i_from, i_to,
                 d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---- the pruned neighbour sweep against a reference (dc_against_nn.hip) -------------------------------------------------
+// Workspace: the layout of the pruned population sweep (which holds the every-pair layout) with more behind it: R's free
+// energies in the order, the free-energy range of its tiles, the reference's box and the cell edge, and the merge words
+// of several reference shares by query position.
+struct NnAgainstLayout {
+  AgainstLayout A;
+  size_t off_fe_c, off_ferange, off_meta, off_merge64, total;
+};
+static NnAgainstLayout make_nn_against_layout(size_t n_q, size_t n_ref, size_t n_cols) {
+  NnAgainstLayout L;
+  L.A = make_against_layout(n_q, n_ref, n_cols);
+  L.off_fe_c = L.A.total;
+  L.off_ferange = L.off_fe_c + align256(sizeof(float) * 32 * (size_t)L.A.T_r);
+  L.off_meta = L.off_ferange + align256(sizeof(float) * 2 * (size_t)L.A.T_r);
+  L.off_merge64 = L.off_meta + 256;
+  L.total = L.off_merge64 + align256(sizeof(unsigned long long) * 2 * 32 * (size_t)L.A.T_q);
+  return L;
+}
+
+size_t nn_cross_pruned_workspace_bytes(size_t n_q, size_t n_ref, size_t n_cols) {
+  if (!mfma_supports(n_cols)) return 0;
+  return make_nn_against_layout(n_q, n_ref, n_cols).total;
+}
+
+int launch_nn_cross_pruned(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                           const float* d_fe_q, const float* d_fe_r, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx,
+                           float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t stream) {
+  // (the candidate queue's positions would reach 2^30; the bound is the population sweep's, one rule for both)
+  if (!cross_pruned_takes(n_ref, n_cols))
+    return launch_nn_cross_mfma(d_query, n_q, d_ref, n_ref, n_cols, d_fe_q, d_fe_r, i_from, i_to, d_nn_idx, d_nn_d2,
+                                d_hd_idx, d_hd_d2, d_ws, stream);
+  const uint32_t n_sel = i_to - i_from;
+  const NnAgainstLayout NL = make_nn_against_layout(n_sel, n_ref, n_cols);   // (no larger than the layout of all n_q rows)
+  const AgainstLayout& L = NL.A;
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
+  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
+  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
+  uint32_t* perm_r = (uint32_t*)(p + L.off_perm_r);
+  uint32_t* perm_q = (uint32_t*)(p + L.off_perm_q);
+  // one origin and one scale for both sets, exactly as the every-pair sweep
+  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
+  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, hdr, -1.0f, n_cols);   // the neighbour scale
+  const dim3 blk(256);
+  const bool have_fe = d_fe_q != nullptr;
+  // the range of the reference's free energies: header words 12 / 13 (a NaN raises the flag: the direct kernel answers)
+  if (have_fe)
+    hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>((n_ref + 255) / 256, 256u)), blk, 0, stream, d_fe_r, n_ref,
+                       (uint32_t*)nullptr, (uint32_t*)nullptr, hdr);
+  // key: (cell of the one grid, quantised free energy) in whole sort passes, as the self neighbour sweep's
+  const unsigned cell_bits = cell_key_bits(n_ref, kNnCellFrames);
+  const unsigned key_bits = (cell_bits + 9u <= 24u) ? 24u : 32u;
+  const unsigned fe_bits = have_fe ? std::min(key_bits - cell_bits, 16u) : 0u;
+  const size_t tmp_bytes = sort_temp_bytes(std::max(n_sel, n_ref));
+  // R: the order, its rows, boxes, free energies, folded A form
+  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_r + 255) / 256, 1024u)), blk, 0, stream, d_ref, n_cols,
+                     (const uint32_t*)hdr, n_ref, cell_frames(true), 0u, n_ref, keys_in, vals_in, perm_r, 32u * L.T_r);
+  if (have_fe)
+    hipLaunchKernelGGL(against_fe_key_kernel, dim3(std::min<uint32_t>((n_ref + 255) / 256, 1024u)), blk, 0, stream, keys_in,
+                       (const uint32_t*)vals_in, n_ref, d_fe_r, (const uint32_t*)hdr, (uint32_t)fe_bits);
+  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_r, n_ref, p + L.off_sort, tmp_bytes, stream, cell_bits + fe_bits)) return -3;
+  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * L.T_r + 255) / 256), blk, 0, stream, d_ref, n_cols,
+                     (const uint32_t*)perm_r, L.T_r, (float*)(p + L.off_coords_r), (float4*)(p + L.off_box_r));
+  hipLaunchKernelGGL(against_fe_rows_kernel, dim3((32u * L.T_r + 255) / 256), blk, 0, stream, have_fe ? d_fe_r : (const float*)nullptr,
+                     (const uint32_t*)perm_r, L.T_r, (float*)(p + NL.off_fe_c), (float2*)(p + NL.off_ferange));
+  hipLaunchKernelGGL(against_meta_kernel, dim3(1), blk, 0, stream, (const uint32_t*)hdr, n_ref, cell_frames(true),
+                     (const float4*)(p + L.off_box_r), L.T_r, (float*)(p + NL.off_meta));
+  image(d_ref, 32u * L.T_r, n_cols, L.NM, L.T_r, perm_r, 2, p + L.off_img_r, nullptr, d_ws, stream);
+  // Q: only the rows of the call, by the cell of the same grid; B form, norms, boxes
+  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_q + 255) / 256, 1024u)), blk, 0, stream, d_query, n_cols,
+                     (const uint32_t*)hdr, n_ref, cell_frames(true), i_from, i_to, keys_in, vals_in, perm_q, 32u * L.T_q);
+  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_q, n_sel, p + L.off_sort, tmp_bytes, stream, cell_bits)) return -3;
+  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * L.T_q + 255) / 256), blk, 0, stream, d_query, n_cols,
+                     (const uint32_t*)perm_q, L.T_q, (float*)nullptr, (float4*)(p + L.off_box_q));
+  image(d_query, 32u * L.T_q, n_cols, L.NM, L.T_q, perm_q, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
+  const NnAgainstArgs A{d_query, d_fe_q, (const uint4*)(p + L.off_img_r), perm_r, (const float4*)(p + L.off_box_r),
+                        (const float2*)(p + NL.off_ferange), (const float*)(p + NL.off_fe_c), (const float*)(p + L.off_coords_r),
+                        (const uint4*)(p + L.off_img_q), (const float*)(p + L.off_norm_q), perm_q, (const float4*)(p + L.off_box_q),
+                        (const float*)(p + NL.off_meta), (unsigned long long*)(p + NL.off_merge64), L.T_r, L.T_q, n_ref, hdr};
+  nn_against_sweep(A, n_cols, d_nn_idx, d_nn_d2, have_fe ? d_hd_idx : nullptr, have_fe ? d_hd_d2 : nullptr, stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

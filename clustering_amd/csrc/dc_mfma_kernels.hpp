@@ -98,7 +98,8 @@ constexpr int kMaxMfma = nm_for(kMaxCols);   // 13
 constexpr size_t kHdrBytes = 1024;     // word 0: max |x'|^2 (float bits, UNSCALED); word 1: non-finite flag;
                                        // words 2..3 / 4..5: evaluated-chain counters (population / neighbour sweep);
                                        // words 8..11: extent of columns 0/1; word 12: ~key of min FE, 13: key of
-                                       // max finite FE; words 20..24: the scale of the current sweep (kHdrScale)
+                                       // max finite FE; words 20..24: the scale of the current sweep (kHdrScale); the
+                                       // other words: the kHdr* constants below
 constexpr size_t kHdrSums = 256;       // byte 256..767: column sums (double) for the centring
 constexpr size_t kHdrMeans = 768;      // byte 768..1023: column means as float (what x' = x - mu uses)
 static_assert(kHdrSums + 8 * kMaxCols <= kHdrMeans && kHdrMeans + 4 * kMaxCols <= kHdrBytes,
@@ -329,8 +330,8 @@ struct Scale {
 };
 constexpr uint32_t kHdrScale = 20;      // header words 20..24: bits(c), bits(s2), g, a, rounded
 constexpr uint32_t kHdrFp = 14;         // words 14..15: content fingerprint of the array the statistics belong to (64 bits); 16..17: the
-                                        // fingerprint a DC_FLAG_STATS_VALID call recomputes for the guard (dc_mfma.hip fp_term); 18..19: hash of the
-                                        // neighbour sweep's order (layout header of the all-gather blocks)
+                                        // fingerprint a DC_FLAG_STATS_VALID call recomputes for the guard (dc_mfma.hip fp_term); 18: kHdrLayoutBad; 19: kHdrShares
+                                        // (claim_guard_kernel clears both with the fingerprints)
 constexpr uint32_t kHdrCookie = 28;     // whose statistics the header holds (array, shape); 0 after a reset
 constexpr uint32_t kHdrMused = 31;      // the extent max |x - origin|^2 the current sweep's scale was chosen for (float bits)
 constexpr uint32_t kHdrOpen = 30;       // neighbour sweeps: queries listed for the search in other components (nn_open_kernel)
@@ -340,6 +341,7 @@ constexpr uint32_t kHdrOpen = 30;       // neighbour sweeps: queries listed for 
 // (words 2..3 / 4..5): + kMfmaCtrPop / + kMfmaCtrNn 64-bit words.
 constexpr uint32_t kHdrMfmaPop = 6, kHdrMfmaNn = 26;
 constexpr uint32_t kHdrLayoutBad = 18;     // nn_block_unpack_kernel: the gathered blocks were packed under different layouts (nothing was unpacked)
+constexpr uint32_t kHdrShares = 19;        // nn_against_kernel (dc_against_nn.hip): reference shares (gridDim.y) of the last pruned cross neighbour sweep; 0: it did not answer
 constexpr uint32_t kHdrStatsBlocks = 25;   // rows of stats_kernel's table that components_kernel has still to add up (dc_prep.hpp)
 constexpr int kMfmaCtrPop = (kHdrMfmaPop - 2) / 2, kMfmaCtrNn = (kHdrMfmaNn - 4) / 2;
 constexpr uint32_t kHdrShift = 32;      // population sweeps: the number of in-place threshold shifts the scale's band pays for (dc_mfma_msym.hpp; 0: none)

@@ -795,3 +795,70 @@ __global__ __launch_bounds__(256) void against_rows_kernel(const float* __restri
   }
   if ((pos & 31u) == 0 && pos < n_pos) boxes[pos >> 5] = make_float4(lo0, hi0, lo1, hi1);
 }
+
+// ---- ... and of the pruned NEIGHBOUR sweep against a reference (sweep: dc_against_nn.hip) -----------------------------
+// R's cell keys widened by the quantised free energy of the row: the combined (cell, free energy) key of the self
+// neighbour sweep (order_key_kernel), so ONE sort leaves the frames of a cell in ascending free energy and a tile's
+// free-energy range is narrow.  hdr words 12 / 13: the range of fe (fe_key_kernel ran before).
+__global__ __launch_bounds__(256) void against_fe_key_kernel(uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                             uint32_t n, const float* __restrict__ fe,
+                                                             const uint32_t* __restrict__ hdr, uint32_t fe_bits) {
+  const float fe_lo = fkey_inv(~hdr[12]), fe_hi = fkey_inv(hdr[13]);
+  const float span = fe_hi - fe_lo;
+  const uint32_t levels = (1u << fe_bits) - 1u;
+  for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) {
+    float u = (span > 0.0f && span <= FLT_MAX) ? (fe[vals[j]] - fe_lo) / span : 0.0f;
+    u = fminf(fmaxf(u, 0.0f), 1.0f);                                // (+inf -> 1, -inf / NaN -> 0)
+    keys[j] = (keys[j] << fe_bits) | (uint32_t)((double)u * (double)levels);
+  }
+}
+// the free energies gathered into the order (+inf on the pad positions; fe == nullptr, a call for nn only: +inf
+// everywhere, no tile has a lower frame) and the range [fe_lo, fe_hi] of every tile's real rows
+__global__ __launch_bounds__(256) void against_fe_rows_kernel(const float* __restrict__ fe, const uint32_t* __restrict__ perm,
+                                                              uint32_t T, float* __restrict__ fe_c,
+                                                              float2* __restrict__ ferange) {
+  const uint32_t n_pos = 32u * T;
+  const uint32_t pos = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t frame = (pos < n_pos) ? perm[pos] : kInvalidFrame;
+  const bool live = frame != kInvalidFrame;
+  const float f = (live && fe) ? fe[frame] : INFINITY;
+  float lo = live ? f : INFINITY, hi = live ? f : -INFINITY;
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, off, 64));
+    hi = fmaxf(hi, __shfl_xor(hi, off, 64));
+  }
+  if (pos < n_pos) fe_c[pos] = f;
+  if ((pos & 31u) == 0 && pos < n_pos) ferange[pos >> 5] = make_float2(lo, hi);
+}
+// meta[0..3]: the bounding box of R's tiles in the (col 0, col 1) plane; meta[4]: the squared cell edge of the grid
+__global__ __launch_bounds__(256) void against_meta_kernel(const uint32_t* __restrict__ hdr, uint32_t n_ref,
+                                                           float frames_per_cell, const float4* __restrict__ boxes,
+                                                           uint32_t T, float* __restrict__ meta) {
+  __shared__ float4 part[4];
+  float4 bb = make_float4(INFINITY, -INFINITY, INFINITY, -INFINITY);
+  for (uint32_t t = threadIdx.x; t < T; t += 256u) {
+    const float4 v = boxes[t];
+    bb.x = fminf(bb.x, v.x);
+    bb.y = fmaxf(bb.y, v.y);
+    bb.z = fminf(bb.z, v.z);
+    bb.w = fmaxf(bb.w, v.w);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    bb.x = fminf(bb.x, __shfl_xor(bb.x, off, 64));
+    bb.y = fmaxf(bb.y, __shfl_xor(bb.y, off, 64));
+    bb.z = fminf(bb.z, __shfl_xor(bb.z, off, 64));
+    bb.w = fmaxf(bb.w, __shfl_xor(bb.w, off, 64));
+  }
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = bb;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    meta[0] = fminf(fminf(part[0].x, part[1].x), fminf(part[2].x, part[3].x));
+    meta[1] = fmaxf(fmaxf(part[0].y, part[1].y), fmaxf(part[2].y, part[3].y));
+    meta[2] = fminf(fminf(part[0].z, part[1].z), fminf(part[2].z, part[3].z));
+    meta[3] = fmaxf(fmaxf(part[0].w, part[1].w), fmaxf(part[2].w, part[3].w));
+    const float cell = against_grid(hdr, n_ref, frames_per_cell).cell;
+    meta[4] = cell * cell;
+  }
+}

@@ -44,6 +44,10 @@ def _cross_pruned_bytes(n_q, n_ref, n_cols):
     return capi.lib.dc_hip_cross_workspace_bytes_for(n_q, n_ref, n_cols, capi.VARIANT_CROSS_PRUNED)
 
 
+def _nearest_pruned_bytes(n_q, n_ref, n_cols):
+    return capi.lib.dc_hip_nearest_cross_pruned_workspace_bytes(n_q, n_ref, n_cols)
+
+
 class Workspace:
     """Device scratch of one kind of sweep (MFMA operand images); grown on demand, reused across calls.
     ``size`` is the library's byte count for a call's shape: get(*shape) asks it and returns (pointer, bytes)."""
@@ -65,6 +69,7 @@ class Workspace:
 _workspaces = {}        # self sweeps, per device
 _cross_workspaces = {}  # sweeps against a reference, per device
 _cross_pruned_workspaces = {}  # ... of variant="cross_pruned" (the larger layout of its two orders), per device
+_nearest_pruned_workspaces = {}  # ... of nearest_reference(pruned=True), per device
 
 
 def _cached(cache, device, size):
@@ -84,6 +89,10 @@ def _cross_workspace(device):
 
 def _cross_pruned_workspace(device):
     return _cached(_cross_pruned_workspaces, device, _cross_pruned_bytes)
+
+
+def _nearest_pruned_workspace(device):
+    return _cached(_nearest_pruned_workspaces, device, _nearest_pruned_bytes)
 
 
 def _variant(variant, stats_valid):
@@ -257,10 +266,16 @@ def calculate_free_energies_against(pops, max_pop):
     return fe
 
 
-def nearest_reference(queries, reference, fe_query=None, fe_ref=None, i_from=0, i_to=None, variant="auto"):
+def nearest_reference(queries, reference, fe_query=None, fe_ref=None, i_from=0, i_to=None, variant="auto", pruned=False):
     """Nearest reference frame of every query, and nearest reference frame of strictly lower free energy
     (dc_hip_nearest_neighbors_cross_dev).  -> (nn_idx int32, nn_d2 float32, hd_idx, hd_d2), each [n_q]; "none" is
-    (n_ref + 1, FLT_MAX).  Without free energies hd_idx / hd_d2 are None."""
+    (n_ref + 1, FLT_MAX).  Without free energies hd_idx / hd_d2 are None.
+    pruned=True (n_cols <= 64, variant must be "auto"): the matrix-core sweep that skips the tile pairs which cannot
+    matter (dc_hip_nearest_neighbors_cross_pruned_dev), in a cached workspace of its own; the same results bit for bit.
+    evaluated_tiles_nearest_reference tells what it evaluated."""
+    if pruned and variant != "auto":
+        raise ValueError(f"nearest_reference(pruned=True) takes variant='auto', not {variant!r}: the pruned sweep is "
+                         "an entry point of its own")
     n_q, n_ref, n_cols = _check_pair(queries, reference)
     i_to = n_q if i_to is None else i_to
     with_fe = fe_query is not None
@@ -273,18 +288,37 @@ def nearest_reference(queries, reference, fe_query=None, fe_ref=None, i_from=0, 
     nn_d2 = torch.empty(n_q, dtype=torch.float32, device=dev)
     hd_idx = torch.empty(n_q, dtype=torch.int32, device=dev) if with_fe else None
     hd_d2 = torch.empty(n_q, dtype=torch.float32, device=dev) if with_fe else None
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _cross_workspace(dev).get(n_q, n_ref, n_cols)
-        rc = capi.lib.dc_hip_nearest_neighbors_cross_dev(
-            _dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
+    args = (_dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
             _dev(fe_ref) if with_fe else None, i_from, i_to, _dev(nn_idx), _dev(nn_d2),
-            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None, ws, ws_bytes,
-            capi.VARIANTS[variant], _stream_ptr())
-    capi.check(rc, "dc_hip_nearest_neighbors_cross_dev")
+            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None)
+    with torch.cuda.device(dev):
+        if pruned:
+            ws, ws_bytes = _nearest_pruned_workspace(dev).get(n_q, n_ref, n_cols)
+            rc = capi.lib.dc_hip_nearest_neighbors_cross_pruned_dev(*args, ws, ws_bytes, _stream_ptr())
+        else:
+            ws, ws_bytes = _cross_workspace(dev).get(n_q, n_ref, n_cols)
+            rc = capi.lib.dc_hip_nearest_neighbors_cross_dev(*args, ws, ws_bytes, capi.VARIANTS[variant], _stream_ptr())
+    capi.check(rc, "dc_hip_nearest_neighbors_cross_pruned_dev" if pruned else "dc_hip_nearest_neighbors_cross_dev")
     return nn_idx, nn_d2, hd_idx, hd_d2
 
 
-def assign_frames(queries, reference, radius, ref_states, variant="auto"):
+def evaluated_tiles_nearest_reference(device):
+    """(nn_tiles, nn_mfma, n_shares): 32x32 frame-pair tiles evaluated, MFMA instructions issued and reference shares of
+    the launch of the last nearest_reference(..., pruned=True) on this device (dc_hip_nearest_cross_pruned_info_dev).
+    (0, 0, 0) after a call the pruned kernel did not answer: flagged data, a reference beyond 2^24 positions, nothing
+    to sweep."""
+    ws = _nearest_pruned_workspace(device)
+    if ws.buf is None:
+        return 0, 0, 0
+    t, m, n = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_nearest_cross_pruned_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(n),
+                                                                 _stream_ptr()),
+                   "dc_hip_nearest_cross_pruned_info_dev")
+    return int(t.value), int(m.value), int(n.value)
+
+
+def assign_frames(queries, reference, radius, ref_states, variant="auto", pruned_neighbours=False):
     """Assign new frames to the states of an already clustered reference trajectory, end to end:
       1. the reference's own populations at ``radius`` (self sweep), their maximum and the reference free energies;
       2. the query populations in the reference and the query free energies on the reference's scale;
@@ -293,7 +327,9 @@ def assign_frames(queries, reference, radius, ref_states, variant="auto"):
          reference's density_clustering.cpp:345-360).
     ref_states: int array-like [n_ref].  -> dict of CUDA tensors (states int32 [n_q] among them).
     variant="cross_pruned": step 2 runs the pruned sweep against the reference; the self sweep of step 1 and the
-    neighbours of step 3, which have no such variant, run on "auto"."""
+    neighbours of step 3 run on "auto".  pruned_neighbours=True: step 3 runs the pruned neighbour sweep
+    (nearest_reference(pruned=True); the variant must then be "auto" or "cross_pruned").  The two can be combined; the
+    results are the same either way."""
     n_q, n_ref, n_cols = _check_pair(queries, reference)
     pop_variant = variant
     if variant == "cross_pruned":
@@ -307,7 +343,8 @@ def assign_frames(queries, reference, radius, ref_states, variant="auto"):
     pops_q = calculate_populations_against(queries, reference, [radius], variant=pop_variant)[0].contiguous()
     fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
         torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
-    nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference(queries, reference, fe_q, fe_ref, variant=variant)
+    nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference(queries, reference, fe_q, fe_ref, variant=variant,
+                                                     pruned=pruned_neighbours)
     none = n_ref + 1
     states = torch.zeros(n_q, dtype=torch.int32, device=dev)
     if n_ref:

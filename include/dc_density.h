@@ -370,6 +370,30 @@ DC_API int dc_hip_nearest_neighbors_cross_dev(const float* d_query, size_t n_que
                                               uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
                                               int variant, void* stream);
 
+/* The neighbour sweep with tile-pair pruning: an entry point of its own (no variant value: the variant argument of
+ * dc_hip_nearest_neighbors_cross_dev keeps refusing DC_VARIANT_CROSS_PRUNED).  Same pointers, outputs and contract as
+ * dc_hip_nearest_neighbors_cross_dev -- results are bit-identical to its DC_VARIANT_DIRECT -- for n_cols <= 64 only
+ * (more: DC_ERR_INVALID_ARGUMENT, like DC_VARIANT_MFMA).  Both sets are ordered by the cells of one grid on columns 0/1,
+ * the reference inside a cell by free energy; a query group visits the reference's 32-frame tiles in rings of growing
+ * box distance and stops when the exact incumbents of all its queries lie inside the last ring, so tile pairs that
+ * cannot matter are never evaluated.  Answered exactly as the other cross sweeps answer them, with all counters 0:
+ * flagged data (a non-finite or overflowing row in either set, a NaN in fe_ref: the direct kernel, chosen on the
+ * device), a reference of more than 2^24 positions (the every-pair matrix-core sweep in the same workspace),
+ * n_ref == 0 or an empty row range ("none" everywhere).
+ * Workspace: dc_hip_nearest_cross_pruned_workspace_bytes -- 0 for n_cols > 64, otherwise at least
+ * dc_hip_cross_workspace_bytes of the same shape and monotone in either row count; smaller: DC_ERR_WORKSPACE. */
+DC_API size_t dc_hip_nearest_cross_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols);
+DC_API int dc_hip_nearest_neighbors_cross_pruned_dev(const float* d_query, size_t n_query, const float* d_ref,
+                                                     size_t n_ref, size_t n_cols, const float* d_fe_query,
+                                                     const float* d_fe_ref, size_t i_from, size_t i_to,
+                                                     uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                                     float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
+/* the last dc_hip_nearest_neighbors_cross_pruned_dev call in that workspace: 32x32 tile pairs evaluated, MFMA
+ * instructions issued, reference shares of the launch; all 0 when the pruned kernel did not answer.  Any pointer may
+ * be NULL.  Synchronises the stream. */
+DC_API int dc_hip_nearest_cross_pruned_info_dev(const void* d_ws, uint64_t* nn_tiles, uint64_t* nn_mfma,
+                                                uint32_t* n_shares, void* stream);
+
 /* free energies on ANOTHER array's scale: fe[i] = (float)-log((double)((float)pop[i] * (1.0f / (float)max_pop))),
  * with the device log + host-libm referee of dc_hip_free_energies_dev.  pop = 0 gives +inf, pop > max_pop a negative
  * value; max_pop = 0 is DC_ERR_INVALID_ARGUMENT.  Synchronises the stream. */
