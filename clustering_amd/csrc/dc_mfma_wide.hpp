@@ -1,0 +1,30 @@
+// dc_mfma_wide.hpp -- the matrix-core sweeps for rows of 65..256 columns (dc_mfma_wide.hip): host-side entry points.
+// An every-pair self sweep whose K axis streams through LDS in chunks while the accumulator tiles stay in registers
+// (kernels and the reasoning: dc_mfma_wide_kernels.hpp).  Entry points of their own in the C ABI
+// (dc_hip_*_wide_dev); no variant value selects them.
+#pragma once
+#include "dc_common.hpp"
+
+namespace dc {
+
+constexpr size_t kWideMinCols = 65, kWideMaxCols = 256;
+inline bool wide_mfma_supports(size_t n_cols) { return n_cols >= kWideMinCols && n_cols <= kWideMaxCols; }
+// bytes of device scratch (header, column means, both operand images, norms, the neighbour merge words); 0 if the
+// column count is not served or there are no rows; monotone in n_rows
+size_t wide_workspace_bytes(size_t n_rows, size_t n_cols);
+constexpr size_t kWideInfoBytes = 256;   // the head of the workspace dc_hip_wide_info_dev reads (header words 40..45)
+
+// statistics, scale and operand images of d_coords in the workspace (d_fe: the neighbour call's free energies, a NaN
+// among them flags the data like a non-finite row); returns 0 on success
+int wide_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, void* d_ws,
+                 hipStream_t stream);
+// populations of the rows [i_from, i_to) for up to kMaxRadiiPerLaunch radii with ONE chain per tile pair, ADDED to
+// d_pops_first_row (zeroed by the caller); stands down on flagged data (the gated direct kernel answers)
+void launch_pop_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                          const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t stream);
+// nn / nn_hd of the rows [i_from, i_to) (outputs preset to "none" by the caller); stands down on flagged data
+int launch_nn_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, uint32_t i_from,
+                        uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
+                        void* d_ws, hipStream_t stream);
+
+}  // namespace dc

@@ -1,0 +1,619 @@
+// dc_mfma_wide_kernels.hpp -- matrix-core sweeps for rows of 65..256 columns (gfx950, v_mfma_f32_32x32x16_f16).
+// Included by dc_mfma_wide.hip and by tests/cpp/test_wide_model.hip.
+//
+// The sweeps of dc_mfma_kernels.hpp keep the query fragments of a chain in VGPRs (NM x 4 registers per query tile),
+// which ends at 64 columns (NM = 13).  Here NEITHER operand is resident: a workgroup of four waves owns a block of
+// 4 query tiles x 4 reference tiles (128 x 128 frames), every wave 2 x 2 of them as four accumulator tiles of 16
+// registers, and the K axis of both operand images streams through LDS in chunks of kWideKC MFMAs (64 K slots),
+// double-buffered: while the waves run the 4 x kWideKC MFMAs of a chunk, the next chunk is already on its way from
+// global memory into registers, and is stored into the other buffer behind the MFMAs.  After the last chunk of a block the
+// accumulators hold acc ~ S d2 for 64 x 64 pairs per wave, and the epilogue classifies them.
+//
+// Operand model, slot order and band are those of dc_mfma_kernels.hpp (file header, "guard band"): two fp16 pieces per
+// centred, scaled coordinate, products hi*hi, mid*hi, hi*mid, the slots laid out by the same rule (two constant slots,
+// then ALL hi*hi products, then the small products), C-init = reference norm (+inf for pad rows), and the chain of a
+// tile pair runs its MFMAs in slot order whatever the chunking -- the chunks only decide when an operand fragment
+// reaches LDS.  So the accumulator of a pair is, bit for bit, what a resident-operand chain of nm_for(D) MFMAs would
+// give, and guard_e0 / guard_kappa bound it as they stand (they are written in D, nb and ns).  The folded constant is
+// c_q = |x''|^2 (the neighbour form) for BOTH sweeps: one chain serves every radius of the call, so no threshold
+// can be folded, and the epilogue compares acc with per-radius windows instead of reading two bits.  With that the
+// population scale (band <= 1) buys nothing, and both sweeps run under pick_scale_nn: a power of two, exact.
+//     | acc - S d2 |  <=  e0 + kappa S d2,     e0 = guard_e0(S M, 0, D, g = 0, a = 15, rounded = 0), kappa = guard_kappa(D, 0)
+// populations, threshold t = S fl32(r^2):   acc <  t (1 - kappa) - e0  =>  d2 <  fl32(r^2)    (inside)
+//                                           acc >= t (1 + kappa) + e0  =>  d2 >= fl32(r^2)    (outside)
+//                                           otherwise the pair is deferred to the exact path
+// neighbours, m = the least acc a lane has met so far (its own tile included): the nearest frame j* has
+//     acc* <= (S d2* + e0) + kappa S d2*  and  S d2* <= S d2_j <= (acc_j + e0) / (1 - kappa)  for every j, so
+//     acc* <= cut(m) = (m + e0) (1 + kappa) / (1 - kappa) + e0
+// whenever it is met: every element with acc <= cut(m) is a candidate and goes to the exact path, which merges
+// (d2, index) lexicographically -- ties, duplicates included, all pass the same test.  nn_hd: the same over the
+// references with fe[j] < fe[i].
+// Exact path: dist2_canon_rt on the original coordinates, from a per-wave LDS queue that is drained when the next
+// push might not fit (never dropped) and at the end; results go out through integer atomics (counts: atomicAdd;
+// neighbours: atomicMin on (d2 bits << 32 | index), finished by wide_nn_finish_kernel).
+#pragma once
+#include "dc_mfma_kernels.hpp"
+#include "dc_mfma_wide.hpp"
+
+namespace dc {
+
+namespace {
+
+constexpr int kWideKC = 4;               // MFMAs (16 K slots each) per LDS chunk
+constexpr int kWideBlockTiles = 4;       // tiles per side of a workgroup's block
+constexpr uint32_t kWideBlockRows = 32 * kWideBlockTiles;
+constexpr uint32_t kWideQueue = 256;     // deferred pairs a wave parks before it drains them
+constexpr uint32_t kWideChunkVec = kWideKC * 2 * kWideBlockTiles * 64;   // 16-byte fragments of one chunk: 2048 = 32 KiB
+static_assert(kWideChunkVec % 256 == 0 && kWideQueue >= 128, "staging shape; a push of 64 fits after a drain");
+// header (1024 bytes, words as in dc_mfma_kernels.hpp: 0 max |x'|^2, 1 flag, kHdrScale..+4 the scale) and behind it
+// the regions the 64-column header has no room for
+constexpr uint32_t kWideHdrTiles = 40, kWideHdrMfma = 42, kWideHdrExact = 44;   // 64-bit counters of the last sweep
+constexpr size_t kWideOffSums = kHdrBytes;                             // [256] double: column sums
+constexpr size_t kWideOffMeans = kWideOffSums + 8 * kWideMaxCols;      // [256] float: column means
+constexpr size_t kWideOffImages = kWideOffMeans + 4 * kWideMaxCols;    // 4096
+static_assert(4 * (kWideHdrExact + 2) <= kWideInfoBytes && kWideInfoBytes <= kHdrBytes, "counters inside the info head");
+static_assert(kWideHdrTiles > kHdrShift && kWideHdrTiles > kHdrScale + 4 && kWideHdrTiles % 2 == 0, "counters clear of the shared header words, 64-bit aligned");
+
+// Workgroup -> (query block, reference share).  A workgroup re-reads the fragments of its query block for every
+// reference block it meets, and streams the reference blocks of its share: both come out of L2 only if the workgroups
+// that run side by side on an XCD need few DIFFERENT blocks.  Workgroups are dealt round-robin to the 8 XCDs by their
+// linear id (dc_mfma_kernels.hpp xcd_block), so the ids are decoded such that 64 consecutive workgroups of one XCD are
+// 8 query blocks x 8 shares: 8 + 8 blocks in flight per XCD (1.2 MB at 100 columns, 3.1 MB at 256, of 4 MB), each
+// used by 8 workgroups, and every XCD only ever touches its own eighth of the reference image.  (With the query blocks
+// along x and one share per launch row, the 64 workgroups of an XCD hold 64 different query blocks: 4.9 MB at 100 columns.)
+// The shares of a launch: a power of two, at most kWideShares, and no more than leave every share kWideShareBlocks
+// reference blocks -- every share of a query starts its neighbour search from nothing, and a share of one block sends
+// its whole first harvest of candidates to the exact path (1 500 rows: 12 blocks, one share).  With n < 64 shares the 64
+// (XCD, share slot) pairs of a group are n shares x 64 / n further query blocks, so every XCD has work at every size.
+constexpr uint32_t kWideShares = 64;        // reference shares at most: share s owns the reference blocks s, s + n_shares, ...
+constexpr uint32_t kWideShareBlocks = 8;    // reference blocks a share holds at least (while there are that many)
+__host__ __device__ inline uint32_t wide_shares(uint32_t ref_blocks) {
+  uint32_t s = 1;
+  while (2u * s <= kWideShares && 2u * s * kWideShareBlocks <= ref_blocks) s *= 2u;
+  return s;
+}
+struct WideUnit {
+  uint32_t q_block, share;
+};
+__host__ __device__ inline WideUnit wide_unit(uint32_t id, uint32_t n_shares) {
+  const uint32_t xcd = id & 7u, slot = id >> 3, g = xcd * 8u + ((slot >> 3) & 7u), mult = kWideShares / n_shares;
+  return WideUnit{((slot >> 6) * 8u + (slot & 7u)) * mult + g / n_shares, g % n_shares};
+}
+inline uint32_t wide_grid_size(uint32_t q_blocks, uint32_t n_shares) {
+  const uint32_t per_group = 8u * (kWideShares / n_shares);   // query blocks of 512 consecutive workgroups
+  return 8u * 64u * ((q_blocks + per_group - 1u) / per_group);
+}
+
+struct WideLayout {
+  uint32_t T, Tp, NM;   // tiles, tiles padded to whole blocks, MFMAs per chain
+  size_t off_img_a, off_img_b, off_norms, off_merge, total;
+};
+inline WideLayout wide_layout(size_t n_rows, size_t n_cols) {
+  WideLayout L;
+  L.T = (uint32_t)((n_rows + 31) / 32);
+  L.Tp = (L.T + kWideBlockTiles - 1) / kWideBlockTiles * kWideBlockTiles;
+  L.NM = (uint32_t)nm_for((int)n_cols);
+  const size_t img_bytes = (size_t)16 * 64 * (size_t)L.Tp * L.NM;
+  L.off_img_a = kWideOffImages;
+  L.off_img_b = align256(L.off_img_a + img_bytes);
+  L.off_norms = align256(L.off_img_b + img_bytes);
+  L.off_merge = align256(L.off_norms + sizeof(float) * 32 * (size_t)L.Tp);
+  L.total = align256(L.off_merge + sizeof(unsigned long long) * 2 * n_rows);
+  return L;
+}
+
+// ---- the band of the wide sweeps, host and device (scaled units) ------------------------------------------------------
+struct WideBand {
+  float e0, kappa;
+};
+__host__ __device__ inline WideBand wide_band(float M_scaled, int D, const Scale& sc) {
+  const GuardBand gb = guard_band(M_scaled, 0.0f, D, sc);
+  return WideBand{gb.e0, gb.kappa};
+}
+// float roundings of the window arithmetic below: a few ulp of the largest term
+constexpr float kWideRoundMargin = 6.0e-7f;
+// population window of one scaled threshold: [lo, hi) is undecided
+__host__ __device__ inline void wide_window(float thr, const WideBand& b, float& lo, float& hi) {
+  if (!(thr <= FLT_MAX)) {   // a radius beyond every float: every finite accumulator is inside
+    lo = hi = INFINITY;
+    return;
+  }
+  const float band = thr * b.kappa + b.e0, marg = (thr + b.e0) * kWideRoundMargin;
+  lo = (thr - band) - marg;
+  hi = (thr + band) + marg;
+}
+// neighbour cut of a running minimum m (+inf: nothing met yet -> +inf)
+__host__ __device__ inline float wide_cut(float m, const WideBand& b, float ratio) {
+  const float c = (m + b.e0) * ratio + b.e0;
+  return c + fabsf(c) * kWideRoundMargin;
+}
+__host__ __device__ inline float wide_cut_ratio(const WideBand& b) {
+  return (1.0f + b.kappa) / (1.0f - b.kappa) * (1.0f + kWideRoundMargin);
+}
+
+// ---- statistics, scale, images: the instances of dc_mfma.hip's passes for up to kWideMaxCols columns ------------------
+// (the partial sums meet in atomics, in an order that follows the scheduling: the float means, and with them M, the images
+//  and the number of pairs in the band, may differ in the last bit from run to run of one call -- any origin near the mean
+//  serves, the band covers it, the results are exact either way; only the exact-pair counter is not reproducible)
+__global__ void wide_colsum_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D, double* __restrict__ sums) {
+  __shared__ double part[kWideMaxCols];
+  if (threadIdx.x < (uint32_t)kWideMaxCols) part[threadIdx.x] = 0.0;
+  __syncthreads();
+  const uint32_t nthreads = gridDim.x * blockDim.x;
+  const uint32_t used = (nthreads / D) * D;   // stride is a multiple of D: fixed column
+  const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t total = (size_t)n_rows * D;
+  if (id < used) {
+    double s0 = 0.0, s1 = 0.0;
+    size_t e = id;
+    for (; e + (size_t)used < total; e += 2 * (size_t)used) {
+      const float v0 = coords[e], v1 = coords[e + used];
+      if (fabsf(v0) <= FLT_MAX) s0 += (double)v0;   // non-finite entries do not poison the mean
+      if (fabsf(v1) <= FLT_MAX) s1 += (double)v1;
+    }
+    if (e < total) {
+      const float v = coords[e];
+      if (fabsf(v) <= FLT_MAX) s0 += (double)v;
+    }
+    atomicAdd(&part[id % D], s0 + s1);
+  }
+  __syncthreads();
+  if (threadIdx.x < D) atomicAdd(&sums[threadIdx.x], part[threadIdx.x]);
+}
+
+__global__ void wide_mean_kernel(const double* __restrict__ sums, uint32_t n_rows, uint32_t D, float* __restrict__ means) {
+  const uint32_t k = threadIdx.x;
+  if (k >= D) return;
+  float muf = (float)(sums[k] / (double)n_rows);
+  if (!(fabsf(muf) <= FLT_MAX)) muf = 0.0f;
+  means[k] = muf;
+}
+
+// max |x'|^2 (word 0) and the non-finite / overflow flag (word 1); one wave per row, the columns across its lanes.
+// |x'|^2 is formed from the same centred floats as wide_image_kernel forms it, so word 0 bounds every norm.
+__global__ void wide_rowstats_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D,
+                                     const float* __restrict__ means, uint32_t* __restrict__ hdr) {
+  const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+  uint32_t m_norm = 0;
+  bool bad = false;
+  for (uint32_t row = wave; row < n_rows; row += n_waves) {
+    const float* x = coords + (size_t)row * D;
+    double nrm = 0.0;
+    for (uint32_t k = lane; k < D; k += 64u) {
+      const float v = x[k] - means[k];
+      nrm += (double)v * (double)v;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nrm += __shfl_xor(nrm, off, 64);
+    const float nf = (float)nrm * (1.0f + 4.0e-7f);   // (the image builder sums in column order: a few ulp apart at most)
+    const bool ok = nf <= kNormLimit;
+    bad = bad | !ok;
+    m_norm = max(m_norm, ok ? __float_as_uint(nf) : 0u);
+  }
+  if (lane == 0) {
+    if (bad) atomicOr(hdr + 1, 1u);
+    if (m_norm > __atomic_load_n(hdr, __ATOMIC_RELAXED)) atomicMax(hdr, m_norm);
+  }
+}
+
+// a NaN free energy flags the data (the comparisons of the neighbour sweep are IEEE: the direct kernel answers)
+__global__ void wide_fe_flag_kernel(const float* __restrict__ fe, uint32_t n_rows, uint32_t* __restrict__ hdr) {
+  bool nan = false;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += gridDim.x * blockDim.x) nan = nan | (fe[i] != fe[i]);
+  if (__builtin_amdgcn_ballot_w64(nan) != 0 && (threadIdx.x & 63u) == 0) atomicOr(hdr + 1, 1u);
+}
+
+__global__ void wide_scale_kernel(uint32_t* __restrict__ hdr) {
+  const float M = __uint_as_float(hdr[0]);
+  hdr[kHdrMused] = __float_as_uint(M);
+  const ScaleExp e = pick_scale_nn(M);
+  hdr[kHdrScale + 0] = __float_as_uint(e.c);
+  hdr[kHdrScale + 1] = __float_as_uint(e.s2);
+  hdr[kHdrScale + 2] = (uint32_t)e.g;
+  hdr[kHdrScale + 3] = (uint32_t)e.a;
+  hdr[kHdrScale + 4] = (uint32_t)e.rounded;
+}
+
+// Both operand images in the slot layout of dc_mfma_kernels.hpp (slot_value): one thread writes the 16-byte fragment of
+// one lane of one MFMA of one tile, reference side (A form) and query side (B form: the pieces of -2x'', and in the
+// two constant slots the pieces of c_q / 2^a = |x''|^2 / 2^a, which the resident-operand kernels patch in when they
+// load a query).  Rows beyond n_rows and the tiles that pad the last block: zero fragments, norm +inf.
+__global__ void wide_image_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D, uint32_t NM, uint32_t Tp,
+                                  const float* __restrict__ means, const uint32_t* __restrict__ hdr,
+                                  uint4* __restrict__ img_a, uint4* __restrict__ img_b, float* __restrict__ norms) {
+  const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lane = (uint32_t)(id & 63), m = (uint32_t)((id >> 6) % NM), t = (uint32_t)((id >> 6) / NM);
+  if (t >= Tp) return;
+  const uint32_t row = 32 * t + (lane & 31), h = lane >> 5;
+  const bool live = row < n_rows;
+  const float* x = coords + (size_t)(live ? row : 0u) * D;
+  const Scale sc = load_scale(hdr);
+  auto col = [&](uint32_t k) -> float { return (x[k] - means[k]) * sc.sa; };   // x'' = 2^k fl(x - mu)
+  uint32_t wa[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
+  double nrm = 0.0;
+  if (live && m == 0 && h == 0)
+    for (uint32_t k = 0; k < D; ++k) {
+      const float v = col(k);
+      nrm += (double)v * (double)v;
+    }
+  if (live) {
+    const uint32_t s0 = 16 * m + 8 * h;
+    uint32_t G = 0, k = 0;
+    if (s0 >= (uint32_t)kConstSlots) {
+      G = (s0 - kConstSlots) / D;
+      k = (s0 - kConstSlots) - G * D;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) {
+      uint32_t va = 0u, vb = 0u;
+      if (s0 + j < (uint32_t)kConstSlots) {
+        const Pieces pn = split2((float)nrm * sc.cinv);   // (as load_query splits c_q)
+        va = const_a_bits(sc.a);
+        vb = (j == 0) ? pn.hi : pn.mid;
+      } else {
+        if (G < (uint32_t)kPieceGroups) {
+          const float v = col(k);
+          const Pieces pa = split2(v, sc.up, sc.dn), pb = split2(-2.0f * v, sc.up, sc.dn);
+          va = (G == 0u) ? pa.hi : (G == 1u ? pa.mid : pa.hi_dn);
+          vb = (G == 0u) ? pb.hi : (G == 2u ? pb.mid : pb.hi_dn);
+        }
+        if (++k == D) {
+          k = 0;
+          ++G;
+        }
+      }
+      wa[j >> 1] |= (va & 0xFFFFu) << (16 * (j & 1));
+      wb[j >> 1] |= (vb & 0xFFFFu) << (16 * (j & 1));
+    }
+  }
+  const size_t o = ((size_t)t * NM + m) * 64 + lane;
+  img_a[o] = make_uint4(wa[0], wa[1], wa[2], wa[3]);
+  img_b[o] = make_uint4(wb[0], wb[1], wb[2], wb[3]);
+  if (m == 0 && h == 0) norms[row] = live ? (float)nrm : INFINITY;
+}
+
+inline size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
+// the preparation of a call: header reset, statistics, scale, both images (dc_mfma_wide.hip wide_prepare; the model test
+// runs the same launches)
+inline int wide_prepare_launches(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, void* d_ws,
+                                 hipStream_t s) {
+  const WideLayout L = wide_layout(n_rows, n_cols);
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  double* sums = (double*)(p + kWideOffSums);
+  float* means = (float*)(p + kWideOffMeans);
+  // header, counters of the last sweep, column sums
+  if (hipMemsetAsync(d_ws, 0, kWideOffImages, s) != hipSuccess) return -1;
+  const size_t elems = (size_t)n_rows * n_cols;
+  const uint32_t sum_blocks = (uint32_t)min_sz(1024, (elems + 255) / 256);
+  hipLaunchKernelGGL(wide_colsum_kernel, dim3(sum_blocks), dim3(256), 0, s, d_coords, n_rows, n_cols, sums);
+  hipLaunchKernelGGL(wide_mean_kernel, dim3(1), dim3(256), 0, s, (const double*)sums, n_rows, n_cols, means);
+  const uint32_t stat_blocks = (uint32_t)min_sz(4096, ((size_t)n_rows + 3) / 4);
+  hipLaunchKernelGGL(wide_rowstats_kernel, dim3(stat_blocks), dim3(256), 0, s, d_coords, n_rows, n_cols, (const float*)means, hdr);
+  if (d_fe)
+    hipLaunchKernelGGL(wide_fe_flag_kernel, dim3((uint32_t)min_sz(1024, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s, d_fe, n_rows, hdr);
+  hipLaunchKernelGGL(wide_scale_kernel, dim3(1), dim3(1), 0, s, hdr);
+  const size_t frags = (size_t)L.Tp * L.NM * 64;
+  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags + 255) / 256)), dim3(256), 0, s, d_coords, n_rows, n_cols, L.NM,
+                     L.Tp, (const float*)means, (const uint32_t*)hdr, (uint4*)(p + L.off_img_a), (uint4*)(p + L.off_img_b),
+                     (float*)(p + L.off_norms));
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- the sweep ------------------------------------------------------------------------------------------------------
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+enum WideMode { kWidePop = 0, kWideNn = 1, kWideDump = 2 };
+
+struct WideArgs {
+  const float* coords;
+  uint32_t n_rows, n_cols, NM, Tp;
+  const uint4* img_a;
+  const uint4* img_b;
+  const float* norms;
+  uint32_t* hdr;
+  uint32_t i_from, i_to;
+  Rad2 rad2;                   // populations: fl32(r^2) per radius, unscaled
+  int n_rad;
+  uint32_t* pops;              // [n_rad][n_rows], zeroed: the sweep adds
+  const float* fe;             // neighbours
+  unsigned long long* merge;   // [2][n_rows] (d2 bits << 32 | index), preset to ~0
+  float* dump;                 // kWideDump (the model test): acc of (reference row i, query row j) at [i * 32 Tp + j]
+};
+
+// the deferred pairs of a wave, evaluated in the canonical order from the original coordinates, a pair per lane
+template <int MODE>
+__device__ __attribute__((noinline)) void wide_drain(const uint2* queue, uint32_t fill, const float* coords, uint32_t n_rows,
+                                                     uint32_t n_cols, uint32_t qrow0, Rad2 rad2, uint32_t* pops,
+                                                     unsigned long long* merge) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the queue writes of all lanes before their reads)
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t e = lane; e < fill; e += 64u) {
+    const uint2 en = queue[e];
+    const uint32_t i = en.x, j = qrow0 + (en.y & 127u), flags = en.y >> 8;
+    const float d2 = dist2_canon_rt(coords + (size_t)j * n_cols, 1, coords + (size_t)i * n_cols, 1, (int)n_cols);
+    if constexpr (MODE == kWidePop) {
+#pragma unroll
+      for (int k = 0; k < kMaxRadiiPerLaunch; ++k)
+        if (((flags >> k) & 1u) && d2 < rad2.v[k]) atomicAdd(&pops[(size_t)k * n_rows + j], 1u);
+    } else {
+      const unsigned long long w = ((unsigned long long)__float_as_uint(d2) << 32) | i;
+      if (flags & 1u) atomicMin(&merge[j], w);
+      if (flags & 2u) atomicMin(&merge[(size_t)n_rows + j], w);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <int MODE, int NR>
+__global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
+  if (X.hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
+  __shared__ u32x4 stage[2 * kWideChunkVec];
+  __shared__ uint2 queue_s[4][kWideQueue];
+  __shared__ float fe_s[kWideBlockRows];
+  __shared__ float min_s[4][2][2][32];   // neighbours: running minima (nn, nn_hd) per wave and query, exchanged per block
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, h = lane >> 5, c = lane & 31u;
+  const uint32_t wq = wave & 1u, wr = wave >> 1;
+  const uint32_t NM = X.NM, NC = (NM + kWideKC - 1) / kWideKC, D = X.n_cols;
+  const uint32_t RB = X.Tp / kWideBlockTiles, Sy = wide_shares(RB);
+  const WideUnit unit = wide_unit(blockIdx.x, Sy);
+  const uint32_t qb = X.i_from / kWideBlockRows + unit.q_block, y = unit.share;
+  // (whole workgroups: the query blocks that pad the last group)
+  if (qb * kWideBlockRows >= X.i_to) return;
+  const uint32_t nblk = (RB - y + Sy - 1) / Sy, n_it = nblk * NC;
+  uint2* queue = queue_s[wave];
+  uint32_t fill = 0;
+  unsigned long long n_exact = 0;
+
+  const Scale sc = load_scale(X.hdr);
+  const WideBand band = wide_band(__uint_as_float(X.hdr[0]) * sc.s2, (int)D, sc);
+
+  // per query tile of this wave: the lane's row
+  uint32_t jq[2];
+  bool live[2];
+  unsigned long long livemask[2];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    jq[qt] = (qb * kWideBlockTiles + 2 * wq + qt) * 32 + c;
+    live[qt] = jq[qt] >= X.i_from && jq[qt] < X.i_to;
+    livemask[qt] = __builtin_amdgcn_ballot_w64(live[qt]);
+  }
+
+  // populations: windows and counts; neighbours: running minima
+  float lo[NR], hi[NR], hi_max = -INFINITY;
+  uint32_t cnt[2][NR];
+  float m_nn[2], m_hd[2], feq[2];
+  const float ratio = wide_cut_ratio(band);
+  if constexpr (MODE == kWidePop) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      lo[k] = hi[k] = -INFINITY;   // (a radius the launch does not have: nothing inside, nothing undecided)
+      if (k < X.n_rad) wide_window(X.rad2.v[k] * sc.s2, band, lo[k], hi[k]);
+      hi_max = fmaxf(hi_max, hi[k]);
+      cnt[0][k] = cnt[1][k] = 0;
+    }
+  }
+  if constexpr (MODE == kWideNn) {
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      m_nn[qt] = m_hd[qt] = INFINITY;
+      feq[qt] = live[qt] ? X.fe[jq[qt]] : -INFINITY;   // (a dead lane: no reference lies lower)
+    }
+  }
+
+  // one pair per lane into the wave's queue (ok: this lane has one); drained before a push that might not fit
+  auto push = [&](bool ok, uint32_t i, uint32_t word) {
+    const unsigned long long mk = __builtin_amdgcn_ballot_w64(ok);
+    if (mk == 0) return;
+    if (fill + 64u > kWideQueue) {
+      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, X.n_rows, D, qb * kWideBlockRows, X.rad2, X.pops, X.merge);
+      n_exact += fill;
+      fill = 0;
+    }
+    if (ok) queue[fill + lanes_below(mk)] = make_uint2(i, word);
+    fill += (uint32_t)__popcll(mk);
+  };
+
+  // chunk `it` of the workgroup's sequence (block it / NC, chunk it % NC) -> registers -> LDS buffer
+  // (the last chunk of a chain may hold fewer than kWideKC MFMAs: the surplus slots re-load the chunk's last MFMA and are
+  //  never read -- unconditional loads and stores keep `pre` in registers and the eight loads in flight together)
+  // (u32x4, a native vector type: an array of HIP's uint4 -- a struct -- is kept in scratch, with a wait and a scratch store
+  //  behind every load)
+  u32x4 pre[kWideChunkVec / 256];
+  auto fetch = [&](uint32_t it) {
+    const uint32_t blk = it / NC, ch = it - blk * NC, rb = y + blk * Sy;
+    const uint32_t m0 = ch * kWideKC, nmc = min((uint32_t)kWideKC, NM - m0);
+#pragma unroll
+    for (uint32_t i = 0; i < kWideChunkVec / 256; ++i) {
+      const uint32_t e = tid + 256u * i, ml = min(e >> 9, nmc - 1u), tl = (e >> 6) & 7u;   // (MFMA of the chunk, tile 0..3 reference / 4..7 query)
+      const uint32_t t = (tl < 4u) ? rb * kWideBlockTiles + tl : qb * kWideBlockTiles + (tl - 4u);
+      const u32x4* img = reinterpret_cast<const u32x4*>((tl < 4u) ? X.img_a : X.img_b);
+      pre[i] = img[((size_t)t * NM + m0 + ml) * 64 + lane];
+    }
+  };
+  auto store = [&](uint32_t it) {
+    u32x4* dst = stage + (it & 1u) * kWideChunkVec;
+#pragma unroll
+    for (uint32_t i = 0; i < kWideChunkVec / 256; ++i) dst[tid + 256u * i] = pre[i];
+  };
+
+  f32x16 acc[2][2];
+  fetch(0);
+  store(0);
+  __syncthreads();
+  for (uint32_t it = 0; it < n_it; ++it) {
+    const uint32_t blk = it / NC, ch = it - blk * NC, rb = y + blk * Sy;
+    const uint32_t nmc = min((uint32_t)kWideKC, NM - ch * kWideKC);
+    const bool last = ch == NC - 1;
+    if (ch == 0) {
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        float4 nv[4];
+        load_frag(X.norms, rb * kWideBlockTiles + 2 * wr + rt, (int)h, nv);
+        acc[rt][0] = frag16(nv);
+        acc[rt][1] = acc[rt][0];
+      }
+      if constexpr (MODE == kWideNn) {
+        // (read by the epilogue of this block's LAST chunk, a barrier later; the previous block's epilogue ended before
+        //  the barrier that closed its last chunk)
+        if (tid < kWideBlockRows) {
+          const uint32_t row = rb * kWideBlockRows + tid;
+          fe_s[tid] = row < X.n_rows ? X.fe[row] : INFINITY;
+        }
+      }
+    }
+    // the next chunk leaves for the registers before this chunk's MFMAs (behind the norm loads above: the memory counter
+    // is in order, and the wait for the norms must not wait for the chunk)
+    if (it + 1 < n_it) fetch(it + 1);
+    const u32x4* sb = stage + (it & 1u) * kWideChunkVec;
+#pragma unroll
+    for (uint32_t ml = 0; ml < (uint32_t)kWideKC; ++ml) {
+      if (ml < nmc) {
+        const s16x8 a0 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 2 * wr) * 64 + lane]);
+        const s16x8 a1 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 2 * wr + 1) * 64 + lane]);
+        const s16x8 b0 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 4 + 2 * wq) * 64 + lane]);
+        const s16x8 b1 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 5 + 2 * wq) * 64 + lane]);
+        acc[0][0] = mfma16(a0, b0, acc[0][0]);
+        acc[0][1] = mfma16(a0, b1, acc[0][1]);
+        acc[1][0] = mfma16(a1, b0, acc[1][0]);
+        acc[1][1] = mfma16(a1, b1, acc[1][1]);
+      }
+    }
+    if (last) {
+      // ---- epilogue of the block: acc[rt][qt][g] ~ S d2(reference row of (rt, g, h), query jq[qt]) ----
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+          if (MODE != kWideDump && rb * kWideBlockTiles + 2 * wr + rt == qb * kWideBlockTiles + 2 * wq + qt) {
+            // the diagonal tile: the self pair leaves the sweep (populations add their 1 at the end, neighbours exclude it)
+#pragma unroll
+            for (int g = 0; g < 16; ++g)
+              if (tile_row_local(g, (int)h) == c) acc[rt][qt][g] = INFINITY;
+          }
+      if constexpr (MODE == kWideDump) {
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+              const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
+              X.dump[(size_t)i * (32u * X.Tp) + jq[qt]] = acc[rt][qt][g];
+            }
+      }
+      if constexpr (MODE == kWidePop) {
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+          for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+              const float v = acc[rt][qt][g];
+              if (__builtin_amdgcn_ballot_w64(v < hi_max) == 0) continue;   // outside every radius, the whole wave
+              uint32_t und = 0;
+#pragma unroll
+              for (int k = 0; k < NR; ++k) {
+                cnt[qt][k] += (v < lo[k]) ? 1u : 0u;
+                und |= ((v >= lo[k]) & (v < hi[k])) ? (1u << k) : 0u;
+              }
+              if ((__builtin_amdgcn_ballot_w64(und != 0) & livemask[qt]) != 0) {
+                const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
+                push(und != 0 && live[qt] && i < X.n_rows, i, ((2 * wq + qt) * 32 + c) | (und << 8));
+              }
+            }
+      }
+      if constexpr (MODE == kWideNn) {
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+#pragma unroll
+          for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+              const float v = acc[rt][qt][g], fr = fe_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
+              m_nn[qt] = fminf(m_nn[qt], v);
+              m_hd[qt] = fminf(m_hd[qt], (fr < feq[qt]) ? v : INFINITY);
+            }
+          // (the two halves of the wave hold other reference rows of the same queries: any minimum met serves both)
+          m_nn[qt] = fminf(m_nn[qt], __shfl_xor(m_nn[qt], 32, 64));
+          m_hd[qt] = fminf(m_hd[qt], __shfl_xor(m_hd[qt], 32, 64));
+          if (h == 0) {
+            min_s[wave][qt][0][c] = m_nn[qt];
+            min_s[wave][qt][1][c] = m_hd[qt];
+          }
+        }
+        // ... and so do the two waves that hold the other reference tiles of the same queries (wave ^ 2): one search per
+        // query and share instead of two.  Every wave of the workgroup is in this epilogue (the chunk count is uniform);
+        // the next block's minima are written behind the barrier that closes this chunk.
+        __syncthreads();
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          m_nn[qt] = fminf(m_nn[qt], min_s[wave ^ 2u][qt][0][c]);
+          m_hd[qt] = fminf(m_hd[qt], min_s[wave ^ 2u][qt][1][c]);
+          const float cut_nn = wide_cut(m_nn[qt], band, ratio), cut_hd = wide_cut(m_hd[qt], band, ratio);
+#pragma unroll
+          for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+              const float v = acc[rt][qt][g], fr = fe_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
+              const uint32_t fl = ((v <= cut_nn) ? 1u : 0u) | (((fr < feq[qt]) & (v <= cut_hd)) ? 2u : 0u);
+              if ((__builtin_amdgcn_ballot_w64(fl != 0) & livemask[qt]) != 0) {
+                const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
+                push(fl != 0 && live[qt] && i < X.n_rows && i != jq[qt], i, ((2 * wq + qt) * 32 + c) | (fl << 8));
+              }
+            }
+        }
+      }
+    }
+    if (it + 1 < n_it) store(it + 1);
+    __syncthreads();
+  }
+
+  if constexpr (MODE != kWideDump) {
+    if (fill != 0) {
+      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, X.n_rows, D, qb * kWideBlockRows, X.rad2, X.pops, X.merge);
+      n_exact += fill;
+    }
+  }
+  if constexpr (MODE == kWidePop) {
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+      for (int k = 0; k < NR; ++k) {
+        const uint32_t total = cnt[qt][k] + (uint32_t)__shfl_xor((int)cnt[qt][k], 32, 64);
+        // the frame itself: the 1 the reference starts every population at, added once per row
+        const uint32_t add = total + ((y == 0 && wr == 0) ? 1u : 0u);
+        if (h == 0 && live[qt] && k < X.n_rad && add != 0) atomicAdd(&X.pops[(size_t)k * X.n_rows + jq[qt]], add);
+      }
+  }
+  if (lane == 0 && n_exact != 0) atomicAdd(reinterpret_cast<unsigned long long*>(X.hdr + kWideHdrExact), n_exact);
+  if (tid == 0) {
+    const unsigned long long tiles = (unsigned long long)nblk * kWideBlockTiles * kWideBlockTiles;
+    atomicAdd(reinterpret_cast<unsigned long long*>(X.hdr + kWideHdrTiles), tiles);
+    atomicAdd(reinterpret_cast<unsigned long long*>(X.hdr + kWideHdrMfma), tiles * NM);
+  }
+}
+
+// the merged words of the rows [i_from, i_to) -> the four outputs ("none" stays where nothing was found)
+__global__ void wide_nn_finish_kernel(const uint32_t* __restrict__ hdr, const unsigned long long* __restrict__ merge,
+                                      uint32_t n_rows, uint32_t i_from, uint32_t i_to, uint32_t* __restrict__ nn_idx,
+                                      float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx, float* __restrict__ hd_d2) {
+  if (hdr[1] != 0) return;
+  const uint32_t j = i_from + blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= i_to) return;
+  const unsigned long long a = merge[j], b = merge[(size_t)n_rows + j];
+  if (a != ~0ull) {
+    nn_idx[j] = (uint32_t)a;
+    nn_d2[j] = __uint_as_float((uint32_t)(a >> 32));
+  }
+  if (b != ~0ull) {
+    hd_idx[j] = (uint32_t)b;
+    hd_d2[j] = __uint_as_float((uint32_t)(b >> 32));
+  }
+}
+
+}  // namespace
+
+}  // namespace dc

@@ -48,6 +48,10 @@ def _nearest_pruned_bytes(n_q, n_ref, n_cols):
     return capi.lib.dc_hip_nearest_cross_pruned_workspace_bytes(n_q, n_ref, n_cols)
 
 
+def _wide_bytes(n_rows, n_cols, n_radii=1):
+    return capi.lib.dc_hip_wide_workspace_bytes(n_rows, n_cols, n_radii)
+
+
 class Workspace:
     """Device scratch of one kind of sweep (MFMA operand images); grown on demand, reused across calls.
     ``size`` is the library's byte count for a call's shape: get(*shape) asks it and returns (pointer, bytes)."""
@@ -70,6 +74,7 @@ _workspaces = {}        # self sweeps, per device
 _cross_workspaces = {}  # sweeps against a reference, per device
 _cross_pruned_workspaces = {}  # ... of variant="cross_pruned" (the larger layout of its two orders), per device
 _nearest_pruned_workspaces = {}  # ... of nearest_reference(pruned=True), per device
+_wide_workspaces = {}   # the matrix-core sweeps for rows of 65..256 columns, per device
 
 
 def _cached(cache, device, size):
@@ -93,6 +98,10 @@ def _cross_pruned_workspace(device):
 
 def _nearest_pruned_workspace(device):
     return _cached(_nearest_pruned_workspaces, device, _nearest_pruned_bytes)
+
+
+def _wide_workspace(device):
+    return _cached(_wide_workspaces, device, _wide_bytes)
 
 
 def _variant(variant, stats_valid):
@@ -217,6 +226,60 @@ def nearest_neighbors_partial(coords, fe, i_from=0, i_to=None, variant="auto", s
             _dev(hd_idx), _dev(hd_d2), ws, ws_bytes, _variant(variant, stats_valid), _stream_ptr())
     capi.check(rc, "dc_hip_nearest_neighbors_dev")
     return nn_idx, nn_d2, hd_idx, hd_d2
+
+
+# ---- matrix-core sweeps for rows of 65..256 columns (include/dc_density.h "wide" sweeps) ---------------------------
+def calculate_populations_wide(coords, radii, i_from=0, i_to=None, out=None):
+    """calculate_populations_partial for rows of 65..256 columns on the matrix cores (dc_hip_populations_wide_dev):
+    the same populations bit for bit, one matrix-core chain per tile pair for all radii (up to 8 per launch), radii in
+    any order, in a cached workspace of its own (wide_sweep_info reads its counters).  Other column counts raise."""
+    n_rows, n_cols = _check_coords(coords)
+    i_to = n_rows if i_to is None else i_to
+    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    if out is None:
+        out = torch.empty((rad.size, n_rows), dtype=torch.int32, device=coords.device)
+    assert out.shape == (rad.size, n_rows) and out.dtype == torch.int32 and out.is_contiguous()
+    with torch.cuda.device(coords.device):
+        ws, ws_bytes = _wide_workspace(coords.device).get(n_rows, n_cols, rad.size)
+        rc = capi.lib.dc_hip_populations_wide_dev(
+            _dev(coords), n_rows, n_cols, rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size, i_from, i_to, _dev(out),
+            ws, ws_bytes, _stream_ptr())
+    capi.check(rc, "dc_hip_populations_wide_dev")
+    return out
+
+
+def nearest_neighbors_wide(coords, fe, i_from=0, i_to=None):
+    """nearest_neighbors_partial for rows of 65..256 columns on the matrix cores (dc_hip_nearest_neighbors_wide_dev).
+    -> (nn_idx int32, nn_d2 float32, hd_idx int32, hd_d2 float32), each [n_rows]; "none" is (n_rows+1, FLT_MAX)."""
+    n_rows, n_cols = _check_coords(coords)
+    i_to = n_rows if i_to is None else i_to
+    assert fe.is_cuda and fe.dtype == torch.float32 and fe.shape == (n_rows,) and fe.is_contiguous()
+    dev = coords.device
+    nn_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    hd_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    nn_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    hd_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _wide_workspace(dev).get(n_rows, n_cols, 1)
+        rc = capi.lib.dc_hip_nearest_neighbors_wide_dev(
+            _dev(coords), n_rows, n_cols, _dev(fe), i_from, i_to, _dev(nn_idx), _dev(nn_d2), _dev(hd_idx), _dev(hd_d2),
+            ws, ws_bytes, _stream_ptr())
+    capi.check(rc, "dc_hip_nearest_neighbors_wide_dev")
+    return nn_idx, nn_d2, hd_idx, hd_d2
+
+
+def wide_sweep_info(device):
+    """(tiles, mfmas, exact_pairs): 32x32 frame-pair tiles evaluated, MFMA instructions issued and frame pairs sent
+    to the exact path by the last wide sweep on this device (dc_hip_wide_info_dev); (0, 0, 0) when the direct
+    kernels answered (flagged data), nothing was swept, or no wide sweep has run."""
+    ws = _wide_workspace(device)
+    if ws.buf is None:
+        return 0, 0, 0
+    t, m, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
+                   "dc_hip_wide_info_dev")
+    return int(t.value), int(m.value), int(e.value)
 
 
 # ---- cross sweeps: new frames against a reference trajectory (include/dc_density.h "cross sweeps") ----------------

@@ -394,6 +394,33 @@ DC_API int dc_hip_nearest_neighbors_cross_pruned_dev(const float* d_query, size_
 DC_API int dc_hip_nearest_cross_pruned_info_dev(const void* d_ws, uint64_t* nn_tiles, uint64_t* nn_mfma,
                                                 uint32_t* n_shares, void* stream);
 
+/* ---- matrix-core sweeps for rows of 65..256 columns ("wide" sweeps) ----------------------------------------------
+ * Every-pair self sweeps on the f16 matrix cores whose K axis streams through LDS, with the results of
+ * dc_hip_populations_dev / dc_hip_nearest_neighbors_dev bit for bit (classifier + guard band + canonical re-check;
+ * flagged data -- a non-finite or overflow-prone row, a NaN free energy -- is answered by the direct kernels behind
+ * a device-side gate).  Entry points of their own: no dc_variant value selects them, DC_VARIANT_AUTO / _MFMA keep
+ * sending rows wider than 64 columns to the direct kernels.
+ * Contracts as for the two sweeps above: outputs fully overwritten, 0 / "none" = (n_rows + 1, FLT_MAX) outside
+ * [i_from, i_to); radii in any order, one matrix-core chain per tile pair for up to 8 radii of a call.
+ * n_cols outside 65..256: DC_ERR_INVALID_ARGUMENT; a workspace smaller than dc_hip_wide_workspace_bytes:
+ * DC_ERR_WORKSPACE; sizes: DC_ERR_TOO_LARGE as above; n_rows == 0 or an empty range: DC_OK.
+ * dc_hip_wide_workspace_bytes: 0 outside 65..256 columns (and for no rows), monotone in n_rows. */
+DC_API size_t dc_hip_wide_workspace_bytes(size_t n_rows, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_populations_wide_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* radii,
+                                       size_t n_radii, size_t i_from, size_t i_to, uint32_t* d_pops, void* d_ws,
+                                       size_t ws_bytes, void* stream);
+DC_API int dc_hip_nearest_neighbors_wide_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* d_fe,
+                                             size_t i_from, size_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+                                             uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
+                                             void* stream);
+/* the last wide sweep CALL in that workspace: 32x32 tile pairs evaluated, MFMA instructions issued, frame pairs sent
+ * to the exact path, summed over the launches of the call (a population call with more than 8 radii runs one launch
+ * per 8: its counts are that multiple of a one-launch call's); all 0 when the direct kernels answered or there was
+ * nothing to sweep.  The exact-pair count may differ by a few between runs of the same call (the column means are
+ * summed in scheduling order; the results are not affected).  Any pointer may be NULL.  Synchronises the stream. */
+DC_API int dc_hip_wide_info_dev(const void* d_ws, uint64_t* tiles, uint64_t* mfmas, uint64_t* exact_pairs,
+                                void* stream);
+
 /* free energies on ANOTHER array's scale: fe[i] = (float)-log((double)((float)pop[i] * (1.0f / (float)max_pop))),
  * with the device log + host-libm referee of dc_hip_free_energies_dev.  pop = 0 gives +inf, pop > max_pop a negative
  * value; max_pop = 0 is DC_ERR_INVALID_ARGUMENT.  Synchronises the stream. */
