@@ -46,6 +46,7 @@ SYMBOLS = (
     "dc_hip_nearest_cross_pruned_workspace_bytes", "dc_hip_nearest_neighbors_cross_pruned_dev",
     "dc_hip_nearest_cross_pruned_info_dev",
     "dc_hip_wide_workspace_bytes", "dc_hip_populations_wide_dev", "dc_hip_nearest_neighbors_wide_dev", "dc_hip_wide_info_dev",
+    "dc_hip_cross_wide_workspace_bytes", "dc_hip_populations_cross_wide_dev", "dc_hip_nearest_neighbors_cross_wide_dev",
 )
 
 
@@ -187,6 +188,12 @@ def _load():
     lib.dc_hip_nearest_neighbors_wide_dev.argtypes = [vp, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]
     lib.dc_hip_wide_info_dev.restype = i32
     lib.dc_hip_wide_info_dev.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+    lib.dc_hip_cross_wide_workspace_bytes.restype = sz
+    lib.dc_hip_cross_wide_workspace_bytes.argtypes = [sz, sz, sz, sz]
+    lib.dc_hip_populations_cross_wide_dev.restype = i32
+    lib.dc_hip_populations_cross_wide_dev.argtypes = [vp, sz, vp, sz, sz, C.POINTER(C.c_float), sz, sz, sz, vp, vp, sz, vp]
+    lib.dc_hip_nearest_neighbors_cross_wide_dev.restype = i32
+    lib.dc_hip_nearest_neighbors_cross_wide_dev.argtypes = [vp, sz, vp, sz, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]
     lib.dc_hip_free_energies_scaled_dev.restype = i32
     lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
     lib.dc_hip_populations_cross.restype = i32

@@ -9,6 +9,11 @@ size_t wide_workspace_bytes(size_t n_rows, size_t n_cols) {
   return wide_layout(n_rows, n_cols).total;
 }
 
+size_t wide_against_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols) {
+  if (!wide_mfma_supports(n_cols) || n_query == 0 || n_ref == 0) return 0;
+  return wide_layout_against(n_query, n_ref, n_cols).total;
+}
+
 namespace {
 
 WideArgs wide_args(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from, uint32_t i_to, void* d_ws) {
@@ -27,6 +32,29 @@ WideArgs wide_args(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint
   X.i_from = i_from;
   X.i_to = i_to;
   X.merge = (unsigned long long*)(p + L.off_merge);
+  return X;
+}
+
+// the reference side in the self sweep's fields, the queries in the fields of their own
+WideArgs wide_args_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                           uint32_t i_from, uint32_t i_to, void* d_ws) {
+  const WideLayout L = wide_layout_against(n_query, n_ref, n_cols);
+  char* p = (char*)d_ws;
+  WideArgs X{};
+  X.coords = d_ref;
+  X.n_rows = n_ref;
+  X.n_cols = n_cols;
+  X.NM = L.NM;
+  X.Tp = L.Tp;
+  X.img_a = (const uint4*)(p + L.off_img_a);
+  X.img_b = (const uint4*)(p + L.off_img_b);
+  X.norms = (const float*)(p + L.off_norms);
+  X.hdr = (uint32_t*)p;
+  X.i_from = i_from;
+  X.i_to = i_to;
+  X.merge = (unsigned long long*)(p + L.off_merge);
+  X.q_coords = d_query;
+  X.n_query = n_query;
   return X;
 }
 
@@ -72,6 +100,48 @@ int launch_nn_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols,
   sweep_timer_mark(1, false, s);
   hipLaunchKernelGGL(wide_nn_finish_kernel, dim3((i_to - i_from + 255) / 256), dim3(256), 0, s, (const uint32_t*)X.hdr,
                      (const unsigned long long*)X.merge, n_rows, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
+  return 0;
+}
+
+int wide_prepare_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                         void* d_ws, hipStream_t s) {
+  return wide_prepare_against_launches(d_query, n_query, d_ref, n_ref, n_cols, d_ws, s);
+}
+
+void launch_pop_wide_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                             uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row,
+                             void* d_ws, hipStream_t s) {
+  if (i_from >= i_to || n_rad <= 0 || n_ref == 0) return;
+  WideArgs X = wide_args_against(d_query, n_query, d_ref, n_ref, n_cols, i_from, i_to, d_ws);
+  X.rad2 = rad2;
+  X.n_rad = n_rad;
+  X.pops = d_pops_first_row;
+  const dim3 grid = wide_grid(i_from, i_to, X.Tp);
+  sweep_timer_mark(0, true, s);
+  if (n_rad == 1)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, kAgainst>), grid, dim3(256), 0, s, X);
+  else if (n_rad <= 4)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 4, kAgainst>), grid, dim3(256), 0, s, X);
+  else
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, kAgainst>), grid, dim3(256), 0, s, X);
+  sweep_timer_mark(0, false, s);
+}
+
+int launch_nn_wide_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                           const float* d_fe_query, const float* d_fe_ref, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx,
+                           float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t s) {
+  if (i_from >= i_to || n_ref == 0) return 0;
+  WideArgs X = wide_args_against(d_query, n_query, d_ref, n_ref, n_cols, i_from, i_to, d_ws);
+  X.q_fe = d_fe_query;
+  X.fe = d_fe_query ? d_fe_ref : nullptr;
+  if (hipMemsetAsync(X.merge, 0xFF, sizeof(unsigned long long) * 2 * (size_t)n_query, s) != hipSuccess) return -1;
+  const dim3 grid = wide_grid(i_from, i_to, X.Tp);
+  sweep_timer_mark(1, true, s);
+  hipLaunchKernelGGL((wide_sweep_kernel<kWideNn, 1, kAgainst>), grid, dim3(256), 0, s, X);
+  sweep_timer_mark(1, false, s);
+  // (nn only: no word of the hd half was merged, so the null hd outputs are never written)
+  hipLaunchKernelGGL(wide_nn_finish_kernel, dim3((i_to - i_from + 255) / 256), dim3(256), 0, s, (const uint32_t*)X.hdr,
+                     (const unsigned long long*)X.merge, n_query, i_from, i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
   return 0;
 }
 

@@ -27,4 +27,20 @@ int launch_nn_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols,
                         uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
                         void* d_ws, hipStream_t stream);
 
+// ---- the cross form: query rows against a reference (dc_hip_*_cross_wide_dev) -----------------------------
+// The same kernel in its kAgainst instances: one origin and one scale over both sets, the A form and the norms of the
+// reference, the B form and the merge words of the queries; every pair counts (no self term, no exclusion).
+// bytes of device scratch; 0 if the column count is not served or either set is empty; monotone in either row count
+size_t wide_against_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols);
+int wide_prepare_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                         void* d_ws, hipStream_t stream);
+// ADDED to d_pops_first_row ([n_rad][n_query], zeroed by the caller); stands down on flagged data
+void launch_pop_wide_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                             uint32_t i_from, uint32_t i_to, const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row,
+                             void* d_ws, hipStream_t stream);
+// outputs preset to "none" by the caller; d_fe_query == nullptr: nn only (d_fe_ref and the hd outputs are not touched)
+int launch_nn_wide_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                           const float* d_fe_query, const float* d_fe_ref, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx,
+                           float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t stream);
+
 }  // namespace dc

@@ -31,6 +31,14 @@
 // Exact path: dist2_canon_rt on the original coordinates, from a per-wave LDS queue that is drained when the next
 // push might not fit (never dropped) and at the end; results go out through integer atomics (counts: atomicAdd;
 // neighbours: atomicMin on (d2 bits << 32 | index), finished by wide_nn_finish_kernel).
+//
+// The cross form (SweepMode kAgainst, dc_hip_*_cross_wide_dev): queries Q against a reference R.  The sweep is an
+// every-pair sweep without symmetry, order or pruning, so a rectangle is the same chain over two images of different
+// length: the A form and the norms are built from R, the B form from Q, under ONE origin (the mean of Q and R together)
+// and ONE scale (pick_scale_nn of M, the largest |x'|^2 of either set).  The band holds unchanged:
+//   M bounds the norm of every row of BOTH operands, which is all guard_e0 / guard_kappa ask of the data;
+//   slot order and chain are those of the self sweep, so the accumulator of a pair is the same sum of the same terms.
+// What differs is bookkeeping: no diagonal, no +1 for the frame itself, no i != j exclusion, outputs strided by n_query.
 #pragma once
 #include "dc_mfma_kernels.hpp"
 #include "dc_mfma_wide.hpp"
@@ -85,22 +93,28 @@ inline uint32_t wide_grid_size(uint32_t q_blocks, uint32_t n_shares) {
 }
 
 struct WideLayout {
-  uint32_t T, Tp, NM;   // tiles, tiles padded to whole blocks, MFMAs per chain
+  uint32_t T, Tp, NM;   // reference tiles, tiles padded to whole blocks, MFMAs per chain
+  uint32_t Tq, Tqp;     // query tiles, padded (the self sweep: T, Tp)
   size_t off_img_a, off_img_b, off_norms, off_merge, total;
 };
-inline WideLayout wide_layout(size_t n_rows, size_t n_cols) {
+inline uint32_t wide_pad_tiles(uint32_t T) { return (T + kWideBlockTiles - 1) / kWideBlockTiles * kWideBlockTiles; }
+// n_query rows against n_ref rows: the A form and the norms of the reference, the B form and the merge words of the queries
+inline WideLayout wide_layout_against(size_t n_query, size_t n_ref, size_t n_cols) {
   WideLayout L;
-  L.T = (uint32_t)((n_rows + 31) / 32);
-  L.Tp = (L.T + kWideBlockTiles - 1) / kWideBlockTiles * kWideBlockTiles;
+  L.T = (uint32_t)((n_ref + 31) / 32);
+  L.Tp = wide_pad_tiles(L.T);
+  L.Tq = (uint32_t)((n_query + 31) / 32);
+  L.Tqp = wide_pad_tiles(L.Tq);
   L.NM = (uint32_t)nm_for((int)n_cols);
-  const size_t img_bytes = (size_t)16 * 64 * (size_t)L.Tp * L.NM;
+  const size_t tile_bytes = (size_t)16 * 64 * L.NM;
   L.off_img_a = kWideOffImages;
-  L.off_img_b = align256(L.off_img_a + img_bytes);
-  L.off_norms = align256(L.off_img_b + img_bytes);
+  L.off_img_b = align256(L.off_img_a + tile_bytes * L.Tp);
+  L.off_norms = align256(L.off_img_b + tile_bytes * L.Tqp);
   L.off_merge = align256(L.off_norms + sizeof(float) * 32 * (size_t)L.Tp);
-  L.total = align256(L.off_merge + sizeof(unsigned long long) * 2 * n_rows);
+  L.total = align256(L.off_merge + sizeof(unsigned long long) * 2 * n_query);
   return L;
 }
+inline WideLayout wide_layout(size_t n_rows, size_t n_cols) { return wide_layout_against(n_rows, n_rows, n_cols); }
 
 // ---- the band of the wide sweeps, host and device (scaled units) ------------------------------------------------------
 struct WideBand {
@@ -161,7 +175,7 @@ __global__ void wide_colsum_kernel(const float* __restrict__ coords, uint32_t n_
   if (threadIdx.x < D) atomicAdd(&sums[threadIdx.x], part[threadIdx.x]);
 }
 
-__global__ void wide_mean_kernel(const double* __restrict__ sums, uint32_t n_rows, uint32_t D, float* __restrict__ means) {
+__global__ void wide_mean_kernel(const double* __restrict__ sums, size_t n_rows, uint32_t D, float* __restrict__ means) {
   const uint32_t k = threadIdx.x;
   if (k >= D) return;
   float muf = (float)(sums[k] / (double)n_rows);
@@ -218,6 +232,8 @@ __global__ void wide_scale_kernel(uint32_t* __restrict__ hdr) {
 // one lane of one MFMA of one tile, reference side (A form) and query side (B form: the pieces of -2x'', and in the
 // two constant slots the pieces of c_q / 2^a = |x''|^2 / 2^a, which the resident-operand kernels patch in when they
 // load a query).  Rows beyond n_rows and the tiles that pad the last block: zero fragments, norm +inf.
+// A cross sweep builds the A form and the norms from the reference and the B form from the queries: a form whose
+// pointer is null is not written (norms goes with img_a).
 __global__ void wide_image_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D, uint32_t NM, uint32_t Tp,
                                   const float* __restrict__ means, const uint32_t* __restrict__ hdr,
                                   uint4* __restrict__ img_a, uint4* __restrict__ img_b, float* __restrict__ norms) {
@@ -267,9 +283,9 @@ __global__ void wide_image_kernel(const float* __restrict__ coords, uint32_t n_r
     }
   }
   const size_t o = ((size_t)t * NM + m) * 64 + lane;
-  img_a[o] = make_uint4(wa[0], wa[1], wa[2], wa[3]);
-  img_b[o] = make_uint4(wb[0], wb[1], wb[2], wb[3]);
-  if (m == 0 && h == 0) norms[row] = live ? (float)nrm : INFINITY;
+  if (img_a) img_a[o] = make_uint4(wa[0], wa[1], wa[2], wa[3]);
+  if (img_b) img_b[o] = make_uint4(wb[0], wb[1], wb[2], wb[3]);
+  if (img_a && m == 0 && h == 0) norms[row] = live ? (float)nrm : INFINITY;
 }
 
 inline size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
@@ -287,7 +303,7 @@ inline int wide_prepare_launches(const float* d_coords, uint32_t n_rows, uint32_
   const size_t elems = (size_t)n_rows * n_cols;
   const uint32_t sum_blocks = (uint32_t)min_sz(1024, (elems + 255) / 256);
   hipLaunchKernelGGL(wide_colsum_kernel, dim3(sum_blocks), dim3(256), 0, s, d_coords, n_rows, n_cols, sums);
-  hipLaunchKernelGGL(wide_mean_kernel, dim3(1), dim3(256), 0, s, (const double*)sums, n_rows, n_cols, means);
+  hipLaunchKernelGGL(wide_mean_kernel, dim3(1), dim3(256), 0, s, (const double*)sums, (size_t)n_rows, n_cols, means);
   const uint32_t stat_blocks = (uint32_t)min_sz(4096, ((size_t)n_rows + 3) / 4);
   hipLaunchKernelGGL(wide_rowstats_kernel, dim3(stat_blocks), dim3(256), 0, s, d_coords, n_rows, n_cols, (const float*)means, hdr);
   if (d_fe)
@@ -297,6 +313,41 @@ inline int wide_prepare_launches(const float* d_coords, uint32_t n_rows, uint32_
   hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags + 255) / 256)), dim3(256), 0, s, d_coords, n_rows, n_cols, L.NM,
                      L.Tp, (const float*)means, (const uint32_t*)hdr, (uint4*)(p + L.off_img_a), (uint4*)(p + L.off_img_b),
                      (float*)(p + L.off_norms));
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ... of a cross sweep: ONE origin and ONE scale over the queries and the reference together (column sums over both
+// sets, the mean over n_query + n_ref rows, header word 0 = the largest |x'|^2 of either set), then the A form and the
+// norms of the reference and the B form of the queries.  d_query == d_ref is an ordinary pair of sets.
+inline int wide_prepare_against_launches(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref,
+                                         uint32_t n_cols, void* d_ws, hipStream_t s) {
+  const WideLayout L = wide_layout_against(n_query, n_ref, n_cols);
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  double* sums = (double*)(p + kWideOffSums);
+  float* means = (float*)(p + kWideOffMeans);
+  if (hipMemsetAsync(d_ws, 0, kWideOffImages, s) != hipSuccess) return -1;
+  struct Side {
+    const float* x;
+    uint32_t n;
+  } const sides[2] = {{d_query, n_query}, {d_ref, n_ref}};
+  for (const Side& side : sides) {
+    const size_t elems = (size_t)side.n * n_cols;
+    hipLaunchKernelGGL(wide_colsum_kernel, dim3((uint32_t)min_sz(1024, (elems + 255) / 256)), dim3(256), 0, s, side.x, side.n,
+                       n_cols, sums);
+  }
+  hipLaunchKernelGGL(wide_mean_kernel, dim3(1), dim3(256), 0, s, (const double*)sums, (size_t)n_query + n_ref, n_cols, means);
+  for (const Side& side : sides)
+    hipLaunchKernelGGL(wide_rowstats_kernel, dim3((uint32_t)min_sz(4096, ((size_t)side.n + 3) / 4)), dim3(256), 0, s, side.x,
+                       side.n, n_cols, (const float*)means, hdr);
+  hipLaunchKernelGGL(wide_scale_kernel, dim3(1), dim3(1), 0, s, hdr);
+  const size_t frags_r = (size_t)L.Tp * L.NM * 64, frags_q = (size_t)L.Tqp * L.NM * 64;
+  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags_r + 255) / 256)), dim3(256), 0, s, d_ref, n_ref, n_cols, L.NM,
+                     L.Tp, (const float*)means, (const uint32_t*)hdr, (uint4*)(p + L.off_img_a), (uint4*)nullptr,
+                     (float*)(p + L.off_norms));
+  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags_q + 255) / 256)), dim3(256), 0, s, d_query, n_query, n_cols, L.NM,
+                     L.Tqp, (const float*)means, (const uint32_t*)hdr, (uint4*)nullptr, (uint4*)(p + L.off_img_b),
+                     (float*)nullptr);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -319,13 +370,25 @@ struct WideArgs {
   const float* fe;             // neighbours
   unsigned long long* merge;   // [2][n_rows] (d2 bits << 32 | index), preset to ~0
   float* dump;                 // kWideDump (the model test): acc of (reference row i, query row j) at [i * 32 Tp + j]
+  // the kAgainst instances only (a zero-initialised struct is the self sweep): there coords / n_rows / Tp / img_a /
+  // norms / fe are the REFERENCE's, img_b is built from the queries, i_from / i_to are query rows, and pops and merge
+  // are strided by n_query
+  const float* q_coords;       // [n_query][n_cols]
+  uint32_t n_query;
+  const float* q_fe;           // nullptr: nn only (fe is not read, no candidate of the hd half is raised)
 };
 
 // the deferred pairs of a wave, evaluated in the canonical order from the original coordinates, a pair per lane
 template <int MODE>
 __device__ __attribute__((noinline)) void wide_drain(const uint2* queue, uint32_t fill, const float* coords, uint32_t n_rows,
-                                                     uint32_t n_cols, uint32_t qrow0, Rad2 rad2, uint32_t* pops,
-                                                     unsigned long long* merge) {
+                                                     uint32_t n_cols, uint32_t qrow0, Rad2 rad2, void* out,
+                                                     const float* q_coords) {
+  // (n_rows: the QUERY rows, the stride of the output; i indexes coords, the reference side; q_coords: the query rows,
+  //  coords itself in the self sweep.  out: the populations or the merge words, by MODE.  The order of the parameters
+  //  matters to the code: with a second pointer in FRONT of rad2 the compiler passes rad2 through scratch, a store of
+  //  eight dwords at each of the 65 call sites of a population instance -- check .private_segment_fixed_size after a change)
+  uint32_t* const pops = static_cast<uint32_t*>(out);
+  unsigned long long* const merge = static_cast<unsigned long long*>(out);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the queue writes of all lanes before their reads)
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -333,7 +396,7 @@ __device__ __attribute__((noinline)) void wide_drain(const uint2* queue, uint32_
   for (uint32_t e = lane; e < fill; e += 64u) {
     const uint2 en = queue[e];
     const uint32_t i = en.x, j = qrow0 + (en.y & 127u), flags = en.y >> 8;
-    const float d2 = dist2_canon_rt(coords + (size_t)j * n_cols, 1, coords + (size_t)i * n_cols, 1, (int)n_cols);
+    const float d2 = dist2_canon_rt(q_coords + (size_t)j * n_cols, 1, coords + (size_t)i * n_cols, 1, (int)n_cols);
     if constexpr (MODE == kWidePop) {
 #pragma unroll
       for (int k = 0; k < kMaxRadiiPerLaunch; ++k)
@@ -347,7 +410,9 @@ __device__ __attribute__((noinline)) void wide_drain(const uint2* queue, uint32_
   __builtin_amdgcn_wave_barrier();
 }
 
-template <int MODE, int NR>
+// SM: kSelf -- queries and reference are the rows of one array: the diagonal pair leaves the sweep, populations get the
+// frame's own 1, a frame is not its own neighbour; kAgainst -- X.q_coords against X.coords: every pair counts.
+template <int MODE, int NR, SweepMode SM = kSelf>
 __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   if (X.hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
   __shared__ u32x4 stage[2 * kWideChunkVec];
@@ -357,6 +422,10 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, h = lane >> 5, c = lane & 31u;
   const uint32_t wq = wave & 1u, wr = wave >> 1;
   const uint32_t NM = X.NM, NC = (NM + kWideKC - 1) / kWideKC, D = X.n_cols;
+  const float* const q_coords = (SM == kAgainst) ? X.q_coords : X.coords;
+  const float* const q_fe = (SM == kAgainst) ? X.q_fe : X.fe;
+  const uint32_t n_q = (SM == kAgainst) ? X.n_query : X.n_rows;
+  const bool has_fe = SM == kSelf || q_fe != nullptr;
   const uint32_t RB = X.Tp / kWideBlockTiles, Sy = wide_shares(RB);
   const WideUnit unit = wide_unit(blockIdx.x, Sy);
   const uint32_t qb = X.i_from / kWideBlockRows + unit.q_block, y = unit.share;
@@ -399,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       m_nn[qt] = m_hd[qt] = INFINITY;
-      feq[qt] = live[qt] ? X.fe[jq[qt]] : -INFINITY;   // (a dead lane: no reference lies lower)
+      feq[qt] = (live[qt] && has_fe) ? q_fe[jq[qt]] : -INFINITY;   // (a dead lane, nn only: no reference lies lower)
     }
   }
 
@@ -408,7 +477,8 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
     const unsigned long long mk = __builtin_amdgcn_ballot_w64(ok);
     if (mk == 0) return;
     if (fill + 64u > kWideQueue) {
-      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, X.n_rows, D, qb * kWideBlockRows, X.rad2, X.pops, X.merge);
+      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.rad2,
+                                                       MODE == kWideNn ? (void*)X.merge : (void*)X.pops, q_coords);
       n_exact += fill;
       fill = 0;
     }
@@ -460,7 +530,7 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
         //  the barrier that closed its last chunk)
         if (tid < kWideBlockRows) {
           const uint32_t row = rb * kWideBlockRows + tid;
-          fe_s[tid] = row < X.n_rows ? X.fe[row] : INFINITY;
+          fe_s[tid] = (row < X.n_rows && has_fe) ? X.fe[row] : INFINITY;
         }
       }
     }
@@ -487,7 +557,7 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
       for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt)
-          if (MODE != kWideDump && rb * kWideBlockTiles + 2 * wr + rt == qb * kWideBlockTiles + 2 * wq + qt) {
+          if (MODE != kWideDump && SM == kSelf && rb * kWideBlockTiles + 2 * wr + rt == qb * kWideBlockTiles + 2 * wq + qt) {
             // the diagonal tile: the self pair leaves the sweep (populations add their 1 at the end, neighbours exclude it)
 #pragma unroll
             for (int g = 0; g < 16; ++g)
@@ -561,7 +631,7 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
               const uint32_t fl = ((v <= cut_nn) ? 1u : 0u) | (((fr < feq[qt]) & (v <= cut_hd)) ? 2u : 0u);
               if ((__builtin_amdgcn_ballot_w64(fl != 0) & livemask[qt]) != 0) {
                 const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
-                push(fl != 0 && live[qt] && i < X.n_rows && i != jq[qt], i, ((2 * wq + qt) * 32 + c) | (fl << 8));
+                push(fl != 0 && live[qt] && i < X.n_rows && (SM == kAgainst || i != jq[qt]), i, ((2 * wq + qt) * 32 + c) | (fl << 8));
               }
             }
         }
@@ -573,7 +643,8 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
 
   if constexpr (MODE != kWideDump) {
     if (fill != 0) {
-      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, X.n_rows, D, qb * kWideBlockRows, X.rad2, X.pops, X.merge);
+      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.rad2,
+                                                       MODE == kWideNn ? (void*)X.merge : (void*)X.pops, q_coords);
       n_exact += fill;
     }
   }
@@ -584,8 +655,8 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
       for (int k = 0; k < NR; ++k) {
         const uint32_t total = cnt[qt][k] + (uint32_t)__shfl_xor((int)cnt[qt][k], 32, 64);
         // the frame itself: the 1 the reference starts every population at, added once per row
-        const uint32_t add = total + ((y == 0 && wr == 0) ? 1u : 0u);
-        if (h == 0 && live[qt] && k < X.n_rad && add != 0) atomicAdd(&X.pops[(size_t)k * X.n_rows + jq[qt]], add);
+        const uint32_t add = total + ((SM == kSelf && y == 0 && wr == 0) ? 1u : 0u);
+        if (h == 0 && live[qt] && k < X.n_rad && add != 0) atomicAdd(&X.pops[(size_t)k * n_q + jq[qt]], add);
       }
   }
   if (lane == 0 && n_exact != 0) atomicAdd(reinterpret_cast<unsigned long long*>(X.hdr + kWideHdrExact), n_exact);

@@ -52,6 +52,10 @@ def _wide_bytes(n_rows, n_cols, n_radii=1):
     return capi.lib.dc_hip_wide_workspace_bytes(n_rows, n_cols, n_radii)
 
 
+def _wide_against_bytes(n_q, n_ref, n_cols, n_radii=1):
+    return capi.lib.dc_hip_cross_wide_workspace_bytes(n_q, n_ref, n_cols, n_radii)
+
+
 class Workspace:
     """Device scratch of one kind of sweep (MFMA operand images); grown on demand, reused across calls.
     ``size`` is the library's byte count for a call's shape: get(*shape) asks it and returns (pointer, bytes)."""
@@ -75,6 +79,7 @@ _cross_workspaces = {}  # sweeps against a reference, per device
 _cross_pruned_workspaces = {}  # ... of variant="cross_pruned" (the larger layout of its two orders), per device
 _nearest_pruned_workspaces = {}  # ... of nearest_reference(pruned=True), per device
 _wide_workspaces = {}   # the matrix-core sweeps for rows of 65..256 columns, per device
+_wide_against_workspaces = {}  # ... of their cross form (calculate_populations_against_wide, nearest_reference_wide), per device
 
 
 def _cached(cache, device, size):
@@ -102,6 +107,10 @@ def _nearest_pruned_workspace(device):
 
 def _wide_workspace(device):
     return _cached(_wide_workspaces, device, _wide_bytes)
+
+
+def _wide_against_workspace(device):
+    return _cached(_wide_against_workspaces, device, _wide_against_bytes)
 
 
 def _variant(variant, stats_valid):
@@ -408,6 +417,110 @@ def assign_frames(queries, reference, radius, ref_states, variant="auto", pruned
         torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
     nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference(queries, reference, fe_q, fe_ref, variant=variant,
                                                      pruned=pruned_neighbours)
+    none = n_ref + 1
+    states = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    if n_ref:
+        pick = torch.where(hd_idx != none, hd_idx, nn_idx)
+        ok = pick != none
+        states[ok] = states_r[pick[ok].long()]
+    return {"states": states, "pops_ref": pops_ref, "max_pop": max_pop, "fe_ref": fe_ref, "pops": pops_q, "fe": fe_q,
+            "nn_idx": nn_idx, "nn_d2": nn_d2, "hd_idx": hd_idx, "hd_d2": hd_d2}
+
+
+# ---- the cross sweeps for rows of 65..256 columns on the matrix cores (include/dc_density.h, the wide sweeps' cross form) ----
+def _wide_against_ws(device, *shape):
+    """(pointer, bytes) for a cross-wide call.  A call with an empty side needs no workspace; it gets the cached buffer, if
+    there is one, so that wide_against_info reports that nothing was swept rather than the call before."""
+    cache = _wide_against_workspace(device)
+    ws, ws_bytes = cache.get(*shape)
+    if ws_bytes == 0 and cache.buf is not None:
+        return _dev(cache.buf), int(cache.buf.numel())
+    return ws, ws_bytes
+
+
+def _check_pair_wide(queries, reference):
+    """_check_pair, the column count (refused here as the library refuses it: 65..256) first"""
+    for t in (queries, reference):
+        if isinstance(t, torch.Tensor) and t.dim() == 2 and not 65 <= t.shape[1] <= 256:
+            raise ValueError(f"n_cols={t.shape[1]}: the wide matrix-core sweeps take 65..256 columns")
+    return _check_pair(queries, reference)
+
+
+def calculate_populations_against_wide(queries, reference, radii, i_from=0, i_to=None, out=None):
+    """calculate_populations_against(variant="direct") for rows of 65..256 columns on the matrix cores
+    (dc_hip_populations_cross_wide_dev): the same populations bit for bit -- no self term -- with one matrix-core chain
+    per tile pair for all radii (up to 8 per launch), radii in any order, in a cached workspace of its own
+    (wide_against_info reads its counters).  Other column counts raise."""
+    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
+    i_to = n_q if i_to is None else i_to
+    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    if out is None:
+        out = torch.empty((rad.size, n_q), dtype=torch.int32, device=queries.device)
+    assert out.shape == (rad.size, n_q) and out.dtype == torch.int32 and out.is_contiguous()
+    with torch.cuda.device(queries.device):
+        ws, ws_bytes = _wide_against_ws(queries.device, n_q, n_ref, n_cols, rad.size)
+        rc = capi.lib.dc_hip_populations_cross_wide_dev(
+            _dev(queries), n_q, _dev(reference), n_ref, n_cols, rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size,
+            i_from, i_to, _dev(out), ws, ws_bytes, _stream_ptr())
+    capi.check(rc, "dc_hip_populations_cross_wide_dev")
+    return out
+
+
+def nearest_reference_wide(queries, reference, fe_query=None, fe_ref=None, i_from=0, i_to=None):
+    """nearest_reference(variant="direct") for rows of 65..256 columns on the matrix cores
+    (dc_hip_nearest_neighbors_cross_wide_dev).  -> (nn_idx int32, nn_d2 float32, hd_idx, hd_d2), each [n_q]; "none" is
+    (n_ref + 1, FLT_MAX).  Without free energies hd_idx / hd_d2 are None.  Other column counts raise."""
+    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
+    i_to = n_q if i_to is None else i_to
+    with_fe = fe_query is not None
+    if with_fe:
+        assert fe_ref is not None
+        for f, n in ((fe_query, n_q), (fe_ref, n_ref)):
+            assert f.is_cuda and f.dtype == torch.float32 and f.shape == (n,) and f.is_contiguous()
+    dev = queries.device
+    nn_idx = torch.empty(n_q, dtype=torch.int32, device=dev)
+    nn_d2 = torch.empty(n_q, dtype=torch.float32, device=dev)
+    hd_idx = torch.empty(n_q, dtype=torch.int32, device=dev) if with_fe else None
+    hd_d2 = torch.empty(n_q, dtype=torch.float32, device=dev) if with_fe else None
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _wide_against_ws(dev, n_q, n_ref, n_cols, 1)
+        rc = capi.lib.dc_hip_nearest_neighbors_cross_wide_dev(
+            _dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
+            _dev(fe_ref) if with_fe else None, i_from, i_to, _dev(nn_idx), _dev(nn_d2),
+            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None, ws, ws_bytes, _stream_ptr())
+    capi.check(rc, "dc_hip_nearest_neighbors_cross_wide_dev")
+    return nn_idx, nn_d2, hd_idx, hd_d2
+
+
+def wide_against_info(device):
+    """(tiles, mfmas, exact_pairs) of the last calculate_populations_against_wide / nearest_reference_wide on this
+    device, as wide_sweep_info gives them for the self sweeps (dc_hip_wide_info_dev on the cross sweeps' own workspace);
+    (0, 0, 0) when the direct kernels answered (flagged data), nothing was swept, or no such sweep has run."""
+    ws = _wide_against_workspace(device)
+    if ws.buf is None:
+        return 0, 0, 0
+    t, m, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
+                   "dc_hip_wide_info_dev")
+    return int(t.value), int(m.value), int(e.value)
+
+
+def assign_frames_wide(queries, reference, radius, ref_states):
+    """assign_frames for rows of 65..256 columns, every sweep on the matrix cores: calculate_populations_wide on the
+    reference, calculate_populations_against_wide and nearest_reference_wide for the queries; the same four steps, the
+    same state rule, the same dict, the same values."""
+    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
+    dev = queries.device
+    states_r = torch.as_tensor(np.ascontiguousarray(ref_states, dtype=np.int32), device=dev)
+    assert states_r.shape == (n_ref,)
+    pops_ref = calculate_populations_wide(reference, [radius])[0].contiguous()
+    max_pop = int(pops_ref.max().item()) if n_ref else 0
+    fe_ref = calculate_free_energies(pops_ref)
+    pops_q = calculate_populations_against_wide(queries, reference, [radius])[0].contiguous()
+    fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
+        torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
+    nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference_wide(queries, reference, fe_q, fe_ref)
     none = n_ref + 1
     states = torch.zeros(n_q, dtype=torch.int32, device=dev)
     if n_ref:

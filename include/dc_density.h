@@ -413,7 +413,37 @@ DC_API int dc_hip_nearest_neighbors_wide_dev(const float* d_coords, size_t n_row
                                              size_t i_from, size_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
                                              uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
                                              void* stream);
-/* the last wide sweep CALL in that workspace: 32x32 tile pairs evaluated, MFMA instructions issued, frame pairs sent
+/* ---- ... and their cross form: query frames against a reference trajectory at 65..256 columns ------------------------
+ * The wide sweep over a rectangle Q x R: the contract of the "cross sweeps" block above -- populations without a self
+ * term, nn[q] the lexicographic minimum of (d2, j) over ALL j with no exclusion, nn_hd[q] the same over
+ * { j : fe_ref[j] < fe_query[q] } compared as IEEE, d_fe_query == NULL: nn only (d_fe_ref, d_hd_idx, d_hd_d2 may be
+ * NULL and are not written), "none" = (n_ref + 1, FLT_MAX), 0 / "none" outside [i_from, i_to), outputs fully
+ * overwritten, d_query == d_ref allowed, radii in any order -- with results bit-identical to dc_hip_*_cross_dev under
+ * DC_VARIANT_DIRECT.  One origin and one scale serve Q and R together; one matrix-core chain per tile pair serves up
+ * to 8 radii, more radii run one launch per 8.  Entry points of their own: no dc_variant value selects them, and
+ * dc_hip_*_cross_dev keep sending rows wider than 64 columns to the direct kernels.
+ * Flagged data -- a non-finite or overflow-prone row in Q or in R -- is answered by the direct kernels behind the
+ * device-side gate, without a host synchronisation.  A NaN in fe_query or fe_ref does NOT flag the data: the sweep has
+ * no order by free energy, its test is the same IEEE comparison as the direct kernel's (a NaN is never lower and has no
+ * lower neighbour), so the matrix-core kernel answers such a call too.
+ * n_cols outside 65..256: DC_ERR_INVALID_ARGUMENT; a workspace smaller than dc_hip_cross_wide_workspace_bytes:
+ * DC_ERR_WORKSPACE; n_ref + 1 and n_query must fit uint32: DC_ERR_TOO_LARGE; n_query == 0, n_ref == 0 or an empty
+ * range: DC_OK with zeros / "none".
+ * dc_hip_cross_wide_workspace_bytes: 0 outside 65..256 columns and for an empty side (such a call takes d_ws == NULL; a
+ * workspace that is given anyway reports that nothing was swept), monotone in either row count.  The workspace keeps the
+ * info head of the wide self sweeps: dc_hip_wide_info_dev reads the counters of the last cross-wide call in it. */
+DC_API size_t dc_hip_cross_wide_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_populations_cross_wide_dev(const float* d_query, size_t n_query, const float* d_ref, size_t n_ref,
+                                             size_t n_cols, const float* radii, size_t n_radii, size_t i_from,
+                                             size_t i_to, uint32_t* d_pops, void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_nearest_neighbors_cross_wide_dev(const float* d_query, size_t n_query, const float* d_ref,
+                                                   size_t n_ref, size_t n_cols, const float* d_fe_query,
+                                                   const float* d_fe_ref, size_t i_from, size_t i_to,
+                                                   uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                                   float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
+
+/* the last wide sweep CALL in that workspace -- a self sweep (dc_hip_*_wide_dev) or a cross sweep
+ * (dc_hip_*_cross_wide_dev), the counters sit at the same place of either workspace: 32x32 tile pairs evaluated, MFMA instructions issued, frame pairs sent
  * to the exact path, summed over the launches of the call (a population call with more than 8 radii runs one launch
  * per 8: its counts are that multiple of a one-launch call's); all 0 when the direct kernels answered or there was
  * nothing to sweep.  The exact-pair count may differ by a few between runs of the same call (the column means are
