@@ -10,7 +10,13 @@
 //   test_wide_model --band D M    host only (no device is touched): the scale and band the sweeps use for D columns
 //                                 and max |x - mean|^2 = M, as "band D S e0 kappa" (e0 in scaled units) -- what the
 //                                 case generators of tests/wideref.py measure their data with.
-// Built by clustering_amd/csrc/Makefile, run by tests/test_gpu_wide_model.py and tests/test_wide_mfma_cases.py.
+//   test_wide_model --shares RB   host only: "shares RB S", S = wide_shares(RB), the reference shares of a sweep over RB
+//                                 reference blocks of 128 rows.
+//   test_wide_model --units S QB  host only: "grid G", G = wide_grid_size(QB, S), then one line "id q_block share" per
+//                                 workgroup id 0 .. G - 1 as wide_unit(id, S) decodes it (tests/test_wide_big_cases.py
+//                                 checks that every query block meets every share exactly once).
+// Built by clustering_amd/csrc/Makefile, run by tests/test_gpu_wide_model.py, tests/test_wide_mfma_cases.py and
+// tests/test_wide_big_cases.py.
 #include "../../clustering_amd/csrc/dc_mfma_wide_kernels.hpp"
 
 #include <hip/hip_runtime.h>
@@ -129,6 +135,25 @@ int main(int argc, char** argv) {
     const Scale sc = make_scale(se);
     const WideBand b = wide_band(M * sc.s2, D, sc);
     printf("band %d %.9g %.9g %.9g\n", D, (double)sc.s2, (double)b.e0, (double)b.kappa);
+    return 0;
+  }
+  if (argc == 3 && strcmp(argv[1], "--shares") == 0) {
+    const uint32_t rb = (uint32_t)strtoul(argv[2], nullptr, 10);
+    printf("shares %u %u\n", rb, wide_shares(rb));
+    return 0;
+  }
+  if (argc == 4 && strcmp(argv[1], "--units") == 0) {
+    const uint32_t n_shares = (uint32_t)strtoul(argv[2], nullptr, 10), q_blocks = (uint32_t)strtoul(argv[3], nullptr, 10);
+    if (n_shares == 0 || n_shares > kWideShares || (n_shares & (n_shares - 1u)) != 0) {
+      fprintf(stderr, "--units: the shares are a power of two up to %u\n", kWideShares);
+      return 2;
+    }
+    const uint32_t grid = wide_grid_size(q_blocks, n_shares);
+    printf("grid %u\n", grid);
+    for (uint32_t id = 0; id < grid; ++id) {
+      const WideUnit u = wide_unit(id, n_shares);
+      printf("%u %u %u\n", id, u.q_block, u.share);
+    }
     return 0;
   }
   int bad = 0;
