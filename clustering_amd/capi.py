@@ -47,6 +47,7 @@ SYMBOLS = (
     "dc_hip_nearest_cross_pruned_info_dev",
     "dc_hip_wide_workspace_bytes", "dc_hip_populations_wide_dev", "dc_hip_nearest_neighbors_wide_dev", "dc_hip_wide_info_dev",
     "dc_hip_cross_wide_workspace_bytes", "dc_hip_populations_cross_wide_dev", "dc_hip_nearest_neighbors_cross_wide_dev",
+    "dc_hip_radius_pairs_wide_dev", "dc_hip_radius_min_edge_wide_dev", "dc_hip_radius_forest_wide",
 )
 
 
@@ -194,6 +195,12 @@ def _load():
     lib.dc_hip_populations_cross_wide_dev.argtypes = [vp, sz, vp, sz, sz, C.POINTER(C.c_float), sz, sz, sz, vp, vp, sz, vp]
     lib.dc_hip_nearest_neighbors_cross_wide_dev.restype = i32
     lib.dc_hip_nearest_neighbors_cross_wide_dev.argtypes = [vp, sz, vp, sz, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]
+    lib.dc_hip_radius_pairs_wide_dev.restype = i32
+    lib.dc_hip_radius_pairs_wide_dev.argtypes = [vp, sz, sz, C.c_float, vp, vp, sz, vp, vp, sz, vp]
+    lib.dc_hip_radius_min_edge_wide_dev.restype = i32
+    lib.dc_hip_radius_min_edge_wide_dev.argtypes = [vp, sz, sz, C.c_float, vp, vp, sz, sz, vp, vp, vp, sz, vp]
+    lib.dc_hip_radius_forest_wide.restype = i32
+    lib.dc_hip_radius_forest_wide.argtypes = [vp, sz, sz, C.c_float, vp, i32, vp, C.POINTER(sz), C.POINTER(C.c_uint32)]
     lib.dc_hip_free_energies_scaled_dev.restype = i32
     lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
     lib.dc_hip_populations_cross.restype = i32

@@ -103,6 +103,40 @@ int launch_nn_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols,
   return 0;
 }
 
+// ---- the radius graph (dc_hip_radius_*_wide_dev): the one-radius self sweep with a sink --------------------
+void launch_pairs_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops, uint2* d_pairs,
+                            unsigned long long capacity, unsigned long long* d_count, void* d_ws, hipStream_t s) {
+  if (n_rows == 0) return;
+  WideArgs X = wide_args(d_coords, n_rows, n_cols, 0, n_rows, d_ws);
+  for (float& v : X.rad2.v) v = -1.0f;
+  X.rad2.v[0] = r2;
+  X.n_rad = 1;
+  X.pops = d_pops;
+  X.pairs = d_pairs;
+  X.capacity = d_pairs ? capacity : 0ull;   // (counting only: every slot is beyond the list)
+  X.count = d_count;
+  sweep_timer_mark(0, true, s);
+  hipLaunchKernelGGL((wide_sweep_kernel<kWidePairs, 1>), wide_grid(0, n_rows, X.Tp), dim3(256), 0, s, X);
+  sweep_timer_mark(0, false, s);
+}
+
+void launch_min_edge_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, const uint32_t* d_comp,
+                               const uint32_t* d_rank, uint32_t i_from, uint32_t i_to, unsigned long long* d_best,
+                               uint32_t* d_pops, void* d_ws, hipStream_t s) {
+  if (i_from >= i_to) return;
+  WideArgs X = wide_args(d_coords, n_rows, n_cols, i_from, i_to, d_ws);
+  for (float& v : X.rad2.v) v = -1.0f;
+  X.rad2.v[0] = r2;
+  X.n_rad = 1;
+  X.pops = d_pops;
+  X.comp = d_comp;
+  X.rank = d_rank;
+  X.best = d_best;
+  sweep_timer_mark(0, true, s);
+  hipLaunchKernelGGL((wide_sweep_kernel<kWideMinEdge, 1>), wide_grid(i_from, i_to, X.Tp), dim3(256), 0, s, X);
+  sweep_timer_mark(0, false, s);
+}
+
 int wide_prepare_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
                          void* d_ws, hipStream_t s) {
   return wide_prepare_against_launches(d_query, n_query, d_ref, n_ref, n_cols, d_ws, s);

@@ -1,7 +1,7 @@
 // dc_mfma_wide.hpp -- the matrix-core sweeps for rows of 65..256 columns (dc_mfma_wide.hip): host-side entry points.
 // An every-pair self sweep whose K axis streams through LDS in chunks while the accumulator tiles stay in registers
-// (kernels and the reasoning: dc_mfma_wide_kernels.hpp).  Entry points of their own in the C ABI
-// (dc_hip_*_wide_dev); no variant value selects them.
+// (kernels and the reasoning: dc_mfma_wide_kernels.hpp; the radius graph on the same sweep: 4.20).  Entry
+// points of their own in the C ABI (dc_hip_*_wide_dev); no variant value selects them.
 #pragma once
 #include "dc_common.hpp"
 
@@ -26,6 +26,17 @@ void launch_pop_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_col
 int launch_nn_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, uint32_t i_from,
                         uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
                         void* d_ws, hipStream_t stream);
+
+// ---- the radius graph at one threshold r2 = the squared distance itself (dc_hip_radius_*_wide_dev) ------
+// Both run behind wide_prepare in the same workspace, ADD the populations to d_pops (zeroed by the caller) and stand down
+// on flagged data (the gated launch_pairs_direct / launch_min_edge_direct answer).
+// every unordered pair once into d_pairs[0 .. capacity) (nullptr: counting only), the number found ADDED to d_count
+void launch_pairs_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops, uint2* d_pairs,
+                            unsigned long long capacity, unsigned long long* d_count, void* d_ws, hipStream_t stream);
+// what the queries [i_from, i_to) see of one Boruvka round: atomicMin into d_best (preset to ~0 by the caller)
+void launch_min_edge_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, float r2, const uint32_t* d_comp,
+                               const uint32_t* d_rank, uint32_t i_from, uint32_t i_to, unsigned long long* d_best,
+                               uint32_t* d_pops, void* d_ws, hipStream_t stream);
 
 // ---- the cross form: query rows against a reference (dc_hip_*_cross_wide_dev) -----------------------------
 // The same kernel in its kAgainst instances: one origin and one scale over both sets, the A form and the norms of the

@@ -39,6 +39,11 @@
 //   M bounds the norm of every row of BOTH operands, which is all guard_e0 / guard_kappa ask of the data;
 //   slot order and chain are those of the self sweep, so the accumulator of a pair is the same sum of the same terms.
 // What differs is bookkeeping: no diagonal, no +1 for the frame itself, no i != j exclusion, outputs strided by n_query.
+//
+// The radius graph (WideMode kWidePairs / kWideMinEdge, dc_hip_radius_*_wide_dev): the one-radius population sweep with a
+// sink on its two decision points -- the accumulator window (acc < lo: decided inside) and the exact drain (d2 < r2).
+// Preparation, images, scale, band, window, shares, unit map and counting are the population sweep's; see "the sinks
+// of the radius graph" below for the i < j rule of the list and the smallest-rank rule of a Boruvka round.
 #pragma once
 #include "dc_mfma_kernels.hpp"
 #include "dc_mfma_wide.hpp"
@@ -354,7 +359,10 @@ inline int wide_prepare_against_launches(const float* d_query, uint32_t n_query,
 // ---- the sweep ------------------------------------------------------------------------------------------------------
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-enum WideMode { kWidePop = 0, kWideNn = 1, kWideDump = 2 };
+// kWidePairs / kWideMinEdge (the radius graph): the one-radius population sweep with a sink on its two
+// decision points, the accumulator window and the exact drain; they count as kWidePop does
+enum WideMode { kWidePop = 0, kWideNn = 1, kWideDump = 2, kWidePairs = 3, kWideMinEdge = 4 };
+constexpr bool wide_counts(int mode) { return mode == kWidePop || mode == kWidePairs || mode == kWideMinEdge; }
 
 struct WideArgs {
   const float* coords;
@@ -376,6 +384,13 @@ struct WideArgs {
   const float* q_coords;       // [n_query][n_cols]
   uint32_t n_query;
   const float* q_fe;           // nullptr: nn only (fe is not read, no candidate of the hd half is raised)
+  // the graph instances only (self sweeps of one radius, rad2.v[0]; pops as for kWidePop)
+  uint2* pairs;                // kWidePairs: [capacity] (i, j), i < j
+  unsigned long long capacity;
+  unsigned long long* count;   // zeroed: the sweep adds every pair it finds, written or not
+  const uint32_t* comp;        // kWideMinEdge: [n_rows] component ids
+  const uint32_t* rank;        // [n_rows], a permutation
+  unsigned long long* best;    // [n_rows] preset to ~0: atomicMin of (max rank << 32 | min rank)
 };
 
 // the deferred pairs of a wave, evaluated in the canonical order from the original coordinates, a pair per lane
@@ -410,6 +425,69 @@ __device__ __attribute__((noinline)) void wide_drain(const uint2* queue, uint32_
   __builtin_amdgcn_wave_barrier();
 }
 
+// ---- the sinks of the radius graph (kWidePairs, kWideMinEdge) -----------------------------------------------------------
+// kWidePairs.  The every-pair sweep meets an unordered pair {a, b} twice, as (reference a, query b) and as (reference b,
+// query a), in different workgroups, shares, waves or halves of a wave.  Both meetings COUNT (each end's population needs
+// the other), and exactly one EMITS: the one with reference row i < query row j.  Whether that meeting decides the pair
+// in the accumulator window or in the drain does not matter: the rule is applied at both places.
+// kWideMinEdge.  The weight of a pair is (max rank, min rank), compared lexicographically, and the ranks are a permutation.
+// For a fixed query q of rank a, a partner of rank b has the key (a, b) if b < a and (b, a) if b > a.  Every b < a gives
+// the high word a, every b > a a larger high word, so all partners below a come before all partners above a; among
+// those below, the low word b orders them; among those above, the high word b does.  Hence over ANY set of partners the
+// lightest key is the key of the partner of SMALLEST rank, and a lane carries one 32-bit running minimum of ranks per
+// query tile instead of a 64-bit key.  A query's partners are split over shares, the two waves of a query tile, the two
+// halves of a wave and the drain: each part's smallest rank gives that part's lightest key, and the 64-bit atomicMin on
+// best[comp[q]] merges the parts -- and the queries of a component -- into the definition's minimum.
+
+// n slots of the pair list for the wave: ONE atomic, by lane 0, the base broadcast (every lane of the wave is active)
+__device__ __forceinline__ unsigned long long wide_reserve(unsigned long long* count, uint32_t n, uint32_t lane) {
+  unsigned long long base = 0;
+  if (lane == 0) base = atomicAdd(count, (unsigned long long)n);
+  const uint32_t b_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+  const uint32_t b_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+  return ((unsigned long long)b_hi << 32) | b_lo;
+}
+// wide_drain for the graph instances: the deferred pairs of one threshold, counted as kWidePop counts them and handed to
+// the sink.  A function of its own: one float instead of the eight of Rad2, a sink behind it -- and wide_drain's
+// parameter list, which is what keeps rad2 out of scratch in the population instances, stays as it is.  Called with
+// every lane of the wave active; the loop is wave-uniform (one ballot and one atomic on the count per pass).
+// The sink is three scalars -- kWidePairs: the list, its capacity, the count; kWideMinEdge: comp, rank, best -- and not a
+// struct: a struct of three pointers is passed through the stack, 24 bytes stored at each of the 65 call sites.
+template <int MODE, class A, class B, class C>
+__device__ __attribute__((noinline)) void wide_graph_drain(const uint2* queue, uint32_t fill, const float* coords, uint32_t n_rows,
+                                                           uint32_t n_cols, uint32_t qrow0, float r2, uint32_t* pops, A s0, B s1,
+                                                           C s2) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t e0 = 0; e0 < fill; e0 += 64u) {
+    const bool valid = e0 + lane < fill;
+    const uint2 en = queue[valid ? e0 + lane : 0u];
+    const uint32_t i = en.x, j = qrow0 + (en.y & 127u);
+    const float d2 = dist2_canon_rt(coords + (size_t)j * n_cols, 1, coords + (size_t)i * n_cols, 1, (int)n_cols);
+    const bool hit = valid && d2 < r2;
+    if (hit) atomicAdd(&pops[j], 1u);
+    if constexpr (MODE == kWidePairs) {
+      const bool emit = hit && i < j;
+      const unsigned long long mk = __builtin_amdgcn_ballot_w64(emit);
+      if (mk != 0) {
+        const unsigned long long slot = wide_reserve(s2, (uint32_t)__popcll(mk), lane) + lanes_below(mk);
+        if (emit && slot < s1) s0[slot] = make_uint2(i, j);
+      }
+    } else {
+      if (hit) {
+        const uint32_t cj = s0[j];
+        if (s0[i] != cj) {
+          const uint32_t ri = s1[i], rj = s1[j];
+          atomicMin(&s2[cj], ((unsigned long long)max(ri, rj) << 32) | min(ri, rj));
+        }
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
 // SM: kSelf -- queries and reference are the rows of one array: the diagonal pair leaves the sweep, populations get the
 // frame's own 1, a frame is not its own neighbour; kAgainst -- X.q_coords against X.coords: every pair counts.
 template <int MODE, int NR, SweepMode SM = kSelf>
@@ -419,6 +497,9 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   __shared__ uint2 queue_s[4][kWideQueue];
   __shared__ float fe_s[kWideBlockRows];
   __shared__ float min_s[4][2][2][32];   // neighbours: running minima (nn, nn_hd) per wave and query, exchanged per block
+  __shared__ uint2 cr_s[kWideBlockRows];  // min edge: (component, rank) of the reference block's rows
+  constexpr bool kCount = wide_counts(MODE);
+  static_assert((MODE != kWidePairs && MODE != kWideMinEdge) || (NR == 1 && SM == kSelf), "the graph instances: one radius, self sweeps");
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, h = lane >> 5, c = lane & 31u;
   const uint32_t wq = wave & 1u, wr = wave >> 1;
   const uint32_t NM = X.NM, NC = (NM + kWideKC - 1) / kWideKC, D = X.n_cols;
@@ -435,6 +516,7 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   uint2* queue = queue_s[wave];
   uint32_t fill = 0;
   unsigned long long n_exact = 0;
+  unsigned long long n_found = 0;   // kWidePairs, counting only: the pairs this wave decided inside, from their i < j meeting
 
   const Scale sc = load_scale(X.hdr);
   const WideBand band = wide_band(__uint_as_float(X.hdr[0]) * sc.s2, (int)D, sc);
@@ -455,7 +537,7 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   uint32_t cnt[2][NR];
   float m_nn[2], m_hd[2], feq[2];
   const float ratio = wide_cut_ratio(band);
-  if constexpr (MODE == kWidePop) {
+  if constexpr (kCount) {
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
       lo[k] = hi[k] = -INFINITY;   // (a radius the launch does not have: nothing inside, nothing undecided)
@@ -471,14 +553,34 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
       feq[qt] = (live[qt] && has_fe) ? q_fe[jq[qt]] : -INFINITY;   // (a dead lane, nn only: no reference lies lower)
     }
   }
+  // min edge: component and rank of the lane's queries, the smallest rank met among their partners of another component
+  uint32_t comp_q[2], rank_q[2], rmin[2];
+  if constexpr (MODE == kWideMinEdge) {
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      comp_q[qt] = live[qt] ? X.comp[jq[qt]] : 0u;
+      rank_q[qt] = live[qt] ? X.rank[jq[qt]] : 0u;
+      rmin[qt] = ~0u;
+    }
+  }
 
   // one pair per lane into the wave's queue (ok: this lane has one); drained before a push that might not fit
+  auto drain = [&]() {
+    if constexpr (MODE == kWidePairs)
+      wide_graph_drain<MODE>(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.rad2.v[0], X.pops,
+                             X.pairs, X.capacity, X.count);
+    else if constexpr (MODE == kWideMinEdge)
+      wide_graph_drain<MODE>(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.rad2.v[0], X.pops,
+                             X.comp, X.rank, X.best);
+    else
+      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.rad2,
+                                                       MODE == kWideNn ? (void*)X.merge : (void*)X.pops, q_coords);
+  };
   auto push = [&](bool ok, uint32_t i, uint32_t word) {
     const unsigned long long mk = __builtin_amdgcn_ballot_w64(ok);
     if (mk == 0) return;
     if (fill + 64u > kWideQueue) {
-      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.rad2,
-                                                       MODE == kWideNn ? (void*)X.merge : (void*)X.pops, q_coords);
+      drain();
       n_exact += fill;
       fill = 0;
     }
@@ -533,6 +635,12 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
           fe_s[tid] = (row < X.n_rows && has_fe) ? X.fe[row] : INFINITY;
         }
       }
+      if constexpr (MODE == kWideMinEdge) {   // (as fe_s: read a barrier later, written behind the last epilogue's barrier)
+        if (tid < kWideBlockRows) {
+          const uint32_t row = rb * kWideBlockRows + tid;
+          cr_s[tid] = (row < X.n_rows) ? make_uint2(X.comp[row], X.rank[row]) : make_uint2(0u, ~0u);
+        }
+      }
     }
     // the next chunk leaves for the registers before this chunk's MFMAs (behind the norm loads above: the memory counter
     // is in order, and the wait for the norms must not wait for the chunk)
@@ -574,11 +682,11 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
               X.dump[(size_t)i * (32u * X.Tp) + jq[qt]] = acc[rt][qt][g];
             }
       }
-      if constexpr (MODE == kWidePop) {
+      if constexpr (kCount) {
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-          for (int rt = 0; rt < 2; ++rt)
+          for (int rt = 0; rt < 2; ++rt) {
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
               const float v = acc[rt][qt][g];
@@ -594,6 +702,56 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
                 push(und != 0 && live[qt] && i < X.n_rows, i, ((2 * wq + qt) * 32 + c) | (und << 8));
               }
             }
+            if constexpr (MODE == kWideMinEdge) {
+              // (the self pair is +inf on the diagonal tile and of the query's own component; a pad row is +inf)
+#pragma unroll
+              for (int g = 0; g < 16; ++g) {
+                const uint2 cr = cr_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
+                rmin[qt] = min(rmin[qt], (acc[rt][qt][g] < lo[0] && cr.x != comp_q[qt]) ? cr.y : ~0u);
+              }
+            }
+          }
+        if constexpr (MODE == kWidePairs) {
+          // the pairs this block decided inside, each from its meeting with i < j.  A reference tile above the query tile
+          // holds no such element (wave-uniform; it has been counted above all the same).  The slots of the wave's four
+          // tiles come from ONE atomic: a ballot per element, the popcounts summed on the scalar side, and a lane's slot
+          // is the base + the popcounts of the earlier elements + the set lanes below it.  Every wave of the grid adds
+          // to the same word, which takes an add every ~10 ns: one per tile made a dense list 6 x the population sweep.
+          // Counting only (no list: capacity 0) needs no slot: the wave keeps its sum and adds it once, at the end.
+          const uint32_t rt0 = rb * kWideBlockTiles + 2 * wr, qt0 = qb * kWideBlockTiles + 2 * wq;
+          auto inside = [&](int rt, int qt, int g) {
+            const uint32_t i = (rt0 + rt) * 32 + tile_row_local(g, (int)h);
+            return acc[rt][qt][g] < lo[0] && live[qt] && i < X.n_rows && i < jq[qt];
+          };
+          uint32_t total = 0;
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+              if (rt0 + rt <= qt0 + qt) {
+#pragma unroll
+                for (int g = 0; g < 16; ++g) total += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(inside(rt, qt, g)));
+              }
+          if (X.capacity == 0) {
+            n_found += total;
+          } else if (total != 0) {
+            unsigned long long slot0 = wide_reserve(X.count, total, lane);
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+              for (int rt = 0; rt < 2; ++rt)
+                if (rt0 + rt <= qt0 + qt) {
+#pragma unroll
+                  for (int g = 0; g < 16; ++g) {
+                    const bool ok = inside(rt, qt, g);
+                    const unsigned long long mk = __builtin_amdgcn_ballot_w64(ok);
+                    const unsigned long long slot = slot0 + lanes_below(mk);
+                    if (ok && slot < X.capacity) X.pairs[slot] = make_uint2((rt0 + rt) * 32 + tile_row_local(g, (int)h), jq[qt]);
+                    slot0 += (unsigned long long)__popcll(mk);
+                  }
+                }
+          }
+        }
       }
       if constexpr (MODE == kWideNn) {
 #pragma unroll
@@ -643,12 +801,23 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
 
   if constexpr (MODE != kWideDump) {
     if (fill != 0) {
-      wide_drain<MODE == kWideNn ? kWideNn : kWidePop>(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.rad2,
-                                                       MODE == kWideNn ? (void*)X.merge : (void*)X.pops, q_coords);
+      drain();
       n_exact += fill;
     }
   }
-  if constexpr (MODE == kWidePop) {
+  if constexpr (MODE == kWidePairs) {
+    if (lane == 0 && n_found != 0) atomicAdd(X.count, n_found);
+  }
+  if constexpr (MODE == kWideMinEdge) {
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      // (the two halves of the wave hold other reference rows of the same queries)
+      const uint32_t m = min(rmin[qt], (uint32_t)__shfl_xor((int)rmin[qt], 32, 64));
+      if (h == 0 && live[qt] && m != ~0u)
+        atomicMin(&X.best[comp_q[qt]], ((unsigned long long)max(rank_q[qt], m) << 32) | min(rank_q[qt], m));
+    }
+  }
+  if constexpr (kCount) {
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll

@@ -20,6 +20,7 @@
 #include "../../include/dc_density.h"
 #include "dc_common.hpp"
 #include "dc_mfma.hpp"
+#include "dc_forest_host.hpp"
 
 #include <rccl/rccl.h>   // types and enums only; the functions are resolved with dlsym
 
@@ -695,13 +696,10 @@ int dc_hip_session_radius_forest(dc_hip_session* s, float r2, const uint32_t* ra
   const size_t n = s->n_rows, G = s->dev.size();
   if (n <= 1) return DC_OK;
   if (!rank || !edges) return failf(DC_ERR_INVALID_ARGUMENT, "null pointer");
-  // frame of every rank (and: is it a permutation?)
-  std::vector<uint32_t> frame_of(n, 0xFFFFFFFFu);
-  for (size_t i = 0; i < n; ++i) {
-    if (rank[i] >= n || frame_of[rank[i]] != 0xFFFFFFFFu)
-      return failf(DC_ERR_INVALID_ARGUMENT, "rank is not a permutation of 0..n_rows-1");
-    frame_of[rank[i]] = (uint32_t)i;
-  }
+  // the host part of the rounds (dc_forest_host.hpp): frame of every rank (and: is it a permutation?), the union-find
+  // over frame ids with the smaller id as root, the join loop
+  dc::ForestHost forest;
+  if (!forest.init(rank, n)) return failf(DC_ERR_INVALID_ARGUMENT, "rank is not a permutation of 0..n_rows-1");
   s->n_radii = 0;   // (the resident populations serve as scratch below)
   int rc = on_every_device(s, [&](int g) -> int {
     DevState& d = s->dev[g];
@@ -717,27 +715,13 @@ int dc_hip_session_radius_forest(dc_hip_session* s, float r2, const uint32_t* ra
     return DC_OK;
   });
   if (rc != DC_OK) return rc;
-  // components: union-find over frame ids, the smaller id is the root (= the component's id)
-  std::vector<uint32_t> parent(n), comp(n);
-  for (size_t i = 0; i < n; ++i) parent[i] = comp[i] = (uint32_t)i;
-  auto find = [&](uint32_t x) {
-    uint32_t root = x;
-    while (parent[root] != root) root = parent[root];
-    while (parent[x] != root) {
-      const uint32_t next = parent[x];
-      parent[x] = root;
-      x = next;
-    }
-    return root;
-  };
   std::vector<unsigned long long> best(n);
-  size_t found = 0;
   uint32_t rounds = 0;
   // every round at least halves the number of components that still have a partner
-  for (; rounds < 64; ++rounds) {
+  for (; rounds < dc::kForestMaxRounds; ++rounds) {
     rc = on_every_device(s, [&](int g) -> int {
       DevState& d = s->dev[g];
-      SESSION_HIP_TRY(hipMemcpyAsync(d.d_comp, comp.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, d.stream));
+      SESSION_HIP_TRY(hipMemcpyAsync(d.d_comp, forest.comp.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, d.stream));
       // (G devices: each sees the pairs of its own segment's queries; every pair is seen from both ends)
       return dc_hip_radius_min_edge_segment_dev(d.d_coords, n, s->n_cols, r2, d.d_comp, d.d_rank, (size_t)g,
                                                 G > 1 ? G : 0, d.d_words, d.d_pops, d.d_ws, d.ws_bytes, d.stream);
@@ -750,24 +734,11 @@ int dc_hip_session_radius_forest(dc_hip_session* s, float r2, const uint32_t* ra
     SESSION_HIP_TRY(hipSetDevice(d0.device));
     SESSION_HIP_TRY(hipMemcpyAsync(best.data(), d0.d_words, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, d0.stream));
     if ((rc = sync_all(s, "radius forest sweep")) != DC_OK) return rc;
-    size_t joined = 0;
-    for (size_t c = 0; c < n; ++c) {
-      if (best[c] == ~0ull) continue;
-      const uint32_t a = frame_of[(uint32_t)(best[c] >> 32)], b = frame_of[(uint32_t)best[c]];
-      const uint32_t ra = find(a), rb = find(b);
-      if (ra == rb) continue;   // the partner component chose the same pair
-      parent[std::max(ra, rb)] = std::min(ra, rb);
-      edges[2 * found] = a;
-      edges[2 * found + 1] = b;
-      ++found;
-      ++joined;
-    }
-    if (joined == 0) break;
-    for (size_t i = 0; i < n; ++i) comp[i] = find((uint32_t)i);
+    if (forest.join(best.data(), edges) == 0) break;
   }
-  *n_edges = found;
-  if (n_rounds) *n_rounds = rounds + (rounds < 64 ? 1 : 0);
-  if (rounds >= 64)   // (every round at least halves the joinable components: 64 rounds cannot be needed)
+  *n_edges = forest.found;
+  if (n_rounds) *n_rounds = rounds + (rounds < dc::kForestMaxRounds ? 1 : 0);
+  if (rounds >= dc::kForestMaxRounds)   // (every round at least halves the joinable components: 64 rounds cannot be needed)
     return failf(DC_ERR_HIP, "radius forest: components still merging after %u rounds (incomplete forest)", rounds);
   return DC_OK;
 }

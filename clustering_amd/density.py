@@ -668,6 +668,81 @@ def radius_forest(coords_host, r2, rank, device=0):
     return edges[:n_edges.value].copy(), int(n_rounds.value)
 
 
+# ---- the radius graph on the wide matrix-core sweep (65..256 columns; include/dc_density.h) -------------------------
+def _check_coords_wide(coords):
+    """_check_coords, the column count (refused here as the library refuses it: 65..256) first"""
+    if isinstance(coords, (torch.Tensor, np.ndarray)) and coords.ndim == 2 and not 65 <= coords.shape[1] <= 256:
+        raise ValueError(f"n_cols={coords.shape[1]}: the wide matrix-core sweeps take 65..256 columns")
+    return _check_coords(coords) if isinstance(coords, torch.Tensor) else coords.shape
+
+
+def radius_pairs_wide(coords, r2, capacity=None):
+    """radius_pairs for rows of 65..256 columns on the matrix cores (dc_hip_radius_pairs_wide_dev): all unordered frame
+    pairs with canonical d2 < r2 -> (pairs int64 [n_pairs, 2] on the device, pops int32 [n_rows]).  One counting sweep
+    sizes the buffer unless a capacity is given.  Rows with inf / NaN have no partners (population 1; the direct kernel
+    answers such data).  In the cached workspace of the wide sweeps (wide_sweep_info reads its counters).  Other column
+    counts raise."""
+    n_rows, n_cols = _check_coords_wide(coords)
+    dev = coords.device
+    pops = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def sweep(pairs, cap):
+        with torch.cuda.device(dev):
+            ws, ws_bytes = _wide_workspace(dev).get(n_rows, n_cols, 1)
+            rc = capi.lib.dc_hip_radius_pairs_wide_dev(_dev(coords), n_rows, n_cols, float(r2), _dev(pops),
+                                                       _dev(pairs) if pairs is not None else None, cap,
+                                                       _dev(count), ws, ws_bytes, _stream_ptr())
+        capi.check(rc, "dc_hip_radius_pairs_wide_dev")
+        return int(count.item())
+
+    if capacity is None:
+        capacity = sweep(None, 0)
+    pairs = torch.empty((max(capacity, 1), 2), dtype=torch.int32, device=dev)
+    n = sweep(pairs, capacity)
+    if n > capacity:
+        return radius_pairs_wide(coords, r2, n)
+    return pairs[:n].to(torch.int64), pops
+
+
+def radius_min_edge_wide(coords, r2, comp, rank, segment=0, n_segments=0):
+    """radius_min_edge for rows of 65..256 columns on the matrix cores (dc_hip_radius_min_edge_wide_dev): comp, rank
+    int32 CUDA [n_rows] -> (best int64 [n_rows]: (max rank << 32 | min rank) of the lightest pair leaving component
+    id, -1 (all ones) if none; pops int32 [n_rows]).  n_segments > 0: what the queries of one row block of a sharded
+    run see (partials merge by unsigned minimum / summation), array-equal to radius_min_edge of that segment.  Other
+    column counts raise."""
+    n_rows, n_cols = _check_coords_wide(coords)
+    dev = coords.device
+    for t in (comp, rank):
+        assert t.is_cuda and t.dtype == torch.int32 and t.shape == (n_rows,) and t.is_contiguous()
+    best = torch.empty(n_rows, dtype=torch.int64, device=dev)
+    pops = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _wide_workspace(dev).get(n_rows, n_cols, 1)
+        rc = capi.lib.dc_hip_radius_min_edge_wide_dev(_dev(coords), n_rows, n_cols, float(r2), _dev(comp), _dev(rank),
+                                                      segment, n_segments, _dev(best), _dev(pops), ws, ws_bytes,
+                                                      _stream_ptr())
+    capi.check(rc, "dc_hip_radius_min_edge_wide_dev")
+    return best, pops
+
+
+def radius_forest_wide(coords_host, r2, rank, device=0):
+    """radius_forest for rows of 65..256 columns on the matrix cores (dc_hip_radius_forest_wide; one device, no
+    session).  coords_host: float32 numpy [n_rows, n_cols]; rank: permutation of 0..n_rows-1 -> (edges uint32 numpy
+    [n_edges, 2] of frame ids, number of sweeps).  Other column counts raise."""
+    coords_host = np.ascontiguousarray(coords_host, dtype=np.float32)
+    n_rows, n_cols = _check_coords_wide(coords_host)
+    rank = np.ascontiguousarray(rank, dtype=np.uint32)
+    assert rank.shape == (n_rows,)
+    edges = np.empty((max(n_rows - 1, 1), 2), dtype=np.uint32)
+    n_edges, n_rounds = C.c_size_t(0), C.c_uint32(0)
+    rc = capi.lib.dc_hip_radius_forest_wide(coords_host.ctypes.data_as(C.c_void_p), n_rows, n_cols, float(r2),
+                                            rank.ctypes.data_as(C.c_void_p), device,
+                                            edges.ctypes.data_as(C.c_void_p), C.byref(n_edges), C.byref(n_rounds))
+    capi.check(rc, "dc_hip_radius_forest_wide")
+    return edges[:n_edges.value].copy(), int(n_rounds.value)
+
+
 def pack_neighbors(nn_idx, nn_d2, hd_idx, hd_d2):
     """-> int64 CUDA [2, n_rows]: (d2 bits << 32 | index) words of nn and nn_hd (dc_hip_neighbors_pack_dev);
     partial results of a sharded run merge with all_reduce(min)."""

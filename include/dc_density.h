@@ -283,7 +283,8 @@ DC_API int dc_hip_sigma2_dev(const float* d_nn_d2, size_t n_rows, double* sigma2
  *            pair once; may be NULL with capacity 0 to count only
  *   d_count  device uint64, out: number of pairs found -- if it exceeds capacity only the first
  *            `capacity` were written (call again with a larger buffer).
- * Needs a workspace as above for n_cols <= 64; for n_cols > 64 none (NULL / 0: dc_hip_workspace_bytes is 0). */
+ * Needs a workspace as above for n_cols <= 64; for n_cols > 64 none (NULL / 0: dc_hip_workspace_bytes is 0) -- this
+ * call runs the direct sweep there; for 65..256 columns dc_hip_radius_pairs_wide_dev below is the matrix-core form. */
 DC_API int dc_hip_radius_pairs_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
                                    uint32_t* d_pops, uint32_t* d_pairs, size_t capacity,
                                    unsigned long long* d_count, void* d_workspace,
@@ -442,7 +443,38 @@ DC_API int dc_hip_nearest_neighbors_cross_wide_dev(const float* d_query, size_t 
                                                    uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                                                    float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
 
-/* the last wide sweep CALL in that workspace -- a self sweep (dc_hip_*_wide_dev) or a cross sweep
+/* ---- ... and the radius graph on the wide self sweep (65..256 columns) --------------------------------------------------
+ * The one-radius population sweep with a sink on its two decision points, the accumulator window and the exact drain.
+ * Entry points of their own, like the sweeps above: no dc_variant value selects them, and dc_hip_radius_pairs_dev,
+ * dc_hip_radius_min_edge[_segment]_dev, dc_hip_radius_forest and the sessions keep sending rows wider than 64 columns
+ * to the direct kernels.  Workspace: dc_hip_wide_workspace_bytes(n_rows, n_cols, 1); dc_hip_wide_info_dev reads the
+ * counters of the last graph call in it.  n_cols outside 65..256: DC_ERR_INVALID_ARGUMENT; a short or NULL workspace:
+ * DC_ERR_WORKSPACE; sizes as for the calls they mirror (the min-edge row limit included); n_rows == 0: DC_OK -- all
+ * checked before a device is touched.  Flagged data (a non-finite or overflow-prone row): the direct kernels answer
+ * behind the device-side gate, without a host synchronisation, counters (0, 0, 0).
+ *
+ * dc_hip_radius_pairs_wide_dev: the contract of dc_hip_radius_pairs_dev -- every unordered pair {i, j}, i != j, with
+ * canonical d2 < r2 exactly once, in no particular order; d_pops fully overwritten (1 + number of partners); d_pairs
+ * NULL with capacity 0 counts only; *d_count is the full count even when it exceeds capacity, in which case exactly
+ * `capacity` distinct valid pairs are written and nothing beyond; a NaN, 0 or negative r2 holds no pair. */
+DC_API int dc_hip_radius_pairs_wide_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2, uint32_t* d_pops,
+                                        uint32_t* d_pairs, size_t capacity, unsigned long long* d_count, void* d_ws,
+                                        size_t ws_bytes, void* stream);
+/* the contract of dc_hip_radius_min_edge_segment_dev; n_segments == 0: the whole round.  A segment is the reference's
+ * row block (density_clustering_cuda.cu:149,165-169), the partition that call uses at these widths, so the outputs of
+ * a segment are array-equal to its outputs: d_best merges by unsigned minimum, d_pops by summation.  Both outputs are
+ * preset by the call (~0 / 0). */
+DC_API int dc_hip_radius_min_edge_wide_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
+                                           const uint32_t* d_comp, const uint32_t* d_rank, size_t segment,
+                                           size_t n_segments, unsigned long long* d_best, uint32_t* d_pops, void* d_ws,
+                                           size_t ws_bytes, void* stream);
+/* host-pointer form with the contract of dc_hip_radius_forest (rank, edges, n_edges, n_rounds as there), on ONE device
+ * and without a session: one upload, then Boruvka rounds of dc_hip_radius_min_edge_wide_dev in one workspace with the
+ * components merged on the host.  A rank that is no permutation: DC_ERR_INVALID_ARGUMENT before a device is touched. */
+DC_API int dc_hip_radius_forest_wide(const float* coords, size_t n_rows, size_t n_cols, float r2, const uint32_t* rank,
+                                     int device, uint32_t* edges, size_t* n_edges, uint32_t* n_rounds);
+
+/* the last wide sweep CALL in that workspace -- a self sweep (dc_hip_*_wide_dev, the radius graph included) or a cross sweep
  * (dc_hip_*_cross_wide_dev), the counters sit at the same place of either workspace: 32x32 tile pairs evaluated, MFMA instructions issued, frame pairs sent
  * to the exact path, summed over the launches of the call (a population call with more than 8 radii runs one launch
  * per 8: its counts are that multiple of a one-launch call's); all 0 when the direct kernels answered or there was
