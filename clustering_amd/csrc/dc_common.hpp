@@ -21,6 +21,13 @@ constexpr size_t kMaxColsAny = UINT32_MAX - 64;
 struct Rad2 {
   float v[kMaxRadiiPerLaunch];
 };
+// one squared radius in slot 0; the unused slots hold -1, which no squared distance is below
+inline Rad2 one_radius(float r2) {
+  Rad2 one;
+  for (float& v : one.v) v = -1.0f;
+  one.v[0] = r2;
+  return one;
+}
 
 // what a sweep measures: rows of one array against the same array, without the self pair (kSelf: the query
 // array is the reference array, n_q == n_ref), or query rows against every row of a reference array (kAgainst:

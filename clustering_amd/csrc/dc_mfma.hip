@@ -1049,8 +1049,8 @@ const SweepSwitches& sweep_switches() {
 static float cell_frames(bool nn) { return nn ? sweep_switches().nn_cell_frames : sweep_switches().pop_cell_frames; }
 static float nn_cell_frames() { return cell_frames(true); }
 
-int mfma_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws,
-                 bool natural_image, hipStream_t stream, bool stats_valid, bool pruned, const float* d_fe) {
+int mfma_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t stream,
+                 bool stats_valid, bool pruned, const float* d_fe) {
   // pruned: a pruned sweep follows -- the statistics come from ONE pass (stats_kernel, dc_prep.hpp); the column means and
   // the extents max |x - mean|^2 / max |x - origin|^2 follow in the passes of its preparation that read the rows anyway
   // (components_kernel, order_key_kernel).  The full sweeps and the fp32-MFMA instance need means and max norm before
@@ -1097,7 +1097,7 @@ int mfma_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* 
   //  scratch/pb/rowstats_bench.hip)
   hipLaunchKernelGGL(rowstats_kernel, dim3(std::min<uint32_t>((n_rows + 255) / 256, 512u)), dim3(256), 0, stream, d_coords, n_rows, n_cols,
                      (const float*)(p + kHdrMeans), (uint32_t*)p, cookie);
-  (void)natural_image;   // (the full sweeps build their natural-order images themselves, at their own scale)
+  // (the full sweeps build their natural-order images themselves, at their own scale)
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1106,12 +1106,7 @@ int mfma_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* 
 // sign / min triple per radius of a multi-radius epilogue -- and the MFMAs of a repeated sweep hide
 // behind that epilogue.  Radii are therefore swept one after the other (the pruned sweep then also
 // runs on its own pruned survivor lists).
-static Rad2 single_radius(const Rad2& rad2, int r) {
-  Rad2 one;
-  for (int k = 0; k < kMaxRadiiPerLaunch; ++k) one.v[k] = -1.0f;
-  one.v[0] = rad2.v[r];
-  return one;
-}
+static Rad2 single_radius(const Rad2& rad2, int r) { return one_radius(rad2.v[r]); }
 
 static float max_radius2(const Rad2& rad2, int n_rad) {
   float m = 0.0f;
@@ -1163,34 +1158,56 @@ static void image(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint3
                      (const float*)(p + kHdrMeans), perm, b_form, (uint4*)img, (float*)norms, (const uint32_t*)p);
 }
 
-// Where ordering the references by free energy leaves its results: perm (sorted position -> reference), invpos, fe_s,
-// per query pq, and the sort's scratch
-struct FeOrder {
-  uint32_t *keys_in, *keys_out, *vals_in, *perm, *invpos, *pq;
-  float* fe_s;
-  void* sort_tmp;
+// The three buffers of the library's key / value sort (dc_sort.hip) and its temp region, wherever a workspace keeps them
+struct SortBufs {
+  uint32_t *keys_in, *keys_out, *vals_in;
+  void* tmp;
+  size_t tmp_bytes;
+  // the values in the order of their keys -> vals_out; non-zero when the sort failed
+  int run(uint32_t* vals_out, size_t n, hipStream_t stream, unsigned key_bits = 32, const SortRemap* remap = nullptr) const {
+    return sort_pairs_u32(keys_in, keys_out, vals_in, vals_out, n, tmp, tmp_bytes, stream, key_bits, remap);
+  }
 };
+// (every layout names the three buffers alike; where the temp region lies and how large it is differs)
+template <class LayoutT>
+static SortBufs sort_bufs(void* d_ws, const LayoutT& L, size_t off_tmp, size_t tmp_bytes) {
+  char* p = (char*)d_ws;
+  return SortBufs{(uint32_t*)(p + L.off_keys_in), (uint32_t*)(p + L.off_keys_out), (uint32_t*)(p + L.off_vals_in),
+                  p + off_tmp, tmp_bytes};
+}
 
-// The references of a neighbour sweep ordered by free energy (a NaN raises the flag: the direct kernel answers), per
-// query the number of references with strictly lower free energy -- its candidates for nn_hd are a prefix of that
-// order -- and the A-form image + norms of the references in that order.  d_fe_q == nullptr (nn only): natural order.
-// Returns non-zero when the sort failed.
-static int order_by_fe(const float* d_ref, uint32_t n_ref, uint32_t n_cols, uint32_t NM, uint32_t T_r,
-                       const float* d_fe_r, const float* d_fe_q, uint32_t n_q, const FeOrder& B, void* img,
-                       void* norms, void* d_ws, hipStream_t stream) {
+// Where ordering the references by free energy leaves its results: perm (sorted position -> reference), invpos, fe_s,
+// per query pq, and the sort's buffers
+struct FeOrder {
+  SortBufs sort;
+  uint32_t *perm, *invpos, *pq;
+  float* fe_s;
+};
+// (Layout and CrossLayout: the same names; off_tmp: where the layout leaves room for the sort of n_ref keys)
+template <class LayoutT>
+static FeOrder fe_order(void* d_ws, const LayoutT& L, size_t off_tmp, size_t n_ref) {
+  char* p = (char*)d_ws;
+  return FeOrder{sort_bufs(d_ws, L, off_tmp, sort_temp_bytes(n_ref)), (uint32_t*)(p + L.off_perm),
+                 (uint32_t*)(p + L.off_invpos), (uint32_t*)(p + L.off_pq), (float*)(p + L.off_fe_s)};
+}
+
+// The references of a neighbour sweep ordered by free energy (a NaN raises the flag: the direct kernel answers) and, per
+// query, the number of references with strictly lower free energy -- its candidates for nn_hd are a prefix of that
+// order.  d_fe_q == nullptr (nn only): natural order.  The callers build the image of the references in that order
+// (fp16 x 2 or fp32) afterwards.  Returns non-zero when the sort failed.
+static int order_by_fe(uint32_t n_ref, uint32_t T_r, const float* d_fe_r, const float* d_fe_q, uint32_t n_q,
+                       const FeOrder& B, void* d_ws, hipStream_t stream) {
   const dim3 blk(256), grid_r((n_ref + 255) / 256), grid_t((32 * T_r + 255) / 256);
   if (d_fe_q) {
     hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>(grid_r.x, 1024u)), blk, 0, stream, d_fe_r, n_ref,
-                       B.keys_in, B.vals_in, (uint32_t*)d_ws);
-    if (sort_pairs_u32(B.keys_in, B.keys_out, B.vals_in, B.perm, n_ref, B.sort_tmp, sort_temp_bytes(n_ref), stream) != 0)
-      return -3;
+                       B.sort.keys_in, B.sort.vals_in, (uint32_t*)d_ws);
+    if (B.sort.run(B.perm, n_ref, stream) != 0) return -3;
     hipLaunchKernelGGL(fe_scatter_kernel, grid_t, blk, 0, stream, B.perm, d_fe_r, n_ref, T_r, B.invpos, B.fe_s);
     hipLaunchKernelGGL(fe_rank_kernel, dim3((n_q + 255) / 256), blk, 0, stream, d_fe_q, n_q, (const float*)B.fe_s,
                        n_ref, B.pq);
   } else {
     hipLaunchKernelGGL(iota_kernel, grid_t, blk, 0, stream, B.perm, n_ref, 32 * T_r);
   }
-  image(d_ref, n_ref, n_cols, NM, T_r, B.perm, 0, img, norms, d_ws, stream);
   return 0;
 }
 
@@ -1291,9 +1308,7 @@ void launch_radius_pairs(const float* d_coords, uint32_t n_rows, uint32_t n_cols
                          uint32_t* d_pops, uint2* d_pairs, unsigned long long capacity,
                          unsigned long long* d_count, void* d_ws, hipStream_t stream) {
   const Layout L = make_layout(n_rows, n_cols);
-  Rad2 one;
-  for (int k = 0; k < kMaxRadiiPerLaunch; ++k) one.v[k] = -1.0f;
-  one.v[0] = r2;
+  const Rad2 one = one_radius(r2);
   (void)hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream);
   if (d_pairs && capacity) {
     const EdgeSink sink{d_pairs, d_count, capacity, nullptr, nullptr, nullptr};
@@ -1317,9 +1332,7 @@ void launch_radius_min_edge(const float* d_coords, uint32_t n_rows, uint32_t n_c
                             const uint32_t* d_comp, const uint32_t* d_rank, unsigned long long* d_best,
                             uint32_t* d_pops, void* d_ws, hipStream_t stream, uint32_t segment,
                             uint32_t n_segments) {
-  Rad2 one;
-  for (int k = 0; k < kMaxRadiiPerLaunch; ++k) one.v[k] = -1.0f;
-  one.v[0] = r2;
+  const Rad2 one = one_radius(r2);
   (void)hipMemsetAsync(d_best, 0xFF, sizeof(unsigned long long) * n_rows, stream);
   // comp / rank arrive per FRAME; pop_pruned_one gathers them into the sweep's order
   const EdgeSink sink{nullptr, nullptr, 0, d_comp, d_rank, d_best};
@@ -1333,55 +1346,130 @@ uint32_t seg_block(uint32_t n_segments) { return n_segments <= 1u ? 1u : kSegBlo
 // DC_POP_COMPONENTS=0: one component whatever the data looks like (measurements, tests)
 static bool components_off() { return !sweep_switches().components; }
 
+// One view of the pruned self sweeps' workspace (Layout, dc_mfma_kernels.hpp): the regions their host side names
+struct PrunedWs {
+  char* p;
+  uint32_t* hdr;
+  SortBufs sort;       // (temp region: behind the layout, sized for the padded orders)
+  uint32_t *perm_p, *perm_q, *comp, *tile_comp, *tile_comp_q;
+  const float* origins;
+  // per component, reference / query order: first sorted index, tile range, first position of the padded order
+  uint32_t *start_r, *range_r, *base_r, *start_q, *range_q, *base_q;
+  uint32_t* cnt_tab;   // rows per component and block: the sort's temp region, free until the sort
+};
+static PrunedWs pruned_ws(void* d_ws, const Layout& L, uint32_t n_rows) {
+  char* p = (char*)d_ws;
+  uint32_t* comp = (uint32_t*)(p + L.off_comp);
+  PrunedWs W;
+  W.p = p;
+  W.hdr = (uint32_t*)p;
+  W.sort = sort_bufs(d_ws, L, L.fixed_end, sort_temp_bytes(n_rows + kOrderPadRows));
+  W.perm_p = (uint32_t*)(p + L.off_perm_p);
+  W.perm_q = (uint32_t*)(p + L.off_perm_q);
+  W.comp = comp;
+  W.tile_comp = (uint32_t*)(p + L.off_tile_comp);
+  W.tile_comp_q = (uint32_t*)(p + L.off_tile_comp_q);
+  W.origins = (const float*)(comp + kCompOrigin);
+  W.start_r = comp + kCompStart;
+  W.start_q = comp + kCompStart + (kMaxComp + 1);
+  W.range_r = comp + kCompRange;
+  W.range_q = comp + kCompRange + kCompRangeStride;
+  W.base_r = comp + kCompBase;
+  W.base_q = comp + kCompBase + (kMaxComp + 1);
+  W.cnt_tab = (uint32_t*)(p + L.fixed_end);
+  return W;
+}
+
+// The queries of a pruned call and the tiles of its padded orders.  The orders are PADDED: every component of the
+// frames (dc_mfma_kernels.hpp "components") starts at a whole query group of group_tiles tiles; the sort's last pass
+// writes its values straight to the padded positions (SortRemap: segment starts -> bases), the pad positions in between
+// keep the kInvalidFrame that order_meta_kernel's presets left there.
+struct QueryPlan {
+  int q_mode;
+  uint32_t n_q;
+  QSeg q_seg;
+  uint32_t group_rows, T_r, T_q;
+};
+static QueryPlan query_plan(const QuerySel& qs, uint32_t n_rows, uint32_t group_tiles) {
+  QueryPlan Q;
+  const bool full = (qs.i_from == 0 && qs.i_to == n_rows);
+  Q.n_q = qs.i_to - qs.i_from;
+  Q.q_mode = full ? kQueryAll : kQueryOwnOrder;
+  Q.q_seg = QSeg{1u, 0u, 1u};
+  if (qs.n_segments > 0) {   // one segment of a sharded run: every n_segments-th query group of all rows
+    Q.q_mode = kQueryAll;
+    Q.n_q = n_rows;
+    Q.q_seg = QSeg{qs.n_segments, qs.segment, seg_block(qs.n_segments)};
+  }
+  Q.group_rows = 32u * group_tiles;
+  Q.T_r = (n_rows + (uint32_t)kMaxComp * (Q.group_rows - 1u) + 31u) / 32u;
+  Q.T_q = (Q.n_q + (uint32_t)kMaxComp * (Q.group_rows - 1u) + 31u) / 32u;
+  return Q;
+}
+
+// All frames ordered by (component, fine cell[, quantised free energy d_fe in fe_bits bits]): keys, rows per component,
+// the extents and the pad presets; where the components start and the scale of the sweep (r2_scale: its largest squared
+// radius -- the scale follows the components' extents -- or -1, the neighbour scale); the sort on sort_bits bits, whose
+// last pass moves every component to a whole query group of the padded order.  Non-zero when the sort failed.
+static int order_refs(const PrunedWs& W, const QueryPlan& Q, const float* d_coords, uint32_t n_rows, uint32_t n_cols,
+                      unsigned fine_bits, const float* d_fe, unsigned fe_bits, unsigned sort_bits, float r2_scale,
+                      int shift_steps, hipStream_t stream) {
+  const uint32_t kb_r = std::min<uint32_t>((std::max(n_rows, 32u * Q.T_r) + 255) / 256, 1024u);
+  hipLaunchKernelGGL(order_key_kernel, dim3(kb_r), dim3(256), order_key_smem_set(n_cols), stream, d_coords, n_cols, W.hdr,
+                     (const uint32_t*)W.comp, (uint32_t)fine_bits, 0u, n_rows, W.sort.keys_in, W.sort.vals_in, n_rows, d_fe,
+                     (uint32_t)fe_bits, W.cnt_tab, 1, W.perm_p, W.tile_comp, 32u * Q.T_r);
+  hipLaunchKernelGGL(order_meta_kernel, dim3(1), dim3(1024), 0, stream, W.hdr, W.comp, (const uint32_t*)W.cnt_tab, kb_r, W.start_r,
+                     W.range_r, W.base_r, n_rows, Q.group_rows, 1, r2_scale, n_cols, shift_steps);
+  const SortRemap remap{W.start_r, W.base_r, (uint32_t)kMaxComp, W.tile_comp};
+  return W.sort.run(W.perm_p, n_rows, stream, sort_bits, &remap);
+}
+
+// The query rows [i_from, i_to) of a call in an order of their own: the same ordering restricted to them (cell keys
+// only), their tile boxes, B form and norms.  Non-zero when the sort failed.
+static int order_own_queries(const PrunedWs& W, const Layout& L, const QueryPlan& Q, const float* d_coords, uint32_t n_rows,
+                             uint32_t n_cols, unsigned fine_bits, uint32_t i_from, uint32_t i_to, hipStream_t stream) {
+  char* p = W.p;
+  const dim3 blk(256);
+  const uint32_t kb_q = std::min<uint32_t>((std::max(Q.n_q, 32u * Q.T_q) + 255) / 256, 1024u);
+  hipLaunchKernelGGL(order_key_kernel, dim3(kb_q), blk, 0, stream, d_coords, n_cols, W.hdr, (const uint32_t*)W.comp,
+                     (uint32_t)fine_bits, i_from, i_to, W.sort.keys_in, W.sort.vals_in, n_rows, (const float*)nullptr, 0u, W.cnt_tab, 0,
+                     W.perm_q, W.tile_comp_q, 32u * Q.T_q);
+  hipLaunchKernelGGL(order_meta_kernel, dim3(1), dim3(1024), 0, stream, W.hdr, W.comp, (const uint32_t*)W.cnt_tab, kb_q, W.start_q,
+                     W.range_q, W.base_q, Q.n_q, Q.group_rows, 0, 0.0f, n_cols);
+  const SortRemap remap{W.start_q, W.base_q, (uint32_t)kMaxComp, W.tile_comp_q};
+  if (int rc = W.sort.run(W.perm_q, Q.n_q, stream, fine_bits, &remap)) return rc;
+  hipLaunchKernelGGL(order_rows2_kernel, dim3((32 * Q.T_q + 255) / 256), blk, order_rows_smem_set(n_cols), stream, d_coords, n_cols,
+                     L.NM, (const uint32_t*)W.perm_q, Q.T_q, (float*)nullptr, (float4*)(p + L.off_box_q), (const float*)nullptr,
+                     (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (const uint32_t*)W.tile_comp_q, W.origins, W.hdr,
+                     (uint4*)nullptr, 0, (float*)nullptr, (uint4*)(p + L.off_img_q), (float*)(p + L.off_norm_q), 1u,
+                     QSeg{1u, 0u, 1u}, (unsigned long long*)nullptr, (uint32_t*)nullptr, 0u);
+  return 0;
+}
+
 static void pop_pruned_one(const PopPlan& plan, const float* d_coords, uint32_t n_rows, uint32_t n_cols,
                            const QuerySel& qs, const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws,
                            const EdgeSink* sink_in, hipStream_t stream, float r2_scale, bool prep, bool comp_clean) {
   // prep == false: the orderings, images and boxes of the previous call (same coordinates, same query
   // selection) are still in the workspace -- the further radii of one populations call
-  const uint32_t i_from = qs.i_from, i_to = qs.i_to;
   const Layout L = make_layout(n_rows, n_cols);
-  char* p = (char*)d_ws;
-  uint32_t* hdr = (uint32_t*)p;
-  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
-  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
-  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
-  uint32_t* perm_p = (uint32_t*)(p + L.off_perm_p);
-  uint32_t* perm_q = (uint32_t*)(p + L.off_perm_q);
-  uint32_t* comp = (uint32_t*)(p + L.off_comp);
-  uint32_t* tile_comp = (uint32_t*)(p + L.off_tile_comp);
-  uint32_t* tile_comp_q = (uint32_t*)(p + L.off_tile_comp_q);
-  const float* origins = (const float*)(comp + kCompOrigin);
-  constexpr float kCellFramesHere = kPopCellFrames;
+  const PrunedWs W = pruned_ws(d_ws, L, n_rows);
+  char* p = W.p;
   const dim3 blk(256), grid_n((n_rows + 255) / 256);
-  const bool full = (i_from == 0 && i_to == n_rows);
-  uint32_t n_q = i_to - i_from;
-  int q_mode = full ? kQueryAll : kQueryOwnOrder;
-  QSeg q_seg{1u, 0u, 1u};
-  if (qs.n_segments > 0) {   // one segment of a sharded run: every n_segments-th query group of all rows
-    q_mode = kQueryAll;
-    n_q = n_rows;
-    q_seg = QSeg{qs.n_segments, qs.segment, seg_block(qs.n_segments)};
-  }
-  // The orders are PADDED: every component of the frames (dc_mfma_kernels.hpp "components") starts at a whole query
-  // group; the sort's last pass writes its values straight to the padded positions (SortRemap: segment starts -> bases),
-  // the pad positions in between keep the kInvalidFrame that order_meta_kernel's presets left there.
-  const uint32_t tq = plan.group_tiles, group_rows = 32u * tq;
-  const uint32_t T_r = (n_rows + (uint32_t)kMaxComp * (group_rows - 1u) + 31u) / 32u;
-  const uint32_t T_q = (n_q + (uint32_t)kMaxComp * (group_rows - 1u) + 31u) / 32u;
-  const size_t tmp_bytes = sort_temp_bytes(n_rows + kOrderPadRows);
+  // (the padded orders are laid out for the plan's query groups)
+  const QueryPlan Q = query_plan(qs, n_rows, plan.group_tiles);
+  const uint32_t T_r = Q.T_r;
   const float r_max = sqrtf(fmaxf(r2_scale, 0.0f)) * 1.0001f;
   // connectivity length of the components: the largest radius itself for the sweeps that list pairs (no pair between
   // components), half of it for the plain sweeps (pairs between adjacent components: pop_cross_kernel)
   const float r_conn = sink_in ? r_max : 0.5f * r_max;
   // (the cells of all components are numbered consecutively: fewer than 2^fine_bits keys)
   const unsigned fine_bits = cell_key_bits(n_rows, kPopCellFrames) + 1u;
-  const unsigned key_bits = fine_bits;
   EdgeSink sink_local;
   const EdgeSink* sink = sink_in;
   if (sink_in && sink_in->best) {   // (component ids and ranks in the sweep's order: gathered below)
     sink_local = *sink_in;
-    sink_local.comp = keys_in;
-    sink_local.rank = keys_out;
+    sink_local.comp = W.sort.keys_in;
+    sink_local.rank = W.sort.keys_out;
     sink = &sink_local;
   }
   // the counts by position of the one-radius symmetric per-wave sweep (the pq region): cleared by this call's preparation
@@ -1389,76 +1477,47 @@ static void pop_pruned_one(const PopPlan& plan, const float* d_coords, uint32_t 
   if (prep) {
     // (round 5: the passes of dc_prep.hpp -- twelve launches for the thirty of rounds 3 - 4, same values)
     const uint32_t cookie = data_cookie(d_coords, n_rows, n_cols);
-    uint32_t* start_r = comp + kCompStart, *start_q = comp + kCompStart + (kMaxComp + 1);
-    uint32_t* range_r = comp + kCompRange, *range_q = comp + kCompRange + kCompRangeStride;
-    uint32_t* base_r = comp + kCompBase, *base_q = comp + kCompBase + (kMaxComp + 1);
     // components of the frames for this call's largest radius, their origins, the column means and the fine grids
-    if (!comp_clean) (void)hipMemsetAsync(comp, 0, sizeof(uint32_t) * kCompWords, stream);
-    hipLaunchKernelGGL(fine_mark_kernel, grid_n, blk, 0, stream, d_coords, n_rows, n_cols, (const uint32_t*)hdr, r_conn,
-                       comp);
-    hipLaunchKernelGGL(components_kernel, dim3(1), dim3(1024), components_smem(), stream, (const uint32_t*)hdr,
-                       (const float*)(p + kHdrMeans), n_cols, r_conn, n_rows, kPopCellFrames, fine_bits, comp,
+    if (!comp_clean) (void)hipMemsetAsync(W.comp, 0, sizeof(uint32_t) * kCompWords, stream);
+    hipLaunchKernelGGL(fine_mark_kernel, grid_n, blk, 0, stream, d_coords, n_rows, n_cols, (const uint32_t*)W.hdr, r_conn,
+                       W.comp);
+    hipLaunchKernelGGL(components_kernel, dim3(1), dim3(1024), components_smem(), stream, (const uint32_t*)W.hdr,
+                       (const float*)(p + kHdrMeans), n_cols, r_conn, n_rows, kPopCellFrames, fine_bits, W.comp,
                        components_off() ? 1 : 0, r_max, cookie, (const double*)(p + L.fixed_end), cell_frames(false));
-    // order all frames by (component, fine cell): keys, rows per component, the extents, the pad presets ...
-    const uint32_t kb_r = std::min<uint32_t>((std::max(n_rows, 32u * T_r) + 255) / 256, 1024u);
-    uint32_t* cnt_tab = (uint32_t*)(p + L.fixed_end);   // (rows per component and block: the sort's temp region, free until the sort)
-    hipLaunchKernelGGL(order_key_kernel, dim3(kb_r), blk, order_key_smem_set(n_cols), stream, d_coords, n_cols, hdr,
-                       (const uint32_t*)comp, (uint32_t)fine_bits, 0u, n_rows, keys_in, vals_in, n_rows, (const float*)nullptr, 0u,
-                       cnt_tab, 1, perm_p, tile_comp, 32u * T_r);
-    // ... where the components start, the scale of the sweep (it follows the components' extents) ...
-    hipLaunchKernelGGL(order_meta_kernel, dim3(1), dim3(1024), 0, stream, hdr, comp, (const uint32_t*)cnt_tab, kb_r, start_r, range_r,
-                       base_r, n_rows, group_rows, 1, fmaxf(r2_scale, 0.0f), n_cols, plan.shift_steps);
-    // ... the sort, whose last pass moves every component to a whole query group of the padded order ...
-    {
-      const SortRemap remap{start_r, base_r, (uint32_t)kMaxComp, tile_comp};
-      if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_p, n_rows, p + L.fixed_end, tmp_bytes, stream, key_bits, &remap))
-        return;
-    }
+    // all frames by (component, fine cell), into the padded order ...
+    if (order_refs(W, Q, d_coords, n_rows, n_cols, fine_bits, nullptr, 0u, fine_bits, fmaxf(r2_scale, 0.0f), plan.shift_steps,
+                   stream))
+      return;
     // ... and the rows in that order (the deferred exact path reads them without a permutation look-up), the tile boxes
     // and the operand images: A form of every tile, B form of the query groups of this segment (queries in the
     // reference order)
     {
-      const bool ref_queries = q_mode != kQueryOwnOrder;
+      const bool ref_queries = Q.q_mode != kQueryOwnOrder;
       hipLaunchKernelGGL(order_rows2_kernel, dim3((32 * T_r + 255) / 256), blk, order_rows_smem_set(n_cols), stream, d_coords, n_cols,
-                         L.NM, (const uint32_t*)perm_p, T_r, (float*)(p + L.off_coords_p), (float4*)(p + L.off_box_p),
-                         (const float*)nullptr, (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (const uint32_t*)tile_comp,
-                         origins, hdr, (uint4*)(p + L.off_img_p), 0, (float*)(p + L.off_norm_p),
-                         ref_queries ? (uint4*)(p + L.off_img_q) : (uint4*)nullptr, (float*)nullptr, tq, q_seg,
-                         (unsigned long long*)(comp + kCompHash), pos_clean ? (uint32_t*)(p + L.off_pq) : (uint32_t*)nullptr, 1u);
+                         L.NM, (const uint32_t*)W.perm_p, T_r, (float*)(p + L.off_coords_p), (float4*)(p + L.off_box_p),
+                         (const float*)nullptr, (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (const uint32_t*)W.tile_comp,
+                         W.origins, W.hdr, (uint4*)(p + L.off_img_p), 0, (float*)(p + L.off_norm_p),
+                         ref_queries ? (uint4*)(p + L.off_img_q) : (uint4*)nullptr, (float*)nullptr, plan.group_tiles, Q.q_seg,
+                         (unsigned long long*)(W.comp + kCompHash), pos_clean ? (uint32_t*)(p + L.off_pq) : (uint32_t*)nullptr, 1u);
     }
     // lightest-outgoing-pair variant: component ids and ranks in the sweep's order (the sort's key
     // buffers are free again)
     if (sink_in && sink_in->best) {
       hipLaunchKernelGGL(gather_u32_kernel, dim3((32 * T_r + 255) / 256), blk, 0, stream, sink_in->comp,
-                         (const uint32_t*)perm_p, 32u * T_r, keys_in);
+                         (const uint32_t*)W.perm_p, 32u * T_r, W.sort.keys_in);
       hipLaunchKernelGGL(gather_u32_kernel, dim3((32 * T_r + 255) / 256), blk, 0, stream, sink_in->rank,
-                         (const uint32_t*)perm_p, 32u * T_r, keys_out);
+                         (const uint32_t*)W.perm_p, 32u * T_r, W.sort.keys_out);
     }
-    if (q_mode == kQueryOwnOrder) {
-      // query rows of this call: the same ordering restricted to [i_from, i_to)
-      const uint32_t kb_q = std::min<uint32_t>((std::max(n_q, 32u * T_q) + 255) / 256, 1024u);
-      hipLaunchKernelGGL(order_key_kernel, dim3(kb_q), blk, 0, stream, d_coords, n_cols, hdr,
-                         (const uint32_t*)comp, (uint32_t)fine_bits, i_from, i_to, keys_in, vals_in, n_rows, (const float*)nullptr, 0u,
-                         cnt_tab, 0, perm_q, tile_comp_q, 32u * T_q);
-      hipLaunchKernelGGL(order_meta_kernel, dim3(1), dim3(1024), 0, stream, hdr, comp, (const uint32_t*)cnt_tab, kb_q, start_q, range_q,
-                         base_q, n_q, group_rows, 0, 0.0f, n_cols);
-      const SortRemap remap{start_q, base_q, (uint32_t)kMaxComp, tile_comp_q};
-      if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_q, n_q, p + L.fixed_end, tmp_bytes, stream, key_bits, &remap))
-        return;
-      hipLaunchKernelGGL(order_rows2_kernel, dim3((32 * T_q + 255) / 256), blk, order_rows_smem_set(n_cols), stream, d_coords, n_cols,
-                         L.NM, (const uint32_t*)perm_q, T_q, (float*)nullptr, (float4*)(p + L.off_box_q),
-                         (const float*)nullptr, (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (const uint32_t*)tile_comp_q,
-                         origins, hdr, (uint4*)nullptr, 0, (float*)nullptr, (uint4*)(p + L.off_img_q), (float*)(p + L.off_norm_q), 1u,
-                         QSeg{1u, 0u, 1u}, (unsigned long long*)nullptr, (uint32_t*)nullptr, 0u);
-    }
+    if (Q.q_mode == kQueryOwnOrder &&
+        order_own_queries(W, L, Q, d_coords, n_rows, n_cols, fine_bits, qs.i_from, qs.i_to, stream))
+      return;
   }
-  (void)kCellFramesHere;
-  const uint32_t n_pos_q = 32u * ((q_mode == kQueryOwnOrder) ? T_q : T_r);
+  const uint32_t n_pos_q = 32u * ((Q.q_mode == kQueryOwnOrder) ? Q.T_q : T_r);
   switch (nm_for((int)n_cols)) {
 #define X(SV)                                                                                 \
   case SV:                                                                                    \
     if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                      \
-      pop_pruned_step_##SV(plan, d_coords, n_rows, n_cols, d_ws, T_r, n_pos_q, q_mode, q_seg, rad2, n_rad, \
+      pop_pruned_step_##SV(plan, d_coords, n_rows, n_cols, d_ws, T_r, n_pos_q, Q.q_mode, Q.q_seg, rad2, n_rad, \
                            d_pops, sink, stream, pos_clean);                                  \
     break;
     DC_FOR_EACH_S(X)
@@ -1724,36 +1783,16 @@ __global__ void nn_cross_write_kernel(const uint32_t* __restrict__ hdr, const ui
 static void nn_pruned_sel(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe,
                           const QuerySel& qs, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                           float* d_hd_d2, void* d_ws, hipStream_t stream, bool reuse_components, bool comp_clean) {
-  const uint32_t i_from = qs.i_from, i_to = qs.i_to;
   const Layout L = make_layout(n_rows, n_cols);
-  char* p = (char*)d_ws;
-  uint32_t* hdr = (uint32_t*)p;
-  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
-  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
-  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
-  uint32_t* perm_p = (uint32_t*)(p + L.off_perm_p);
-  uint32_t* perm_q = (uint32_t*)(p + L.off_perm_q);
-  uint32_t* comp = (uint32_t*)(p + L.off_comp);
-  uint32_t* tile_comp = (uint32_t*)(p + L.off_tile_comp);
-  uint32_t* tile_comp_q = (uint32_t*)(p + L.off_tile_comp_q);
-  const float* origins = (const float*)(comp + kCompOrigin);
+  const PrunedWs W = pruned_ws(d_ws, L, n_rows);
+  char* p = W.p;
   const dim3 blk(256), grid_n((n_rows + 255) / 256);
-  const size_t tmp_bytes = sort_temp_bytes(n_rows + kOrderPadRows);
-  const bool full = (i_from == 0 && i_to == n_rows);
-  uint32_t n_q = i_to - i_from;
-  int q_mode = full ? kQueryAll : kQueryOwnOrder;
-  QSeg q_seg{1u, 0u, 1u};
-  if (qs.n_segments > 0) {   // one segment of a sharded run: every n_segments-th query group of all rows
-    q_mode = kQueryAll;
-    n_q = n_rows;
-    q_seg = QSeg{qs.n_segments, qs.segment, seg_block(qs.n_segments)};
-  }
   // (query tiles per group: a wave's, or with the shared-operand sweep the workgroup's; the orders are padded so that
-  //  every component starts at a whole group -- see pop_pruned_one)
+  //  every component starts at a whole group -- see query_plan)
   const NnPlan plan = plan_nn(n_rows, n_cols, sweep_switches());
-  const uint32_t tq = plan.group_tiles, group_rows = 32u * tq;
-  const uint32_t T_r = (n_rows + (uint32_t)kMaxComp * (group_rows - 1u) + 31u) / 32u;
-  const uint32_t T_q = (n_q + (uint32_t)kMaxComp * (group_rows - 1u) + 31u) / 32u;
+  const QueryPlan Q = query_plan(qs, n_rows, plan.group_tiles);
+  const uint32_t T_r = Q.T_r;
+  const bool own = Q.q_mode == kQueryOwnOrder;
   // ordering key: (cell number over all components, quantised free energy) in whole sort passes
   const unsigned fine_bits = cell_key_bits(n_rows, kNnCellFrames) + 1u;
   const unsigned key_bits = (fine_bits + 9u <= 24u) ? 24u : 32u;
@@ -1762,9 +1801,6 @@ static void nn_pruned_sel(const float* d_coords, uint32_t n_rows, uint32_t n_col
   if (sweep_switches().nn_fe_bits >= 0) fe_bits = std::min((unsigned)sweep_switches().nn_fe_bits, fe_bits);
   const float r_conn = -8.0f;   // components: connected over 8 cells of the ordering (no radius in this sweep)
   const uint32_t cookie = data_cookie(d_coords, n_rows, n_cols);
-  uint32_t* start_r = comp + kCompStart, *start_q = comp + kCompStart + (kMaxComp + 1);
-  uint32_t* range_r = comp + kCompRange, *range_q = comp + kCompRange + kCompRangeStride;
-  uint32_t* base_r = comp + kCompBase, *base_q = comp + kCompBase + (kMaxComp + 1);
   if (reuse_components) {
     // the partition an earlier sweep over these coordinates left in the workspace (DC_FLAG_STATS_VALID: the
     // populations -> neighbours pair): checked on the device, with the range of the free energies and the fine grids of THIS
@@ -1772,62 +1808,37 @@ static void nn_pruned_sel(const float* d_coords, uint32_t n_rows, uint32_t n_col
   } else {
     // the pass over the free energies finds their range (and raises the flag for NaNs)
     hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>(grid_n.x, 256u)), blk, 0, stream, d_fe, n_rows, (uint32_t*)nullptr,
-                       (uint32_t*)nullptr, hdr);
-    if (!comp_clean) (void)hipMemsetAsync(comp, 0, sizeof(uint32_t) * kCompWords, stream);
-    hipLaunchKernelGGL(fine_mark_kernel, grid_n, blk, 0, stream, d_coords, n_rows, n_cols, (const uint32_t*)hdr, r_conn, comp);
-    hipLaunchKernelGGL(components_kernel, dim3(1), dim3(1024), components_smem(), stream, (const uint32_t*)hdr,
-                       (const float*)(p + kHdrMeans), n_cols, r_conn, n_rows, kNnCellFrames, fine_bits, comp,
+                       (uint32_t*)nullptr, W.hdr);
+    if (!comp_clean) (void)hipMemsetAsync(W.comp, 0, sizeof(uint32_t) * kCompWords, stream);
+    hipLaunchKernelGGL(fine_mark_kernel, grid_n, blk, 0, stream, d_coords, n_rows, n_cols, (const uint32_t*)W.hdr, r_conn, W.comp);
+    hipLaunchKernelGGL(components_kernel, dim3(1), dim3(1024), components_smem(), stream, (const uint32_t*)W.hdr,
+                       (const float*)(p + kHdrMeans), n_cols, r_conn, n_rows, kNnCellFrames, fine_bits, W.comp,
                        components_off() ? 1 : 0, 0.0f, cookie, (const double*)(p + L.fixed_end), cell_frames(true));
   }
   // frames by (component, cell, free energy): ONE sort on a combined key, its last pass writes the padded order
-  const uint32_t kb_r = std::min<uint32_t>((std::max(n_rows, 32u * T_r) + 255) / 256, 1024u);
-  uint32_t* cnt_tab = (uint32_t*)(p + L.fixed_end);   // (rows per component and block: the sort's temp region, free until the sort)
-  hipLaunchKernelGGL(order_key_kernel, dim3(kb_r), blk, order_key_smem_set(n_cols), stream, d_coords, n_cols, hdr,
-                     (const uint32_t*)comp, (uint32_t)fine_bits, 0u, n_rows, keys_in, vals_in, n_rows, d_fe, (uint32_t)fe_bits, cnt_tab, 1,
-                     perm_p, tile_comp, 32u * T_r);
-  hipLaunchKernelGGL(order_meta_kernel, dim3(1), dim3(1024), 0, stream, hdr, comp, (const uint32_t*)cnt_tab, kb_r, start_r, range_r,
-                     base_r, n_rows, group_rows, 1, -1.0f, n_cols);   // (the neighbour scale)
-  {
-    const SortRemap remap{start_r, base_r, (uint32_t)kMaxComp, tile_comp};
-    if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_p, n_rows, p + L.fixed_end, tmp_bytes, stream, fine_bits + fe_bits, &remap))
-      return;
-  }
+  if (order_refs(W, Q, d_coords, n_rows, n_cols, fine_bits, d_fe, fe_bits, fine_bits + fe_bits, -1.0f /* the neighbour scale */,
+                 0, stream))
+    return;
   const float* coords_p = (const float*)(p + L.off_coords_p);
   // rows, boxes, free-energy ranges, and the operand images: the neighbour sweeps take the reference norms through the
   // operand image (dc_mfma_kernels.hpp "reference norms folded": a_form 2), the queries' B form for this segment's groups
   {
-    const bool ref_queries = q_mode != kQueryOwnOrder;
     hipLaunchKernelGGL(order_rows2_kernel, dim3((32 * T_r + 255) / 256), blk, order_rows_smem_set(n_cols), stream, d_coords, n_cols,
-                       L.NM, (const uint32_t*)perm_p, T_r, (float*)(p + L.off_coords_p), (float4*)(p + L.off_box_p), d_fe,
+                       L.NM, (const uint32_t*)W.perm_p, T_r, (float*)(p + L.off_coords_p), (float4*)(p + L.off_box_p), d_fe,
                        (float*)(p + L.off_fe_s), (uint32_t*)(p + L.off_invpos), (float2*)(p + L.off_ferange_p),
-                       (const uint32_t*)tile_comp, origins, hdr, (uint4*)(p + L.off_img_p), 2, (float*)(p + L.off_norm_p),
-                       ref_queries ? (uint4*)(p + L.off_img_q) : (uint4*)nullptr, (float*)nullptr, tq, q_seg,
-                         (unsigned long long*)(comp + kCompHash), (uint32_t*)nullptr, 0u);
+                       (const uint32_t*)W.tile_comp, W.origins, W.hdr, (uint4*)(p + L.off_img_p), 2, (float*)(p + L.off_norm_p),
+                       own ? (uint4*)nullptr : (uint4*)(p + L.off_img_q), (float*)nullptr, plan.group_tiles, Q.q_seg,
+                       (unsigned long long*)(W.comp + kCompHash), (uint32_t*)nullptr, 0u);
   }
-  if (q_mode == kQueryOwnOrder) {
-    // query rows of this call: the cell ordering restricted to [i_from, i_to)
-    const uint32_t kb_q = std::min<uint32_t>((std::max(n_q, 32u * T_q) + 255) / 256, 1024u);
-    hipLaunchKernelGGL(order_key_kernel, dim3(kb_q), blk, 0, stream, d_coords, n_cols, hdr,
-                       (const uint32_t*)comp, (uint32_t)fine_bits, i_from, i_to, keys_in, vals_in, n_rows, (const float*)nullptr, 0u,
-                       cnt_tab, 0, perm_q, tile_comp_q, 32u * T_q);
-    hipLaunchKernelGGL(order_meta_kernel, dim3(1), dim3(1024), 0, stream, hdr, comp, (const uint32_t*)cnt_tab, kb_q, start_q, range_q,
-                       base_q, n_q, group_rows, 0, 0.0f, n_cols);
-    const SortRemap remap{start_q, base_q, (uint32_t)kMaxComp, tile_comp_q};
-    if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_q, n_q, p + L.fixed_end, tmp_bytes, stream, fine_bits, &remap))
-      return;
-    hipLaunchKernelGGL(order_rows2_kernel, dim3((32 * T_q + 255) / 256), blk, order_rows_smem_set(n_cols), stream, d_coords, n_cols,
-                       L.NM, (const uint32_t*)perm_q, T_q, (float*)nullptr, (float4*)(p + L.off_box_q), (const float*)nullptr,
-                       (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (const uint32_t*)tile_comp_q, origins, hdr,
-                       (uint4*)nullptr, 0, (float*)nullptr, (uint4*)(p + L.off_img_q), (float*)(p + L.off_norm_q), 1u,
-                       QSeg{1u, 0u, 1u}, (unsigned long long*)nullptr, (uint32_t*)nullptr, 0u);
-  }
-  const bool own = q_mode == kQueryOwnOrder;
-  const uint32_t n_pos_q = 32u * (own ? T_q : T_r);
+  // query rows of this call: the cell ordering restricted to [i_from, i_to)
+  if (own && order_own_queries(W, L, Q, d_coords, n_rows, n_cols, fine_bits, qs.i_from, qs.i_to, stream))
+    return;
+  const uint32_t n_pos_q = 32u * (own ? Q.T_q : T_r);
   switch (nm_for((int)n_cols)) {
 #define X(SV)                                                                                   \
   case SV:                                                                                      \
     if ((DC_STEP_MASK >> (SV - 1)) & 1u)                                                        \
-      nn_pruned_step_##SV(plan, d_coords, n_rows, n_cols, d_fe, d_ws, T_r, n_pos_q, q_mode, q_seg, -1.0f, \
+      nn_pruned_step_##SV(plan, d_coords, n_rows, n_cols, d_fe, d_ws, T_r, n_pos_q, Q.q_mode, Q.q_seg, -1.0f, \
                           d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream);                        \
     break;
     DC_FOR_EACH_S(X)
@@ -1838,20 +1849,20 @@ static void nn_pruned_sel(const float* d_coords, uint32_t n_rows, uint32_t n_col
   // what lies in other components than the query: exact, for the few queries that can have a neighbour there (listed
   // in the sort's key buffer; their incumbents go through the merge buffer, both free again; the counter is header
   // word kHdrOpen, zeroed by scale_kernel)
-  uint32_t* open_list = keys_in;
-  uint32_t* open_count = hdr + kHdrOpen;
+  uint32_t* open_list = W.sort.keys_in;
+  uint32_t* open_count = W.hdr + kHdrOpen;
   unsigned long long* merge64 = (unsigned long long*)(p + L.off_merge64);
-  const uint32_t n_items = own ? 32u * T_q : n_rows;
+  const uint32_t n_items = own ? 32u * Q.T_q : n_rows;
   hipLaunchKernelGGL(nn_open_kernel, dim3((n_items + 255) / 256), blk, 0, stream, d_coords, n_rows, n_cols, d_fe,
-                     (const uint32_t*)(p + L.off_invpos), own ? (const uint32_t*)perm_q : (const uint32_t*)nullptr, n_items,
-                     (const uint32_t*)comp, 32u * tq, q_seg, (const uint32_t*)hdr, (const float*)d_nn_d2,
+                     (const uint32_t*)(p + L.off_invpos), own ? (const uint32_t*)W.perm_q : (const uint32_t*)nullptr, n_items,
+                     (const uint32_t*)W.comp, Q.group_rows, Q.q_seg, (const uint32_t*)W.hdr, (const float*)d_nn_d2,
                      (const float*)d_hd_d2, (const uint32_t*)d_nn_idx, (const uint32_t*)d_hd_idx,
                      merge64, open_list, open_count);
   hipLaunchKernelGGL(nn_cross_kernel, dim3(8192), dim3(64), 0, stream, d_coords, n_rows, n_cols, d_fe, coords_p,
-                     (const uint32_t*)perm_p, (const float4*)(p + L.off_box_p), (const float2*)(p + L.off_ferange_p),
-                     (const float*)(p + L.off_fe_s), (const uint32_t*)comp, (const uint32_t*)hdr,
+                     (const uint32_t*)W.perm_p, (const float4*)(p + L.off_box_p), (const float2*)(p + L.off_ferange_p),
+                     (const float*)(p + L.off_fe_s), (const uint32_t*)W.comp, (const uint32_t*)W.hdr,
                      (const uint32_t*)open_list, (const uint32_t*)open_count, T_r, merge64);
-  hipLaunchKernelGGL(nn_cross_write_kernel, dim3(64), blk, 0, stream, (const uint32_t*)hdr, (const uint32_t*)comp,
+  hipLaunchKernelGGL(nn_cross_write_kernel, dim3(64), blk, 0, stream, (const uint32_t*)W.hdr, (const uint32_t*)W.comp,
                      (const uint32_t*)open_list, (const uint32_t*)open_count, (const unsigned long long*)merge64, n_rows,
                      d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
 }
@@ -2013,12 +2024,9 @@ void launch_nn_mfma(const float* d_coords, uint32_t n_rows, uint32_t n_cols, con
   char* p = (char*)d_ws;
   hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)p, -1.0f, n_cols);   // the neighbour scale
   image(d_coords, n_rows, n_cols, L.NM, L.T, nullptr, 1, p + L.off_img_b, p + L.off_norm, d_ws, stream);   // queries
-  const FeOrder B{(uint32_t*)(p + L.off_keys_in), (uint32_t*)(p + L.off_keys_out), (uint32_t*)(p + L.off_vals_in),
-                  (uint32_t*)(p + L.off_perm),    (uint32_t*)(p + L.off_invpos),   (uint32_t*)(p + L.off_pq),
-                  (float*)(p + L.off_fe_s),       p + L.fixed_end};
-  if (order_by_fe(d_coords, n_rows, n_cols, L.NM, L.T, d_fe, d_fe, n_rows, B, p + L.off_img_s, p + L.off_norm_s, d_ws,
-                  stream) != 0)
-    return;
+  const FeOrder B = fe_order(d_ws, L, L.fixed_end, n_rows);
+  if (order_by_fe(n_rows, L.T, d_fe, d_fe, n_rows, B, d_ws, stream) != 0) return;
+  image(d_coords, n_rows, n_cols, L.NM, L.T, B.perm, 0, p + L.off_img_s, p + L.off_norm_s, d_ws, stream);
   const SweepArgs X{d_coords, d_coords, n_rows, n_rows, L.T, L.T, (const uint4*)(p + L.off_img_s),
                     (const float*)(p + L.off_norm_s), (const uint4*)(p + L.off_img_b), (const float*)(p + L.off_norm),
                     B.perm, B.invpos, B.pq, (const uint32_t*)p};
@@ -2085,6 +2093,14 @@ static int cross_prepare(const float* d_query, uint32_t n_q, const float* d_ref,
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// ... and the scale of the sweep on them: r2max is the largest squared radius of the call, -1 the neighbour scale
+static int cross_prepare_scaled(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                                float r2max, void* d_ws, hipStream_t stream) {
+  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
+  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)d_ws, r2max, n_cols);
+  return 0;
+}
+
 static SweepArgs against_args(const float* d_query, uint32_t n_q, const float* d_ref, uint32_t n_ref, void* d_ws,
                               const CrossLayout& L, bool with_pq) {
   char* p = (char*)d_ws;
@@ -2099,8 +2115,7 @@ int launch_pop_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref
                           hipStream_t stream) {
   const CrossLayout L = make_cross_layout(n_q, n_ref, n_cols);
   char* p = (char*)d_ws;
-  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
-  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)d_ws, max_radius2(rad2, n_rad), n_cols);
+  if (int rc = cross_prepare_scaled(d_query, n_q, d_ref, n_ref, n_cols, max_radius2(rad2, n_rad), d_ws, stream)) return rc;
   image(d_ref, n_ref, n_cols, L.NM, L.T_r, nullptr, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
   image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
   pop_mfma_steps(against_args(d_query, n_q, d_ref, n_ref, d_ws, L, false), kAgainst, n_cols, i_from, i_to, rad2, n_rad,
@@ -2115,33 +2130,71 @@ int launch_pop_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref
 // for the longer of the two sets.  So the every-pair sweep, which answers where this one cannot, fits the same
 // workspace by construction.
 struct AgainstLayout {
-  uint32_t T_q, T_r, NM;
-  size_t off_img_r, off_norm_r, off_perm_r, off_box_r, off_coords_r, off_img_q, off_norm_q, off_perm_q, off_box_q,
-      off_keys_in, off_keys_out, off_vals_in, off_sort, total;
+  CrossLayout C;   // T_q, T_r, NM, the images and norms of both sets; C.off_perm is R's permutation
+  size_t off_box_r, off_coords_r, off_perm_q, off_box_q, off_keys_in, off_keys_out, off_vals_in, off_sort, total;
 };
 static AgainstLayout make_against_layout(size_t n_q, size_t n_ref, size_t n_cols) {
-  const CrossLayout C = make_cross_layout(n_q, n_ref, n_cols);
   AgainstLayout L;
-  L.T_q = C.T_q;
-  L.T_r = C.T_r;
-  L.NM = C.NM;
-  const size_t rows_q = align256(sizeof(float) * 32 * (size_t)L.T_q);
-  const size_t rows_s = std::max(align256(sizeof(float) * 32 * (size_t)L.T_r), rows_q);
-  L.off_img_r = C.off_img_r;
-  L.off_norm_r = C.off_norm_r;
-  L.off_img_q = C.off_img_q;
-  L.off_norm_q = C.off_norm_q;
-  L.off_perm_r = C.off_perm;
-  L.off_box_r = C.total;
-  L.off_coords_r = align256(L.off_box_r + sizeof(float) * 4 * (size_t)L.T_r);
-  L.off_perm_q = align256(L.off_coords_r + sizeof(float) * 32 * (size_t)L.T_r * n_cols);
+  L.C = make_cross_layout(n_q, n_ref, n_cols);
+  const size_t rows_q = align256(sizeof(float) * 32 * (size_t)L.C.T_q);
+  const size_t rows_s = std::max(align256(sizeof(float) * 32 * (size_t)L.C.T_r), rows_q);
+  L.off_box_r = L.C.total;
+  L.off_coords_r = align256(L.off_box_r + sizeof(float) * 4 * (size_t)L.C.T_r);
+  L.off_perm_q = align256(L.off_coords_r + sizeof(float) * 32 * (size_t)L.C.T_r * n_cols);
   L.off_box_q = L.off_perm_q + rows_q;
-  L.off_keys_in = align256(L.off_box_q + sizeof(float) * 4 * (size_t)L.T_q);
+  L.off_keys_in = align256(L.off_box_q + sizeof(float) * 4 * (size_t)L.C.T_q);
   L.off_keys_out = L.off_keys_in + rows_s;
   L.off_vals_in = L.off_keys_out + rows_s;
   L.off_sort = L.off_vals_in + rows_s;
   L.total = L.off_sort + align256(sort_temp_bytes(std::max(n_q, n_ref)));
   return L;
+}
+
+// One view of that workspace for a call that answers n_sel query rows: both sets in their cell orders
+struct AgainstWs {
+  uint32_t* hdr;
+  uint32_t T_r, T_q, NM;
+  SortBufs sort;   // (sized for the longer of the two sets)
+  uint32_t *perm_r, *perm_q;
+  uint4 *img_r, *img_q;
+  float *norm_r, *norm_q, *coords_r;
+  float4 *box_r, *box_q;
+};
+static AgainstWs against_ws(void* d_ws, const AgainstLayout& L, size_t n_sel, size_t n_ref) {
+  char* p = (char*)d_ws;
+  AgainstWs W;
+  W.hdr = (uint32_t*)p;
+  W.T_r = L.C.T_r;
+  W.T_q = L.C.T_q;
+  W.NM = L.C.NM;
+  W.sort = sort_bufs(d_ws, L, L.off_sort, sort_temp_bytes(std::max(n_sel, n_ref)));
+  W.perm_r = (uint32_t*)(p + L.C.off_perm);
+  W.perm_q = (uint32_t*)(p + L.off_perm_q);
+  W.img_r = (uint4*)(p + L.C.off_img_r);
+  W.img_q = (uint4*)(p + L.C.off_img_q);
+  W.norm_r = (float*)(p + L.C.off_norm_r);
+  W.norm_q = (float*)(p + L.C.off_norm_q);
+  W.coords_r = (float*)(p + L.off_coords_r);
+  W.box_r = (float4*)(p + L.off_box_r);
+  W.box_q = (float4*)(p + L.off_box_q);
+  return W;
+}
+
+// Ordering one set by the cell of the reference's one grid, in two pieces (the neighbour sweep adds the free energies to
+// R's keys in between).  The keys of rows [i_from, i_to) of d_set and the pad presets of perm [32 T] ...
+static void against_keys(const AgainstWs& W, const float* d_set, uint32_t n_cols, uint32_t n_ref, float frames_per_cell,
+                         uint32_t i_from, uint32_t i_to, uint32_t* perm, uint32_t T, hipStream_t stream) {
+  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * T + 255) / 256, 1024u)), dim3(256), 0, stream, d_set, n_cols,
+                     (const uint32_t*)W.hdr, n_ref, frames_per_cell, i_from, i_to, W.sort.keys_in, W.sort.vals_in, perm, 32u * T);
+}
+// ... then the order of those n rows, and in that order the tile boxes and (coords_o != nullptr: the exact path's) the
+// rows.  The operand image follows at the caller, in the form its sweep takes.  Non-zero when the sort failed.
+static int against_order(const AgainstWs& W, const float* d_set, uint32_t n, uint32_t n_cols, unsigned key_bits,
+                         uint32_t* perm, uint32_t T, float* coords_o, float4* boxes, hipStream_t stream) {
+  if (W.sort.run(perm, n, stream, key_bits)) return -3;
+  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * T + 255) / 256), dim3(256), 0, stream, d_set, n_cols, (const uint32_t*)perm, T,
+                     coords_o, boxes);
+  return 0;
 }
 
 // The queue of band pairs holds 24-bit reference positions (kPopQueuePosBits): a longer reference order takes the
@@ -2161,38 +2214,21 @@ int launch_pop_cross_pruned(const float* d_query, uint32_t n_q, const float* d_r
   if (!cross_pruned_takes(n_ref, n_cols))
     return launch_pop_cross_mfma(d_query, n_q, d_ref, n_ref, n_cols, i_from, i_to, rad2, n_rad, d_pops, d_ws, stream);
   const uint32_t n_sel = i_to - i_from;
-  const AgainstLayout L = make_against_layout(n_sel, n_ref, n_cols);   // (no larger than the layout of all n_q rows)
-  char* p = (char*)d_ws;
-  uint32_t* hdr = (uint32_t*)p;
-  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
-  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
-  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
-  uint32_t* perm_r = (uint32_t*)(p + L.off_perm_r);
-  uint32_t* perm_q = (uint32_t*)(p + L.off_perm_q);
+  // (no larger than the layout of all n_q rows)
+  const AgainstWs W = against_ws(d_ws, make_against_layout(n_sel, n_ref, n_cols), n_sel, n_ref);
   // one origin and one scale for both sets, exactly as the every-pair sweep
-  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
-  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, hdr, max_radius2(rad2, n_rad), n_cols);
+  if (int rc = cross_prepare_scaled(d_query, n_q, d_ref, n_ref, n_cols, max_radius2(rad2, n_rad), d_ws, stream)) return rc;
   const unsigned key_bits = cell_key_bits(n_ref, kPopCellFrames);
-  const size_t tmp_bytes = sort_temp_bytes(std::max(n_sel, n_ref));
-  const dim3 blk(256);
   // R: keys of the one grid, the order, its rows, boxes, A form and norms
-  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_r + 255) / 256, 1024u)), blk, 0, stream, d_ref, n_cols,
-                     (const uint32_t*)hdr, n_ref, cell_frames(false), 0u, n_ref, keys_in, vals_in, perm_r, 32u * L.T_r);
-  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_r, n_ref, p + L.off_sort, tmp_bytes, stream, key_bits)) return -3;
-  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * L.T_r + 255) / 256), blk, 0, stream, d_ref, n_cols,
-                     (const uint32_t*)perm_r, L.T_r, (float*)(p + L.off_coords_r), (float4*)(p + L.off_box_r));
-  image(d_ref, 32u * L.T_r, n_cols, L.NM, L.T_r, perm_r, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
+  against_keys(W, d_ref, n_cols, n_ref, cell_frames(false), 0u, n_ref, W.perm_r, W.T_r, stream);
+  if (int rc = against_order(W, d_ref, n_ref, n_cols, key_bits, W.perm_r, W.T_r, W.coords_r, W.box_r, stream)) return rc;
+  image(d_ref, 32u * W.T_r, n_cols, W.NM, W.T_r, W.perm_r, 0, W.img_r, W.norm_r, d_ws, stream);
   // Q: only the rows of the call, by the same key; B form, norms, boxes
-  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_q + 255) / 256, 1024u)), blk, 0, stream, d_query, n_cols,
-                     (const uint32_t*)hdr, n_ref, cell_frames(false), i_from, i_to, keys_in, vals_in, perm_q, 32u * L.T_q);
-  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_q, n_sel, p + L.off_sort, tmp_bytes, stream, key_bits)) return -3;
-  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * L.T_q + 255) / 256), blk, 0, stream, d_query, n_cols,
-                     (const uint32_t*)perm_q, L.T_q, (float*)nullptr, (float4*)(p + L.off_box_q));
-  image(d_query, 32u * L.T_q, n_cols, L.NM, L.T_q, perm_q, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
-  const AgainstArgs A{d_query, (const uint4*)(p + L.off_img_r), (const float*)(p + L.off_norm_r),
-                      (const float4*)(p + L.off_box_r), (const float*)(p + L.off_coords_r), (const uint4*)(p + L.off_img_q),
-                      (const float*)(p + L.off_norm_q), perm_q, (const float4*)(p + L.off_box_q), L.T_r, L.T_q, n_q,
-                      (const uint32_t*)hdr, (unsigned long long*)(p + 8)};
+  against_keys(W, d_query, n_cols, n_ref, cell_frames(false), i_from, i_to, W.perm_q, W.T_q, stream);
+  if (int rc = against_order(W, d_query, n_sel, n_cols, key_bits, W.perm_q, W.T_q, nullptr, W.box_q, stream)) return rc;
+  image(d_query, 32u * W.T_q, n_cols, W.NM, W.T_q, W.perm_q, 1, W.img_q, W.norm_q, d_ws, stream);
+  const AgainstArgs A{d_query, W.img_r, W.norm_r, W.box_r, W.coords_r, W.img_q, W.norm_q, W.perm_q, W.box_q, W.T_r, W.T_q, n_q,
+                      (const uint32_t*)W.hdr, (unsigned long long*)((char*)d_ws + 8)};
   // one radius at a time on the one preparation, whose scale serves the largest
   for (int r = 0; r < n_rad; ++r) pop_against_sweep(A, n_cols, single_radius(rad2, r), d_pops + (size_t)r * n_q, stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -2203,14 +2239,10 @@ int launch_nn_cross_mfma(const float* d_query, uint32_t n_q, const float* d_ref,
                          float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t stream) {
   const CrossLayout L = make_cross_layout(n_q, n_ref, n_cols);
   char* p = (char*)d_ws;
-  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
-  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, (uint32_t*)p, -1.0f, n_cols);   // the neighbour scale
-  const FeOrder B{(uint32_t*)(p + L.off_keys_in), (uint32_t*)(p + L.off_keys_out), (uint32_t*)(p + L.off_vals_in),
-                  (uint32_t*)(p + L.off_perm),    (uint32_t*)(p + L.off_invpos),   (uint32_t*)(p + L.off_pq),
-                  (float*)(p + L.off_fe_s),       p + L.off_sort};
-  if (int rc = order_by_fe(d_ref, n_ref, n_cols, L.NM, L.T_r, d_fe_r, d_fe_q, n_q, B, p + L.off_img_r,
-                           p + L.off_norm_r, d_ws, stream))
-    return rc;
+  if (int rc = cross_prepare_scaled(d_query, n_q, d_ref, n_ref, n_cols, -1.0f, d_ws, stream)) return rc;
+  const FeOrder B = fe_order(d_ws, L, L.off_sort, n_ref);
+  if (int rc = order_by_fe(n_ref, L.T_r, d_fe_r, d_fe_q, n_q, B, d_ws, stream)) return rc;
+  image(d_ref, n_ref, n_cols, L.NM, L.T_r, B.perm, 0, p + L.off_img_r, p + L.off_norm_r, d_ws, stream);
   image(d_query, n_q, n_cols, L.NM, L.T_q, nullptr, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
   nn_mfma_steps(against_args(d_query, n_q, d_ref, n_ref, d_ws, L, d_fe_q != nullptr), kAgainst, n_cols, i_from, i_to,
                 d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, stream);
@@ -2229,10 +2261,10 @@ static NnAgainstLayout make_nn_against_layout(size_t n_q, size_t n_ref, size_t n
   NnAgainstLayout L;
   L.A = make_against_layout(n_q, n_ref, n_cols);
   L.off_fe_c = L.A.total;
-  L.off_ferange = L.off_fe_c + align256(sizeof(float) * 32 * (size_t)L.A.T_r);
-  L.off_meta = L.off_ferange + align256(sizeof(float) * 2 * (size_t)L.A.T_r);
+  L.off_ferange = L.off_fe_c + align256(sizeof(float) * 32 * (size_t)L.A.C.T_r);
+  L.off_meta = L.off_ferange + align256(sizeof(float) * 2 * (size_t)L.A.C.T_r);
   L.off_merge64 = L.off_meta + 256;
-  L.total = L.off_merge64 + align256(sizeof(unsigned long long) * 2 * 32 * (size_t)L.A.T_q);
+  L.total = L.off_merge64 + align256(sizeof(unsigned long long) * 2 * 32 * (size_t)L.A.C.T_q);
   return L;
 }
 
@@ -2250,53 +2282,38 @@ int launch_nn_cross_pruned(const float* d_query, uint32_t n_q, const float* d_re
                                 d_hd_idx, d_hd_d2, d_ws, stream);
   const uint32_t n_sel = i_to - i_from;
   const NnAgainstLayout NL = make_nn_against_layout(n_sel, n_ref, n_cols);   // (no larger than the layout of all n_q rows)
-  const AgainstLayout& L = NL.A;
+  const AgainstWs W = against_ws(d_ws, NL.A, n_sel, n_ref);
   char* p = (char*)d_ws;
-  uint32_t* hdr = (uint32_t*)p;
-  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
-  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
-  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
-  uint32_t* perm_r = (uint32_t*)(p + L.off_perm_r);
-  uint32_t* perm_q = (uint32_t*)(p + L.off_perm_q);
   // one origin and one scale for both sets, exactly as the every-pair sweep
-  if (int rc = cross_prepare(d_query, n_q, d_ref, n_ref, n_cols, d_ws, stream)) return rc;
-  hipLaunchKernelGGL(scale_kernel, dim3(1), dim3(1), 0, stream, hdr, -1.0f, n_cols);   // the neighbour scale
+  if (int rc = cross_prepare_scaled(d_query, n_q, d_ref, n_ref, n_cols, -1.0f, d_ws, stream)) return rc;
   const dim3 blk(256);
   const bool have_fe = d_fe_q != nullptr;
   // the range of the reference's free energies: header words 12 / 13 (a NaN raises the flag: the direct kernel answers)
   if (have_fe)
     hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>((n_ref + 255) / 256, 256u)), blk, 0, stream, d_fe_r, n_ref,
-                       (uint32_t*)nullptr, (uint32_t*)nullptr, hdr);
+                       (uint32_t*)nullptr, (uint32_t*)nullptr, W.hdr);
   // key: (cell of the one grid, quantised free energy) in whole sort passes, as the self neighbour sweep's
   const unsigned cell_bits = cell_key_bits(n_ref, kNnCellFrames);
   const unsigned key_bits = (cell_bits + 9u <= 24u) ? 24u : 32u;
   const unsigned fe_bits = have_fe ? std::min(key_bits - cell_bits, 16u) : 0u;
-  const size_t tmp_bytes = sort_temp_bytes(std::max(n_sel, n_ref));
   // R: the order, its rows, boxes, free energies, folded A form
-  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_r + 255) / 256, 1024u)), blk, 0, stream, d_ref, n_cols,
-                     (const uint32_t*)hdr, n_ref, cell_frames(true), 0u, n_ref, keys_in, vals_in, perm_r, 32u * L.T_r);
+  against_keys(W, d_ref, n_cols, n_ref, cell_frames(true), 0u, n_ref, W.perm_r, W.T_r, stream);
   if (have_fe)
-    hipLaunchKernelGGL(against_fe_key_kernel, dim3(std::min<uint32_t>((n_ref + 255) / 256, 1024u)), blk, 0, stream, keys_in,
-                       (const uint32_t*)vals_in, n_ref, d_fe_r, (const uint32_t*)hdr, (uint32_t)fe_bits);
-  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_r, n_ref, p + L.off_sort, tmp_bytes, stream, cell_bits + fe_bits)) return -3;
-  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * L.T_r + 255) / 256), blk, 0, stream, d_ref, n_cols,
-                     (const uint32_t*)perm_r, L.T_r, (float*)(p + L.off_coords_r), (float4*)(p + L.off_box_r));
-  hipLaunchKernelGGL(against_fe_rows_kernel, dim3((32u * L.T_r + 255) / 256), blk, 0, stream, have_fe ? d_fe_r : (const float*)nullptr,
-                     (const uint32_t*)perm_r, L.T_r, (float*)(p + NL.off_fe_c), (float2*)(p + NL.off_ferange));
-  hipLaunchKernelGGL(against_meta_kernel, dim3(1), blk, 0, stream, (const uint32_t*)hdr, n_ref, cell_frames(true),
-                     (const float4*)(p + L.off_box_r), L.T_r, (float*)(p + NL.off_meta));
-  image(d_ref, 32u * L.T_r, n_cols, L.NM, L.T_r, perm_r, 2, p + L.off_img_r, nullptr, d_ws, stream);
+    hipLaunchKernelGGL(against_fe_key_kernel, dim3(std::min<uint32_t>((n_ref + 255) / 256, 1024u)), blk, 0, stream, W.sort.keys_in,
+                       (const uint32_t*)W.sort.vals_in, n_ref, d_fe_r, (const uint32_t*)W.hdr, (uint32_t)fe_bits);
+  if (int rc = against_order(W, d_ref, n_ref, n_cols, cell_bits + fe_bits, W.perm_r, W.T_r, W.coords_r, W.box_r, stream)) return rc;
+  hipLaunchKernelGGL(against_fe_rows_kernel, dim3((32u * W.T_r + 255) / 256), blk, 0, stream, have_fe ? d_fe_r : (const float*)nullptr,
+                     (const uint32_t*)W.perm_r, W.T_r, (float*)(p + NL.off_fe_c), (float2*)(p + NL.off_ferange));
+  hipLaunchKernelGGL(against_meta_kernel, dim3(1), blk, 0, stream, (const uint32_t*)W.hdr, n_ref, cell_frames(true),
+                     (const float4*)W.box_r, W.T_r, (float*)(p + NL.off_meta));
+  image(d_ref, 32u * W.T_r, n_cols, W.NM, W.T_r, W.perm_r, 2, W.img_r, nullptr, d_ws, stream);
   // Q: only the rows of the call, by the cell of the same grid; B form, norms, boxes
-  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_q + 255) / 256, 1024u)), blk, 0, stream, d_query, n_cols,
-                     (const uint32_t*)hdr, n_ref, cell_frames(true), i_from, i_to, keys_in, vals_in, perm_q, 32u * L.T_q);
-  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm_q, n_sel, p + L.off_sort, tmp_bytes, stream, cell_bits)) return -3;
-  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * L.T_q + 255) / 256), blk, 0, stream, d_query, n_cols,
-                     (const uint32_t*)perm_q, L.T_q, (float*)nullptr, (float4*)(p + L.off_box_q));
-  image(d_query, 32u * L.T_q, n_cols, L.NM, L.T_q, perm_q, 1, p + L.off_img_q, p + L.off_norm_q, d_ws, stream);
-  const NnAgainstArgs A{d_query, d_fe_q, (const uint4*)(p + L.off_img_r), perm_r, (const float4*)(p + L.off_box_r),
-                        (const float2*)(p + NL.off_ferange), (const float*)(p + NL.off_fe_c), (const float*)(p + L.off_coords_r),
-                        (const uint4*)(p + L.off_img_q), (const float*)(p + L.off_norm_q), perm_q, (const float4*)(p + L.off_box_q),
-                        (const float*)(p + NL.off_meta), (unsigned long long*)(p + NL.off_merge64), L.T_r, L.T_q, n_ref, hdr};
+  against_keys(W, d_query, n_cols, n_ref, cell_frames(true), i_from, i_to, W.perm_q, W.T_q, stream);
+  if (int rc = against_order(W, d_query, n_sel, n_cols, cell_bits, W.perm_q, W.T_q, nullptr, W.box_q, stream)) return rc;
+  image(d_query, 32u * W.T_q, n_cols, W.NM, W.T_q, W.perm_q, 1, W.img_q, W.norm_q, d_ws, stream);
+  const NnAgainstArgs A{d_query, d_fe_q, W.img_r, W.perm_r, W.box_r, (const float2*)(p + NL.off_ferange),
+                        (const float*)(p + NL.off_fe_c), W.coords_r, W.img_q, W.norm_q, W.perm_q, W.box_q,
+                        (const float*)(p + NL.off_meta), (unsigned long long*)(p + NL.off_merge64), W.T_r, W.T_q, n_ref, W.hdr};
   nn_against_sweep(A, n_cols, d_nn_idx, d_nn_d2, have_fe ? d_hd_idx : nullptr, have_fe ? d_hd_d2 : nullptr, stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -2312,15 +2329,13 @@ void launch_pop_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, 
   float* norms = (float*)(p + L.off_norm);
   // the frames in the order of their 2-D cells (cell32_key_kernel; about 64 frames per cell of the bounding box of columns
   // 0 / 1, at most 256 x 256 cells: 16-bit keys, two passes of the library's sort)
-  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
-  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
-  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
+  const SortBufs S = sort_bufs(d_ws, L, L.fixed_end, sort_temp_bytes(n_rows));
   uint32_t* perm = (uint32_t*)(p + L.off_perm);
   uint32_t G = 1, g_bits = 0;
   while (G < 256u && (size_t)(2u * G) * (2u * G) * 64u <= (size_t)n_rows) { G *= 2u; ++g_bits; }
   hipLaunchKernelGGL(cell32_key_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, stream, d_coords, n_rows, n_cols,
-                     (const uint32_t*)p, G, keys_in, vals_in);
-  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm, n_rows, p + L.fixed_end, sort_temp_bytes(n_rows), stream, 2u * g_bits) != 0) return;
+                     (const uint32_t*)p, G, S.keys_in, S.vals_in);
+  if (S.run(perm, n_rows, stream, 2u * g_bits) != 0) return;
   // (ONE image for all radii of the call, scaled for the largest: the band of a smaller radius is narrower than 1)
   float r2max = 0.0f;
   for (int r = 0; r < n_rad; ++r) r2max = std::max(r2max, rad2.v[r]);
@@ -2347,29 +2362,20 @@ void launch_pop_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, 
 void launch_nn_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, uint32_t i_from,
                       uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws,
                       hipStream_t stream) {
-  // the reference frames ordered by free energy, exactly as launch_nn_mfma orders them; fp32 images instead of fp16 x 2
+  // the reference frames ordered by free energy as launch_nn_mfma orders them (order_by_fe); fp32 images instead of fp16 x 2
   const Layout L = make_layout(n_rows, n_cols);
   char* p = (char*)d_ws;
-  uint32_t* keys_in = (uint32_t*)(p + L.off_keys_in);
-  uint32_t* keys_out = (uint32_t*)(p + L.off_keys_out);
-  uint32_t* vals_in = (uint32_t*)(p + L.off_vals_in);
-  uint32_t* perm = (uint32_t*)(p + L.off_perm);
-  const dim3 blk(256), grid_n((n_rows + 255) / 256), grid_t((32 * L.T + 255) / 256);
+  const FeOrder B = fe_order(d_ws, L, L.fixed_end, n_rows);
+  const dim3 blk(256), grid_t((32 * L.T + 255) / 256);
   float* img = (float*)(p + L.off_img);
   float* norms = (float*)(p + L.off_norm);
   float* img_s = (float*)(p + L.off_img_s);
   float* norms_s = (float*)(p + L.off_norm_s);
   hipLaunchKernelGGL(image32_kernel, grid_t, blk, 0, stream, d_coords, n_rows, n_cols, L.T, (const float*)(p + kHdrMeans),
                      (const uint32_t*)nullptr, (const uint32_t*)p, -1.0f, img, norms);
-  hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>(grid_n.x, 1024u)), blk, 0, stream, d_fe, n_rows, keys_in, vals_in,
-                     (uint32_t*)p);
-  if (sort_pairs_u32(keys_in, keys_out, vals_in, perm, n_rows, p + L.fixed_end, sort_temp_bytes(n_rows), stream) != 0) return;
-  hipLaunchKernelGGL(fe_scatter_kernel, grid_t, blk, 0, stream, perm, d_fe, n_rows, L.T, (uint32_t*)(p + L.off_invpos),
-                     (float*)(p + L.off_fe_s));
-  hipLaunchKernelGGL(fe_rank_kernel, grid_n, blk, 0, stream, d_fe, n_rows, (const float*)(p + L.off_fe_s), n_rows,
-                     (uint32_t*)(p + L.off_pq));
+  if (order_by_fe(n_rows, L.T, d_fe, d_fe, n_rows, B, d_ws, stream) != 0) return;
   hipLaunchKernelGGL(image32_kernel, grid_t, blk, 0, stream, d_coords, n_rows, n_cols, L.T, (const float*)(p + kHdrMeans),
-                     (const uint32_t*)perm, (const uint32_t*)p, -1.0f, img_s, norms_s);
+                     (const uint32_t*)B.perm, (const uint32_t*)p, -1.0f, img_s, norms_s);
   constexpr int kTQ = 4;
   const uint32_t env_chunks = sweep_switches().mfma32_chunks;
   // ONE wave per workgroup: a workgroup holds its wave slots until its last wave is done, and the waves of this sweep
@@ -2383,8 +2389,8 @@ void launch_nn_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, c
   sweep_timer_mark(1, true, stream);
   const size_t smem = wpb * sizeof(uint32_t) * (2 * kNormBatch32 * 32 + 2 * kWaveQueue + 4 * kTQ * 32 + kTQ * 32 * (size_t)n_cols);
   hipLaunchKernelGGL((nn_mfma32_kernel<kS32, kTQ>), dim3(blocks, chunks), dim3(64 * wpb), smem, stream, d_coords, n_rows, n_cols,
-                     (const float*)img, (const float*)norms, (const float*)img_s, (const float*)norms_s, (const uint32_t*)perm,
-                     (const uint32_t*)(p + L.off_invpos), (const uint32_t*)(p + L.off_pq), (const uint32_t*)p, L.T, i_from, i_to,
+                     (const float*)img, (const float*)norms, (const float*)img_s, (const float*)norms_s, (const uint32_t*)B.perm,
+                     (const uint32_t*)B.invpos, (const uint32_t*)B.pq, (const uint32_t*)p, L.T, i_from, i_to,
                      merge64, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
   sweep_timer_mark(1, false, stream);
   if (chunks > 1)
