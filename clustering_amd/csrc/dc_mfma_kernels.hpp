@@ -2425,6 +2425,31 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
       }
     }
   }
+  // Free-energy classes of the reference tiles (early-out form): which of a query's two thresholds a tile is tested
+  // against depends on the tile's free-energy range and the query's free energy alone, and the orders make that the
+  // same for nearly every lane of the wave (a tile is a narrow free-energy slice of a cell, the group one of its own
+  // cell).  The range of the group's free energies and of its own tiles, wave-uniform (idle lanes stay out of both):
+  float feq_lo = INFINITY, feq_hi = -INFINITY;
+  uint32_t own_lo = 0xFFFFFFFFu, own_hi = 0u;   // tiles that hold one of the wave's queries lie in [own_lo, own_hi]
+  if constexpr (kNnEarly<NM>) {
+#pragma unroll
+    for (int qt = 0; qt < TQ; ++qt) {
+      const bool live = (livemask[qt] >> lane) & 1;
+      feq_lo = fminf(feq_lo, live ? q[qt].feq : INFINITY);
+      feq_hi = fmaxf(feq_hi, live ? q[qt].feq : -INFINITY);
+      own_lo = min(own_lo, live ? q[qt].spos >> 5 : 0xFFFFFFFFu);
+      own_hi = max(own_hi, live ? q[qt].spos >> 5 : 0u);
+    }
+    feq_lo = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(wave_min(feq_lo))));
+    feq_hi = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(wave_max(feq_hi))));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      own_lo = min(own_lo, (uint32_t)__shfl_xor((int)own_lo, off, 64));
+      own_hi = max(own_hi, (uint32_t)__shfl_xor((int)own_hi, off, 64));
+    }
+    own_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)own_lo);
+    own_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)own_hi);
+  }
   // lowest free energy of the whole data set (header word 12, ordered-integer key, written by the
   // ordering pass): a query at that level has no lower-FE neighbour
   const float fe_floor = fkey_inv(~hdr[12]);
@@ -2475,238 +2500,331 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
       }
       if (cnt == 0) continue;
       visited += cnt;
-      // Reference tile data in two register buffers (the loads run one survivor ahead); the chains
-      // are software-pipelined over two accumulator tiles: while the MFMAs of one chain run, the
-      // tile minimum of the previous chain issues in their shadow (a wave issues in order).
-      s16x8 a0[NM];
-      auto entry = [&](uint32_t i) {
-        return (uint32_t)__builtin_amdgcn_readfirstlane(list[i < cnt ? i : cnt - 1]);
-      };
-      // the rest of an epilogue: free-energy classes, band test, parking of the candidates.
-      // (t, fr) describe the reference tile the accumulator belongs to.
-      auto finish = [&](const f32x16& acc, auto qi_c, float tmin, uint32_t t, float2 fr) __attribute__((always_inline)) {
-        constexpr int qi = decltype(qi_c)::value;
-        NnPQr& Q = q[qi];
-        // Common path: two compares against the cached candidate thresholds.  "Lower free energy" is
-        // taken conservatively here (the tile has SOME lower frame => its minimum might be one), and
-        // the tile holding the query itself always passes (its own d2 ~ 0): whatever needs the
-        // per-element treatment ends up in the rare path.  The running minima can only change there
-        // too (a value below the minimum is below its band).  ONE wave-level test: the scalar
-        // hand-off (v_cmp -> s_cbranch) is a pipeline bubble at two waves per SIMD.
-        // (bh >= bn always -- the minimum over the lower-free-energy frames cannot undercut the minimum over all
-        //  frames -- so a tile that has lower frames is tested against bh alone, any other against bn)
-        const float thr = (fr.x < Q.feq) ? Q.bh : Q.bn;
-        const bool rare = tmin < thr;
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(rare) != 0, 0)) {
-          const bool all_lower = fr.y < Q.feq;
-          const bool mixed = (fr.x < Q.feq) & !all_lower;
-          const bool special = mixed | (t == (Q.spos >> 5));
-          float hmin = all_lower ? tmin : INFINITY;
-          const bool any_special = __builtin_amdgcn_ballot_w64(special) != 0;
-          if (any_special) {
-            // masked per-element minima (the tile holds the query itself and/or straddles feq); the
-            // free energies of the tile's frames are fetched only here
-            float4 fv[4];
-            load_frag(fe_c, t, h, fv);
-            const f32x16 fef = frag16(fv);
-            tmin = INFINITY;
-            hmin = INFINITY;
+      // The survivors sorted by class, each class in scan order: list[0, cN) holds the tiles with NOTHING lower than
+      // any query of the wave (fe_lo >= feq_hi: tested against bn), list[cN, cN + cH) the tiles that are ALL lower
+      // than every query (fe_hi < feq_lo: tested against bh, the tile minimum is the lower-free-energy minimum), the
+      // rest what has to decide per lane -- with it the tiles that hold a query of the wave and the last tile (pad
+      // rows), so that neither of the first two classes ever needs the per-element path.  The ranges of a round's
+      // survivors are fetched together, one lane per survivor; every entry is read before the first is written.
+      uint32_t cN = 0, cH = 0;
+      if constexpr (kNnEarly<NM>) {
+        constexpr int kSteps = kListCap / 64;
+        uint32_t e[kSteps], cls[kSteps];
+        float2 fr[kSteps];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float v = (tile_row(t, r, h) != Q.spos) ? acc[r] : INFINITY;
-              tmin = fminf(tmin, v);
-              hmin = fminf(hmin, (fef[r] < Q.feq) ? v : INFINITY);
-            }
+        for (int j = 0; j < kSteps; ++j) {
+          e[j] = 0;
+          fr[j] = make_float2(0.0f, 0.0f);
+          if ((uint32_t)j * 64u < cnt) {
+            const bool have = (uint32_t)j * 64u + (uint32_t)lane < cnt;
+            e[j] = have ? list[j * 64 + lane] : 0u;
+            if (have) fr[j] = ferange_r[e[j]];
           }
-          // (the two half-wave lanes of a query see different rows of every tile: what either of them has
-          //  found bounds the answer of both, so the running minima are shared whenever they move -- the
-          //  records of one sequence over all rows instead of two over half of them each)
-          float new_nn = fminf(Q.m_nn, nn_unprime(tmin, cq[qi])), new_hd = fminf(Q.m_hd, nn_unprime(hmin, cq[qi]));
-          if constexpr (COOP) {
-            // what the other shares of the group have learnt in the meantime, and what this chain adds to it (a returning
-            // ds_min per kind; idle lanes carry -inf on both sides)
-            const uint32_t o_nn = atomicMin(&smin[qi * 32 + c], fkey(new_nn));
-            const uint32_t o_hd = atomicMin(&smin[TQ * 32 + qi * 32 + c], fkey(new_hd));
-            new_nn = fminf(new_nn, fkey_inv(o_nn));
-            new_hd = fminf(new_hd, fkey_inv(o_hd));
-          }
-          new_nn = fminf(new_nn, __shfl_xor(new_nn, 32, 64));
-          new_hd = fminf(new_hd, __shfl_xor(new_hd, 32, 64));
-          const float bn = nn_prime(nn_band(gb, new_nn), cq[qi]), bh = nn_prime(nn_band(gb, new_hd), cq[qi]);
-          const bool trig = (tmin < bn) | (hmin < bh);
-          if (__builtin_amdgcn_ballot_w64(trig) != 0) {
-            // park this tile's candidates (values within the band of the running minima); element r
-            // of the accumulator is bit (15 - r) of the masks
-            uint32_t mn = 0, mh = 0;
-            if (!any_special && t + 1 != T) {
-              // plain tile: below-threshold sign strings (idle lanes have thresholds of -inf, pad
-              // rows only exist in the last tile)
-              uint32_t sn = 0, sh = 0;
-#pragma unroll
-              for (int r = 0; r < 16; ++r) {
-                sn = __builtin_amdgcn_alignbit(sn, __float_as_uint(acc[r] - bn), 31);
-                sh = __builtin_amdgcn_alignbit(sh, __float_as_uint(acc[r] - bh), 31);
-              }
-              mn = sn & 0xFFFFu;
-              mh = all_lower ? (sh & 0xFFFFu) : 0u;
-            } else {
-              float4 fv[4];
-              load_frag(fe_c, t, h, fv);
-              const f32x16 fef = frag16(fv);
-              const bool live = (livemask[qi] >> lane) & 1;
-#pragma unroll
-              for (int r = 0; r < 16; ++r) {
-                const uint32_t pos = tile_row(t, r, h);
-                const bool other = live & (pos != Q.spos) & (pos < CV.n_pos);
-                mn |= (other & (acc[r] < bn)) ? (0x8000u >> r) : 0u;
-                mh |= (other & (acc[r] < bh) & (fef[r] < Q.feq)) ? (0x8000u >> r) : 0u;
-              }
-            }
-            uint32_t m = mn | mh;
-            for (;;) {
-              const uint64_t have = __builtin_amdgcn_ballot_w64(m != 0);
-              if (have == 0) break;
-              const uint32_t n_new = (uint32_t)__builtin_popcountll(have);
-              if (qn + n_new > (uint32_t)kWaveQueue) flush();
-              if (m != 0) {
-                const int p = __builtin_ctz(m);
-                const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(have >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)have, 0));
-                cand[slot] = make_uint2(tile_row(t, 15 - p, h) | (((mn >> p) & 1u) << 30) | (((mh >> p) & 1u) << 31),
-                                        (uint32_t)(qi * 32 + c));
-                m &= m - 1;
-              }
-              qn += n_new;
-            }
-            if (qn >= 64u) flush();
-          }
-          Q.m_nn = new_nn;
-          Q.m_hd = new_hd;
-          Q.bn = bn + skipb;
-          Q.bh = bh + skipb;
         }
-      };
-      // Full chains (NM = 1 and the single-buffer instances): accB always holds the chain whose epilogue is still
-      // pending -- query tile TQ-1 of reference tile tB (or +inf everywhere: no minimum, no candidates).  The early-out
-      // form (kNnEarly) keeps nothing pending across tiles and uses accA / accB as its two coarse accumulators.
-      f32x16 accA, accB;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) accB[r] = INFINITY;
-      uint32_t tB = 0;
-      float2 frB = make_float2(INFINITY, INFINITY);
-      // (fr: the tile's free-energy range, fetched with its operands one tile ahead -- read at the start of the
-      //  tile's own chains the scalar load's latency sat in front of the second chain of every tile)
-      auto compute = [&](s16x8 (&a)[NM], uint32_t t, uint32_t t_next, float2 fr) {
-        f32x16 c0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) c0[r] = 0.0f;   // (an inline constant of the first MFMA)
-        chains += TQ;
-        static_assert(TQ % 2 == 0, "accumulator ping-pong needs an even number of query tiles");
-        if constexpr (kNnEarly<NM>) {
-          // Early-out (see nn_chain_coarse): the coarse minima of the tile's TQ chains are tested TOGETHER -- one scalar
-          // hand-off per reference tile instead of one per chain (C3: 11.1 -> 10.8 ms) --, and a chain that goes on is
-          // computed again from its first MFMA, so no accumulator has to wait for its test and nothing stays pending
-          // across tiles.
-          float tm[TQ], dmin = INFINITY;
-          auto coarse_first = [&](f32x16& acc, const s16x8 (&bq)[NM]) {
-            acc = mfma16(a[0], bq[0], c0);
-#pragma unroll
-            for (int m = 1; m < kNnCoarse<NM>; ++m) acc = mfma16(a[m], bq[m], acc);
-          };
-          coarse_first(accA, b[0]);
-          constexpr_for_pairs<TQ>([&](auto qt_c) {
-            constexpr int qt = decltype(qt_c)::value;
-            tm[qt] = INFINITY;
-            nn_chain_coarse<NM, kNnCoarse<NM>, NM>(a, b[qt + 1], c0, accB, accA, tm[qt]);
-            tm[qt + 1] = INFINITY;
-            if constexpr (qt + 2 < TQ)
-              nn_chain_coarse<NM, kNnCoarse<NM>, NM>(a, b[qt + 2], c0, accA, accB, tm[qt + 1]);
-            else
-              tile_min<0, 16>(accB, tm[qt + 1]);
-          });
-#pragma unroll
-          for (int qi = 0; qi < TQ; ++qi) dmin = fminf(dmin, tm[qi] - ((fr.x < q[qi].feq) ? q[qi].bh : q[qi].bn));
-          if (__builtin_expect(__builtin_amdgcn_ballot_w64(dmin < 0.0f) != 0, 0)) {
-            constexpr_for_all<TQ>([&](auto qi_c) {
-              constexpr int qi = decltype(qi_c)::value;
-              const float thr_c = (fr.x < q[qi].feq) ? q[qi].bh : q[qi].bn;
-              if (__builtin_amdgcn_ballot_w64(tm[qi] < thr_c) != 0) {
-                chains_on += 1;
-                f32x16 acc = mfma16(a[0], b[qi][0], c0);
-#pragma unroll
-                for (int m = 1; m < NM; ++m) acc = mfma16(a[m], b[qi][m], acc);
-                float tmin = INFINITY;
-                tile_min<0, 16>(acc, tmin);
-                finish(acc, qi_c, tmin, t, fr);
-              }
-            });
+        for (int j = 0; j < kSteps; ++j) {
+          cls[j] = 3u;   // (no entry)
+          if ((uint32_t)j * 64u < cnt) {
+            const bool have = (uint32_t)j * 64u + (uint32_t)lane < cnt;
+            const bool keep = (e[j] - own_lo <= own_hi - own_lo) | (e[j] + 1 == T);
+            const uint32_t k = keep ? 2u : (fr[j].x >= feq_hi) ? 0u : (fr[j].y < feq_lo) ? 1u : 2u;
+            cls[j] = have ? k : 3u;
+            cN += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(cls[j] == 0u));
+            cH += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(cls[j] == 1u));
           }
-          return;
         }
-        auto refill = [&](auto mi_c) {
-          if constexpr (kSingleBuffer<NM>) {
-            constexpr int MI = decltype(mi_c)::value;
-            const uint4 v = img_r[(size_t)t_next * (NM * 64) + MI * 64 + lane];
-            a[MI] = __builtin_bit_cast(s16x8, v);
-          }
-        };
-        constexpr_for_pairs<TQ>([&](auto qt_c) {
-          constexpr int qt = decltype(qt_c)::value;
-          constexpr int qb = (qt == 0) ? TQ - 1 : qt - 1;
-          float tmin = INFINITY;
-          nn_chain<NM>(a, b[qt], c0, accA, accB, tmin);
-          finish(accB, std::integral_constant<int, qb>{}, tmin, (qt == 0) ? tB : t,
-                 (qt == 0) ? frB : fr);
-          tmin = INFINITY;
-          if constexpr (qt + 2 == TQ)   // last chain of the tile
-            nn_chain<NM>(a, b[qt + 1], c0, accB, accA, tmin, refill);
-          else
-            nn_chain<NM>(a, b[qt + 1], c0, accB, accA, tmin);
-          finish(accA, std::integral_constant<int, qt>{}, tmin, t, fr);
-        });
-        tB = t;
-        frB = fr;
-      };
-      if constexpr (kSingleBuffer<NM>) {
-        uint32_t t0 = entry(0);
-        load_tile_folded<NM>(img_r, t0, lane, a0);
-        float2 f0 = ferange_r[t0];
-        for (uint32_t i = 0; i < cnt; ++i) {
-          const uint32_t t1 = entry(i + 1);
-          const float2 f1 = ferange_r[t1];
-          compute(a0, t0, t1, f0);
-          t0 = t1;
-          f0 = f1;
-        }
-      } else {
-        s16x8 a1[NM];
-        // (the survivor list is read one tile ahead of its use: the LDS latency sat in front of every tile's loads)
-        auto peek = [&](uint32_t i) { return list[i < cnt ? i : cnt - 1]; };
-        uint32_t t0 = entry(0), t1;
-        uint32_t l_next = peek(1);
-        load_tile_folded<NM>(img_r, t0, lane, a0);
-        float2 f0 = ferange_r[t0], f1;
-        for (uint32_t i = 0; i < cnt; i += 2) {
-          t1 = (uint32_t)__builtin_amdgcn_readfirstlane(l_next);
-          l_next = peek(i + 2);
-          load_tile_folded<NM>(img_r, t1, lane, a1);
-          f1 = ferange_r[t1];
-          compute(a0, t0, t1, f0);
-          if (i + 1 < cnt) {
-            t0 = (uint32_t)__builtin_amdgcn_readfirstlane(l_next);
-            l_next = peek(i + 3);
-            load_tile_folded<NM>(img_r, t0, lane, a0);
-            f0 = ferange_r[t0];
-            compute(a1, t1, t0, f1);
+        uint32_t at0 = 0, at1 = cN, at2 = cN + cH;
+#pragma unroll
+        for (int j = 0; j < kSteps; ++j) {
+          if ((uint32_t)j * 64u < cnt) {
+            const uint64_t m0 = __builtin_amdgcn_ballot_w64(cls[j] == 0u), m1 = __builtin_amdgcn_ballot_w64(cls[j] == 1u),
+                           m2 = __builtin_amdgcn_ballot_w64(cls[j] == 2u);
+            const uint64_t mine = cls[j] == 0u ? m0 : cls[j] == 1u ? m1 : m2;
+            const uint32_t at = cls[j] == 0u ? at0 : cls[j] == 1u ? at1 : at2;
+            if (cls[j] < 3u)
+              list[at + __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0))] = e[j];
+            at0 += (uint32_t)__builtin_popcountll(m0);
+            at1 += (uint32_t)__builtin_popcountll(m1);
+            at2 += (uint32_t)__builtin_popcountll(m2);
           }
         }
       }
-      {  // drain: epilogue of the last pending chain of this round
-        float tmin = INFINITY;
-        tile_min<0, 16>(accB, tmin);
-        if constexpr (kNnEarly<NM>)
-          (void)tmin;   // (nothing stays pending across tiles)
-        else
-          finish(accB, std::integral_constant<int, TQ - 1>{}, tmin, tB, frB);
+      // one instance of the survivor loop per class (a class is a compile-time property of its loop: a wave-uniform
+      // flag inside one loop costs more than the selects it would save)
+      // (the survivors list[lo, hi) of one class)
+      auto sweep = [&](auto cls_c, const uint32_t lo, const uint32_t hi) __attribute__((always_inline)) {
+        constexpr int kCls = decltype(cls_c)::value;   // 0: nothing lower, 1: all lower, 2: decided per lane
+        // Reference tile data in two register buffers (the loads run one survivor ahead); the chains
+        // are software-pipelined over two accumulator tiles: while the MFMAs of one chain run, the
+        // tile minimum of the previous chain issues in their shadow (a wave issues in order).
+        s16x8 a0[NM];
+        auto entry = [&](uint32_t i) {
+          return (uint32_t)__builtin_amdgcn_readfirstlane(list[i < hi ? i : hi - 1]);
+        };
+        const int c_wave = c, h_wave = h, lane_wave = lane;   // (shadowed inside the candidate path, see there)
+        // the threshold a chain of this class is tested against
+        auto thr_of = [&](const NnPQr& Q, float2 fr) {
+          return kCls == 0 ? Q.bn : kCls == 1 ? Q.bh : (fr.x < Q.feq) ? Q.bh : Q.bn;
+        };
+        // the rest of an epilogue: free-energy classes, band test, parking of the candidates.
+        // (t, fr) describe the reference tile the accumulator belongs to.
+        auto finish = [&](const f32x16& acc, auto qi_c, float tmin, uint32_t t, float2 fr) __attribute__((always_inline)) {
+          constexpr int qi = decltype(qi_c)::value;
+          NnPQr& Q = q[qi];
+          // Common path: two compares against the cached candidate thresholds.  "Lower free energy" is
+          // taken conservatively here (the tile has SOME lower frame => its minimum might be one), and
+          // the tile holding the query itself always passes (its own d2 ~ 0): whatever needs the
+          // per-element treatment ends up in the rare path.  The running minima can only change there
+          // too (a value below the minimum is below its band).  ONE wave-level test: the scalar
+          // hand-off (v_cmp -> s_cbranch) is a pipeline bubble at two waves per SIMD.
+          // (bh >= bn always -- the minimum over the lower-free-energy frames cannot undercut the minimum over all
+          //  frames -- so a tile that has lower frames is tested against bh alone, any other against bn)
+          const float thr = thr_of(Q, fr);
+          const bool rare = tmin < thr;
+          if (__builtin_expect(__builtin_amdgcn_ballot_w64(rare) != 0, 0)) {
+            // (the lane's coordinates once more, opaque to the optimiser: what this path derives from them -- addresses,
+            //  record words -- is formed here and not kept in registers across the whole sweep)
+            int c = c_wave, h = h_wave, lane = lane_wave;
+            asm volatile("" : "+v"(c), "+v"(h), "+v"(lane));
+            float cq_q = cq[qi];
+            asm volatile("" : "+v"(cq_q));
+            uint32_t spos_q = Q.spos;
+            asm volatile("" : "+v"(spos_q));
+            // (what the class of the tile decides is a constant here: the first two classes have no mixed tile, no tile of
+            //  the wave's own and no pad row, so neither the per-element path nor -- without lower frames -- the second
+            //  sign string and the lower-free-energy minimum)
+            const bool all_lower = kCls == 0 ? false : kCls == 1 ? true : (fr.y < Q.feq);
+            const bool mixed = kCls == 2 ? ((fr.x < Q.feq) & !all_lower) : false;
+            const bool special = kCls == 2 ? (mixed | (t == (spos_q >> 5))) : false;
+            float hmin = all_lower ? tmin : INFINITY;
+            const bool any_special = kCls == 2 ? (__builtin_amdgcn_ballot_w64(special) != 0) : false;
+            if (any_special) {
+              // masked per-element minima (the tile holds the query itself and/or straddles feq); the
+              // free energies of the tile's frames are fetched only here
+              float4 fv[4];
+              load_frag(fe_c, t, h, fv);
+              const f32x16 fef = frag16(fv);
+              tmin = INFINITY;
+              hmin = INFINITY;
+#pragma unroll
+              for (int r = 0; r < 16; ++r) {
+                const float v = (tile_row(t, r, h) != spos_q) ? acc[r] : INFINITY;
+                tmin = fminf(tmin, v);
+                hmin = fminf(hmin, (fef[r] < Q.feq) ? v : INFINITY);
+              }
+            }
+            // (the two half-wave lanes of a query see different rows of every tile: what either of them has
+            //  found bounds the answer of both, so the running minima are shared whenever they move -- the
+            //  records of one sequence over all rows instead of two over half of them each)
+            float new_nn = fminf(Q.m_nn, nn_unprime(tmin, cq_q));
+            float new_hd = kCls == 0 ? Q.m_hd : fminf(Q.m_hd, nn_unprime(hmin, cq_q));   // (hmin = +inf changes nothing)
+            if constexpr (COOP) {
+              // what the other shares of the group have learnt in the meantime, and what this chain adds to it (a returning
+              // ds_min per kind; idle lanes carry -inf on both sides)
+              const uint32_t o_nn = atomicMin(&smin[qi * 32 + c], fkey(new_nn));
+              const uint32_t o_hd = atomicMin(&smin[TQ * 32 + qi * 32 + c], fkey(new_hd));
+              new_nn = fminf(new_nn, fkey_inv(o_nn));
+              new_hd = fminf(new_hd, fkey_inv(o_hd));
+            }
+            new_nn = fminf(new_nn, __shfl_xor(new_nn, 32, 64));
+            new_hd = fminf(new_hd, __shfl_xor(new_hd, 32, 64));
+            const float bn = nn_prime(nn_band(gb, new_nn), cq_q), bh = nn_prime(nn_band(gb, new_hd), cq_q);
+            const bool trig = (tmin < bn) | (hmin < bh);
+            if (__builtin_amdgcn_ballot_w64(trig) != 0) {
+              // park this tile's candidates (values within the band of the running minima); element r
+              // of the accumulator is bit (15 - r) of the masks
+              uint32_t mn = 0, mh = 0;
+              if (kCls != 2 || (!any_special && t + 1 != T)) {
+                // plain tile: below-threshold sign strings (idle lanes have thresholds of -inf, pad
+                // rows only exist in the last tile)
+                uint32_t sn = 0, sh = 0;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                  sn = __builtin_amdgcn_alignbit(sn, __float_as_uint(acc[r] - bn), 31);
+                  sh = __builtin_amdgcn_alignbit(sh, __float_as_uint(acc[r] - bh), 31);
+                }
+                mn = sn & 0xFFFFu;
+                mh = all_lower ? (sh & 0xFFFFu) : 0u;
+              } else {
+                float4 fv[4];
+                load_frag(fe_c, t, h, fv);
+                const f32x16 fef = frag16(fv);
+                const bool live = (livemask[qi] >> lane) & 1;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                  const uint32_t pos = tile_row(t, r, h);
+                  const bool other = live & (pos != spos_q) & (pos < CV.n_pos);
+                  mn |= (other & (acc[r] < bn)) ? (0x8000u >> r) : 0u;
+                  mh |= (other & (acc[r] < bh) & (fef[r] < Q.feq)) ? (0x8000u >> r) : 0u;
+                }
+              }
+              uint32_t m = mn | mh;
+              for (;;) {
+                const uint64_t have = __builtin_amdgcn_ballot_w64(m != 0);
+                if (have == 0) break;
+                const uint32_t n_new = (uint32_t)__builtin_popcountll(have);
+                if (qn + n_new > (uint32_t)kWaveQueue) flush();
+                if (m != 0) {
+                  const int p = __builtin_ctz(m);
+                  const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(have >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)have, 0));
+                  cand[slot] = make_uint2(tile_row(t, 15 - p, h) | (((mn >> p) & 1u) << 30) | (((mh >> p) & 1u) << 31),
+                                          (uint32_t)(qi * 32 + c));
+                  m &= m - 1;
+                }
+                qn += n_new;
+              }
+              if (qn >= 64u) flush();
+            }
+            Q.m_nn = new_nn;
+            Q.m_hd = new_hd;
+            Q.bn = bn + skipb;
+            Q.bh = bh + skipb;
+          }
+        };
+        // Full chains (NM = 1 and the single-buffer instances): accB always holds the chain whose epilogue is still
+        // pending -- query tile TQ-1 of reference tile tB (or +inf everywhere: no minimum, no candidates).  The early-out
+        // form (kNnEarly) keeps nothing pending across tiles and uses accA / accB as its two coarse accumulators.
+        f32x16 accA, accB;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accB[r] = INFINITY;
+        uint32_t tB = 0;
+        float2 frB = make_float2(INFINITY, INFINITY);
+        // (fr: the tile's free-energy range, fetched with its operands one tile ahead -- read at the start of the
+        //  tile's own chains the scalar load's latency sat in front of the second chain of every tile)
+        auto compute = [&](s16x8 (&a)[NM], uint32_t t, uint32_t t_next, float2 fr) {
+          f32x16 c0;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) c0[r] = 0.0f;   // (an inline constant of the first MFMA)
+          chains += TQ;
+          static_assert(TQ % 2 == 0, "accumulator ping-pong needs an even number of query tiles");
+          if constexpr (kNnEarly<NM>) {
+            // Early-out (see nn_chain_coarse): the coarse minima of the tile's TQ chains are tested TOGETHER -- one scalar
+            // hand-off per reference tile instead of one per chain (C3: 11.1 -> 10.8 ms) --, and a chain that goes on is
+            // computed again from its first MFMA, so no accumulator has to wait for its test and nothing stays pending
+            // across tiles.
+            float tm[TQ];
+            auto coarse_first = [&](f32x16& acc, const s16x8 (&bq)[NM]) {
+              acc = mfma16(a[0], bq[0], c0);
+#pragma unroll
+              for (int m = 1; m < kNnCoarse<NM>; ++m) acc = mfma16(a[m], bq[m], acc);
+            };
+            coarse_first(accA, b[0]);
+            constexpr_for_pairs<TQ>([&](auto qt_c) {
+              constexpr int qt = decltype(qt_c)::value;
+              tm[qt] = INFINITY;
+              nn_chain_coarse<NM, kNnCoarse<NM>, NM>(a, b[qt + 1], c0, accB, accA, tm[qt]);
+              tm[qt + 1] = INFINITY;
+              if constexpr (qt + 2 < TQ)
+                nn_chain_coarse<NM, kNnCoarse<NM>, NM>(a, b[qt + 2], c0, accA, accB, tm[qt + 1]);
+              else
+                tile_min<0, 16>(accB, tm[qt + 1]);
+            });
+            // (the smallest of the TQ differences, three operands per v_min3)
+            float dmin = tm[0] - thr_of(q[0], fr);
+            constexpr_for_pairs<TQ>([&](auto qt_c) {
+              constexpr int qt = decltype(qt_c)::value;
+              const float d1 = tm[qt + 1] - thr_of(q[qt + 1], fr);
+              if constexpr (qt + 2 < TQ)
+                dmin = fminf(fminf(dmin, d1), tm[qt + 2] - thr_of(q[qt + 2], fr));
+              else
+                dmin = fminf(dmin, d1);
+            });
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(dmin < 0.0f) != 0, 0)) {
+              constexpr_for_all<TQ>([&](auto qi_c) {
+                constexpr int qi = decltype(qi_c)::value;
+                const float thr_c = thr_of(q[qi], fr);
+                const bool goes_on = __builtin_amdgcn_ballot_w64(tm[qi] < thr_c) != 0;
+                chains_on = (uint32_t)__builtin_amdgcn_readfirstlane((int)(chains_on + (goes_on ? 1u : 0u)));
+                if (goes_on) {
+                  f32x16 acc = mfma16(a[0], b[qi][0], c0);
+#pragma unroll
+                  for (int m = 1; m < NM; ++m) acc = mfma16(a[m], b[qi][m], acc);
+                  float tmin = INFINITY;
+                  tile_min<0, 16>(acc, tmin);
+                  finish(acc, qi_c, tmin, t, fr);
+                }
+              });
+            }
+            return;
+          }
+          auto refill = [&](auto mi_c) {
+            if constexpr (kSingleBuffer<NM>) {
+              constexpr int MI = decltype(mi_c)::value;
+              const uint4 v = img_r[(size_t)t_next * (NM * 64) + MI * 64 + lane];
+              a[MI] = __builtin_bit_cast(s16x8, v);
+            }
+          };
+          constexpr_for_pairs<TQ>([&](auto qt_c) {
+            constexpr int qt = decltype(qt_c)::value;
+            constexpr int qb = (qt == 0) ? TQ - 1 : qt - 1;
+            float tmin = INFINITY;
+            nn_chain<NM>(a, b[qt], c0, accA, accB, tmin);
+            finish(accB, std::integral_constant<int, qb>{}, tmin, (qt == 0) ? tB : t,
+                   (qt == 0) ? frB : fr);
+            tmin = INFINITY;
+            if constexpr (qt + 2 == TQ)   // last chain of the tile
+              nn_chain<NM>(a, b[qt + 1], c0, accB, accA, tmin, refill);
+            else
+              nn_chain<NM>(a, b[qt + 1], c0, accB, accA, tmin);
+            finish(accA, std::integral_constant<int, qt>{}, tmin, t, fr);
+          });
+          tB = t;
+          frB = fr;
+        };
+        // (the tile's free-energy range: only the per-lane class looks at it)
+        auto range_of = [&](uint32_t t) {
+          if constexpr (kCls == 2) return ferange_r[t];
+          else return make_float2(0.0f, 0.0f);
+        };
+        if constexpr (kSingleBuffer<NM>) {
+          uint32_t t0 = entry(lo);
+          load_tile_folded<NM>(img_r, t0, lane, a0);
+          float2 f0 = range_of(t0);
+          for (uint32_t i = lo; i < hi; ++i) {
+            const uint32_t t1 = entry(i + 1);
+            const float2 f1 = range_of(t1);
+            compute(a0, t0, t1, f0);
+            t0 = t1;
+            f0 = f1;
+          }
+        } else {
+          s16x8 a1[NM];
+          // (the survivor list is read one tile ahead of its use: the LDS latency sat in front of every tile's loads)
+          auto peek = [&](uint32_t i) { return list[i < hi ? i : hi - 1]; };
+          uint32_t t0 = entry(lo), t1;
+          uint32_t l_next = peek(lo + 1);
+          load_tile_folded<NM>(img_r, t0, lane, a0);
+          float2 f0 = range_of(t0), f1;
+          for (uint32_t i = lo; i < hi; i += 2) {
+            t1 = (uint32_t)__builtin_amdgcn_readfirstlane(l_next);
+            l_next = peek(i + 2);
+            load_tile_folded<NM>(img_r, t1, lane, a1);
+            f1 = range_of(t1);
+            compute(a0, t0, t1, f0);
+            if (i + 1 < hi) {
+              t0 = (uint32_t)__builtin_amdgcn_readfirstlane(l_next);
+              l_next = peek(i + 3);
+              load_tile_folded<NM>(img_r, t0, lane, a0);
+              f0 = range_of(t0);
+              compute(a1, t1, t0, f1);
+            }
+          }
+        }
+        {  // drain: epilogue of the last pending chain of this round
+          float tmin = INFINITY;
+          tile_min<0, 16>(accB, tmin);
+          if constexpr (kNnEarly<NM>)
+            (void)tmin;   // (nothing stays pending across tiles)
+          else
+            finish(accB, std::integral_constant<int, TQ - 1>{}, tmin, tB, frB);
+        }
+      };
+      if constexpr (kNnEarly<NM>) {
+        if (cN != 0) sweep(std::integral_constant<int, 0>{}, 0u, cN);
+        if (cH != 0) sweep(std::integral_constant<int, 1>{}, cN, cN + cH);
+        if (cN + cH != cnt) sweep(std::integral_constant<int, 2>{}, cN + cH, cnt);
+      } else {
+        sweep(std::integral_constant<int, 2>{}, 0u, cnt);
       }
     }
     flush();                                          // the settle test needs the exact incumbents (in LDS)
@@ -2748,6 +2866,7 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
 #pragma unroll
   for (int qt = 0; qt < TQ; ++qt) {
     if (h == 0 && ((livemask[qt] >> lane) & 1)) {
+      jq[qt] = perm_q[(qt0 + qt) * 32 + c];
       const unsigned long long w_nn = best64[qt * 32 + c], w_hd = best64[TQ * 32 + qt * 32 + c];
       if (n_chunks == 1) {
         nn_idx[jq[qt]] = (uint32_t)w_nn;
