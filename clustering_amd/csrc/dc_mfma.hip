@@ -1032,6 +1032,7 @@ const SweepSwitches& sweep_switches() {
     if ((v = env("DC_NN_SHARED"))) w.nn_shared = atoi(v);
     w.waves_per_group = one_of_124(env("DC_WAVES_PER_GROUP"), 0);
     if ((v = env("DC_NN_COOP"))) w.nn_coop = atoi(v);
+    if ((v = env("DC_NN_RHO"))) w.nn_rho = v[0] != '0';
     if ((v = env("DC_WAVE_TARGET"))) w.wave_target = (uint32_t)atoi(v);
     if ((v = env("DC_SHARE_FLOOR"))) w.share_floor = (uint32_t)atoi(v);
     if ((v = env("DC_POP_COMPONENTS"))) w.components = v[0] != '0';
@@ -1440,7 +1441,8 @@ static int order_own_queries(const PrunedWs& W, const Layout& L, const QueryPlan
   if (int rc = W.sort.run(W.perm_q, Q.n_q, stream, fine_bits, &remap)) return rc;
   hipLaunchKernelGGL(order_rows2_kernel, dim3((32 * Q.T_q + 255) / 256), blk, order_rows_smem_set(n_cols), stream, d_coords, n_cols,
                      L.NM, (const uint32_t*)W.perm_q, Q.T_q, (float*)nullptr, (float4*)(p + L.off_box_q), (const float*)nullptr,
-                     (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (const uint32_t*)W.tile_comp_q, W.origins, W.hdr,
+                     (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (float2*)nullptr, (const uint32_t*)W.tile_comp_q, W.origins,
+                     W.hdr,
                      (uint4*)nullptr, 0, (float*)nullptr, (uint4*)(p + L.off_img_q), (float*)(p + L.off_norm_q), 1u,
                      QSeg{1u, 0u, 1u}, (unsigned long long*)nullptr, (uint32_t*)nullptr, 0u);
   return 0;
@@ -1495,7 +1497,8 @@ static void pop_pruned_one(const PopPlan& plan, const float* d_coords, uint32_t 
       const bool ref_queries = Q.q_mode != kQueryOwnOrder;
       hipLaunchKernelGGL(order_rows2_kernel, dim3((32 * T_r + 255) / 256), blk, order_rows_smem_set(n_cols), stream, d_coords, n_cols,
                          L.NM, (const uint32_t*)W.perm_p, T_r, (float*)(p + L.off_coords_p), (float4*)(p + L.off_box_p),
-                         (const float*)nullptr, (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (const uint32_t*)W.tile_comp,
+                         (const float*)nullptr, (float*)nullptr, (uint32_t*)nullptr, (float2*)nullptr, (float2*)nullptr,
+                         (const uint32_t*)W.tile_comp,
                          W.origins, W.hdr, (uint4*)(p + L.off_img_p), 0, (float*)(p + L.off_norm_p),
                          ref_queries ? (uint4*)(p + L.off_img_q) : (uint4*)nullptr, (float*)nullptr, plan.group_tiles, Q.q_seg,
                          (unsigned long long*)(W.comp + kCompHash), pos_clean ? (uint32_t*)(p + L.off_pq) : (uint32_t*)nullptr, 1u);
@@ -1823,9 +1826,12 @@ static void nn_pruned_sel(const float* d_coords, uint32_t n_rows, uint32_t n_col
   // rows, boxes, free-energy ranges, and the operand images: the neighbour sweeps take the reference norms through the
   // operand image (dc_mfma_kernels.hpp "reference norms folded": a_form 2), the queries' B form for this segment's groups
   {
+    // (the tiles' radial ranges, dc_rho_gap.hpp: for the sweep whose queries are rows of this order)
+    const bool with_rho = !own && sweep_switches().nn_rho;
     hipLaunchKernelGGL(order_rows2_kernel, dim3((32 * T_r + 255) / 256), blk, order_rows_smem_set(n_cols), stream, d_coords, n_cols,
                        L.NM, (const uint32_t*)W.perm_p, T_r, (float*)(p + L.off_coords_p), (float4*)(p + L.off_box_p), d_fe,
                        (float*)(p + L.off_fe_s), (uint32_t*)(p + L.off_invpos), (float2*)(p + L.off_ferange_p),
+                       with_rho ? (float2*)(p + L.off_rhorange_p) : (float2*)nullptr,
                        (const uint32_t*)W.tile_comp, W.origins, W.hdr, (uint4*)(p + L.off_img_p), 2, (float*)(p + L.off_norm_p),
                        own ? (uint4*)nullptr : (uint4*)(p + L.off_img_q), (float*)nullptr, plan.group_tiles, Q.q_seg,
                        (unsigned long long*)(W.comp + kCompHash), (uint32_t*)nullptr, 0u);

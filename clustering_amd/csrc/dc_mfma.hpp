@@ -31,6 +31,7 @@ struct SweepSwitches {
   int nn_shared = -1;             // DC_NN_SHARED=0 / 1: the same for the neighbour sweep
   int waves_per_group = 0;        // DC_WAVES_PER_GROUP=1 / 2 / 4: waves per workgroup of the per-wave sweeps
   int nn_coop = -1;               // DC_NN_COOP=0 / 1: COOP neighbour workgroups never / from four shares on
+  bool nn_rho = true;             // DC_NN_RHO=0: the neighbour sweep's rings without the radial gap (dc_rho_gap.hpp)
   uint32_t wave_target = 0;       // DC_WAVE_TARGET: waves a pruned launch aims at (0: the sweep's own)
   uint32_t share_floor = 0;       // DC_SHARE_FLOOR: least reference tiles per share (0: the sweep's own)
   bool components = true;         // DC_POP_COMPONENTS=0: one component whatever the data

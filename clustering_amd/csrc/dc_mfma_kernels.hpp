@@ -74,6 +74,7 @@
 #pragma once
 #include "dc_mfma.hpp"
 #include "dc_credit.hpp"
+#include "dc_rho_gap.hpp"
 
 #include <assert.h>
 #include <float.h>
@@ -165,9 +166,11 @@ struct Layout {
       // rows (B form)
       off_img_p, off_norm_p, off_perm_p, off_box_p, off_img_q, off_norm_q, off_perm_q, off_box_q,
       off_ferange_p,   // per reference tile (fe_lo, fe_hi) -- pruned neighbour sweep
+      off_rhorange_p,  // per reference tile (rho_lo, rho_hi), the radial range behind columns 0/1 (dc_rho_gap.hpp)
       off_coords_p,    // ORIGINAL coordinates gathered into the reference order (exact path reads)
       off_merge64,     // [2][n_rows] packed (d2, id) for merging reference chunks (neighbour sweep)
       off_box_t,       // tile boxes regrouped by reference share (neighbour sweep: contiguous scans)
+      off_rho_t,       // ... and the tiles' radial ranges, regrouped the same way
       off_comp,        // component region (kComp* words) + per-tile component of the reference / query order
       off_tile_comp, off_tile_comp_q,
       fixed_end;
@@ -206,10 +209,12 @@ inline Layout make_layout(size_t n_rows, size_t n_cols) {
   L.off_perm_q = L.off_norm_q + row_bytes;
   L.off_box_q = L.off_perm_q + row_bytes;
   L.off_ferange_p = align256(L.off_box_q + sizeof(float) * 4 * (size_t)L.Tp);
-  L.off_coords_p = align256(L.off_ferange_p + sizeof(float) * 2 * (size_t)L.Tp);
+  L.off_rhorange_p = align256(L.off_ferange_p + sizeof(float) * 2 * (size_t)L.Tp);
+  L.off_coords_p = align256(L.off_rhorange_p + sizeof(float) * 2 * (size_t)L.Tp);
   L.off_merge64 = align256(L.off_coords_p + sizeof(float) * 32 * (size_t)L.Tp * n_cols);
   L.off_box_t = align256(L.off_merge64 + sizeof(unsigned long long) * 2 * n_rows);
-  L.off_tile_comp = align256(L.off_box_t + sizeof(float) * 4 * ((size_t)L.Tp + L.Tp / 32 + 64));   // (+ one pad box per share)
+  L.off_rho_t = align256(L.off_box_t + sizeof(float) * 4 * ((size_t)L.Tp + L.Tp / 32 + 64));   // (+ one pad box per share)
+  L.off_tile_comp = align256(L.off_rho_t + sizeof(float) * 2 * ((size_t)L.Tp + L.Tp / 32 + 64));
   L.off_tile_comp_q = align256(L.off_tile_comp + sizeof(uint32_t) * (size_t)L.Tp);
   L.fixed_end = align256(L.off_tile_comp_q + sizeof(uint32_t) * (size_t)L.Tp);
   return L;
@@ -2150,6 +2155,7 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
     const float* __restrict__ fe, const uint4* __restrict__ img_r,
     const float* __restrict__ norms_r, const uint32_t* __restrict__ perm_r,
     const float4* __restrict__ box_r, const float4* __restrict__ box_t,
+    const float2* __restrict__ rho_r, const float2* __restrict__ rho_t,
     const float2* __restrict__ ferange_r,
     const float* __restrict__ fe_c, const float* __restrict__ coords_c,
     const uint32_t* __restrict__ invpos_r, uint32_t T,
@@ -2159,6 +2165,8 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
     const uint32_t* __restrict__ hdr, unsigned long long* __restrict__ chain_counter,
     unsigned long long* __restrict__ merge64, uint32_t* __restrict__ nn_idx,
     float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx, float* __restrict__ hd_d2, CompView CV) {
+  // (rho_r / rho_t: the radial ranges of the reference tiles by tile and regrouped by share like box_t, or both null:
+  //  the queries are not rows of the reference order, or DC_NN_RHO = 0 -- the rings then go by the boxes alone)
   // dynamic LDS, per wave of the workgroup: the survivor list of a scan round [kListCap], then [TQ*32][n_cols] query
   // rows (original coordinates), then the candidate queues [TQ][kQueueCap][64]
   extern __shared__ __attribute__((aligned(16))) float nn_dyn_lds[];
@@ -2470,6 +2478,22 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
   cell2 = comp_cell * comp_cell;
   const uint32_t U_stride = (T + n_chunks - 1) / n_chunks;   // boxes of a share in box_t
   const float dgx = gbox.y - gbox.x, dgy = gbox.w - gbox.z;
+  // The radial range of the group, wave-uniform: the union of the ranges of its own query tiles, which are tiles of the
+  // reference order (so a tile of the wave's own is never a positive gap away).  Without ranges (0, 0) on both sides:
+  // no gap.  An all-pad query tile holds (+inf, -inf) and widens nothing.
+  float grho_lo = 0.0f, grho_hi = 0.0f;
+  if (rho_r) {
+    grho_lo = INFINITY;
+    grho_hi = -INFINITY;
+#pragma unroll
+    for (int qt = 0; qt < TQ; ++qt) {
+      const float2 v = (qt0 + qt < TQT) ? rho_r[qt0 + qt] : make_float2(INFINITY, -INFINITY);
+      grho_lo = fminf(grho_lo, v.x);
+      grho_hi = fmaxf(grho_hi, v.y);
+    }
+    grho_lo = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(grho_lo)));
+    grho_hi = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(grho_hi)));
+  }
   float r2_lo = -1.0f;                                     // rings: r2_lo <= gap2 < r2_hi
   float r2_hi = fmaxf(dgx * dgx + dgy * dgy, cell2);
   if (!(r2_hi > 0.0f)) r2_hi = FLT_MIN;
@@ -2483,13 +2507,25 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
       const float4* box_s = box_t + (size_t)chunk * U_stride;
       float4 rb_next = ((uint32_t)lane < lim) ? box_s[base + lane]
                                               : make_float4(INFINITY, -INFINITY, INFINITY, -INFINITY);
+      // (the radial ranges of the share, stored like its boxes and fetched with them; without ranges the group's (0, 0))
+      const float2* rho_s = rho_t ? rho_t + (size_t)chunk * U_stride : nullptr;
+      float2 rr_next = (rho_s && (uint32_t)lane < lim) ? rho_s[base + lane] : make_float2(0.0f, 0.0f);
       for (uint32_t k = 0; k < lim; k += 64) {
         const uint32_t t = tile_of(base + k + lane);
         const float4 rb = rb_next;   // fetched one step ahead: the scan is latency-bound otherwise
-        if (k + 64 + lane < lim) rb_next = box_s[base + k + 64 + lane];
+        const float2 rr = rr_next;
+        if (k + 64 + lane < lim) {
+          rb_next = box_s[base + k + 64 + lane];
+          if (rho_s) rr_next = rho_s[base + k + 64 + lane];
+        }
         bool ok = false;
         if (k + lane < lim) {
-          const float g2 = box_gap2(gbox, rb);
+          // Lower bound of d2 between the group's rows and the tile's: the box gap in columns 0/1 plus the squared gap
+          // of the radial ranges in the other columns (dc_rho_gap.hpp: d2 >= d2_01 + (rho(x) - rho(y))^2 within a
+          // component, and a share only holds tiles of the group's component).  rho_gap2 is rounded down; the sum
+          // rounds once more, by 2^-24 -- three orders of magnitude inside the margins the rings keep around every
+          // use of a gap (sure = 0.9999 r2_hi, the next ring at 1.001 of the need).
+          const float g2 = box_gap2(gbox, rb) + rho_gap2(grho_lo, grho_hi, rr.x, rr.y);
           ok = (g2 < r2_hi) & (g2 >= r2_lo);
         }
         // (the ring logic below only ever sees this wave's share of the references: its incumbents
@@ -2963,12 +2999,15 @@ void pop_dispatch(const SweepArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t
 
 // tile boxes regrouped by reference share: share c holds the tiles c, c + n, c + 2n, ... at
 // box_t[c * ceil(T / n) + u]
+// (rho_r / rho_t: the tiles' radial ranges the same way, or null)
 __global__ void box_by_share_kernel(const float4* __restrict__ box_r, uint32_t T, uint32_t n_chunks,
-                                    float4* __restrict__ box_t) {
+                                    float4* __restrict__ box_t, const float2* __restrict__ rho_r,
+                                    float2* __restrict__ rho_t) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
   const uint32_t stride = (T + n_chunks - 1) / n_chunks;
   box_t[(size_t)(t % n_chunks) * stride + t / n_chunks] = box_r[t];
+  if (rho_r) rho_t[(size_t)(t % n_chunks) * stride + t / n_chunks] = rho_r[t];
 }
 
 struct NnPrunedArgs {     // regions of the neighbour sweep's (cell, free energy) ordering
@@ -2977,6 +3016,8 @@ struct NnPrunedArgs {     // regions of the neighbour sweep's (cell, free energy
   const uint32_t* perm_r;
   const float4* box_r;
   float4* box_t;
+  const float2* rho_r;       // per tile [rho_lo, rho_hi] (dc_rho_gap.hpp) and its copy by share; both null: no radial gap
+  float2* rho_t;
   const float2* ferange_r;
   const float* fe_c;
   const float* coords_c;
@@ -3143,10 +3184,12 @@ void timed_launch(int kind, hipStream_t s, F&& launch) {
 }
 // around a neighbour sweep of n_chunks reference shares: the merge buffer of several shares and the boxes of every share
 // in front, the merged results back to the frames behind (group_tiles: query tiles per group)
-inline void nn_shares_begin(const NnPrunedArgs& A, uint32_t n_rows, uint32_t T, uint32_t n_chunks, hipStream_t s) {
+// (with_rho: the per-wave sweep's radial ranges go along, where the call has them)
+inline void nn_shares_begin(const NnPrunedArgs& A, uint32_t n_rows, uint32_t T, uint32_t n_chunks, bool with_rho, hipStream_t s) {
   if (n_chunks > 1)
     hipLaunchKernelGGL(nn_merge_fill_kernel, dim3((2 * n_rows + 255) / 256), dim3(256), 0, s, A.merge64, n_rows);
-  hipLaunchKernelGGL(box_by_share_kernel, dim3((T + 255) / 256), dim3(256), 0, s, A.box_r, T, n_chunks, A.box_t);
+  hipLaunchKernelGGL(box_by_share_kernel, dim3((T + 255) / 256), dim3(256), 0, s, A.box_r, T, n_chunks, A.box_t,
+                     with_rho ? A.rho_r : (const float2*)nullptr, A.rho_t);
 }
 inline void nn_shares_end(const NnPrunedArgs& A, uint32_t n_rows, uint32_t n_chunks, uint32_t group_tiles,
                           uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
@@ -3179,7 +3222,7 @@ void nn_pruned_dispatch(const NnPlan& pl, const float* coords, uint32_t n_rows, 
       if (groups == 0) return;
       const uint32_t n_chunks = pick_chunks(groups * 4 * TQV, TQV, kNnWaveTarget, T, kNnShareFloor, (size_t)S * 1024 + 128);
       const size_t smem = (size_t)kRing * (S * 64 + kNnRingExtra) * 16 + sizeof(uint32_t) * 4 * (TQV * kQueueCap * 64 + TQV * 32);
-      nn_shares_begin(A, n_rows, T, n_chunks, s);
+      nn_shares_begin(A, n_rows, T, n_chunks, false, s);
       // (the MFMAs in front of the early-out test: the most this NM can need, or one fewer for its narrowest rows)
       constexpr int kNbMax = kNnCoarseMax<S>;
       constexpr int kNbMin = (S > 1) ? nn_coarse_for((16 * (S - 1) - kConstSlots) / kPieceGroups + 1) : kNbMax;
@@ -3213,11 +3256,11 @@ void nn_pruned_dispatch(const NnPlan& pl, const float* coords, uint32_t n_rows, 
     n_chunks = (n_chunks + kNnCoopWaves - 1) / kNnCoopWaves * kNnCoopWaves;
     const size_t smem_c = sizeof(uint32_t) * (kNnCoopWaves * (kListCap + 2 * kWaveQueue) + 8 * TQV * 32) +
                           sizeof(float) * TQV * 32 * (size_t)n_cols;
-    nn_shares_begin(A, n_rows, T, n_chunks, s);
+    nn_shares_begin(A, n_rows, T, n_chunks, true, s);
     timed_launch(1, s, [&] {
       hipLaunchKernelGGL((nn_pruned_kernel<S, TQV, true>), dim3(grid_x8(waves), n_chunks / kNnCoopWaves), dim3(64 * kNnCoopWaves), smem_c, s,
-                         coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.ferange_r,
-                         A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
+                         coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.rho_r,
+                         (const float2*)(A.rho_r ? A.rho_t : nullptr), A.ferange_r, A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
                          A.full_range, A.cell2, hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
     });
   } else {
@@ -3225,11 +3268,11 @@ void nn_pruned_dispatch(const NnPlan& pl, const float* coords, uint32_t n_rows, 
     const uint32_t wpb = pl.waves;
     const size_t smem = wpb * (sizeof(uint32_t) * kListCap + sizeof(float) * TQV * 32 * (size_t)n_cols +
                                sizeof(uint32_t) * (TQV * kQueueCap * 64 + 2 * TQV * 32));
-    nn_shares_begin(A, n_rows, T, n_chunks, s);
+    nn_shares_begin(A, n_rows, T, n_chunks, true, s);
     timed_launch(1, s, [&] {
       hipLaunchKernelGGL((nn_pruned_kernel<S, TQV>), dim3(grid_x8((waves + wpb - 1) / wpb), n_chunks), dim3(64 * wpb), smem, s,
-                         coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.ferange_r,
-                         A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
+                         coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.rho_r,
+                         (const float2*)(A.rho_r ? A.rho_t : nullptr), A.ferange_r, A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
                          A.full_range, A.cell2, hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
     });
   }

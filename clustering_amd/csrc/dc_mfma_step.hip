@@ -41,6 +41,10 @@ void DC_CAT(nn_pruned_step_, DC_STEP)(const NnPlan& plan, const float* coords, u
   A.box_r = (const float4*)(p + L.off_box_p);
   A.box_t = (float4*)(p + L.off_box_t);
   A.ferange_r = (const float2*)(p + L.off_ferange_p);
+  // the radial ranges of the reference tiles, where the queries are rows of the reference order (DC_NN_RHO = 0: none)
+  const bool rho = q_mode == kQueryAll && sweep_switches().nn_rho;
+  A.rho_r = rho ? (const float2*)(p + L.off_rhorange_p) : nullptr;
+  A.rho_t = (float2*)(p + L.off_rho_t);
   A.fe_c = (const float*)(p + L.off_fe_s);
   A.coords_c = (const float*)(p + L.off_coords_p);
   A.invpos_r = (const uint32_t*)(p + L.off_invpos);

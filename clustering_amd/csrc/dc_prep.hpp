@@ -621,7 +621,8 @@ static inline size_t order_rows_smem(uint32_t n_cols) {
 __global__ __launch_bounds__(256) void order_rows2_kernel(
     const float* __restrict__ coords, uint32_t D, uint32_t NM, const uint32_t* __restrict__ perm, uint32_t T,
     float* __restrict__ coords_o, float4* __restrict__ boxes, const float* __restrict__ fe, float* __restrict__ fe_s,
-    uint32_t* __restrict__ invpos, float2* __restrict__ ferange, const uint32_t* __restrict__ tile_comp,
+    uint32_t* __restrict__ invpos, float2* __restrict__ ferange, float2* __restrict__ rhorange,
+    const uint32_t* __restrict__ tile_comp,
     const float* __restrict__ origins, uint32_t* __restrict__ hdr, uint4* __restrict__ img_a, int a_form,
     float* __restrict__ norms_a, uint4* __restrict__ img_b, float* __restrict__ norms_b, uint32_t grp_tq, QSeg grp,
     unsigned long long* __restrict__ hash_slots, uint32_t* __restrict__ zero_pos, uint32_t zero_planes) {
@@ -691,6 +692,33 @@ __global__ __launch_bounds__(256) void order_rows2_kernel(
   if ((pos & 31u) == 0 && in_range) {
     boxes[t] = make_float4(lo0, hi0, lo1, hi1);   // empty tile: (+inf, -inf, ..): infinitely far
     if (ferange) ferange[t] = make_float2(flo, fhi);
+  }
+  if (rhorange) {
+    // the range of rho = |(x - o)[2..D)| over the tile's live rows, o the origin the tile's operand image uses (below):
+    // the radial gap of the neighbour sweep's ring rule (dc_rho_gap.hpp).  Formed in double -- the differences of two
+    // floats are exact there, the sum of at most kMaxCols squares is good to 2^-45 --, so the float is within half an ulp
+    // (and 2^-29 of one) of the real number; rho_range_widen adds four.
+    float rlo = INFINITY, rhi = -INFINITY;
+    if (live) {
+      const uint32_t tc = tile_comp[t];
+      const float* o = (tc < (uint32_t)kMaxComp) ? origins + (size_t)tc * kMaxCols
+                                                 : reinterpret_cast<const float*>(reinterpret_cast<const char*>(hdr) + kHdrMeans);
+      double r2 = 0.0;
+      for (uint32_t k = 2; k < D; ++k) {
+        const double d = (double)row[k] - (double)o[k];
+        r2 += d * d;
+      }
+      rlo = rhi = (float)sqrt(r2);
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {
+      rlo = fminf(rlo, __shfl_xor(rlo, off, 64));
+      rhi = fmaxf(rhi, __shfl_xor(rhi, off, 64));
+    }
+    if ((pos & 31u) == 0 && in_range) {
+      if (D > 2) rho_range_widen(rlo, rhi);   // (D <= 2: (0, 0) as it is; no live row: (+inf, -inf))
+      rhorange[t] = make_float2(rlo, rhi);
+    }
   }
   // ---- operand images: wave w builds tiles 2 w and 2 w + 1 of the block
   const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
