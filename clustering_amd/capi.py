@@ -48,6 +48,7 @@ SYMBOLS = (
     "dc_hip_wide_workspace_bytes", "dc_hip_populations_wide_dev", "dc_hip_nearest_neighbors_wide_dev", "dc_hip_wide_info_dev",
     "dc_hip_cross_wide_workspace_bytes", "dc_hip_populations_cross_wide_dev", "dc_hip_nearest_neighbors_cross_wide_dev",
     "dc_hip_radius_pairs_wide_dev", "dc_hip_radius_min_edge_wide_dev", "dc_hip_radius_forest_wide",
+    "dc_hip_wide_pruned_workspace_bytes", "dc_hip_populations_wide_pruned_dev", "dc_hip_wide_pruned_order_dev",
 )
 
 
@@ -201,6 +202,12 @@ def _load():
     lib.dc_hip_radius_min_edge_wide_dev.argtypes = [vp, sz, sz, C.c_float, vp, vp, sz, sz, vp, vp, vp, sz, vp]
     lib.dc_hip_radius_forest_wide.restype = i32
     lib.dc_hip_radius_forest_wide.argtypes = [vp, sz, sz, C.c_float, vp, i32, vp, C.POINTER(sz), C.POINTER(C.c_uint32)]
+    lib.dc_hip_wide_pruned_workspace_bytes.restype = sz
+    lib.dc_hip_wide_pruned_workspace_bytes.argtypes = [sz, sz, sz]
+    lib.dc_hip_populations_wide_pruned_dev.restype = i32
+    lib.dc_hip_populations_wide_pruned_dev.argtypes = [vp, sz, sz, C.POINTER(C.c_float), sz, sz, sz, vp, vp, sz, vp]
+    lib.dc_hip_wide_pruned_order_dev.restype = i32
+    lib.dc_hip_wide_pruned_order_dev.argtypes = [vp, sz, sz, vp, vp]
     lib.dc_hip_free_energies_scaled_dev.restype = i32
     lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
     lib.dc_hip_populations_cross.restype = i32

@@ -75,6 +75,7 @@
 #include "dc_mfma.hpp"
 #include "dc_credit.hpp"
 #include "dc_rho_gap.hpp"
+#include "dc_wide_prune.hpp"
 
 #include <assert.h>
 #include <float.h>
@@ -288,14 +289,18 @@ __device__ __forceinline__ float fkey_inv(uint32_t k) {
 // Measured on C3: neighbours 38.6 ms at 8192 frames per cell, 30.0 at 512, 27.4 at 128; populations
 // 36.1 ms with cell = radius (about 15000 frames), 31.7 ms at about 60 frames per cell.
 constexpr float kPopCellFrames = 64.0f, kNnCellFrames = 128.0f;
-__device__ __forceinline__ float auto_cell(const uint32_t* __restrict__ hdr, uint32_t n_rows,
-                                           float frames_per_cell) {
-  const float e0 = fkey_inv(hdr[9]) - fkey_inv(~hdr[8]), e1 = fkey_inv(hdr[11]) - fkey_inv(~hdr[10]);
+// (e0, e1: the extents of columns 0 / 1; anything but a positive number counts as no extent)
+__device__ __forceinline__ float auto_cell_of(float e0, float e1, uint32_t n_rows, float frames_per_cell) {
   const double a0 = (e0 > 0.0f && e0 <= FLT_MAX) ? (double)e0 : 0.0;
   const double a1 = (e1 > 0.0f && e1 <= FLT_MAX) ? (double)e1 : 0.0;
   const double f = (double)frames_per_cell / (double)(n_rows ? n_rows : 1u);
   const double c = (a0 > 0.0 && a1 > 0.0) ? sqrt(a0 * a1 * f) : (a0 + a1) * f;
   return (float)c;
+}
+// ... from the bounding box in header words 8..11
+__device__ __forceinline__ float auto_cell(const uint32_t* __restrict__ hdr, uint32_t n_rows,
+                                           float frames_per_cell) {
+  return auto_cell_of(fkey_inv(hdr[9]) - fkey_inv(~hdr[8]), fkey_inv(hdr[11]) - fkey_inv(~hdr[10]), n_rows, frames_per_cell);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1199,10 +1204,9 @@ __device__ __forceinline__ void ref_credit(const uint32_t (&sb)[TQ], uint32_t t,
 }
 
 __device__ __forceinline__ float box_gap2(const float4& a, const float4& b) {
-  // boxes are (lo0, hi0, lo1, hi1); squared distance between them in the (col 0, col 1) plane
-  const float dx = fmaxf(0.0f, fmaxf(a.x - b.y, b.x - a.y));
-  const float dy = fmaxf(0.0f, fmaxf(a.z - b.w, b.z - a.w));
-  return dx * dx + dy * dy;
+  // boxes are (lo0, hi0, lo1, hi1); squared distance between them in the (col 0, col 1) plane: ONE copy of the
+  // arithmetic, which the host tests can call (dc_wide_prune.hpp)
+  return wide_box_gap2(WideBox{a.x, a.y, a.z, a.w}, WideBox{b.x, b.y, b.z, b.w});
 }
 
 // what a pruned population sweep needs to know about the components (file header of this section): the component of

@@ -130,6 +130,102 @@ void launch_min_edge_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t 
   sweep_timer_mark(0, false, s);
 }
 
+// ---- the pruned self population sweep (dc_hip_populations_wide_pruned_dev) --------------------------------
+namespace {
+struct WidePrunedLayout {
+  WideLayout L;      // the head: what the unpruned sweeps lay out
+  uint32_t blocks;   // blocks of kWideBlockRows positions (= L.Tp / kWideBlockTiles)
+  size_t off_perm, off_keys, off_keys_o, off_vals, off_coords, off_boxes, off_cnt, off_sort, sort_bytes, total;
+};
+WidePrunedLayout wide_pruned_layout(size_t n_rows, size_t n_cols) {
+  WidePrunedLayout P;
+  P.L = wide_layout(n_rows, n_cols);
+  P.blocks = P.L.Tp / kWideBlockTiles;
+  const size_t words = align256(sizeof(uint32_t) * n_rows);
+  P.off_perm = P.L.total;   // [n_rows] position -> row
+  P.off_keys = P.off_perm + words;
+  P.off_keys_o = P.off_keys + words;
+  P.off_vals = P.off_keys_o + words;
+  P.off_coords = P.off_vals + words;   // [n_rows][n_cols] the rows in the order
+  P.off_boxes = align256(P.off_coords + sizeof(float) * n_rows * n_cols);
+  P.off_cnt = align256(P.off_boxes + sizeof(float4) * P.blocks);   // [kMaxRadiiPerLaunch][n_rows] counts by position
+  P.off_sort = align256(P.off_cnt + sizeof(uint32_t) * kMaxRadiiPerLaunch * n_rows);
+  P.sort_bytes = sort_temp_bytes(n_rows);
+  P.total = align256(P.off_sort + P.sort_bytes);
+  return P;
+}
+}  // namespace
+
+size_t wide_pruned_workspace_bytes(size_t n_rows, size_t n_cols) {
+  if (!wide_mfma_supports(n_cols) || n_rows == 0) return 0;
+  return wide_pruned_layout(n_rows, n_cols).total;
+}
+
+int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t s) {
+  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  uint32_t* perm = (uint32_t*)(p + P.off_perm);
+  uint32_t* keys = (uint32_t*)(p + P.off_keys);
+  uint32_t* vals = (uint32_t*)(p + P.off_vals);
+  float* coords_o = (float*)(p + P.off_coords);
+  if (wide_stats_launches(d_coords, n_rows, n_cols, nullptr, d_ws, s) != 0) return -1;
+  hipLaunchKernelGGL(wide_extent_kernel, dim3((uint32_t)min_sz(1024, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s, d_coords,
+                     n_rows, n_cols, hdr);
+  hipLaunchKernelGGL(wide_prune_key_kernel, dim3((uint32_t)min_sz(4096, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s, d_coords,
+                     n_rows, n_cols, (const uint32_t*)hdr, keys, vals);
+  if (sort_pairs_u32(keys, (uint32_t*)(p + P.off_keys_o), vals, perm, n_rows, p + P.off_sort, P.sort_bytes, s, kCellKeyBits) != 0)
+    return -1;
+  hipLaunchKernelGGL(wide_prune_rows_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, d_coords, n_rows, n_cols,
+                     (const uint32_t*)perm, P.blocks, coords_o, (float4*)(p + P.off_boxes), hdr);
+  return wide_image_launches(coords_o, n_rows, n_cols, d_ws, s);
+}
+
+int launch_pop_wide_pruned(uint32_t n_rows, uint32_t n_cols, size_t segment, size_t n_segments, const Rad2& rad2, int n_rad,
+                           uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
+  if (n_rows == 0 || n_rad <= 0 || n_segments == 0) return 0;
+  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
+  if (segment >= P.blocks) return 0;   // no block of the order: zeros (the caller's), no tile pair
+  char* p = (char*)d_ws;
+  uint32_t* cnt = (uint32_t*)(p + P.off_cnt);
+  if (hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (size_t)n_rad * n_rows, s) != hipSuccess) return -1;
+  WidePrunedArgs X{};
+  static_cast<WideArgs&>(X) = wide_args(P.L, (const float*)(p + P.off_coords), n_rows, n_cols, 0, n_rows, d_ws);
+  X.rad2 = rad2;
+  X.n_rad = n_rad;
+  X.pops = cnt;
+  X.boxes = (const float4*)(p + P.off_boxes);
+  X.seg = (uint32_t)segment;
+  X.n_seg = (uint32_t)(n_segments < 0xFFFFFFFFull ? n_segments : 0xFFFFFFFFull);
+  float r2max = 0.0f;
+  for (int k = 0; k < n_rad; ++k) r2max = rad2.v[k] > r2max ? rad2.v[k] : r2max;
+  X.far2 = wide_prune_far2(r2max);
+  const uint32_t q_blocks = (uint32_t)((P.blocks - segment + n_segments - 1) / n_segments);
+  const dim3 grid(wide_grid_size(q_blocks, wide_shares(P.blocks)));
+  sweep_timer_mark(0, true, s);
+  if (n_rad == 1)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, kSelf, true>), grid, dim3(256), 0, s, X);
+  else if (n_rad <= 4)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 4, kSelf, true>), grid, dim3(256), 0, s, X);
+  else
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, kSelf, true>), grid, dim3(256), 0, s, X);
+  sweep_timer_mark(0, false, s);
+  hipLaunchKernelGGL(wide_prune_scatter_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,
+                     (const uint32_t*)(p + P.off_perm), (const uint32_t*)cnt, n_rows, n_rad, d_pops_first_row);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int wide_pruned_order(const void* d_ws, uint32_t n_rows, uint32_t n_cols, uint32_t* d_perm, hipStream_t s) {
+  uint32_t tag[3] = {0u, 0u, 0u};
+  if (hipMemcpyAsync(tag, (const char*)d_ws + 4 * kWideHdrOrder, sizeof(tag), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
+  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  if (tag[0] != kWideOrderMark || tag[1] != n_rows || tag[2] != n_cols) return 1;
+  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
+  if (hipMemcpyAsync(d_perm, (const char*)d_ws + P.off_perm, sizeof(uint32_t) * (size_t)n_rows, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return -1;
+  return 0;
+}
+
 int wide_prepare_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
                          void* d_ws, hipStream_t s) {
   return wide_prepare_against_launches(d_query, n_query, d_ref, n_ref, n_cols, d_ws, s);

@@ -38,6 +38,24 @@ void launch_min_edge_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t 
                                const uint32_t* d_rank, uint32_t i_from, uint32_t i_to, unsigned long long* d_best,
                                uint32_t* d_pops, void* d_ws, hipStream_t stream);
 
+// ---- the pruned self population sweep (dc_hip_populations_wide_pruned_dev) --------------------------------
+// The rows in a spatial order on columns 0 / 1 (cell keys, one stable sort), gathered once into that order, a box per
+// block of 128 positions; a workgroup scans the boxes of its share and runs the chains of the blocks that can hold a
+// pair within the launch's largest radius (dc_wide_prune.hpp).  Counts by position, scattered to the rows behind the sweep.
+// bytes: the workspace of the unpruned sweeps at its head (header, images, norms), then the order, the gathered rows, the
+// boxes, the counts and the sort's scratch; 0 if the column count is not served or there are no rows; monotone in n_rows
+size_t wide_pruned_workspace_bytes(size_t n_rows, size_t n_cols);
+// statistics, order, gathered rows, boxes and images, on the stream, no host synchronisation; returns 0 on success
+int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t stream);
+// the populations of the query blocks segment, segment + n_segments, ... of the order (n_segments >= 1) for up to
+// kMaxRadiiPerLaunch radii, WRITTEN to d_pops_first_row for every row (zeros for the rows of other blocks); stands down
+// on flagged data, scatter included (the gated direct kernel answers).  Returns 0 on success.
+int launch_pop_wide_pruned(uint32_t n_rows, uint32_t n_cols, size_t segment, size_t n_segments, const Rad2& rad2, int n_rad,
+                           uint32_t* d_pops_first_row, void* d_ws, hipStream_t stream);
+// the order the workspace holds, position -> row, copied to d_perm; 0 ok, 1 the workspace holds no order of that shape,
+// -1 a HIP error (synchronises)
+int wide_pruned_order(const void* d_ws, uint32_t n_rows, uint32_t n_cols, uint32_t* d_perm, hipStream_t stream);
+
 // ---- the cross form: query rows against a reference (dc_hip_*_cross_wide_dev) -----------------------------
 // The same kernel in its kAgainst instances: one origin and one scale over both sets, the A form and the norms of the
 // reference, the B form and the merge words of the queries; every pair counts (no self term, no exclusion).

@@ -66,6 +66,13 @@ constexpr size_t kWideOffMeans = kWideOffSums + 8 * kWideMaxCols;      // [256] 
 constexpr size_t kWideOffImages = kWideOffMeans + 4 * kWideMaxCols;    // 4096
 static_assert(4 * (kWideHdrExact + 2) <= kWideInfoBytes && kWideInfoBytes <= kHdrBytes, "counters inside the info head");
 static_assert(kWideHdrTiles > kHdrShift && kWideHdrTiles > kHdrScale + 4 && kWideHdrTiles % 2 == 0, "counters clear of the shared header words, 64-bit aligned");
+// the pruned population sweep: extent of columns 0 / 1 as ~key(min0), key(max0), ~key(min1), key(max1)
+// (words 8..11 of the 64-column header, here clear of the counters), and what order the workspace holds: mark, rows, columns
+constexpr uint32_t kWideHdrExt = 48, kWideHdrOrder = 52, kWideOrderMark = 0x57504F52u;
+static_assert(kWideHdrExt >= kWideHdrExact + 2 && 4 * (kWideHdrOrder + 3) <= kWideInfoBytes, "the pruned sweep's words: behind the counters, inside the info head");
+constexpr float kWidePruneCellFrames = (float)kWideBlockRows;   // frames per cell of the order's grid: one block's worth
+constexpr uint32_t kWideListCap = 1024;   // surviving reference blocks a workgroup lists per scan round (4 KiB of LDS)
+static_assert(kWideListCap % 256 == 0, "a round: whole chunks of 64 boxes for each of the four waves");
 
 // Workgroup -> (query block, reference share).  A workgroup re-reads the fragments of its query block for every
 // reference block it meets, and streams the reference blocks of its share: both come out of L2 only if the workgroups
@@ -296,9 +303,9 @@ __global__ void wide_image_kernel(const float* __restrict__ coords, uint32_t n_r
 inline size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
 // the preparation of a call: header reset, statistics, scale, both images (dc_mfma_wide.hip wide_prepare; the model test
 // runs the same launches)
-inline int wide_prepare_launches(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, void* d_ws,
-                                 hipStream_t s) {
-  const WideLayout L = wide_layout(n_rows, n_cols);
+// ... its first half: header reset, statistics, scale
+inline int wide_stats_launches(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, void* d_ws,
+                               hipStream_t s) {
   char* p = (char*)d_ws;
   uint32_t* hdr = (uint32_t*)p;
   double* sums = (double*)(p + kWideOffSums);
@@ -314,11 +321,139 @@ inline int wide_prepare_launches(const float* d_coords, uint32_t n_rows, uint32_
   if (d_fe)
     hipLaunchKernelGGL(wide_fe_flag_kernel, dim3((uint32_t)min_sz(1024, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s, d_fe, n_rows, hdr);
   hipLaunchKernelGGL(wide_scale_kernel, dim3(1), dim3(1), 0, s, hdr);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// ... and its second: both images and the norms of the rows of d_coords (the pruned sweep: the rows gathered into its order)
+inline int wide_image_launches(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t s) {
+  const WideLayout L = wide_layout(n_rows, n_cols);
+  char* p = (char*)d_ws;
   const size_t frags = (size_t)L.Tp * L.NM * 64;
   hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags + 255) / 256)), dim3(256), 0, s, d_coords, n_rows, n_cols, L.NM,
-                     L.Tp, (const float*)means, (const uint32_t*)hdr, (uint4*)(p + L.off_img_a), (uint4*)(p + L.off_img_b),
-                     (float*)(p + L.off_norms));
+                     L.Tp, (const float*)(p + kWideOffMeans), (const uint32_t*)p, (uint4*)(p + L.off_img_a),
+                     (uint4*)(p + L.off_img_b), (float*)(p + L.off_norms));
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+inline int wide_prepare_launches(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, void* d_ws,
+                                 hipStream_t s) {
+  if (wide_stats_launches(d_coords, n_rows, n_cols, d_fe, d_ws, s) != 0) return -1;
+  return wide_image_launches(d_coords, n_rows, n_cols, d_ws, s);
+}
+
+// ---- the order of the pruned population sweep ----------------------------------------------------------
+// exact extent of columns 0 / 1 over their finite entries (header words kWideHdrExt.., zero before)
+__global__ __launch_bounds__(256) void wide_extent_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D,
+                                                          uint32_t* __restrict__ hdr) {
+  uint32_t m[4] = {0u, 0u, 0u, 0u};
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_rows; i += gridDim.x * 256u) {
+    const float x = coords[(size_t)i * D], y = coords[(size_t)i * D + 1];
+    if (fabsf(x) <= FLT_MAX) {
+      m[0] = max(m[0], ~fkey(x));
+      m[1] = max(m[1], fkey(x));
+    }
+    if (fabsf(y) <= FLT_MAX) {
+      m[2] = max(m[2], ~fkey(y));
+      m[3] = max(m[3], fkey(y));
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m[q] = max(m[q], (uint32_t)__shfl_xor((int)m[q], off, 64));
+    if ((threadIdx.x & 63u) == 0 && m[q] > __atomic_load_n(hdr + kWideHdrExt + q, __ATOMIC_RELAXED)) atomicMax(hdr + kWideHdrExt + q, m[q]);
+  }
+}
+// The cell grid on columns 0 / 1 over that extent, as against_grid (dc_prep.hpp) lays it: the edge gives about
+// kWidePruneCellFrames of the frames per cell of the bounding box, at most 4001 cells per dimension.
+struct WidePruneGrid {
+  float lo0, lo1, cell;
+  uint32_t ny;
+};
+__device__ __forceinline__ WidePruneGrid wide_prune_grid(const uint32_t* __restrict__ hdr, uint32_t n_rows) {
+  const uint32_t* ext = hdr + kWideHdrExt;
+  WidePruneGrid g;
+  g.lo0 = fkey_inv(~ext[0]);
+  g.lo1 = fkey_inv(~ext[2]);
+  float e0 = fkey_inv(ext[1]) - g.lo0, e1 = fkey_inv(ext[3]) - g.lo1;
+  if (!(fabsf(g.lo0) <= FLT_MAX)) g.lo0 = 0.0f;
+  if (!(fabsf(g.lo1) <= FLT_MAX)) g.lo1 = 0.0f;
+  if (!(e0 >= 0.0f) || !(e0 <= FLT_MAX)) e0 = 0.0f;
+  if (!(e1 >= 0.0f) || !(e1 <= FLT_MAX)) e1 = 0.0f;
+  g.cell = fmaxf(auto_cell_of(fkey_inv(ext[1]) - fkey_inv(~ext[0]), fkey_inv(ext[3]) - fkey_inv(~ext[2]), n_rows, kWidePruneCellFrames),
+                 fmaxf(e0, e1) / 4000.0f);
+  if (!(g.cell > 0.0f) || !(g.cell <= FLT_MAX)) g.cell = 1.0f;   // (every row on one point of the plane: one cell)
+  g.ny = (uint32_t)fminf(e1 / g.cell, 4000.0f) + 1u;
+  return g;
+}
+// cell key and value of every row (against_key_kernel's arithmetic: the cells numbered column by column, every other
+// column downwards, key 0 for a non-finite row)
+__global__ __launch_bounds__(256) void wide_prune_key_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D,
+                                                             const uint32_t* __restrict__ hdr, uint32_t* __restrict__ keys,
+                                                             uint32_t* __restrict__ vals) {
+  const WidePruneGrid g = wide_prune_grid(hdr, n_rows);
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_rows; i += gridDim.x * 256u) {
+    const float x = coords[(size_t)i * D], y = coords[(size_t)i * D + 1];
+    uint32_t key = 0;
+    if (fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX) {
+      const uint32_t bx = (uint32_t)fminf(fmaxf((x - g.lo0) / g.cell, 0.0f), 4000.0f);
+      const uint32_t by = min((uint32_t)fminf(fmaxf((y - g.lo1) / g.cell, 0.0f), 4000.0f), g.ny - 1u);
+      key = bx * g.ny + ((bx & 1u) ? g.ny - 1u - by : by);
+    }
+    keys[i] = key;
+    vals[i] = i;
+  }
+}
+// The rows gathered into the order (coords_o: [n_rows][D]) and the box of every block of kWideBlockRows positions in the
+// (col 0, col 1) plane, from the original floats of its live rows; a workgroup takes two blocks.  Thread 0 signs the order.
+__global__ __launch_bounds__(256) void wide_prune_rows_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D,
+                                                              const uint32_t* __restrict__ perm, uint32_t n_blocks,
+                                                              float* __restrict__ coords_o, float4* __restrict__ boxes,
+                                                              uint32_t* __restrict__ hdr) {
+  static_assert(kWideBlockRows == 128, "two waves per block of the order");
+  __shared__ uint32_t s_frame[256];
+  __shared__ float4 part[4];
+  const uint32_t pos0 = blockIdx.x * 256u, pos = pos0 + threadIdx.x;
+  const uint32_t frame = (pos < n_rows) ? perm[pos] : kInvalidFrame;
+  s_frame[threadIdx.x] = frame;
+  __syncthreads();
+  const uint32_t rows_here = min(256u, n_rows - pos0);
+  const size_t base = (size_t)pos0 * D;
+#pragma unroll 4
+  for (uint32_t e = threadIdx.x; e < rows_here * D; e += 256u) {
+    const uint32_t r = e / D, k = e - r * D;
+    coords_o[base + e] = coords[(size_t)s_frame[r] * D + k];
+  }
+  const bool live = frame != kInvalidFrame;
+  const float x = live ? coords[(size_t)frame * D] : 0.0f, y = live ? coords[(size_t)frame * D + 1] : 0.0f;
+  float lo0 = live ? x : INFINITY, hi0 = live ? x : -INFINITY;
+  float lo1 = live ? y : INFINITY, hi1 = live ? y : -INFINITY;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo0 = fminf(lo0, __shfl_xor(lo0, off, 64));
+    hi0 = fmaxf(hi0, __shfl_xor(hi0, off, 64));
+    lo1 = fminf(lo1, __shfl_xor(lo1, off, 64));
+    hi1 = fmaxf(hi1, __shfl_xor(hi1, off, 64));
+  }
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = make_float4(lo0, hi0, lo1, hi1);
+  __syncthreads();
+  if (threadIdx.x < 2u && 2u * blockIdx.x + threadIdx.x < n_blocks) {
+    const float4 a = part[2 * threadIdx.x], b = part[2 * threadIdx.x + 1];   // empty block: (+inf, -inf, ..)
+    boxes[2u * blockIdx.x + threadIdx.x] = make_float4(fminf(a.x, b.x), fmaxf(a.y, b.y), fminf(a.z, b.z), fmaxf(a.w, b.w));
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    hdr[kWideHdrOrder] = kWideOrderMark;
+    hdr[kWideHdrOrder + 1] = n_rows;
+    hdr[kWideHdrOrder + 2] = D;
+  }
+}
+// counts by position -> populations by row: pops[k][perm[p]] = cnt[k][p]; stands down with the sweep
+__global__ __launch_bounds__(256) void wide_prune_scatter_kernel(const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ perm,
+                                                                 const uint32_t* __restrict__ cnt, uint32_t n_rows, int n_rad,
+                                                                 uint32_t* __restrict__ pops) {
+  if (hdr[1] != 0) return;
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_rows) return;
+  const uint32_t i = perm[p];
+  for (int k = 0; k < n_rad; ++k) pops[(size_t)k * n_rows + i] = cnt[(size_t)k * n_rows + p];
 }
 
 // ... of a cross sweep: ONE origin and ONE scale over the queries and the reference together (column sums over both
@@ -392,6 +527,16 @@ struct WideArgs {
   const uint32_t* rank;        // [n_rows], a permutation
   unsigned long long* best;    // [n_rows] preset to ~0: atomicMin of (max rank << 32 | min rank)
 };
+
+// the pruned form (self population sweeps): coords / images / norms are the rows GATHERED into the spatial
+// order, so the kernel sees an ordinary self problem in positions; pops counts by position
+struct WidePrunedArgs : WideArgs {
+  const float4* boxes;    // [blocks]: the box of every block of kWideBlockRows positions in the (col 0, col 1) plane
+  uint32_t seg, n_seg;    // the query blocks seg, seg + n_seg, ... (the whole sweep: 0, 1)
+  float far2;             // wide_prune_far2 of the launch's largest fl32(r^2)
+};
+template <bool PR>
+using WideKernelArgs = std::conditional_t<PR, WidePrunedArgs, WideArgs>;
 
 // the deferred pairs of a wave, evaluated in the canonical order from the original coordinates, a pair per lane
 template <int MODE>
@@ -490,9 +635,16 @@ __device__ __attribute__((noinline)) void wide_graph_drain(const uint2* queue, u
 
 // SM: kSelf -- queries and reference are the rows of one array: the diagonal pair leaves the sweep, populations get the
 // frame's own 1, a frame is not its own neighbour; kAgainst -- X.q_coords against X.coords: every pair counts.
-template <int MODE, int NR, SweepMode SM = kSelf>
-__global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
+// PR: the pruned form.  A workgroup still owns (query block, share); it first scans the boxes of its share's blocks
+// y, y + Sy, ... against the box of its query block -- 64 per wave and step, a ballot each -- and compacts the survivors
+// (wide_prune_survives) into an LDS list, in rounds of kWideListCap blocks; the chunk sequence then runs over the list.
+// A round without a survivor runs no chunk and fetches nothing.
+template <int MODE, int NR, SweepMode SM = kSelf, bool PR = false>
+__global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X) {
+  static_assert(!PR || (MODE == kWidePop && SM == kSelf), "the pruned form: self population sweeps");
   if (X.hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
+  __shared__ uint32_t list_s[PR ? kWideListCap : 1];                  // pruned: the surviving reference blocks of a round
+  __shared__ unsigned long long mask_s[PR ? kWideListCap / 64 : 1];   // ... and the ballots they are compacted from
   __shared__ u32x4 stage[2 * kWideChunkVec];
   __shared__ uint2 queue_s[4][kWideQueue];
   __shared__ float fe_s[kWideBlockRows];
@@ -509,7 +661,13 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   const bool has_fe = SM == kSelf || q_fe != nullptr;
   const uint32_t RB = X.Tp / kWideBlockTiles, Sy = wide_shares(RB);
   const WideUnit unit = wide_unit(blockIdx.x, Sy);
-  const uint32_t qb = X.i_from / kWideBlockRows + unit.q_block, y = unit.share;
+  uint32_t qb_of_unit = X.i_from / kWideBlockRows + unit.q_block;
+  if constexpr (PR) {   // every n_seg-th block of the order (64 bits: n_seg is any number)
+    const unsigned long long q = X.seg + (unsigned long long)unit.q_block * X.n_seg;
+    if (q >= RB) return;
+    qb_of_unit = (uint32_t)q;
+  }
+  const uint32_t qb = qb_of_unit, y = unit.share;
   // (whole workgroups: the query blocks that pad the last group)
   if (qb * kWideBlockRows >= X.i_to) return;
   const uint32_t nblk = (RB - y + Sy - 1) / Sy, n_it = nblk * NC;
@@ -593,9 +751,16 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   //  never read -- unconditional loads and stores keep `pre` in registers and the eight loads in flight together)
   // (u32x4, a native vector type: an array of HIP's uint4 -- a struct -- is kept in scratch, with a wait and a scratch store
   //  behind every load)
+  // block `blk` of the workgroup's sequence: of its share, or -- pruned -- of the round's list of survivors
+  auto ref_block = [&](uint32_t blk) -> uint32_t {
+    if constexpr (PR)
+      return (uint32_t)__builtin_amdgcn_readfirstlane((int)list_s[blk]);
+    else
+      return y + blk * Sy;
+  };
   u32x4 pre[kWideChunkVec / 256];
   auto fetch = [&](uint32_t it) {
-    const uint32_t blk = it / NC, ch = it - blk * NC, rb = y + blk * Sy;
+    const uint32_t blk = it / NC, ch = it - blk * NC, rb = ref_block(blk);
     const uint32_t m0 = ch * kWideKC, nmc = min((uint32_t)kWideKC, NM - m0);
 #pragma unroll
     for (uint32_t i = 0; i < kWideChunkVec / 256; ++i) {
@@ -612,192 +777,230 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   };
 
   f32x16 acc[2][2];
-  fetch(0);
-  store(0);
-  __syncthreads();
-  for (uint32_t it = 0; it < n_it; ++it) {
-    const uint32_t blk = it / NC, ch = it - blk * NC, rb = y + blk * Sy;
-    const uint32_t nmc = min((uint32_t)kWideKC, NM - ch * kWideKC);
-    const bool last = ch == NC - 1;
-    if (ch == 0) {
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt) {
-        float4 nv[4];
-        load_frag(X.norms, rb * kWideBlockTiles + 2 * wr + rt, (int)h, nv);
-        acc[rt][0] = frag16(nv);
-        acc[rt][1] = acc[rt][0];
-      }
-      if constexpr (MODE == kWideNn) {
-        // (read by the epilogue of this block's LAST chunk, a barrier later; the previous block's epilogue ended before
-        //  the barrier that closed its last chunk)
-        if (tid < kWideBlockRows) {
-          const uint32_t row = rb * kWideBlockRows + tid;
-          fe_s[tid] = (row < X.n_rows && has_fe) ? X.fe[row] : INFINITY;
+  uint32_t n_eval = PR ? 0u : nblk;   // reference blocks this workgroup evaluates
+  WideBox qbox{};
+  if constexpr (PR) {
+    const float4 b = X.boxes[qb];
+    qbox = WideBox{b.x, b.y, b.z, b.w};
+  }
+  uint32_t round0 = 0;
+  do {
+    uint32_t n_run = n_it;   // chunks of this round (unpruned: one round, every block of the share)
+    if constexpr (PR) {
+      // ---- scan: which of the share's blocks round0 .. round0 + lim can hold a pair within the largest radius?
+      const uint32_t lim = min(nblk - round0, kWideListCap), n_ck = (lim + 63u) >> 6;
+      for (uint32_t ck = wave; ck < n_ck; ck += 4u) {
+        const uint32_t e = ck * 64u + lane;
+        bool ok = false;
+        if (e < lim) {
+          const float4 b = X.boxes[y + (round0 + e) * Sy];
+          ok = wide_prune_survives(qbox, WideBox{b.x, b.y, b.z, b.w}, X.far2);
         }
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
+        if (lane == 0) mask_s[ck] = m;
       }
-      if constexpr (MODE == kWideMinEdge) {   // (as fe_s: read a barrier later, written behind the last epilogue's barrier)
-        if (tid < kWideBlockRows) {
-          const uint32_t row = rb * kWideBlockRows + tid;
-          cr_s[tid] = (row < X.n_rows) ? make_uint2(X.comp[row], X.rank[row]) : make_uint2(0u, ~0u);
-        }
+      __syncthreads();
+      // every wave adds up all ballots (the count is uniform); the wave that took a chunk lists its survivors
+      uint32_t cnt = 0;
+      for (uint32_t ck = 0; ck < n_ck; ++ck) {
+        const unsigned long long m = mask_s[ck];
+        if ((ck & 3u) == wave && ((m >> lane) & 1ull)) list_s[cnt + lanes_below(m)] = y + (round0 + ck * 64u + lane) * Sy;
+        cnt += (uint32_t)__popcll(m);
       }
+      __syncthreads();   // (the list before its readers; the ballots before the next round writes them)
+      n_eval += cnt;
+      n_run = cnt * NC;
     }
-    // the next chunk leaves for the registers before this chunk's MFMAs (behind the norm loads above: the memory counter
-    // is in order, and the wait for the norms must not wait for the chunk)
-    if (it + 1 < n_it) fetch(it + 1);
-    const u32x4* sb = stage + (it & 1u) * kWideChunkVec;
-#pragma unroll
-    for (uint32_t ml = 0; ml < (uint32_t)kWideKC; ++ml) {
-      if (ml < nmc) {
-        const s16x8 a0 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 2 * wr) * 64 + lane]);
-        const s16x8 a1 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 2 * wr + 1) * 64 + lane]);
-        const s16x8 b0 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 4 + 2 * wq) * 64 + lane]);
-        const s16x8 b1 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 5 + 2 * wq) * 64 + lane]);
-        acc[0][0] = mfma16(a0, b0, acc[0][0]);
-        acc[0][1] = mfma16(a0, b1, acc[0][1]);
-        acc[1][0] = mfma16(a1, b0, acc[1][0]);
-        acc[1][1] = mfma16(a1, b1, acc[1][1]);
-      }
-    }
-    if (last) {
-      // ---- epilogue of the block: acc[rt][qt][g] ~ S d2(reference row of (rt, g, h), query jq[qt]) ----
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt)
-          if (MODE != kWideDump && SM == kSelf && rb * kWideBlockTiles + 2 * wr + rt == qb * kWideBlockTiles + 2 * wq + qt) {
-            // the diagonal tile: the self pair leaves the sweep (populations add their 1 at the end, neighbours exclude it)
-#pragma unroll
-            for (int g = 0; g < 16; ++g)
-              if (tile_row_local(g, (int)h) == c) acc[rt][qt][g] = INFINITY;
-          }
-      if constexpr (MODE == kWideDump) {
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-              const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
-              X.dump[(size_t)i * (32u * X.Tp) + jq[qt]] = acc[rt][qt][g];
-            }
-      }
-      if constexpr (kCount) {
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt)
+    if (!PR || n_run != 0) {
+      fetch(0);
+      store(0);
+      __syncthreads();
+      for (uint32_t it = 0; it < n_run; ++it) {
+        const uint32_t blk = it / NC, ch = it - blk * NC, rb = ref_block(blk);
+        const uint32_t nmc = min((uint32_t)kWideKC, NM - ch * kWideKC);
+        const bool last = ch == NC - 1;
+        if (ch == 0) {
 #pragma unroll
           for (int rt = 0; rt < 2; ++rt) {
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-              const float v = acc[rt][qt][g];
-              if (__builtin_amdgcn_ballot_w64(v < hi_max) == 0) continue;   // outside every radius, the whole wave
-              uint32_t und = 0;
-#pragma unroll
-              for (int k = 0; k < NR; ++k) {
-                cnt[qt][k] += (v < lo[k]) ? 1u : 0u;
-                und |= ((v >= lo[k]) & (v < hi[k])) ? (1u << k) : 0u;
-              }
-              if ((__builtin_amdgcn_ballot_w64(und != 0) & livemask[qt]) != 0) {
-                const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
-                push(und != 0 && live[qt] && i < X.n_rows, i, ((2 * wq + qt) * 32 + c) | (und << 8));
-              }
-            }
-            if constexpr (MODE == kWideMinEdge) {
-              // (the self pair is +inf on the diagonal tile and of the query's own component; a pad row is +inf)
-#pragma unroll
-              for (int g = 0; g < 16; ++g) {
-                const uint2 cr = cr_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
-                rmin[qt] = min(rmin[qt], (acc[rt][qt][g] < lo[0] && cr.x != comp_q[qt]) ? cr.y : ~0u);
-              }
+            float4 nv[4];
+            load_frag(X.norms, rb * kWideBlockTiles + 2 * wr + rt, (int)h, nv);
+            acc[rt][0] = frag16(nv);
+            acc[rt][1] = acc[rt][0];
+          }
+          if constexpr (MODE == kWideNn) {
+            // (read by the epilogue of this block's LAST chunk, a barrier later; the previous block's epilogue ended before
+            //  the barrier that closed its last chunk)
+            if (tid < kWideBlockRows) {
+              const uint32_t row = rb * kWideBlockRows + tid;
+              fe_s[tid] = (row < X.n_rows && has_fe) ? X.fe[row] : INFINITY;
             }
           }
-        if constexpr (MODE == kWidePairs) {
-          // the pairs this block decided inside, each from its meeting with i < j.  A reference tile above the query tile
-          // holds no such element (wave-uniform; it has been counted above all the same).  The slots of the wave's four
-          // tiles come from ONE atomic: a ballot per element, the popcounts summed on the scalar side, and a lane's slot
-          // is the base + the popcounts of the earlier elements + the set lanes below it.  Every wave of the grid adds
-          // to the same word, which takes an add every ~10 ns: one per tile made a dense list 6 x the population sweep.
-          // Counting only (no list: capacity 0) needs no slot: the wave keeps its sum and adds it once, at the end.
-          const uint32_t rt0 = rb * kWideBlockTiles + 2 * wr, qt0 = qb * kWideBlockTiles + 2 * wq;
-          auto inside = [&](int rt, int qt, int g) {
-            const uint32_t i = (rt0 + rt) * 32 + tile_row_local(g, (int)h);
-            return acc[rt][qt][g] < lo[0] && live[qt] && i < X.n_rows && i < jq[qt];
-          };
-          uint32_t total = 0;
+          if constexpr (MODE == kWideMinEdge) {   // (as fe_s: read a barrier later, written behind the last epilogue's barrier)
+            if (tid < kWideBlockRows) {
+              const uint32_t row = rb * kWideBlockRows + tid;
+              cr_s[tid] = (row < X.n_rows) ? make_uint2(X.comp[row], X.rank[row]) : make_uint2(0u, ~0u);
+            }
+          }
+        }
+        // the next chunk leaves for the registers before this chunk's MFMAs (behind the norm loads above: the memory counter
+        // is in order, and the wait for the norms must not wait for the chunk)
+        if (it + 1 < n_run) fetch(it + 1);
+        const u32x4* sb = stage + (it & 1u) * kWideChunkVec;
 #pragma unroll
-          for (int qt = 0; qt < 2; ++qt)
+        for (uint32_t ml = 0; ml < (uint32_t)kWideKC; ++ml) {
+          if (ml < nmc) {
+            const s16x8 a0 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 2 * wr) * 64 + lane]);
+            const s16x8 a1 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 2 * wr + 1) * 64 + lane]);
+            const s16x8 b0 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 4 + 2 * wq) * 64 + lane]);
+            const s16x8 b1 = __builtin_bit_cast(s16x8, sb[(ml * 8 + 5 + 2 * wq) * 64 + lane]);
+            acc[0][0] = mfma16(a0, b0, acc[0][0]);
+            acc[0][1] = mfma16(a0, b1, acc[0][1]);
+            acc[1][0] = mfma16(a1, b0, acc[1][0]);
+            acc[1][1] = mfma16(a1, b1, acc[1][1]);
+          }
+        }
+        if (last) {
+          // ---- epilogue of the block: acc[rt][qt][g] ~ S d2(reference row of (rt, g, h), query jq[qt]) ----
+#pragma unroll
+          for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt)
+              if (MODE != kWideDump && SM == kSelf && rb * kWideBlockTiles + 2 * wr + rt == qb * kWideBlockTiles + 2 * wq + qt) {
+                // the diagonal tile: the self pair leaves the sweep (populations add their 1 at the end, neighbours exclude it)
+#pragma unroll
+                for (int g = 0; g < 16; ++g)
+                  if (tile_row_local(g, (int)h) == c) acc[rt][qt][g] = INFINITY;
+              }
+          if constexpr (MODE == kWideDump) {
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)
-              if (rt0 + rt <= qt0 + qt) {
 #pragma unroll
-                for (int g = 0; g < 16; ++g) total += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(inside(rt, qt, g)));
-              }
-          if (X.capacity == 0) {
-            n_found += total;
-          } else if (total != 0) {
-            unsigned long long slot0 = wide_reserve(X.count, total, lane);
+              for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                  const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
+                  X.dump[(size_t)i * (32u * X.Tp) + jq[qt]] = acc[rt][qt][g];
+                }
+          }
+          if constexpr (kCount) {
 #pragma unroll
             for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-              for (int rt = 0; rt < 2; ++rt)
-                if (rt0 + rt <= qt0 + qt) {
+              for (int rt = 0; rt < 2; ++rt) {
 #pragma unroll
-                  for (int g = 0; g < 16; ++g) {
-                    const bool ok = inside(rt, qt, g);
-                    const unsigned long long mk = __builtin_amdgcn_ballot_w64(ok);
-                    const unsigned long long slot = slot0 + lanes_below(mk);
-                    if (ok && slot < X.capacity) X.pairs[slot] = make_uint2((rt0 + rt) * 32 + tile_row_local(g, (int)h), jq[qt]);
-                    slot0 += (unsigned long long)__popcll(mk);
+                for (int g = 0; g < 16; ++g) {
+                  const float v = acc[rt][qt][g];
+                  if (__builtin_amdgcn_ballot_w64(v < hi_max) == 0) continue;   // outside every radius, the whole wave
+                  uint32_t und = 0;
+#pragma unroll
+                  for (int k = 0; k < NR; ++k) {
+                    cnt[qt][k] += (v < lo[k]) ? 1u : 0u;
+                    und |= ((v >= lo[k]) & (v < hi[k])) ? (1u << k) : 0u;
+                  }
+                  if ((__builtin_amdgcn_ballot_w64(und != 0) & livemask[qt]) != 0) {
+                    const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
+                    push(und != 0 && live[qt] && i < X.n_rows, i, ((2 * wq + qt) * 32 + c) | (und << 8));
                   }
                 }
-          }
-        }
-      }
-      if constexpr (MODE == kWideNn) {
+                if constexpr (MODE == kWideMinEdge) {
+                  // (the self pair is +inf on the diagonal tile and of the query's own component; a pad row is +inf)
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
+                  for (int g = 0; g < 16; ++g) {
+                    const uint2 cr = cr_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
+                    rmin[qt] = min(rmin[qt], (acc[rt][qt][g] < lo[0] && cr.x != comp_q[qt]) ? cr.y : ~0u);
+                  }
+                }
+              }
+            if constexpr (MODE == kWidePairs) {
+              // the pairs this block decided inside, each from its meeting with i < j.  A reference tile above the query tile
+              // holds no such element (wave-uniform; it has been counted above all the same).  The slots of the wave's four
+              // tiles come from ONE atomic: a ballot per element, the popcounts summed on the scalar side, and a lane's slot
+              // is the base + the popcounts of the earlier elements + the set lanes below it.  Every wave of the grid adds
+              // to the same word, which takes an add every ~10 ns: one per tile made a dense list 6 x the population sweep.
+              // Counting only (no list: capacity 0) needs no slot: the wave keeps its sum and adds it once, at the end.
+              const uint32_t rt0 = rb * kWideBlockTiles + 2 * wr, qt0 = qb * kWideBlockTiles + 2 * wq;
+              auto inside = [&](int rt, int qt, int g) {
+                const uint32_t i = (rt0 + rt) * 32 + tile_row_local(g, (int)h);
+                return acc[rt][qt][g] < lo[0] && live[qt] && i < X.n_rows && i < jq[qt];
+              };
+              uint32_t total = 0;
 #pragma unroll
-          for (int rt = 0; rt < 2; ++rt)
+              for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-            for (int g = 0; g < 16; ++g) {
-              const float v = acc[rt][qt][g], fr = fe_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
-              m_nn[qt] = fminf(m_nn[qt], v);
-              m_hd[qt] = fminf(m_hd[qt], (fr < feq[qt]) ? v : INFINITY);
-            }
-          // (the two halves of the wave hold other reference rows of the same queries: any minimum met serves both)
-          m_nn[qt] = fminf(m_nn[qt], __shfl_xor(m_nn[qt], 32, 64));
-          m_hd[qt] = fminf(m_hd[qt], __shfl_xor(m_hd[qt], 32, 64));
-          if (h == 0) {
-            min_s[wave][qt][0][c] = m_nn[qt];
-            min_s[wave][qt][1][c] = m_hd[qt];
-          }
-        }
-        // ... and so do the two waves that hold the other reference tiles of the same queries (wave ^ 2): one search per
-        // query and share instead of two.  Every wave of the workgroup is in this epilogue (the chunk count is uniform);
-        // the next block's minima are written behind the barrier that closes this chunk.
-        __syncthreads();
+                for (int rt = 0; rt < 2; ++rt)
+                  if (rt0 + rt <= qt0 + qt) {
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-          m_nn[qt] = fminf(m_nn[qt], min_s[wave ^ 2u][qt][0][c]);
-          m_hd[qt] = fminf(m_hd[qt], min_s[wave ^ 2u][qt][1][c]);
-          const float cut_nn = wide_cut(m_nn[qt], band, ratio), cut_hd = wide_cut(m_hd[qt], band, ratio);
+                    for (int g = 0; g < 16; ++g) total += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(inside(rt, qt, g)));
+                  }
+              if (X.capacity == 0) {
+                n_found += total;
+              } else if (total != 0) {
+                unsigned long long slot0 = wide_reserve(X.count, total, lane);
 #pragma unroll
-          for (int rt = 0; rt < 2; ++rt)
+                for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-            for (int g = 0; g < 16; ++g) {
-              const float v = acc[rt][qt][g], fr = fe_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
-              const uint32_t fl = ((v <= cut_nn) ? 1u : 0u) | (((fr < feq[qt]) & (v <= cut_hd)) ? 2u : 0u);
-              if ((__builtin_amdgcn_ballot_w64(fl != 0) & livemask[qt]) != 0) {
-                const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
-                push(fl != 0 && live[qt] && i < X.n_rows && (SM == kAgainst || i != jq[qt]), i, ((2 * wq + qt) * 32 + c) | (fl << 8));
+                  for (int rt = 0; rt < 2; ++rt)
+                    if (rt0 + rt <= qt0 + qt) {
+#pragma unroll
+                      for (int g = 0; g < 16; ++g) {
+                        const bool ok = inside(rt, qt, g);
+                        const unsigned long long mk = __builtin_amdgcn_ballot_w64(ok);
+                        const unsigned long long slot = slot0 + lanes_below(mk);
+                        if (ok && slot < X.capacity) X.pairs[slot] = make_uint2((rt0 + rt) * 32 + tile_row_local(g, (int)h), jq[qt]);
+                        slot0 += (unsigned long long)__popcll(mk);
+                      }
+                    }
               }
             }
+          }
+          if constexpr (MODE == kWideNn) {
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt) {
+#pragma unroll
+              for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                  const float v = acc[rt][qt][g], fr = fe_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
+                  m_nn[qt] = fminf(m_nn[qt], v);
+                  m_hd[qt] = fminf(m_hd[qt], (fr < feq[qt]) ? v : INFINITY);
+                }
+              // (the two halves of the wave hold other reference rows of the same queries: any minimum met serves both)
+              m_nn[qt] = fminf(m_nn[qt], __shfl_xor(m_nn[qt], 32, 64));
+              m_hd[qt] = fminf(m_hd[qt], __shfl_xor(m_hd[qt], 32, 64));
+              if (h == 0) {
+                min_s[wave][qt][0][c] = m_nn[qt];
+                min_s[wave][qt][1][c] = m_hd[qt];
+              }
+            }
+            // ... and so do the two waves that hold the other reference tiles of the same queries (wave ^ 2): one search per
+            // query and share instead of two.  Every wave of the workgroup is in this epilogue (the chunk count is uniform);
+            // the next block's minima are written behind the barrier that closes this chunk.
+            __syncthreads();
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt) {
+              m_nn[qt] = fminf(m_nn[qt], min_s[wave ^ 2u][qt][0][c]);
+              m_hd[qt] = fminf(m_hd[qt], min_s[wave ^ 2u][qt][1][c]);
+              const float cut_nn = wide_cut(m_nn[qt], band, ratio), cut_hd = wide_cut(m_hd[qt], band, ratio);
+#pragma unroll
+              for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                  const float v = acc[rt][qt][g], fr = fe_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
+                  const uint32_t fl = ((v <= cut_nn) ? 1u : 0u) | (((fr < feq[qt]) & (v <= cut_hd)) ? 2u : 0u);
+                  if ((__builtin_amdgcn_ballot_w64(fl != 0) & livemask[qt]) != 0) {
+                    const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
+                    push(fl != 0 && live[qt] && i < X.n_rows && (SM == kAgainst || i != jq[qt]), i, ((2 * wq + qt) * 32 + c) | (fl << 8));
+                  }
+                }
+            }
+          }
         }
+        if (it + 1 < n_run) store(it + 1);
+        __syncthreads();
       }
     }
-    if (it + 1 < n_it) store(it + 1);
-    __syncthreads();
-  }
+    round0 += kWideListCap;
+  } while (PR && round0 < nblk);
 
   if constexpr (MODE != kWideDump) {
     if (fill != 0) {
@@ -830,7 +1033,7 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideArgs X) {
   }
   if (lane == 0 && n_exact != 0) atomicAdd(reinterpret_cast<unsigned long long*>(X.hdr + kWideHdrExact), n_exact);
   if (tid == 0) {
-    const unsigned long long tiles = (unsigned long long)nblk * kWideBlockTiles * kWideBlockTiles;
+    const unsigned long long tiles = (unsigned long long)n_eval * kWideBlockTiles * kWideBlockTiles;
     atomicAdd(reinterpret_cast<unsigned long long*>(X.hdr + kWideHdrTiles), tiles);
     atomicAdd(reinterpret_cast<unsigned long long*>(X.hdr + kWideHdrMfma), tiles * NM);
   }

@@ -52,6 +52,10 @@ def _wide_bytes(n_rows, n_cols, n_radii=1):
     return capi.lib.dc_hip_wide_workspace_bytes(n_rows, n_cols, n_radii)
 
 
+def _wide_pruned_bytes(n_rows, n_cols, n_radii=1):
+    return capi.lib.dc_hip_wide_pruned_workspace_bytes(n_rows, n_cols, n_radii)
+
+
 def _wide_against_bytes(n_q, n_ref, n_cols, n_radii=1):
     return capi.lib.dc_hip_cross_wide_workspace_bytes(n_q, n_ref, n_cols, n_radii)
 
@@ -79,6 +83,8 @@ _cross_workspaces = {}  # sweeps against a reference, per device
 _cross_pruned_workspaces = {}  # ... of variant="cross_pruned" (the larger layout of its two orders), per device
 _nearest_pruned_workspaces = {}  # ... of nearest_reference(pruned=True), per device
 _wide_workspaces = {}   # the matrix-core sweeps for rows of 65..256 columns, per device
+_wide_pruned_workspaces = {}   # ... of the pruned self population sweep (calculate_populations_wide_pruned), per device
+_wide_pruned_shapes = {}       # ... and the shape of the last call in each, which wide_pruned_order asks the order of
 _wide_against_workspaces = {}  # ... of their cross form (calculate_populations_against_wide, nearest_reference_wide), per device
 
 
@@ -107,6 +113,10 @@ def _nearest_pruned_workspace(device):
 
 def _wide_workspace(device):
     return _cached(_wide_workspaces, device, _wide_bytes)
+
+
+def _wide_pruned_workspace(device):
+    return _cached(_wide_pruned_workspaces, device, _wide_pruned_bytes)
 
 
 def _wide_against_workspace(device):
@@ -289,6 +299,54 @@ def wide_sweep_info(device):
         capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
                    "dc_hip_wide_info_dev")
     return int(t.value), int(m.value), int(e.value)
+
+
+# ---- ... the pruned self population sweep (include/dc_density.h, the PRUNED wide sweep) ------------------------------
+def calculate_populations_wide_pruned(coords, radii, segment=0, n_segments=0, out=None):
+    """calculate_populations_wide without the block pairs that cannot hold a pair within the radii
+    (dc_hip_populations_wide_pruned_dev): the same populations bit for bit.  n_segments == 0: the whole sweep (segment is not read);
+    otherwise the query blocks segment, segment + n_segments, ... of the spatial order (wide_pruned_order): final counts
+    for their rows, zeros elsewhere.  In a cached workspace of its own (wide_pruned_info reads its counters)."""
+    n_rows, n_cols = _check_coords(coords)
+    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    if out is None:
+        out = torch.empty((rad.size, n_rows), dtype=torch.int32, device=coords.device)
+    assert out.shape == (rad.size, n_rows) and out.dtype == torch.int32 and out.is_contiguous()
+    with torch.cuda.device(coords.device):
+        ws, ws_bytes = _wide_pruned_workspace(coords.device).get(n_rows, n_cols, rad.size)
+        rc = capi.lib.dc_hip_populations_wide_pruned_dev(
+            _dev(coords), n_rows, n_cols, rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size, segment, n_segments,
+            _dev(out), ws, ws_bytes, _stream_ptr())
+    capi.check(rc, "dc_hip_populations_wide_pruned_dev")
+    _wide_pruned_shapes[str(coords.device)] = (n_rows, n_cols)
+    return out
+
+
+def wide_pruned_info(device):
+    """(tiles, mfmas, exact_pairs) of the last calculate_populations_wide_pruned on this device, as wide_sweep_info
+    gives them; the tile pairs are the evaluated ones.  (0, 0, 0) when the direct kernel answered (flagged data), the
+    segment held no block, or no such sweep has run."""
+    ws = _wide_pruned_workspace(device)
+    if ws.buf is None:
+        return 0, 0, 0
+    t, m, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
+                   "dc_hip_wide_info_dev")
+    return int(t.value), int(m.value), int(e.value)
+
+
+def wide_pruned_order(device):
+    """the spatial order of the last calculate_populations_wide_pruned on this device: int32 [n_rows], position -> row
+    (block b of the order: positions 128 b .. 128 b + 127) (dc_hip_wide_pruned_order_dev)."""
+    ws, shape = _wide_pruned_workspace(device), _wide_pruned_shapes.get(str(device))
+    if ws.buf is None or shape is None:
+        raise ValueError("no pruned wide sweep has run on this device")
+    perm = torch.empty(shape[0], dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_wide_pruned_order_dev(_dev(ws.buf), shape[0], shape[1], _dev(perm), _stream_ptr()),
+                   "dc_hip_wide_pruned_order_dev")
+    return perm
 
 
 # ---- cross sweeps: new frames against a reference trajectory (include/dc_density.h "cross sweeps") ----------------

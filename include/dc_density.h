@@ -414,6 +414,33 @@ DC_API int dc_hip_nearest_neighbors_wide_dev(const float* d_coords, size_t n_row
                                              size_t i_from, size_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
                                              uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
                                              void* stream);
+/* ---- ... the PRUNED wide self population sweep (65..256 columns) -----------------------------------------------------------
+ * dc_hip_populations_wide_dev's populations bit for bit, without the block pairs that cannot hold a pair within the
+ * call's radii: the rows are put into a spatial order on columns 0 / 1 (cell keys, one stable sort), gathered into it,
+ * every block of 128 positions gets a box in that plane, and a workgroup only runs the chains of the reference blocks
+ * whose box lies within 1.0001 x the launch's largest r^2 of its query block's.  Entry points of their own; no
+ * dc_variant value selects them.
+ * d_pops: [n_radii][n_rows], fully overwritten.  Radii in any order, checked as dc_hip_populations_wide_dev checks them;
+ * more than 8 radii run one launch per 8, each pruned by its own largest radius.
+ * n_segments == 0: the whole sweep (`segment` is not read).  n_segments > 0: rank `segment` sweeps every n_segments-th query block (128
+ * positions) of the order and writes the final counts of those rows, zeros elsewhere -- the sum over the segments is
+ * the population (the contract of dc_hip_populations_segment_dev); a segment without a block gives zeros.  Flagged data
+ * (a non-finite or overflow-prone row): the direct kernel answers behind the device-side gate, for a segment on the
+ * row block dc_hip_populations_segment_dev uses.
+ * Errors, all before a device is touched: segment >= n_segments > 0 and n_cols outside 65..256:
+ * DC_ERR_INVALID_ARGUMENT; a workspace smaller than dc_hip_wide_pruned_workspace_bytes (or none): DC_ERR_WORKSPACE;
+ * sizes: DC_ERR_TOO_LARGE as above; n_rows == 0 or n_radii == 0: DC_OK.
+ * dc_hip_wide_pruned_workspace_bytes: 0 outside 65..256 columns (and for no rows), monotone in n_rows, never below
+ * dc_hip_wide_workspace_bytes.  The workspace keeps the info head of the wide sweeps: dc_hip_wide_info_dev reads the
+ * counters of the last pruned call; its tile pairs are the EVALUATED ones.
+ * dc_hip_wide_pruned_order_dev: the order of the last pruned call in that workspace, position -> row, into d_perm
+ * [n_rows] (block b of the order: positions 128 b .. 128 b + 127); a workspace that holds no order of that shape:
+ * DC_ERR_INVALID_ARGUMENT.  Synchronises the stream. */
+DC_API size_t dc_hip_wide_pruned_workspace_bytes(size_t n_rows, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_populations_wide_pruned_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* radii,
+                                              size_t n_radii, size_t segment, size_t n_segments, uint32_t* d_pops,
+                                              void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_wide_pruned_order_dev(const void* d_ws, size_t n_rows, size_t n_cols, uint32_t* d_perm, void* stream);
 /* ---- ... and their cross form: query frames against a reference trajectory at 65..256 columns ------------------------
  * The wide sweep over a rectangle Q x R: the contract of the "cross sweeps" block above -- populations without a self
  * term, nn[q] the lexicographic minimum of (d2, j) over ALL j with no exclusion, nn_hd[q] the same over
