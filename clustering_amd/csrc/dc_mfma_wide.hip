@@ -181,11 +181,11 @@ int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols,
   return wide_image_launches(coords_o, n_rows, n_cols, d_ws, s);
 }
 
-int launch_pop_wide_pruned(uint32_t n_rows, uint32_t n_cols, size_t segment, size_t n_segments, const Rad2& rad2, int n_rad,
-                           uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
-  if (n_rows == 0 || n_rad <= 0 || n_segments == 0) return 0;
-  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
-  if (segment >= P.blocks) return 0;   // no block of the order: zeros (the caller's), no tile pair
+namespace {
+// the operands of a pruned launch of one chunk of radii over the query blocks segment, segment + n_segments, ... of the
+// order, counting by position into row 0 of the count region (zeroed here); *grid: its workgroups
+int wide_pruned_args(const WidePrunedLayout& P, uint32_t n_rows, uint32_t n_cols, size_t segment, size_t n_segments,
+                     const Rad2& rad2, int n_rad, void* d_ws, hipStream_t s, WidePrunedArgs* out, dim3* grid) {
   char* p = (char*)d_ws;
   uint32_t* cnt = (uint32_t*)(p + P.off_cnt);
   if (hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (size_t)n_rad * n_rows, s) != hipSuccess) return -1;
@@ -200,8 +200,29 @@ int launch_pop_wide_pruned(uint32_t n_rows, uint32_t n_cols, size_t segment, siz
   float r2max = 0.0f;
   for (int k = 0; k < n_rad; ++k) r2max = rad2.v[k] > r2max ? rad2.v[k] : r2max;
   X.far2 = wide_prune_far2(r2max);
+  X.perm = (const uint32_t*)(p + P.off_perm);
   const uint32_t q_blocks = (uint32_t)((P.blocks - segment + n_segments - 1) / n_segments);
-  const dim3 grid(wide_grid_size(q_blocks, wide_shares(P.blocks)));
+  *grid = dim3(wide_grid_size(q_blocks, wide_shares(P.blocks)));
+  *out = X;
+  return 0;
+}
+// counts by position -> populations by row, behind the sweep
+int wide_pruned_scatter(const WidePrunedLayout& P, uint32_t n_rows, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
+  char* p = (char*)d_ws;
+  hipLaunchKernelGGL(wide_prune_scatter_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,
+                     (const uint32_t*)(p + P.off_perm), (const uint32_t*)(p + P.off_cnt), n_rows, n_rad, d_pops_first_row);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+}  // namespace
+
+int launch_pop_wide_pruned(uint32_t n_rows, uint32_t n_cols, size_t segment, size_t n_segments, const Rad2& rad2, int n_rad,
+                           uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
+  if (n_rows == 0 || n_rad <= 0 || n_segments == 0) return 0;
+  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
+  if (segment >= P.blocks) return 0;   // no block of the order: zeros (the caller's), no tile pair
+  WidePrunedArgs X;
+  dim3 grid;
+  if (wide_pruned_args(P, n_rows, n_cols, segment, n_segments, rad2, n_rad, d_ws, s, &X, &grid) != 0) return -1;
   sweep_timer_mark(0, true, s);
   if (n_rad == 1)
     hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, kSelf, true>), grid, dim3(256), 0, s, X);
@@ -210,9 +231,53 @@ int launch_pop_wide_pruned(uint32_t n_rows, uint32_t n_cols, size_t segment, siz
   else
     hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, kSelf, true>), grid, dim3(256), 0, s, X);
   sweep_timer_mark(0, false, s);
-  hipLaunchKernelGGL(wide_prune_scatter_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,
-                     (const uint32_t*)(p + P.off_perm), (const uint32_t*)cnt, n_rows, n_rad, d_pops_first_row);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return wide_pruned_scatter(P, n_rows, n_rad, d_pops_first_row, d_ws, s);
+}
+
+// ---- the pruned radius graph (dc_hip_radius_*_wide_pruned_dev): the pruned one-radius sweep with a sink ----
+int launch_pairs_wide_pruned(uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops, uint2* d_pairs,
+                             unsigned long long capacity, unsigned long long* d_count, void* d_ws, hipStream_t s) {
+  if (n_rows == 0) return 0;
+  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
+  WidePrunedArgs X;
+  dim3 grid;
+  if (wide_pruned_args(P, n_rows, n_cols, 0, 1, one_radius(r2), 1, d_ws, s, &X, &grid) != 0) return -1;
+  X.pairs = d_pairs;
+  X.capacity = d_pairs ? capacity : 0ull;   // (counting only: every slot is beyond the list)
+  X.count = d_count;
+  sweep_timer_mark(0, true, s);
+  hipLaunchKernelGGL((wide_sweep_kernel<kWidePairs, 1, kSelf, true>), grid, dim3(256), 0, s, X);
+  sweep_timer_mark(0, false, s);
+  return wide_pruned_scatter(P, n_rows, 1, d_pops, d_ws, s);
+}
+
+static_assert(kMaxRadiiPerLaunch >= 3, "rows 1 and 2 of the count region hold the gathered comp and rank of a one-radius call");
+int launch_min_edge_wide_pruned(uint32_t n_rows, uint32_t n_cols, float r2, const uint32_t* d_comp, const uint32_t* d_rank,
+                                size_t segment, size_t n_segments, unsigned long long* d_best, uint32_t* d_pops, void* d_ws,
+                                hipStream_t s) {
+  if (n_rows == 0 || n_segments == 0) return 0;
+  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
+  if (segment >= P.blocks) return 0;   // no block of the order: nothing found (the caller's presets), no tile pair
+  WidePrunedArgs X;
+  dim3 grid;
+  if (wide_pruned_args(P, n_rows, n_cols, segment, n_segments, one_radius(r2), 1, d_ws, s, &X, &grid) != 0) return -1;
+  uint32_t* comp_o = X.pops + n_rows;
+  uint32_t* rank_o = X.pops + 2 * (size_t)n_rows;
+  hipLaunchKernelGGL(wide_prune_gather_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, X.perm, d_comp, d_rank, n_rows, comp_o,
+                     rank_o);
+  X.comp = comp_o;
+  X.rank = rank_o;
+  X.best = d_best;
+  sweep_timer_mark(0, true, s);
+  hipLaunchKernelGGL((wide_sweep_kernel<kWideMinEdge, 1, kSelf, true>), grid, dim3(256), 0, s, X);
+  sweep_timer_mark(0, false, s);
+  return wide_pruned_scatter(P, n_rows, 1, d_pops, d_ws, s);
+}
+
+// the counters of the last sweep back to zero: a further round in a prepared workspace reports its own
+int wide_clear_counters(void* d_ws, hipStream_t s) {
+  static_assert(kWideHdrMfma == kWideHdrTiles + 2 && kWideHdrExact == kWideHdrTiles + 4, "three 64-bit counters side by side");
+  return hipMemsetAsync((char*)d_ws + 4 * kWideHdrTiles, 0, 24, s) == hipSuccess ? 0 : -1;
 }
 
 int wide_pruned_order(const void* d_ws, uint32_t n_rows, uint32_t n_cols, uint32_t* d_perm, hipStream_t s) {

@@ -56,6 +56,23 @@ int launch_pop_wide_pruned(uint32_t n_rows, uint32_t n_cols, size_t segment, siz
 // -1 a HIP error (synchronises)
 int wide_pruned_order(const void* d_ws, uint32_t n_rows, uint32_t n_cols, uint32_t* d_perm, hipStream_t stream);
 
+// ---- the pruned radius graph (dc_hip_radius_*_wide_pruned_dev) --------------------------------------------
+// The pruned sweep of ONE threshold r2 = the squared distance itself, with the sinks of the radius graph.  Both run behind
+// wide_pruned_prepare in the same workspace (wide_pruned_workspace_bytes: rows 1 and 2 of its count region hold comp and
+// rank gathered into the order), WRITE the populations to d_pops for every row and stand down on flagged data, scatter
+// included (the gated launch_pairs_direct / launch_min_edge_direct answer).  Return 0 on success.
+// every unordered pair once into d_pairs[0 .. capacity) as rows, in no order -- neither of the list nor within a pair --
+// (nullptr: counting only), the number found ADDED to d_count
+int launch_pairs_wide_pruned(uint32_t n_rows, uint32_t n_cols, float r2, uint32_t* d_pops, uint2* d_pairs,
+                             unsigned long long capacity, unsigned long long* d_count, void* d_ws, hipStream_t stream);
+// what the queries of the blocks segment, segment + n_segments, ... of the order (n_segments >= 1) see of one Boruvka
+// round: atomicMin into d_best (preset to ~0 by the caller); d_comp / d_rank are by row, as the caller holds them
+int launch_min_edge_wide_pruned(uint32_t n_rows, uint32_t n_cols, float r2, const uint32_t* d_comp, const uint32_t* d_rank,
+                                size_t segment, size_t n_segments, unsigned long long* d_best, uint32_t* d_pops, void* d_ws,
+                                hipStream_t stream);
+// the three counters of the last sweep back to zero (a further round in a workspace that stays prepared)
+int wide_clear_counters(void* d_ws, hipStream_t stream);
+
 // ---- the cross form: query rows against a reference (dc_hip_*_cross_wide_dev) -----------------------------
 // The same kernel in its kAgainst instances: one origin and one scale over both sets, the A form and the norms of the
 // reference, the B form and the merge words of the queries; every pair counts (no self term, no exclusion).

@@ -44,6 +44,11 @@
 // sink on its two decision points -- the accumulator window (acc < lo: decided inside) and the exact drain (d2 < r2).
 // Preparation, images, scale, band, window, shares, unit map and counting are the population sweep's; see "the sinks
 // of the radius graph" below for the i < j rule of the list and the smallest-rank rule of a Boruvka round.
+// Their pruned form (dc_hip_radius_*_wide_pruned_dev) is the pruned population sweep with the same sinks:
+// the kernel works in positions of the order, the contract speaks of rows.  The i < j rule and the tile-level skip are
+// taken on positions (each unordered pair still has exactly one meeting with i < j), the pair written is (perm[i],
+// perm[j]) -- each unordered pair once, in no order within the pair; comp and rank are read by position from arrays
+// gathered into the order once per call, their values and the index of best stay component ids and ranks.
 #pragma once
 #include "dc_mfma_kernels.hpp"
 #include "dc_mfma_wide.hpp"
@@ -455,6 +460,16 @@ __global__ __launch_bounds__(256) void wide_prune_scatter_kernel(const uint32_t*
   const uint32_t i = perm[p];
   for (int k = 0; k < n_rad; ++k) pops[(size_t)k * n_rows + i] = cnt[(size_t)k * n_rows + p];
 }
+// the pruned min-edge round: component and rank of every row, by position (the values stay component ids and ranks)
+__global__ __launch_bounds__(256) void wide_prune_gather_kernel(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ comp,
+                                                                const uint32_t* __restrict__ rank, uint32_t n_rows,
+                                                                uint32_t* __restrict__ comp_o, uint32_t* __restrict__ rank_o) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_rows) return;
+  const uint32_t i = perm[p];
+  comp_o[p] = comp[i];
+  rank_o[p] = rank[i];
+}
 
 // ... of a cross sweep: ONE origin and ONE scale over the queries and the reference together (column sums over both
 // sets, the mean over n_query + n_ref rows, header word 0 = the largest |x'|^2 of either set), then the A form and the
@@ -520,7 +535,7 @@ struct WideArgs {
   uint32_t n_query;
   const float* q_fe;           // nullptr: nn only (fe is not read, no candidate of the hd half is raised)
   // the graph instances only (self sweeps of one radius, rad2.v[0]; pops as for kWidePop)
-  uint2* pairs;                // kWidePairs: [capacity] (i, j), i < j
+  uint2* pairs;                // kWidePairs: [capacity] (i, j), i < j (the pruned form: rows, in no order within a pair)
   unsigned long long capacity;
   unsigned long long* count;   // zeroed: the sweep adds every pair it finds, written or not
   const uint32_t* comp;        // kWideMinEdge: [n_rows] component ids
@@ -534,6 +549,9 @@ struct WidePrunedArgs : WideArgs {
   const float4* boxes;    // [blocks]: the box of every block of kWideBlockRows positions in the (col 0, col 1) plane
   uint32_t seg, n_seg;    // the query blocks seg, seg + n_seg, ... (the whole sweep: 0, 1)
   float far2;             // wide_prune_far2 of the launch's largest fl32(r^2)
+  // the graph instances: comp / rank are GATHERED into the order as well (their values stay component
+  // ids and ranks, best stays indexed by component id); the pair list speaks of rows
+  const uint32_t* perm;   // kWidePairs: [n_rows] position -> row
 };
 template <bool PR>
 using WideKernelArgs = std::conditional_t<PR, WidePrunedArgs, WideArgs>;
@@ -598,10 +616,14 @@ __device__ __forceinline__ unsigned long long wide_reserve(unsigned long long* c
 // every lane of the wave active; the loop is wave-uniform (one ballot and one atomic on the count per pass).
 // The sink is three scalars -- kWidePairs: the list, its capacity, the count; kWideMinEdge: comp, rank, best -- and not a
 // struct: a struct of three pointers is passed through the stack, 24 bytes stored at each of the 65 call sites.
-template <int MODE, class A, class B, class C>
-__device__ __attribute__((noinline)) void wide_graph_drain(const uint2* queue, uint32_t fill, const float* coords, uint32_t n_rows,
-                                                           uint32_t n_cols, uint32_t qrow0, float r2, uint32_t* pops, A s0, B s1,
-                                                           C s2) {
+// The pruned form sweeps POSITIONS of the spatial order: coords, pops, comp and rank are by position, so
+// the min-edge sink is the same code; the pair list speaks of rows, so its sink takes the permutation as a fourth scalar
+// -- a pack, empty for every other instance, whose code therefore stays what it was.  The i < j rule is on positions.
+__device__ __forceinline__ uint2 wide_pair_ids(uint32_t i, uint32_t j) { return make_uint2(i, j); }
+__device__ __forceinline__ uint2 wide_pair_ids(uint32_t i, uint32_t j, const uint32_t* perm) { return make_uint2(perm[i], perm[j]); }
+template <int MODE, class A, class B, class C, class... P>
+__device__ __forceinline__ void wide_graph_drain_body(const uint2* queue, uint32_t fill, const float* coords, uint32_t n_cols,
+                                                      uint32_t qrow0, float r2, uint32_t* pops, A s0, B s1, C s2, P... perm) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -618,7 +640,7 @@ __device__ __attribute__((noinline)) void wide_graph_drain(const uint2* queue, u
       const unsigned long long mk = __builtin_amdgcn_ballot_w64(emit);
       if (mk != 0) {
         const unsigned long long slot = wide_reserve(s2, (uint32_t)__popcll(mk), lane) + lanes_below(mk);
-        if (emit && slot < s1) s0[slot] = make_uint2(i, j);
+        if (emit && slot < s1) s0[slot] = wide_pair_ids(i, j, perm...);
       }
     } else {
       if (hit) {
@@ -632,6 +654,19 @@ __device__ __attribute__((noinline)) void wide_graph_drain(const uint2* queue, u
   }
   __builtin_amdgcn_wave_barrier();
 }
+template <int MODE, class A, class B, class C>
+__device__ __attribute__((noinline)) void wide_graph_drain(const uint2* queue, uint32_t fill, const float* coords, uint32_t n_rows,
+                                                           uint32_t n_cols, uint32_t qrow0, float r2, uint32_t* pops, A s0, B s1,
+                                                           C s2) {
+  wide_graph_drain_body<MODE>(queue, fill, coords, n_cols, qrow0, r2, pops, s0, s1, s2);
+}
+// ... of the pruned pair list: (i, j) are positions, the pair written is (perm[i], perm[j])
+__device__ __attribute__((noinline)) void wide_pairs_drain_pruned(const uint2* queue, uint32_t fill, const float* coords,
+                                                                  uint32_t n_cols, uint32_t qrow0, float r2, uint32_t* pops,
+                                                                  uint2* pairs, unsigned long long capacity,
+                                                                  unsigned long long* count, const uint32_t* perm) {
+  wide_graph_drain_body<kWidePairs>(queue, fill, coords, n_cols, qrow0, r2, pops, pairs, capacity, count, perm);
+}
 
 // SM: kSelf -- queries and reference are the rows of one array: the diagonal pair leaves the sweep, populations get the
 // frame's own 1, a frame is not its own neighbour; kAgainst -- X.q_coords against X.coords: every pair counts.
@@ -641,7 +676,7 @@ __device__ __attribute__((noinline)) void wide_graph_drain(const uint2* queue, u
 // A round without a survivor runs no chunk and fetches nothing.
 template <int MODE, int NR, SweepMode SM = kSelf, bool PR = false>
 __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X) {
-  static_assert(!PR || (MODE == kWidePop && SM == kSelf), "the pruned form: self population sweeps");
+  static_assert(!PR || (wide_counts(MODE) && SM == kSelf), "the pruned form: self sweeps that count -- populations and the radius graph");
   if (X.hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
   __shared__ uint32_t list_s[PR ? kWideListCap : 1];                  // pruned: the surviving reference blocks of a round
   __shared__ unsigned long long mask_s[PR ? kWideListCap / 64 : 1];   // ... and the ballots they are compacted from
@@ -722,9 +757,19 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X
     }
   }
 
+  // the pruned pair list: the rows of the lane's queries (the kernel's own indices are positions of the order)
+  uint32_t row_q[2] = {0u, 0u};
+  if constexpr (PR && MODE == kWidePairs) {
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) row_q[qt] = live[qt] ? X.perm[jq[qt]] : 0u;
+  }
+
   // one pair per lane into the wave's queue (ok: this lane has one); drained before a push that might not fit
   auto drain = [&]() {
-    if constexpr (MODE == kWidePairs)
+    if constexpr (PR && MODE == kWidePairs)
+      wide_pairs_drain_pruned(queue, fill, X.coords, D, qb * kWideBlockRows, X.rad2.v[0], X.pops, X.pairs, X.capacity, X.count,
+                              X.perm);
+    else if constexpr (MODE == kWidePairs)
       wide_graph_drain<MODE>(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.rad2.v[0], X.pops,
                              X.pairs, X.capacity, X.count);
     else if constexpr (MODE == kWideMinEdge)
@@ -946,7 +991,13 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X
                         const bool ok = inside(rt, qt, g);
                         const unsigned long long mk = __builtin_amdgcn_ballot_w64(ok);
                         const unsigned long long slot = slot0 + lanes_below(mk);
-                        if (ok && slot < X.capacity) X.pairs[slot] = make_uint2((rt0 + rt) * 32 + tile_row_local(g, (int)h), jq[qt]);
+                        if (ok && slot < X.capacity) {
+                          const uint32_t i = (rt0 + rt) * 32 + tile_row_local(g, (int)h);
+                          if constexpr (PR)
+                            X.pairs[slot] = make_uint2(X.perm[i], row_q[qt]);
+                          else
+                            X.pairs[slot] = make_uint2(i, jq[qt]);
+                        }
                         slot0 += (unsigned long long)__popcll(mk);
                       }
                     }

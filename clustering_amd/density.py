@@ -740,6 +740,10 @@ def radius_pairs_wide(coords, r2, capacity=None):
     sizes the buffer unless a capacity is given.  Rows with inf / NaN have no partners (population 1; the direct kernel
     answers such data).  In the cached workspace of the wide sweeps (wide_sweep_info reads its counters).  Other column
     counts raise."""
+    return _radius_pairs_wide("dc_hip_radius_pairs_wide_dev", _wide_workspace, coords, r2, capacity)
+
+
+def _radius_pairs_wide(fn, workspace, coords, r2, capacity):
     n_rows, n_cols = _check_coords_wide(coords)
     dev = coords.device
     pops = torch.empty(n_rows, dtype=torch.int32, device=dev)
@@ -747,11 +751,11 @@ def radius_pairs_wide(coords, r2, capacity=None):
 
     def sweep(pairs, cap):
         with torch.cuda.device(dev):
-            ws, ws_bytes = _wide_workspace(dev).get(n_rows, n_cols, 1)
-            rc = capi.lib.dc_hip_radius_pairs_wide_dev(_dev(coords), n_rows, n_cols, float(r2), _dev(pops),
-                                                       _dev(pairs) if pairs is not None else None, cap,
-                                                       _dev(count), ws, ws_bytes, _stream_ptr())
-        capi.check(rc, "dc_hip_radius_pairs_wide_dev")
+            ws, ws_bytes = workspace(dev).get(n_rows, n_cols, 1)
+            rc = getattr(capi.lib, fn)(_dev(coords), n_rows, n_cols, float(r2), _dev(pops),
+                                       _dev(pairs) if pairs is not None else None, cap,
+                                       _dev(count), ws, ws_bytes, _stream_ptr())
+        capi.check(rc, fn)
         return int(count.item())
 
     if capacity is None:
@@ -759,7 +763,7 @@ def radius_pairs_wide(coords, r2, capacity=None):
     pairs = torch.empty((max(capacity, 1), 2), dtype=torch.int32, device=dev)
     n = sweep(pairs, capacity)
     if n > capacity:
-        return radius_pairs_wide(coords, r2, n)
+        return _radius_pairs_wide(fn, workspace, coords, r2, n)
     return pairs[:n].to(torch.int64), pops
 
 
@@ -769,6 +773,10 @@ def radius_min_edge_wide(coords, r2, comp, rank, segment=0, n_segments=0):
     id, -1 (all ones) if none; pops int32 [n_rows]).  n_segments > 0: what the queries of one row block of a sharded
     run see (partials merge by unsigned minimum / summation), array-equal to radius_min_edge of that segment.  Other
     column counts raise."""
+    return _radius_min_edge_wide("dc_hip_radius_min_edge_wide_dev", _wide_workspace, coords, r2, comp, rank, segment, n_segments)
+
+
+def _radius_min_edge_wide(fn, workspace, coords, r2, comp, rank, segment, n_segments):
     n_rows, n_cols = _check_coords_wide(coords)
     dev = coords.device
     for t in (comp, rank):
@@ -776,11 +784,10 @@ def radius_min_edge_wide(coords, r2, comp, rank, segment=0, n_segments=0):
     best = torch.empty(n_rows, dtype=torch.int64, device=dev)
     pops = torch.empty(n_rows, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        ws, ws_bytes = _wide_workspace(dev).get(n_rows, n_cols, 1)
-        rc = capi.lib.dc_hip_radius_min_edge_wide_dev(_dev(coords), n_rows, n_cols, float(r2), _dev(comp), _dev(rank),
-                                                      segment, n_segments, _dev(best), _dev(pops), ws, ws_bytes,
-                                                      _stream_ptr())
-    capi.check(rc, "dc_hip_radius_min_edge_wide_dev")
+        ws, ws_bytes = workspace(dev).get(n_rows, n_cols, 1)
+        rc = getattr(capi.lib, fn)(_dev(coords), n_rows, n_cols, float(r2), _dev(comp), _dev(rank), segment, n_segments,
+                                   _dev(best), _dev(pops), ws, ws_bytes, _stream_ptr())
+    capi.check(rc, fn)
     return best, pops
 
 
@@ -788,17 +795,49 @@ def radius_forest_wide(coords_host, r2, rank, device=0):
     """radius_forest for rows of 65..256 columns on the matrix cores (dc_hip_radius_forest_wide; one device, no
     session).  coords_host: float32 numpy [n_rows, n_cols]; rank: permutation of 0..n_rows-1 -> (edges uint32 numpy
     [n_edges, 2] of frame ids, number of sweeps).  Other column counts raise."""
+    return _radius_forest_wide("dc_hip_radius_forest_wide", coords_host, r2, rank, device)
+
+
+def _radius_forest_wide(fn, coords_host, r2, rank, device):
     coords_host = np.ascontiguousarray(coords_host, dtype=np.float32)
     n_rows, n_cols = _check_coords_wide(coords_host)
     rank = np.ascontiguousarray(rank, dtype=np.uint32)
     assert rank.shape == (n_rows,)
     edges = np.empty((max(n_rows - 1, 1), 2), dtype=np.uint32)
     n_edges, n_rounds = C.c_size_t(0), C.c_uint32(0)
-    rc = capi.lib.dc_hip_radius_forest_wide(coords_host.ctypes.data_as(C.c_void_p), n_rows, n_cols, float(r2),
-                                            rank.ctypes.data_as(C.c_void_p), device,
-                                            edges.ctypes.data_as(C.c_void_p), C.byref(n_edges), C.byref(n_rounds))
-    capi.check(rc, "dc_hip_radius_forest_wide")
+    rc = getattr(capi.lib, fn)(coords_host.ctypes.data_as(C.c_void_p), n_rows, n_cols, float(r2),
+                               rank.ctypes.data_as(C.c_void_p), device,
+                               edges.ctypes.data_as(C.c_void_p), C.byref(n_edges), C.byref(n_rounds))
+    capi.check(rc, fn)
     return edges[:n_edges.value].copy(), int(n_rounds.value)
+
+
+# ---- ... and its pruned form (include/dc_density.h, the PRUNED radius graph) -----------------------------------------
+def radius_pairs_wide_pruned(coords, r2, capacity=None):
+    """radius_pairs_wide without the block pairs that cannot hold a pair within the radius
+    (dc_hip_radius_pairs_wide_pruned_dev): the same set of pairs -- in no order within a pair -- and the same
+    populations.  In the cached workspace of the pruned wide sweeps (wide_pruned_info reads its counters,
+    wide_pruned_order its order)."""
+    out = _radius_pairs_wide("dc_hip_radius_pairs_wide_pruned_dev", _wide_pruned_workspace, coords, r2, capacity)
+    _wide_pruned_shapes[str(coords.device)] = tuple(coords.shape)
+    return out
+
+
+def radius_min_edge_wide_pruned(coords, r2, comp, rank, segment=0, n_segments=0):
+    """radius_min_edge_wide on the pruned sweep (dc_hip_radius_min_edge_wide_pruned_dev): the whole round (n_segments
+    == 0) is array-equal to it; n_segments > 0: what the queries of the blocks segment, segment + n_segments, ... of
+    the spatial order see (partials merge by unsigned minimum / summation; pops are non-zero only on the rows of those
+    blocks).  wide_pruned_info and wide_pruned_order as above."""
+    out = _radius_min_edge_wide("dc_hip_radius_min_edge_wide_pruned_dev", _wide_pruned_workspace, coords, r2, comp, rank,
+                                segment, n_segments)
+    _wide_pruned_shapes[str(coords.device)] = tuple(coords.shape)
+    return out
+
+
+def radius_forest_wide_pruned(coords_host, r2, rank, device=0):
+    """radius_forest_wide on the pruned sweep (dc_hip_radius_forest_wide_pruned): the same edges and rounds; the order
+    is built once per forest."""
+    return _radius_forest_wide("dc_hip_radius_forest_wide_pruned", coords_host, r2, rank, device)
 
 
 def pack_neighbors(nn_idx, nn_d2, hd_idx, hd_d2):

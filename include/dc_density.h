@@ -501,6 +501,36 @@ DC_API int dc_hip_radius_min_edge_wide_dev(const float* d_coords, size_t n_rows,
 DC_API int dc_hip_radius_forest_wide(const float* coords, size_t n_rows, size_t n_cols, float r2, const uint32_t* rank,
                                      int device, uint32_t* edges, size_t* n_edges, uint32_t* n_rounds);
 
+/* ---- ... and the PRUNED radius graph (65..256 columns) -------------------------------------------------------------------
+ * The three calls above on the pruned wide sweep: the rows in the spatial order of dc_hip_populations_wide_pruned_dev, a
+ * box per block of 128 positions, and only the chains of the reference blocks whose box lies within 1.0001 x r2 of the
+ * query block's.  The same results; entry points of their own, no dc_variant value selects them.  Workspace:
+ * dc_hip_wide_pruned_workspace_bytes(n_rows, n_cols, 1); dc_hip_wide_info_dev reads the counters of the last call in it
+ * (the EVALUATED tile pairs) and dc_hip_wide_pruned_order_dev its order.  Refusals as for the calls they mirror, with the
+ * same codes, all before a device is touched.  Flagged data: the direct kernels answer on the original rows behind the
+ * device-side gate, a segment on the reference's row block, counters (0, 0, 0), no host synchronisation.
+ *
+ * dc_hip_radius_pairs_wide_pruned_dev: arguments and contract of dc_hip_radius_pairs_wide_dev.  Every unordered pair once,
+ * in no particular order, and in NO ORDER WITHIN A PAIR: (i, j) may come with i > j (the sweep decides which of the two
+ * meetings of a pair emits on positions of the order and writes the rows behind them).
+ * dc_hip_radius_min_edge_wide_pruned_dev: arguments of dc_hip_radius_min_edge_wide_dev.  n_segments == 0: the whole
+ * round (`segment` is not read), outputs array-equal to that call's.  n_segments > 0: rank `segment` takes every
+ * n_segments-th query block of the order, the partition dc_hip_populations_wide_pruned_dev uses; d_best merges by
+ * unsigned minimum, d_pops (final for the rows of its blocks, 0 elsewhere) by summation.  Both outputs are preset by the
+ * call.  The same row limit.
+ * dc_hip_radius_forest_wide_pruned: the host-pointer contract of dc_hip_radius_forest_wide; the order is built once per
+ * forest. */
+DC_API int dc_hip_radius_pairs_wide_pruned_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
+                                               uint32_t* d_pops, uint32_t* d_pairs, size_t capacity,
+                                               unsigned long long* d_count, void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_radius_min_edge_wide_pruned_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
+                                                  const uint32_t* d_comp, const uint32_t* d_rank, size_t segment,
+                                                  size_t n_segments, unsigned long long* d_best, uint32_t* d_pops,
+                                                  void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_radius_forest_wide_pruned(const float* coords, size_t n_rows, size_t n_cols, float r2,
+                                            const uint32_t* rank, int device, uint32_t* edges, size_t* n_edges,
+                                            uint32_t* n_rounds);
+
 /* the last wide sweep CALL in that workspace -- a self sweep (dc_hip_*_wide_dev, the radius graph included) or a cross sweep
  * (dc_hip_*_cross_wide_dev), the counters sit at the same place of either workspace: 32x32 tile pairs evaluated, MFMA instructions issued, frame pairs sent
  * to the exact path, summed over the launches of the call (a population call with more than 8 radii runs one launch
