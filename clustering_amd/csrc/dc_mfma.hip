@@ -8,6 +8,7 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <vector>
 
 #ifndef DC_STEP_MASK
 #define DC_STEP_MASK 0xFFFFu   // bit (n-1) set <=> dc_mfma_step.hip was built with -DDC_STEP=n
@@ -1041,9 +1042,38 @@ const SweepSwitches& sweep_switches() {
     if ((v = env("DC_NN_FE_BITS"))) w.nn_fe_bits = atoi(v);
     w.mfma32_wpb = (uint32_t)one_of_124(env("DC_MFMA32_WPB"), 1);
     if ((v = env("DC_MFMA32_CHUNKS"))) w.mfma32_chunks = (uint32_t)atoi(v);
+    if ((v = env("DC_SWEEP_DISPATCH"))) w.tickets = strcmp(v, "static") != 0;
+    if ((v = env("DC_SWEEP_SLOTS"))) w.sweep_slots = (uint32_t)std::max(atoi(v), 0);
     return w;
   }();
   return sw;
+}
+
+uint32_t sweep_resident_slots(const void* kernel, uint32_t block_threads, size_t dyn_lds) {
+  struct Entry {
+    int dev;
+    const void* kernel;
+    uint32_t block;
+    size_t lds;
+    uint32_t slots;
+  };
+  static std::mutex mu;
+  static std::vector<Entry> known;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lock(mu);
+  for (const Entry& e : known)
+    if (e.dev == dev && e.kernel == kernel && e.block == block_threads && e.lds == dyn_lds) return e.slots;
+  int per_cu = 0, cus = 0;
+  // (a failed query leaves one workgroup per XCD label: slow, and still every unit is drawn)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)block_threads, dyn_lds) != hipSuccess || per_cu < 1 ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
+    (void)hipGetLastError();
+    per_cu = 1;
+    cus = 8;
+  }
+  known.push_back(Entry{dev, kernel, block_threads, dyn_lds, (uint32_t)per_cu * (uint32_t)cus});
+  return known.back().slots;
 }
 
 // DC_POP_CELL_FRAMES / DC_NN_CELL_FRAMES: measurement overrides of the frames per cell of the orderings

@@ -40,8 +40,14 @@ struct SweepSwitches {
   int nn_fe_bits = -1;            // DC_NN_FE_BITS: free-energy bits of the neighbour ordering's key (-1: default)
   uint32_t mfma32_wpb = 1;        // DC_MFMA32_WPB=1 / 2 / 4: waves per workgroup of the fp32-MFMA instance
   uint32_t mfma32_chunks = 0;     // DC_MFMA32_CHUNKS: its reference shares (0: chosen by size)
+  bool tickets = true;            // DC_SWEEP_DISPATCH=static / tickets: the per-wave pruned sweeps on one workgroup per unit /
+                                  // on persistent workgroups that draw their units (dc_mfma_kernels.hpp for_each_unit)
+  uint32_t sweep_slots = 0;       // DC_SWEEP_SLOTS: most persistent workgroups of a ticketed launch (0: all that can be resident)
 };
 const SweepSwitches& sweep_switches();
+// workgroups of `kernel` (a __global__ function) that can be resident on the current device at once with this block size
+// and dynamic LDS: the occupancy query per CU times the CUs, asked once per (device, kernel, block, LDS) and kept
+uint32_t sweep_resident_slots(const void* kernel, uint32_t block_threads, size_t dyn_lds);
 
 // The plan of one pruned sweep: which kernel form runs and how its query groups are cut.  The padded orders are laid
 // out for group_tiles; the kernel that runs must have the same groups, so both come from the plan.

@@ -76,6 +76,7 @@
 #include "dc_credit.hpp"
 #include "dc_rho_gap.hpp"
 #include "dc_wide_prune.hpp"
+#include "dc_sweep_units.hpp"
 
 #include <assert.h>
 #include <float.h>
@@ -356,6 +357,10 @@ constexpr uint32_t kHdrStatsBlocks = 25;   // rows of stats_kernel's table that 
 constexpr int kMfmaCtrPop = (kHdrMfmaPop - 2) / 2, kMfmaCtrNn = (kHdrMfmaNn - 4) / 2;
 constexpr uint32_t kHdrShift = 32;      // population sweeps: the number of in-place threshold shifts the scale's band pays for (dc_mfma_msym.hpp; 0: none)
 constexpr uint32_t kHdrMloc = 29;       // pruned population sweeps: max |x - origin(component of x)|^2 (float bits, with a rounding margin)
+// words 40..47 / 48..55: the ticket counters of the per-wave pruned population / neighbour sweep (SweepTickets: one per queue),
+// zeroed on the stream in front of every ticketed launch
+constexpr uint32_t kHdrTicketsPop = 40, kHdrTicketsNn = 48;
+static_assert(4 * (kHdrTicketsNn + 8) <= kHdrSums && kHdrTicketsPop > kHdrShift, "ticket counters in the free header words");
 constexpr int kMidShiftPop = 6, kConstShiftPop = 6, kConstShiftNn = 15;
 constexpr float kThrCapPop = 1048576.0f;      // 2^20 (population scale: eps <= 1 keeps S r^2 below 2^19.2 and
                                               //  4 S M below 2^19.6; only a radius beyond the clamps of
@@ -1012,14 +1017,102 @@ __global__ __launch_bounds__(256, 2) void pop_mfma_kernel(SweepArgs X, uint32_t 
 // ms with a third of the chip idle in the tail.)  The launchers round gridDim.x up to a multiple of 8, so block (x, y)
 // runs on XCD x & 7; n_blocks: the real number of block-sized units.  Returns the unit of this block, 0xFFFFFFFF for a
 // pad block.
-__device__ __forceinline__ uint32_t xcd_block(uint32_t n_blocks) {
-  const uint32_t b = blockIdx.x, phys = b & 7u, idx = b >> 3;
-  const uint32_t eighth = (phys + blockIdx.y) & 7u;
-  const uint32_t n_full = n_blocks >> 3, rem = n_blocks & 7u;
-  if (idx >= n_full + (eighth < rem ? 1u : 0u)) return 0xFFFFFFFFu;
-  return eighth * n_full + min(eighth, rem) + idx;
-}
+__device__ __forceinline__ uint32_t xcd_block(uint32_t n_blocks) { return xcd_unit(n_blocks, blockIdx.x, blockIdx.y); }
 inline uint32_t grid_x8(uint32_t n_blocks) { return (n_blocks + 7u) & ~7u; }
+
+// ---- persistent workgroups of the per-wave pruned sweeps (DC_SWEEP_DISPATCH=tickets, the default) ------------------
+// The static placement above deals the units out before anyone knows what they cost: an XCD label that meets the heavy
+// eighths twice (ten shares: eighths p and p + 1) ends after the others, and which wave slot gets the next workgroup is
+// the dispatcher's pace.  In the ticketed form the grid is the workgroups that can be RESIDENT; each draws its units
+// from the queue of its own label (dc_sweep_units.hpp: the very sequence that label runs in the static form, so the
+// L2 sees what it saw) with one device-scope atomicAdd per unit, and goes on with the next labels' queues when its own
+// is empty.  Nobody waits for anybody: a workgroup leaves after it has found all eight queues empty, at most units + 8
+// draws in all; which workgroup runs a unit changes nothing of what the unit computes.
+//   ctr == nullptr: the static form -- one trip, the unit of blockIdx
+struct SweepTickets {
+  uint32_t* ctr;       // [kSweepQueues] tickets drawn per queue (header words kHdrTicketsPop / kHdrTicketsNn), zero at launch
+  uint32_t n_chunks;   // reference shares (the grid is one-dimensional)
+};
+// k: the queues this workgroup has found empty (kept across trips: a queue never fills again); one wave calls this
+__device__ __forceinline__ SweepUnit draw_unit(uint32_t* __restrict__ ctr, uint32_t n_blocks, uint32_t n_chunks, uint32_t& k,
+                                               bool first_lane) {
+  while (k < kSweepQueues) {
+    const uint32_t qq = (blockIdx.x + k) & 7u;
+    uint32_t t = 0;
+    if (first_lane) t = atomicAdd(&ctr[qq], 1u);
+    const SweepUnit u = sweep_unit(n_blocks, n_chunks, qq, (uint32_t)__builtin_amdgcn_readfirstlane((int)t));
+    if (u.blk != kNoUnit) return u;
+    ++k;
+  }
+  return SweepUnit{kNoUnit, 0u};
+}
+// What a loop around the body costs in registers, and the two helpers that take it back.  Everything the compiler can
+// prove invariant in the loop -- the kernel's thirty arguments, and what the body derives from the thread number alone
+// (the wave's LDS offsets, lane masks, half-wave selects) -- is computed ONCE in front of it and then lives across a body
+// that already fills both register files: without the helpers pop_pruned_kernel<2, 1, 6, 0, true> went from 238 VGPRs
+// and no spill to 256 with 10 spilled (48 B of scratch per lane), nn_pruned_kernel<2, 6> from none to 60 spilled.  An
+// empty asm hides where a value comes from, so each trip computes it where it is used, as the straight-line kernel did.
+//   kernargs_again   the kernel's one parameter, a struct, read again from the kernel-argument segment (scalar loads;
+//                    the explicit arguments come first in the segment, so the struct lies at its start)
+//   thread_again     threadIdx.x of this trip; the units take lane and wave from it (the wave as a scalar)
+// With them the two C3 instances have no spilled VGPR and no scratch (DESIGN 4.5 has the figures of every instance).
+template <class A>
+__device__ __forceinline__ const A* kernargs_again() {
+  auto* p = (const __attribute__((address_space(4))) A*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return (const A*)p;
+}
+__device__ __forceinline__ uint32_t thread_again() {
+  uint32_t t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+// The loop of a per-wave sweep kernel whose one parameter is the struct A (with a SweepTickets tk): body(arguments, block
+// unit, share, shares) once per unit; n_blocks_of(arguments): the block units of the launch.  One wave per workgroup: the
+// drawing lane's ticket is broadcast by readfirstlane.  Several: wave 0 draws, the unit goes through the first two
+// words of the workgroup's dynamic LDS (slot: dead between two units) and three barriers that every wave reaches in
+// every trip -- the waves have left the last unit; the unit is written; everyone has read it before a body writes there.
+// ONE value lives across the body: k, the queues found empty (the static form's single trip sets it to "all").
+template <class A, class NBlocks, class Body>
+__device__ __forceinline__ void for_each_unit(uint32_t* slot, NBlocks&& n_blocks_of, Body&& body) {
+  for (uint32_t k = 0;;) {   // (one call of the body: the static form is a loop of one trip)
+    const A& a = *kernargs_again<A>();
+    const uint32_t n_blocks = n_blocks_of(a);
+    uint32_t blk, share, shares;
+    if (a.tk.ctr == nullptr) {
+      if (k != 0) return;
+      k = kSweepQueues;
+      blk = xcd_block(n_blocks);
+      share = blockIdx.y;
+      shares = gridDim.y;
+    } else {
+      shares = a.tk.n_chunks;
+      // (the thread number of this trip, and a scalar "wave 0": the loop's control stays wave-uniform for the compiler too)
+      const uint32_t tid = thread_again();
+      const bool first_lane = (tid & 63u) == 0;
+      if (blockDim.x == 64u) {
+        const SweepUnit u = draw_unit(a.tk.ctr, n_blocks, shares, k, first_lane);
+        blk = u.blk;
+        share = u.share;
+      } else {
+        __syncthreads();
+        if (__builtin_amdgcn_readfirstlane((int)(tid >> 6)) == 0) {
+          const SweepUnit u = draw_unit(a.tk.ctr, n_blocks, shares, k, first_lane);
+          if (first_lane) {
+            slot[0] = u.blk;
+            slot[1] = u.share;
+          }
+        }
+        __syncthreads();
+        blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot[0]);
+        share = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot[1]);
+        __syncthreads();
+      }
+    }
+    if (blk == kNoUnit) return;
+    body(a, blk, share, shares);
+  }
+}
 
 // which rows a pruned sweep answers for, and where their operands live:
 //   kQueryOwnOrder  a row range [i_from, i_to): its own spatial ordering (img_q / norms_q / perm_q / box_q)
@@ -1251,8 +1344,11 @@ __device__ __forceinline__ void stage_query_rows(float* __restrict__ dst, const 
   }
 }
 
-template <int NM, int NR, int TQ, int MODE = kSinkNone, bool SYM = false>
-__global__ __launch_bounds__(256, 2) void pop_pruned_kernel(
+// One UNIT of the sweep (for_each_unit): the workgroup's block blk_unit of query groups against reference share `chunk`
+// of n_chunks.  A return is "this unit is empty for this wave"; every piece of per-unit state starts here.
+template <int NM, int NR, int TQ, int MODE, bool SYM>
+__device__ __forceinline__ void pop_pruned_unit(
+    uint32_t blk_unit, uint32_t chunk, uint32_t n_chunks, float* __restrict__ pop_dyn_lds,
     const float* __restrict__ coords, uint32_t n_rows, uint32_t n_cols,
     const uint4* __restrict__ img_r, const float* __restrict__ norms_r,
     const uint32_t* __restrict__ perm_r, const float4* __restrict__ box_r,
@@ -1260,28 +1356,24 @@ __global__ __launch_bounds__(256, 2) void pop_pruned_kernel(
     const uint4* __restrict__ img_q, const float* __restrict__ norms_q,
     const uint32_t* __restrict__ perm_q, const float4* __restrict__ box_q, uint32_t n_q, QSeg q_seg,
     const uint32_t* __restrict__ hdr, unsigned long long* __restrict__ chain_counter, Rad2 rad2,
-    int n_rad, uint32_t* __restrict__ pops, EdgeSink sink, CompView CV, uint32_t* __restrict__ pops_pos = nullptr) {
+    int n_rad, uint32_t* __restrict__ pops, EdgeSink sink, CompView CV, uint32_t* __restrict__ pops_pos) {
   static_assert(!SYM || (MODE == kSinkNone && NR == 1), "the symmetric sweep is the plain one-radius sweep");
   // dynamic LDS, per wave of the workgroup (one wave, see nn_pruned_kernel): the survivor list of a scan round
   // [kListCap], then [TQ*32][n_cols] query rows (original coordinates), then the queues of deferred exact
   // evaluations [TQ][kQueueCap][64]
-  extern __shared__ __attribute__((aligned(16))) float pop_dyn_lds[];
-  if (hdr[1] != 0) return;   // flagged data: the gated direct kernel runs instead
-  const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
-  const int wib = threadIdx.x >> 6;
+  const uint32_t tid = thread_again();
+  const int lane = tid & 63, h = lane >> 5, c = lane & 31;
+  const int wib = __builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (wave-uniform: the wave's LDS offsets are scalar)
   const uint32_t wpb = blockDim.x >> 6;
   uint32_t* lists_all = reinterpret_cast<uint32_t*>(pop_dyn_lds);
   float* pop_qrows_all = pop_dyn_lds + (size_t)wpb * kListCap;
   const uint32_t TQT = (n_q + 31) / 32;
-  const uint32_t blk_unit = xcd_block((seg_groups((TQT + TQ - 1) / TQ, q_seg) + wpb - 1) / wpb);
-  if (blk_unit == 0xFFFFFFFFu) return;   // (pad block of the grid)
   const uint32_t wave = seg_group(blk_unit * wpb + wib, q_seg);
-  // gridDim.y > 1: the reference tiles are dealt round-robin to gridDim.y waves per query group and
+  // n_chunks > 1: the reference tiles are dealt round-robin to n_chunks waves per query group and
   // the partial counts are merged with atomics (keeps small launches, e.g. one rank of an 8-GPU
   // run, at >= 2 waves per SIMD without giving up the operand reuse of TQ query tiles per wave)
-  const uint32_t chunk = blockIdx.y, n_chunks = gridDim.y;
   const uint32_t qt0 = wave * TQ;
-  if (qt0 >= TQT) return;    // whole wave leaves; no block-level barriers in this kernel
+  if (qt0 >= TQT) return;    // whole wave leaves the unit; no block-level barriers in it
   // (the component of the group and its tile range: two dependent look-ups, started before everything else)
   const uint32_t my_comp = CV.tile_comp_q[qt0];
   const uint32_t comp_lo = CV.range_r[2 * my_comp], comp_hi = CV.range_r[2 * my_comp + 1];
@@ -1687,6 +1779,50 @@ __global__ __launch_bounds__(256, 2) void pop_pruned_kernel(
       }
     }
   }
+}
+
+// The arguments of the kernel, in the order pop_pruned_unit takes them.  ONE struct: the loop reads it again from the
+// kernel-argument segment in every trip (kernargs_again)
+struct PopKernArgs {
+  const float* coords;
+  uint32_t n_rows, n_cols;
+  const uint4* img_r;
+  const float* norms_r;
+  const uint32_t* perm_r;
+  const float4* box_r;
+  const float* coords_r;
+  uint32_t T;
+  const uint4* img_q;
+  const float* norms_q;
+  const uint32_t* perm_q;
+  const float4* box_q;
+  uint32_t n_q;
+  QSeg q_seg;
+  const uint32_t* hdr;
+  unsigned long long* chain_counter;
+  Rad2 rad2;
+  int n_rad;
+  uint32_t* pops;
+  EdgeSink sink;
+  CompView CV;
+  uint32_t* pops_pos;   // SYM: counts by position, else nullptr
+  SweepTickets tk;
+};
+template <int NM, int NR, int TQ, int MODE = kSinkNone, bool SYM = false>
+__global__ __launch_bounds__(256, 2) void pop_pruned_kernel(PopKernArgs A0) {
+  extern __shared__ __attribute__((aligned(16))) float pop_dyn_lds[];
+  if (A0.hdr[1] != 0) return;   // flagged data: the gated direct kernel runs instead (the tickets stay undrawn)
+  for_each_unit<PopKernArgs>(
+      reinterpret_cast<uint32_t*>(pop_dyn_lds),
+      [](const PopKernArgs& A) {
+        const uint32_t wpb = blockDim.x >> 6;
+        return (seg_groups(((A.n_q + 31) / 32 + TQ - 1) / TQ, A.q_seg) + wpb - 1) / wpb;
+      },
+      [&](const PopKernArgs& A, uint32_t blk_unit, uint32_t chunk, uint32_t n_chunks) {
+        pop_pruned_unit<NM, NR, TQ, MODE, SYM>(blk_unit, chunk, n_chunks, pop_dyn_lds, A.coords, A.n_rows, A.n_cols, A.img_r, A.norms_r,
+                                               A.perm_r, A.box_r, A.coords_r, A.T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q,
+                                               A.q_seg, A.hdr, A.chain_counter, A.rad2, A.n_rad, A.pops, A.sink, A.CV, A.pops_pos);
+      });
 }
 
 
@@ -2153,8 +2289,12 @@ __device__ __forceinline__ void load_tile_folded(const uint4* __restrict__ img, 
 // a returning ds_min per query and kind, only in the chains that went on): a threshold one share has learnt is learnt
 // for all of them -- DESIGN.md 4.8 measured 0.45 ms of a rank's 1.6 ms (an eighth of C3) as thresholds learnt again by
 // every one of a group's 34 shares.  Taken when a group has many shares (sharded runs); a share is still a wave.
-template <int NM, int TQ, bool COOP = false>
-__global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kernel(
+// One UNIT of the sweep (for_each_unit; COOP: of the static grid): the workgroup's block blk_unit of query groups against
+// reference share share_y of n_shares_y (COOP: each of them kNnCoopWaves shares wide).  A return is "this unit is empty
+// for this wave"; every piece of per-unit state starts here.
+template <int NM, int TQ, bool COOP>
+__device__ __forceinline__ void nn_pruned_unit(
+    uint32_t blk_unit, uint32_t share_y, uint32_t n_shares_y, float* __restrict__ nn_dyn_lds,
     const float* __restrict__ coords, uint32_t n_rows, uint32_t n_cols,
     const float* __restrict__ fe, const uint4* __restrict__ img_r,
     const float* __restrict__ norms_r, const uint32_t* __restrict__ perm_r,
@@ -2173,10 +2313,9 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
   //  the queries are not rows of the reference order, or DC_NN_RHO = 0 -- the rings then go by the boxes alone)
   // dynamic LDS, per wave of the workgroup: the survivor list of a scan round [kListCap], then [TQ*32][n_cols] query
   // rows (original coordinates), then the candidate queues [TQ][kQueueCap][64]
-  extern __shared__ __attribute__((aligned(16))) float nn_dyn_lds[];
-  if (hdr[1] != 0) return;
-  const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
-  const int wib = threadIdx.x >> 6;
+  const uint32_t tid = thread_again();
+  const int lane = tid & 63, h = lane >> 5, c = lane & 31;
+  const int wib = __builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (wave-uniform: the wave's LDS offsets are scalar)
   // waves per workgroup (kWavesPerGroup): the waves share nothing, and a workgroup holds its LDS until its LAST
   // wave is done -- with four waves of unequal cost a fifth of the wave slots sat idle (SQ_WAVE_CYCLES: 1.57 of 2
   // per SIMD at C3), with one wave per workgroup a finished wave is replaced at once (C3: 16.3 -> 15.2 ms)
@@ -2184,13 +2323,11 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
   uint32_t* lists_all = reinterpret_cast<uint32_t*>(nn_dyn_lds);
   float* qrows_all = nn_dyn_lds + (size_t)wpb * kListCap;
   const uint32_t TQT = (n_q + 31) / 32;
-  const uint32_t blk_unit = xcd_block(COOP ? seg_groups((TQT + TQ - 1) / TQ, q_seg) : (seg_groups((TQT + TQ - 1) / TQ, q_seg) + wpb - 1) / wpb);
-  if (blk_unit == 0xFFFFFFFFu) return;   // (pad block of the grid)
   const uint32_t wave = seg_group(COOP ? blk_unit : blk_unit * wpb + wib, q_seg);
   // reference tiles dealt round-robin (COOP: the workgroup's waves take neighbouring shares)
-  const uint32_t chunk = COOP ? blockIdx.y * wpb + (uint32_t)wib : blockIdx.y, n_chunks = COOP ? gridDim.y * wpb : gridDim.y;
+  const uint32_t chunk = COOP ? share_y * wpb + (uint32_t)wib : share_y, n_chunks = COOP ? n_shares_y * wpb : n_shares_y;
   const uint32_t qt0 = wave * TQ;
-  if (qt0 >= TQT) return;   // (COOP: the whole workgroup leaves -- no barrier is ever met by a part of it)
+  if (qt0 >= TQT) return;   // (COOP: the whole workgroup leaves -- no barrier of the unit is ever met by a part of it)
   // (the component of the group, its tile range and cell edge: three dependent look-ups, started before everything else)
   const uint32_t my_comp = CV.tile_comp_q[qt0];
   const uint32_t comp_lo = CV.range_r[2 * my_comp], comp_hi = CV.range_r[2 * my_comp + 1];
@@ -2308,7 +2445,7 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
       }
     }
     __syncthreads();
-    if (blockIdx.y == 0) {
+    if (share_y == 0) {
       // Seeds (see below), dealt to the waves of the group's FIRST workgroup: wave w looks at the frames w + 1, w + 1 + wpb,
       // ... positions away; the results meet in LDS and are published at once
 #pragma unroll
@@ -2923,6 +3060,62 @@ __global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kern
   }
 }
 
+// The arguments of the kernel, in the order nn_pruned_unit takes them (one struct: kernargs_again)
+struct NnKernArgs {
+  const float* coords;
+  uint32_t n_rows, n_cols;
+  const float* fe;
+  const uint4* img_r;
+  const float* norms_r;
+  const uint32_t* perm_r;
+  const float4 *box_r, *box_t;
+  const float2 *rho_r, *rho_t, *ferange_r;
+  const float *fe_c, *coords_c;
+  const uint32_t* invpos_r;
+  uint32_t T;
+  const uint4* img_q;
+  const float* norms_q;
+  const uint32_t* perm_q;
+  const float4* box_q;
+  uint32_t n_q;
+  QSeg q_seg;
+  int full_range;
+  float cell2;
+  const uint32_t* hdr;
+  unsigned long long* chain_counter;
+  unsigned long long* merge64;
+  uint32_t* nn_idx;
+  float* nn_d2;
+  uint32_t* hd_idx;
+  float* hd_d2;
+  CompView CV;
+  SweepTickets tk;   // (COOP stays on the static grid whatever it says: its launcher passes no counters)
+};
+template <int NM, int TQ, bool COOP = false>
+__global__ __launch_bounds__(COOP ? 512 : 256, COOP ? 1 : 2) void nn_pruned_kernel(NnKernArgs A0) {
+  extern __shared__ __attribute__((aligned(16))) float nn_dyn_lds[];
+  if (A0.hdr[1] != 0) return;   // (flagged data; the tickets stay undrawn)
+  auto groups_of = [](const NnKernArgs& A) { return seg_groups(((A.n_q + 31) / 32 + TQ - 1) / TQ, A.q_seg); };
+  auto unit = [&](const NnKernArgs& A, uint32_t blk_unit, uint32_t share_y, uint32_t n_shares_y) {
+    nn_pruned_unit<NM, TQ, COOP>(blk_unit, share_y, n_shares_y, nn_dyn_lds, A.coords, A.n_rows, A.n_cols, A.fe, A.img_r, A.norms_r,
+                                 A.perm_r, A.box_r, A.box_t, A.rho_r, A.rho_t, A.ferange_r, A.fe_c, A.coords_c, A.invpos_r, A.T, A.img_q,
+                                 A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg, A.full_range, A.cell2, A.hdr, A.chain_counter, A.merge64,
+                                 A.nn_idx, A.nn_d2, A.hd_idx, A.hd_d2, A.CV);
+  };
+  if constexpr (COOP) {
+    const uint32_t blk_unit = xcd_block(groups_of(A0));
+    if (blk_unit != kNoUnit) unit(A0, blk_unit, blockIdx.y, gridDim.y);   // (a pad block of the grid leaves whole)
+  } else {
+    for_each_unit<NnKernArgs>(
+        reinterpret_cast<uint32_t*>(nn_dyn_lds),
+        [&](const NnKernArgs& A) {
+          const uint32_t wpb = blockDim.x >> 6;
+          return (groups_of(A) + wpb - 1) / wpb;
+        },
+        unit);
+  }
+}
+
 #include "dc_mfma_nn_shared.hpp"
 
 __global__ void nn_merge_fill_kernel(unsigned long long* __restrict__ merge64, uint32_t n_rows) {
@@ -3003,11 +3196,13 @@ void pop_dispatch(const SweepArgs& X, uint32_t n_cols, uint32_t i_from, uint32_t
 
 // tile boxes regrouped by reference share: share c holds the tiles c, c + n, c + 2n, ... at
 // box_t[c * ceil(T / n) + u]
-// (rho_r / rho_t: the tiles' radial ranges the same way, or null)
+// (rho_r / rho_t: the tiles' radial ranges the same way, or null; tickets: the counters of the ticketed sweep that
+//  follows, or null -- this kernel runs once in front of every neighbour sweep)
 __global__ void box_by_share_kernel(const float4* __restrict__ box_r, uint32_t T, uint32_t n_chunks,
                                     float4* __restrict__ box_t, const float2* __restrict__ rho_r,
-                                    float2* __restrict__ rho_t) {
+                                    float2* __restrict__ rho_t, uint32_t* __restrict__ tickets) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tickets && t < kSweepQueues) tickets[t] = 0u;
   if (t >= T) return;
   const uint32_t stride = (T + n_chunks - 1) / n_chunks;
   box_t[(size_t)(t % n_chunks) * stride + t / n_chunks] = box_r[t];
@@ -3189,11 +3384,25 @@ void timed_launch(int kind, hipStream_t s, F&& launch) {
 // around a neighbour sweep of n_chunks reference shares: the merge buffer of several shares and the boxes of every share
 // in front, the merged results back to the frames behind (group_tiles: query tiles per group)
 // (with_rho: the per-wave sweep's radial ranges go along, where the call has them)
-inline void nn_shares_begin(const NnPrunedArgs& A, uint32_t n_rows, uint32_t T, uint32_t n_chunks, bool with_rho, hipStream_t s) {
+// (tickets: the counters of a ticketed sweep, zeroed along the way)
+inline void nn_shares_begin(const NnPrunedArgs& A, uint32_t n_rows, uint32_t T, uint32_t n_chunks, bool with_rho, hipStream_t s,
+                            uint32_t* tickets = nullptr) {
   if (n_chunks > 1)
     hipLaunchKernelGGL(nn_merge_fill_kernel, dim3((2 * n_rows + 255) / 256), dim3(256), 0, s, A.merge64, n_rows);
   hipLaunchKernelGGL(box_by_share_kernel, dim3((T + 255) / 256), dim3(256), 0, s, A.box_r, T, n_chunks, A.box_t,
-                     with_rho ? A.rho_r : (const float2*)nullptr, A.rho_t);
+                     with_rho ? A.rho_r : (const float2*)nullptr, A.rho_t, tickets);
+}
+// The grid of a ticketed launch: the workgroups that can be resident at once (sweep_resident_slots, dc_mfma.hip; capped by
+// DC_SWEEP_SLOTS), rounded down to a multiple of 8 -- every XCD label then has as many workgroups as the others -- and
+// never more than there are units.  x: the static grid's, which the kernel never reads in this form.
+inline dim3 ticket_grid(const void* kernel, uint32_t block_threads, size_t dyn_lds, uint32_t n_blocks, uint32_t n_chunks,
+                        const SweepSwitches& sw) {
+  uint32_t g = sweep_resident_slots(kernel, block_threads, dyn_lds);
+  if (sw.sweep_slots != 0 && sw.sweep_slots < g) g = sw.sweep_slots;
+  const unsigned long long units = (unsigned long long)n_blocks * n_chunks;
+  if (units < g) g = (uint32_t)units;
+  if (g >= kSweepQueues) g &= ~(kSweepQueues - 1u);
+  return dim3(g < 1u ? 1u : g);
 }
 inline void nn_shares_end(const NnPrunedArgs& A, uint32_t n_rows, uint32_t n_chunks, uint32_t group_tiles,
                           uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2, hipStream_t s) {
@@ -3255,6 +3464,12 @@ void nn_pruned_dispatch(const NnPlan& pl, const float* coords, uint32_t n_rows, 
   const uint32_t waves = seg_groups(((A.n_q + 31) / 32 + TQV - 1) / TQV, A.q_seg), tiles = waves * TQV;
   if (waves == 0) return;
   uint32_t n_chunks = pick_chunks(tiles, TQV, kNnWaveTargetPerWave, T, kNnShareFloor, (size_t)S * 1024 + 128);
+  auto kern_args = [&](const SweepTickets& tk) {
+    return NnKernArgs{coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.rho_r,
+                      (const float2*)(A.rho_r ? A.rho_t : nullptr), A.ferange_r, A.fe_c, A.coords_c, A.invpos_r, T, A.img_q,
+                      A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg, A.full_range, A.cell2, hdr, chain_counter, A.merge64,
+                      nn_idx, nn_d2, hd_idx, hd_d2, CV, tk};
+  };
   if (n_chunks >= pl.coop_shares) {
     // the shares of a group as the waves of ONE workgroup (plan_nn)
     n_chunks = (n_chunks + kNnCoopWaves - 1) / kNnCoopWaves * kNnCoopWaves;
@@ -3263,21 +3478,21 @@ void nn_pruned_dispatch(const NnPlan& pl, const float* coords, uint32_t n_rows, 
     nn_shares_begin(A, n_rows, T, n_chunks, true, s);
     timed_launch(1, s, [&] {
       hipLaunchKernelGGL((nn_pruned_kernel<S, TQV, true>), dim3(grid_x8(waves), n_chunks / kNnCoopWaves), dim3(64 * kNnCoopWaves), smem_c, s,
-                         coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.rho_r,
-                         (const float2*)(A.rho_r ? A.rho_t : nullptr), A.ferange_r, A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
-                         A.full_range, A.cell2, hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
+                         kern_args(SweepTickets{nullptr, 0u}));
     });
   } else {
     // query rows (original coordinates) + candidate queues, per wave
-    const uint32_t wpb = pl.waves;
+    const uint32_t wpb = pl.waves, n_blocks = (waves + wpb - 1) / wpb;
     const size_t smem = wpb * (sizeof(uint32_t) * kListCap + sizeof(float) * TQV * 32 * (size_t)n_cols +
                                sizeof(uint32_t) * (TQV * kQueueCap * 64 + 2 * TQV * 32));
-    nn_shares_begin(A, n_rows, T, n_chunks, true, s);
+    // ticketed (for_each_unit): persistent workgroups, the counters zeroed by box_by_share_kernel
+    const SweepSwitches& sw = sweep_switches();
+    const SweepTickets tk{sw.tickets ? const_cast<uint32_t*>(hdr) + kHdrTicketsNn : nullptr, n_chunks};
+    const dim3 grid = tk.ctr ? ticket_grid((const void*)&nn_pruned_kernel<S, TQV>, 64 * wpb, smem, n_blocks, n_chunks, sw)
+                             : dim3(grid_x8(n_blocks), n_chunks);
+    nn_shares_begin(A, n_rows, T, n_chunks, true, s, tk.ctr);
     timed_launch(1, s, [&] {
-      hipLaunchKernelGGL((nn_pruned_kernel<S, TQV>), dim3(grid_x8((waves + wpb - 1) / wpb), n_chunks), dim3(64 * wpb), smem, s,
-                         coords, n_rows, n_cols, fe, A.img_r, A.norms_r, A.perm_r, A.box_r, (const float4*)A.box_t, A.rho_r,
-                         (const float2*)(A.rho_r ? A.rho_t : nullptr), A.ferange_r, A.fe_c, A.coords_c, A.invpos_r, T, A.img_q, A.norms_q, A.perm_q, A.box_q, A.n_q, A.q_seg,
-                         A.full_range, A.cell2, hdr, chain_counter, A.merge64, nn_idx, nn_d2, hd_idx, hd_d2, CV);
+      hipLaunchKernelGGL((nn_pruned_kernel<S, TQV>), grid, dim3(64 * wpb), smem, s, kern_args(tk));
     });
   }
   nn_shares_end(A, n_rows, n_chunks, (uint32_t)TQV, nn_idx, nn_d2, hd_idx, hd_d2, s);
@@ -3300,7 +3515,7 @@ void pop_pruned_dispatch(const PopPlan& pl, const float* coords, uint32_t n_rows
                          int n_rad, uint32_t* pops, unsigned long long* chain_counter,
                          const EdgeSink* sink, hipStream_t s, bool pos_clean) {
   // pos_clean: the counts by position of the one-radius symmetric per-wave sweep (the pq region) were cleared by the
-  // preparation (order_rows2_kernel) -- no fill in front of the sweep
+  // preparation (order_rows2_kernel), and the sweep's ticket counters with them -- no fill in front of the sweep
   assert(pop_form_built(pl.form, S) && n_rad <= pl.nr);
   if (n_q == 0) return;
   // B form of the query rows: its own image for a row range, else the B form of the rows in the
@@ -3394,20 +3609,25 @@ void pop_pruned_dispatch(const PopPlan& pl, const float* coords, uint32_t n_rows
   // the query groups of this launch: all of them, or one segment's share
   const uint32_t waves = seg_groups(((n_q + 31) / 32 + TQ - 1) / TQ, q_seg), tiles = waves * TQ;
   if (waves == 0) return;
-  const uint32_t wpb = pl.waves;
-  const dim3 grid(grid_x8((waves + wpb - 1) / wpb), pick_chunks(tiles, TQ, kPopWaveTarget, T, pop_share_floor(T), (size_t)S * 1024 + 128)),
-      block(64 * wpb);
+  const uint32_t wpb = pl.waves, n_blocks = (waves + wpb - 1) / wpb;
+  const uint32_t n_chunks = pick_chunks(tiles, TQ, kPopWaveTarget, T, pop_share_floor(T), (size_t)S * 1024 + 128);
+  const dim3 block(64 * wpb);
   // survivor list + query rows (original coordinates) + queues of deferred exact evaluations, per wave
   const size_t smem = wpb * (sizeof(uint32_t) * kListCap + sizeof(float) * TQ * 32 * (size_t)n_cols +
                              sizeof(uint32_t) * TQ * kQueueCap * 64);
   const EdgeSink no_sink{nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+  // ticketed (for_each_unit): persistent workgroups; the counters are zeroed on the stream, outside the timed pair -- by
+  // the preparation along with the counts by position (pos_clean), else by a fill of their own
+  const SweepSwitches& sw = sweep_switches();
+  const SweepTickets tk{sw.tickets ? const_cast<uint32_t*>(P.hdr) + kHdrTicketsPop : nullptr, n_chunks};
   auto launch = [&](auto mode_c, auto sym_c, uint32_t* pops_pos) {
-    timed_launch(0, s, [&] {
-      hipLaunchKernelGGL((pop_pruned_kernel<S, 1, TQ, decltype(mode_c)::value, decltype(sym_c)::value>), grid, block, smem, s,
-                         coords, n_rows, n_cols, P.img_p, P.norms_p, P.perm_p, P.box_p, P.coords_p, T, img_q, norms_q,
-                         perm_q, box_q, n_q, q_seg, P.hdr, chain_counter, rad2, n_rad, pops, sink ? *sink : no_sink, CV,
-                         pops_pos);
-    });
+    auto kernel = &pop_pruned_kernel<S, 1, TQ, decltype(mode_c)::value, decltype(sym_c)::value>;
+    const dim3 grid = tk.ctr ? ticket_grid((const void*)kernel, block.x, smem, n_blocks, n_chunks, sw) : dim3(grid_x8(n_blocks), n_chunks);
+    if (tk.ctr && !pos_clean) (void)hipMemsetAsync(tk.ctr, 0, sizeof(uint32_t) * kSweepQueues, s);
+    const PopKernArgs args{coords, n_rows, n_cols, P.img_p, P.norms_p, P.perm_p, P.box_p, P.coords_p, T, img_q, norms_q,
+                           perm_q, box_q, n_q, q_seg, P.hdr, chain_counter, rad2, n_rad, pops, sink ? *sink : no_sink, CV,
+                           pops_pos, tk};
+    timed_launch(0, s, [&] { hipLaunchKernelGGL(kernel, grid, block, smem, s, args); });
   };
   switch (pl.form) {
     case kPopWaveSym: {

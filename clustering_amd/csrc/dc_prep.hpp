@@ -626,7 +626,8 @@ __global__ __launch_bounds__(256) void order_rows2_kernel(
     const float* __restrict__ origins, uint32_t* __restrict__ hdr, uint4* __restrict__ img_a, int a_form,
     float* __restrict__ norms_a, uint4* __restrict__ img_b, float* __restrict__ norms_b, uint32_t grp_tq, QSeg grp,
     unsigned long long* __restrict__ hash_slots, uint32_t* __restrict__ zero_pos, uint32_t zero_planes) {
-  // (zero_pos: zero_planes arrays of n_pos words cleared by the way -- the counts by position of a symmetric population sweep)
+  // (zero_pos: zero_planes arrays of n_pos words cleared by the way -- the counts by position of a symmetric population
+  //  sweep -- and with them the ticket counters of that sweep, header words kHdrTicketsPop ..)
   extern __shared__ float or_tile[];            // [256][D | 1], then per wave: K rows of a tile, origin
   __shared__ uint32_t s_frame[256];
   __shared__ unsigned long long fp_part[4];
@@ -636,6 +637,7 @@ __global__ __launch_bounds__(256) void order_rows2_kernel(
   s_frame[threadIdx.x] = frame;
   if (zero_pos && pos < n_pos)
     for (uint32_t z = 0; z < zero_planes; ++z) zero_pos[(size_t)z * n_pos + pos] = 0u;
+  if (zero_pos && pos < kSweepQueues) hdr[kHdrTicketsPop + pos] = 0u;
   __syncthreads();
   const size_t base = (size_t)pos0 * D, total = (size_t)n_pos * D;
   // (four elements per thread and step, their loads issued together)
