@@ -161,7 +161,7 @@ size_t wide_pruned_workspace_bytes(size_t n_rows, size_t n_cols) {
   return wide_pruned_layout(n_rows, n_cols).total;
 }
 
-int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t s) {
+int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t s, const float* d_fe) {
   const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
   char* p = (char*)d_ws;
   uint32_t* hdr = (uint32_t*)p;
@@ -169,7 +169,7 @@ int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols,
   uint32_t* keys = (uint32_t*)(p + P.off_keys);
   uint32_t* vals = (uint32_t*)(p + P.off_vals);
   float* coords_o = (float*)(p + P.off_coords);
-  if (wide_stats_launches(d_coords, n_rows, n_cols, nullptr, d_ws, s) != 0) return -1;
+  if (wide_stats_launches(d_coords, n_rows, n_cols, d_fe, d_ws, s) != 0) return -1;
   hipLaunchKernelGGL(wide_extent_kernel, dim3((uint32_t)min_sz(1024, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s, d_coords,
                      n_rows, n_cols, hdr);
   hipLaunchKernelGGL(wide_prune_key_kernel, dim3((uint32_t)min_sz(4096, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s, d_coords,
@@ -272,6 +272,52 @@ int launch_min_edge_wide_pruned(uint32_t n_rows, uint32_t n_cols, float r2, cons
   hipLaunchKernelGGL((wide_sweep_kernel<kWideMinEdge, 1, kSelf, true>), grid, dim3(256), 0, s, X);
   sweep_timer_mark(0, false, s);
   return wide_pruned_scatter(P, n_rows, 1, d_pops, d_ws, s);
+}
+
+// ---- the pruned self neighbour sweep (dc_hip_nearest_neighbors_wide_pruned_dev) ---------------------------
+// Behind wide_pruned_prepare (with the free energies: a NaN among them flags the data).  The count region of the layout
+// (32 bytes per row) holds, for this call, the free energies by position, then per block the (least, largest) free
+// energy and the two bounds: 4 (n_rows + 1) + 16 blocks bytes, under 5 per row.  Three launches of the pruned neighbour
+// instance -- seed, ring 1, ring 2 (dc_wide_prune.hpp) --, the bounds kernel in front of the second and the third, the
+// finish kernel behind them; the counters add up over the launches.
+int launch_nn_wide_pruned(const float* d_fe, uint32_t n_rows, uint32_t n_cols, size_t segment, size_t n_segments,
+                          uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t s) {
+  if (n_rows == 0 || n_segments == 0) return 0;
+  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
+  if (segment >= P.blocks) return 0;   // no block of the order: "none" everywhere (the caller's preset), no tile pair
+  char* p = (char*)d_ws;
+  const size_t off_range = P.off_cnt + sizeof(float) * (((size_t)n_rows + 1) & ~(size_t)1);
+  const size_t off_far2 = off_range + sizeof(float2) * P.blocks;
+  static_assert(sizeof(uint32_t) * kMaxRadiiPerLaunch >= 24, "one row: 8 bytes of free energies and 16 of its block fit the count region");
+  float* fe_o = (float*)(p + P.off_cnt);
+  float2* fe_range = (float2*)(p + off_range);
+  float* far2 = (float*)(p + off_far2);   // [2][blocks]: nn, hd
+  WideNnPrunedArgs X{};
+  static_cast<WideArgs&>(X) = wide_args(P.L, (const float*)(p + P.off_coords), n_rows, n_cols, 0, n_rows, d_ws);
+  X.fe = fe_o;
+  X.boxes = (const float4*)(p + P.off_boxes);
+  X.seg = (uint32_t)segment;
+  X.n_seg = (uint32_t)(n_segments < 0xFFFFFFFFull ? n_segments : 0xFFFFFFFFull);
+  X.perm = (const uint32_t*)(p + P.off_perm);
+  X.far2_nn = far2;
+  X.far2_hd = far2 + P.blocks;
+  X.fe_range = fe_range;
+  if (hipMemsetAsync(X.merge, 0xFF, sizeof(unsigned long long) * 2 * (size_t)n_rows, s) != hipSuccess) return -1;
+  hipLaunchKernelGGL(wide_nn_gather_kernel, dim3(P.blocks), dim3(128), 0, s, X.perm, d_fe, n_rows, fe_o, fe_range);
+  const uint32_t q_blocks = (uint32_t)((P.blocks - segment + n_segments - 1) / n_segments);
+  const dim3 grid(wide_grid_size(q_blocks, wide_shares(P.blocks)));
+  sweep_timer_mark(1, true, s);
+  for (uint32_t ring = kWideRingSeed; ring <= kWideRing2; ++ring) {
+    if (ring != kWideRingSeed)
+      hipLaunchKernelGGL(wide_nn_bounds_kernel, dim3(P.blocks), dim3(128), 0, s, (const unsigned long long*)X.merge, n_rows,
+                         ring - 1u, far2 + (size_t)(ring - 1u) * P.blocks);
+    X.ring = ring;
+    hipLaunchKernelGGL((wide_sweep_kernel<kWideNn, 1, kSelf, true>), grid, dim3(256), 0, s, X);
+  }
+  sweep_timer_mark(1, false, s);
+  hipLaunchKernelGGL(wide_nn_finish_pruned_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,
+                     (const unsigned long long*)X.merge, X.perm, n_rows, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // the counters of the last sweep back to zero: a further round in a prepared workspace reports its own

@@ -46,7 +46,9 @@ void launch_min_edge_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t 
 // boxes, the counts and the sort's scratch; 0 if the column count is not served or there are no rows; monotone in n_rows
 size_t wide_pruned_workspace_bytes(size_t n_rows, size_t n_cols);
 // statistics, order, gathered rows, boxes and images, on the stream, no host synchronisation; returns 0 on success
-int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t stream);
+// (d_fe: the neighbour call's free energies, a NaN among them flags the data like a non-finite row)
+int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t stream,
+                        const float* d_fe = nullptr);
 // the populations of the query blocks segment, segment + n_segments, ... of the order (n_segments >= 1) for up to
 // kMaxRadiiPerLaunch radii, WRITTEN to d_pops_first_row for every row (zeros for the rows of other blocks); stands down
 // on flagged data, scatter included (the gated direct kernel answers).  Returns 0 on success.
@@ -70,6 +72,14 @@ int launch_pairs_wide_pruned(uint32_t n_rows, uint32_t n_cols, float r2, uint32_
 int launch_min_edge_wide_pruned(uint32_t n_rows, uint32_t n_cols, float r2, const uint32_t* d_comp, const uint32_t* d_rank,
                                 size_t segment, size_t n_segments, unsigned long long* d_best, uint32_t* d_pops, void* d_ws,
                                 hipStream_t stream);
+// ---- the pruned self neighbour sweep (dc_hip_nearest_neighbors_wide_pruned_dev) ---------------------------
+// Behind wide_pruned_prepare(.., d_fe) in the same workspace: nn / nn_hd of the query blocks segment, segment + n_segments,
+// ... of the order (n_segments >= 1), WRITTEN to the rows of those blocks (outputs preset to "none" by the caller, where
+// the rows of other blocks stay); three pruned launches -- seed blocks, ring 1, ring 2 (dc_wide_prune.hpp) -- whose
+// counters add up; stands down on flagged data, finish included (the gated direct kernel answers).  Returns 0 on success.
+int launch_nn_wide_pruned(const float* d_fe, uint32_t n_rows, uint32_t n_cols, size_t segment, size_t n_segments,
+                          uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws,
+                          hipStream_t stream);
 // the three counters of the last sweep back to zero (a further round in a workspace that stays prepared)
 int wide_clear_counters(void* d_ws, hipStream_t stream);
 

@@ -49,6 +49,10 @@
 // taken on positions (each unordered pair still has exactly one meeting with i < j), the pair written is (perm[i],
 // perm[j]) -- each unordered pair once, in no order within the pair; comp and rank are read by position from arrays
 // gathered into the order once per call, their values and the index of best stay component ids and ranks.
+// The pruned neighbour sweep (dc_hip_nearest_neighbors_wide_pruned_dev) is the neighbour form on that order
+// in three launches -- the blocks next to the query block, the blocks within the bound of its nearest neighbours, the
+// blocks within the bound of its lower-free-energy neighbours that hold a lower row (dc_wide_prune.hpp) --, the later
+// ones starting from the merged words of the earlier; the words are placed by position and name rows.
 #pragma once
 #include "dc_mfma_kernels.hpp"
 #include "dc_mfma_wide.hpp"
@@ -160,6 +164,18 @@ __host__ __device__ inline float wide_cut(float m, const WideBand& b, float rati
 }
 __host__ __device__ inline float wide_cut_ratio(const WideBand& b) {
   return (1.0f + b.kappa) / (1.0f - b.kappa) * (1.0f + kWideRoundMargin);
+}
+
+// The pruned neighbour sweep: the running minimum a lane starts a later launch with, from the merged word
+// of the launches before (~0: nothing found -> +inf).  The word holds the canonical float sum d2_c of the row it names;
+// that row's real d2 <= d2_c / (1 - u)^(D+1) <= d2_c (1 + 1.6e-5) at D <= 256, and its accumulator is at most
+// S d2 (1 + kappa) + e0 by the band: m0 is that, rounded up.  Every reference whose canonical sum is <= d2_c has an
+// accumulator <= m0 <= cut(m0) as well, so all that could beat or tie the word are still raised.
+__device__ __forceinline__ float wide_nn_start(unsigned long long word, float S, const WideBand& b) {
+  if (word == ~0ull) return INFINITY;
+  const float d2c = __uint_as_float((uint32_t)(word >> 32));
+  const float m = ((S * d2c) * (1.0f + 2.0e-5f)) * (1.0f + b.kappa) + b.e0;
+  return m + fabsf(m) * kWideRoundMargin;
 }
 
 // ---- statistics, scale, images: the instances of dc_mfma.hip's passes for up to kWideMaxCols columns ------------------
@@ -471,6 +487,64 @@ __global__ __launch_bounds__(256) void wide_prune_gather_kernel(const uint32_t* 
   rank_o[p] = rank[i];
 }
 
+// the pruned neighbour sweep: the free energies by position, and per block of the order the least and the
+// largest of its live rows ((+inf, -inf) for a block without one); a workgroup of 128 threads per block
+__global__ __launch_bounds__(128) void wide_nn_gather_kernel(const uint32_t* __restrict__ perm, const float* __restrict__ fe,
+                                                             uint32_t n_rows, float* __restrict__ fe_o, float2* __restrict__ fe_range) {
+  static_assert(kWideBlockRows == 128, "two waves per block of the order");
+  __shared__ float2 part[2];
+  const uint32_t p = blockIdx.x * kWideBlockRows + threadIdx.x;
+  const bool live = p < n_rows;
+  const float f = live ? fe[perm[p]] : 0.0f;
+  if (live) fe_o[p] = f;
+  float lo = live ? f : INFINITY, hi = live ? f : -INFINITY;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, off, 64));
+    hi = fmaxf(hi, __shfl_xor(hi, off, 64));
+  }
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = make_float2(lo, hi);
+  __syncthreads();
+  if (threadIdx.x == 0) fe_range[blockIdx.x] = make_float2(fminf(part[0].x, part[1].x), fmaxf(part[0].y, part[1].y));
+}
+// ... between its launches: far2[qb] = wide_nn_far2(B), B the largest d2 in the words of the block's live positions,
+// +inf if one of them holds none (half: 0 the nn words, 1 the hd words); one thread per position, one result per block
+__global__ __launch_bounds__(128) void wide_nn_bounds_kernel(const unsigned long long* __restrict__ merge, uint32_t n_rows,
+                                                             uint32_t half, float* __restrict__ far2) {
+  __shared__ float part[2];
+  const uint32_t p = blockIdx.x * kWideBlockRows + threadIdx.x;
+  float b = 0.0f;   // (d2 >= 0; a dead position does not raise the bound)
+  if (p < n_rows) {
+    const unsigned long long w = merge[(size_t)half * n_rows + p];
+    b = (w == ~0ull) ? INFINITY : __uint_as_float((uint32_t)(w >> 32));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) b = fmaxf(b, __shfl_xor(b, off, 64));
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = b;
+  __syncthreads();
+  if (threadIdx.x == 0) far2[blockIdx.x] = wide_nn_far2(fmaxf(part[0], part[1]));
+}
+// ... and behind them: the words of position p to row perm[p] ("none", the caller's preset, stays where nothing was found
+// and on the rows of other segments); stands down with the sweep
+__global__ __launch_bounds__(256) void wide_nn_finish_pruned_kernel(const uint32_t* __restrict__ hdr, const unsigned long long* __restrict__ merge,
+                                                                    const uint32_t* __restrict__ perm, uint32_t n_rows,
+                                                                    uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2,
+                                                                    uint32_t* __restrict__ hd_idx, float* __restrict__ hd_d2) {
+  if (hdr[1] != 0) return;
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_rows) return;
+  const unsigned long long a = merge[p], b = merge[(size_t)n_rows + p];
+  const uint32_t j = perm[p];
+  if (a != ~0ull) {
+    nn_idx[j] = (uint32_t)a;
+    nn_d2[j] = __uint_as_float((uint32_t)(a >> 32));
+  }
+  if (b != ~0ull) {
+    hd_idx[j] = (uint32_t)b;
+    hd_d2[j] = __uint_as_float((uint32_t)(b >> 32));
+  }
+}
+
 // ... of a cross sweep: ONE origin and ONE scale over the queries and the reference together (column sums over both
 // sets, the mean over n_query + n_ref rows, header word 0 = the largest |x'|^2 of either set), then the A form and the
 // norms of the reference and the B form of the queries.  d_query == d_ref is an ordinary pair of sets.
@@ -551,10 +625,19 @@ struct WidePrunedArgs : WideArgs {
   float far2;             // wide_prune_far2 of the launch's largest fl32(r^2)
   // the graph instances: comp / rank are GATHERED into the order as well (their values stay component
   // ids and ranks, best stays indexed by component id); the pair list speaks of rows
-  const uint32_t* perm;   // kWidePairs: [n_rows] position -> row
+  const uint32_t* perm;   // kWidePairs, kWideNn: [n_rows] position -> row
 };
-template <bool PR>
-using WideKernelArgs = std::conditional_t<PR, WidePrunedArgs, WideArgs>;
+// the pruned neighbour instance: fe is GATHERED into the order, merge is indexed by the query's position
+// and names the reference's ROW; one launch per ring (dc_wide_prune.hpp), the bounds of a query block from the launches
+// before.  A struct of its own: the argument block of the other pruned instances stays what it was.
+struct WideNnPrunedArgs : WidePrunedArgs {
+  uint32_t ring;             // kWideRingSeed, kWideRing1, kWideRing2
+  const float* far2_nn;      // [blocks], read by rings 1 and 2
+  const float* far2_hd;      // [blocks], read by ring 2
+  const float2* fe_range;    // [blocks]: (least, largest) free energy of the block's live rows
+};
+template <bool PR, bool NN = false>
+using WideKernelArgs = std::conditional_t<PR, std::conditional_t<NN, WideNnPrunedArgs, WidePrunedArgs>, WideArgs>;
 
 // the deferred pairs of a wave, evaluated in the canonical order from the original coordinates, a pair per lane
 template <int MODE>
@@ -668,15 +751,37 @@ __device__ __attribute__((noinline)) void wide_pairs_drain_pruned(const uint2* q
   wide_graph_drain_body<kWidePairs>(queue, fill, coords, n_cols, qrow0, r2, pops, pairs, capacity, count, perm);
 }
 
+// ... of the pruned neighbour sweep: (i, j) are positions and so is the word's place, the reference it
+// names is the row perm[i] -- the contract's tie rule is the least (d2, ROW).  A function of its own for wide_drain's reason.
+__device__ __attribute__((noinline)) void wide_nn_drain_pruned(const uint2* queue, uint32_t fill, const float* coords,
+                                                               uint32_t n_rows, uint32_t n_cols, uint32_t qrow0,
+                                                               unsigned long long* merge, const uint32_t* perm) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t e = lane; e < fill; e += 64u) {
+    const uint2 en = queue[e];
+    const uint32_t i = en.x, j = qrow0 + (en.y & 127u), flags = en.y >> 8;
+    const float d2 = dist2_canon_rt(coords + (size_t)j * n_cols, 1, coords + (size_t)i * n_cols, 1, (int)n_cols);
+    const unsigned long long w = ((unsigned long long)__float_as_uint(d2) << 32) | perm[i];
+    if (flags & 1u) atomicMin(&merge[j], w);
+    if (flags & 2u) atomicMin(&merge[(size_t)n_rows + j], w);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
 // SM: kSelf -- queries and reference are the rows of one array: the diagonal pair leaves the sweep, populations get the
 // frame's own 1, a frame is not its own neighbour; kAgainst -- X.q_coords against X.coords: every pair counts.
 // PR: the pruned form.  A workgroup still owns (query block, share); it first scans the boxes of its share's blocks
 // y, y + Sy, ... against the box of its query block -- 64 per wave and step, a ballot each -- and compacts the survivors
 // (wide_prune_survives) into an LDS list, in rounds of kWideListCap blocks; the chunk sequence then runs over the list.
 // A round without a survivor runs no chunk and fetches nothing.
+// The pruned neighbour instance is launched once per ring; its survivors are the blocks of that ring
+// (wide_nn_ring), rings 1 and 2 start the running minima from the merged words, and the words name rows.
 template <int MODE, int NR, SweepMode SM = kSelf, bool PR = false>
-__global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X) {
-  static_assert(!PR || (wide_counts(MODE) && SM == kSelf), "the pruned form: self sweeps that count -- populations and the radius graph");
+__global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, MODE == kWideNn> X) {
+  static_assert(!PR || ((wide_counts(MODE) || MODE == kWideNn) && SM == kSelf), "the pruned form: self sweeps -- populations, the radius graph, neighbours");
   if (X.hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
   __shared__ uint32_t list_s[PR ? kWideListCap : 1];                  // pruned: the surviving reference blocks of a round
   __shared__ unsigned long long mask_s[PR ? kWideListCap / 64 : 1];   // ... and the ballots they are compacted from
@@ -744,6 +849,13 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X
     for (int qt = 0; qt < 2; ++qt) {
       m_nn[qt] = m_hd[qt] = INFINITY;
       feq[qt] = (live[qt] && has_fe) ? q_fe[jq[qt]] : -INFINITY;   // (a dead lane, nn only: no reference lies lower)
+      if constexpr (PR) {
+        // rings 1 and 2 start from the words of the launches before: a bound on the accumulator of the row a word names
+        if (X.ring != kWideRingSeed && live[qt]) {
+          m_nn[qt] = wide_nn_start(X.merge[jq[qt]], sc.s2, band);
+          m_hd[qt] = wide_nn_start(X.merge[(size_t)X.n_rows + jq[qt]], sc.s2, band);
+        }
+      }
     }
   }
   // min edge: component and rank of the lane's queries, the smallest rank met among their partners of another component
@@ -766,7 +878,9 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X
 
   // one pair per lane into the wave's queue (ok: this lane has one); drained before a push that might not fit
   auto drain = [&]() {
-    if constexpr (PR && MODE == kWidePairs)
+    if constexpr (PR && MODE == kWideNn)
+      wide_nn_drain_pruned(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.merge, X.perm);
+    else if constexpr (PR && MODE == kWidePairs)
       wide_pairs_drain_pruned(queue, fill, X.coords, D, qb * kWideBlockRows, X.rad2.v[0], X.pops, X.pairs, X.capacity, X.count,
                               X.perm);
     else if constexpr (MODE == kWidePairs)
@@ -828,6 +942,15 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X
     const float4 b = X.boxes[qb];
     qbox = WideBox{b.x, b.y, b.z, b.w};
   }
+  // the neighbour instance: the bounds of the query block (wave-uniform; a ring reads what the launches before it wrote)
+  float far2_nn = 0.0f, far2_hd = 0.0f, fe_max_q = 0.0f;
+  if constexpr (PR && MODE == kWideNn) {
+    if (X.ring >= kWideRing1) far2_nn = X.far2_nn[qb];
+    if (X.ring == kWideRing2) {
+      far2_hd = X.far2_hd[qb];
+      fe_max_q = X.fe_range[qb].y;
+    }
+  }
   uint32_t round0 = 0;
   do {
     uint32_t n_run = n_it;   // chunks of this round (unpruned: one round, every block of the share)
@@ -838,8 +961,15 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR> X
         const uint32_t e = ck * 64u + lane;
         bool ok = false;
         if (e < lim) {
-          const float4 b = X.boxes[y + (round0 + e) * Sy];
-          ok = wide_prune_survives(qbox, WideBox{b.x, b.y, b.z, b.w}, X.far2);
+          const uint32_t rb = y + (round0 + e) * Sy;
+          const float4 b = X.boxes[rb];
+          if constexpr (MODE == kWideNn) {
+            const float fe_min_r = (X.ring == kWideRing2) ? X.fe_range[rb].x : 0.0f;
+            ok = wide_nn_ring(wide_nn_is_seed(qb, rb), wide_box_gap2(qbox, WideBox{b.x, b.y, b.z, b.w}), far2_nn, far2_hd, fe_min_r,
+                              fe_max_q) == (int)X.ring;
+          } else {
+            ok = wide_prune_survives(qbox, WideBox{b.x, b.y, b.z, b.w}, X.far2);
+          }
         }
         const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
         if (lane == 0) mask_s[ck] = m;

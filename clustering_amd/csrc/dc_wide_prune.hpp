@@ -37,3 +37,29 @@ DC_PRUNE_FN float wide_prune_far2(float r2max) { return 1.0001f * r2max; }
 DC_PRUNE_FN bool wide_prune_survives(const WideBox& query, const WideBox& ref, float far2) {
   return wide_box_gap2(query, ref) < far2;
 }
+
+// ---- the rings of the pruned wide neighbour sweep --------------------------------------------------------
+// A query block meets its reference blocks in three launches, and the three sets partition the blocks it meets:
+//   seed    the blocks qb - 1, qb, qb + 1 of the order (those there are): no bound is known yet;
+//   ring 1  the other blocks with gap2 < far2_nn, the bound of the block's nearest neighbours after the seed;
+//   ring 2  the blocks of neither with gap2 < far2_hd, the bound of its nearest neighbours of lower free energy after
+//           ring 1, that hold a row of lower free energy than some query of the block: fe_min(ref) < fe_max(query);
+// every other block is never met.  The same stored far2_nn decides "not ring 1" and "ring 1", so whatever the bounds are --
+// +inf, 0, equal, far2_hd below far2_nn -- a block is in exactly one of the four classes.
+enum WideNnRing { kWideRingSeed = 0, kWideRing1 = 1, kWideRing2 = 2, kWideRingNever = 3 };
+
+DC_PRUNE_FN bool wide_nn_is_seed(unsigned query_block, unsigned ref_block) {
+  return (ref_block >= query_block ? ref_block - query_block : query_block - ref_block) <= 1u;
+}
+
+// B: the largest exact d2 among the block's live rows so far (+inf: a row has none).  1.0001 as wide_prune_far2; below
+// the smallest normal float the relative bounds of the proof do not hold, so the bound never falls below it (B = 0, a
+// block of duplicates, keeps the blocks at gap 0: a duplicate of a lower row may sit in any of them)
+DC_PRUNE_FN float wide_nn_far2(float B) { return 1.0001f * fmaxf(B, 1.17549435e-38f); }
+
+DC_PRUNE_FN int wide_nn_ring(bool seed, float gap2, float far2_nn, float far2_hd, float fe_min_ref, float fe_max_query) {
+  if (seed) return kWideRingSeed;
+  if (gap2 < far2_nn) return kWideRing1;
+  if (gap2 < far2_hd && fe_min_ref < fe_max_query) return kWideRing2;
+  return kWideRingNever;
+}

@@ -322,6 +322,29 @@ def calculate_populations_wide_pruned(coords, radii, segment=0, n_segments=0, ou
     return out
 
 
+def nearest_neighbors_wide_pruned(coords, fe, segment=0, n_segments=0):
+    """nearest_neighbors_wide in the spatial order of the pruned wide sweeps, searching outward and stopping
+    (dc_hip_nearest_neighbors_wide_pruned_dev): the same four arrays bit for bit.  n_segments == 0: the whole sweep
+    (segment is not read); otherwise the query blocks segment, segment + n_segments, ... of the order
+    (wide_pruned_order): final results on their rows, "none" elsewhere.  In the cached workspace of the pruned wide
+    sweeps (wide_pruned_info reads its counters, wide_pruned_order its order)."""
+    n_rows, n_cols = _check_coords(coords)
+    assert fe.is_cuda and fe.dtype == torch.float32 and fe.shape == (n_rows,) and fe.is_contiguous()
+    dev = coords.device
+    nn_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    hd_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    nn_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    hd_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _wide_pruned_workspace(dev).get(n_rows, n_cols, 1)
+        rc = capi.lib.dc_hip_nearest_neighbors_wide_pruned_dev(
+            _dev(coords), n_rows, n_cols, _dev(fe), segment, n_segments, _dev(nn_idx), _dev(nn_d2), _dev(hd_idx), _dev(hd_d2),
+            ws, ws_bytes, _stream_ptr())
+    capi.check(rc, "dc_hip_nearest_neighbors_wide_pruned_dev")
+    _wide_pruned_shapes[str(dev)] = (n_rows, n_cols)
+    return nn_idx, nn_d2, hd_idx, hd_d2
+
+
 def wide_pruned_info(device):
     """(tiles, mfmas, exact_pairs) of the last calculate_populations_wide_pruned on this device, as wide_sweep_info
     gives them; the tile pairs are the evaluated ones.  (0, 0, 0) when the direct kernel answered (flagged data), the

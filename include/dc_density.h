@@ -441,6 +441,28 @@ DC_API int dc_hip_populations_wide_pruned_dev(const float* d_coords, size_t n_ro
                                               size_t n_radii, size_t segment, size_t n_segments, uint32_t* d_pops,
                                               void* d_ws, size_t ws_bytes, void* stream);
 DC_API int dc_hip_wide_pruned_order_dev(const void* d_ws, size_t n_rows, size_t n_cols, uint32_t* d_perm, void* stream);
+/* ---- ... the PRUNED wide self neighbour sweep (65..256 columns) ------------------------------------------------------------
+ * dc_hip_nearest_neighbors_wide_dev's four outputs bit for bit -- indices, d2 bits, "none" = (n_rows + 1, FLT_MAX); ties
+ * go to the lowest ROW -- in the spatial order and the workspace of dc_hip_populations_wide_pruned_dev
+ * (dc_hip_wide_pruned_workspace_bytes(n_rows, n_cols, 1)), as the reference's CPU path and the sweeps below 65 columns
+ * search outward and stop: a query block of 128 positions first meets the blocks next to it in the order, then the
+ * blocks whose box lies within 1.0001 x the largest nn_d2 its rows have found, then those within 1.0001 x the largest
+ * hd_d2 that hold a row of lower free energy than one of its own.  Entry point of its own; no dc_variant value selects it.
+ * Outputs fully overwritten.  n_segments == 0: the whole sweep (`segment` is not read).  n_segments > 0: rank `segment`
+ * sweeps every n_segments-th query block of the order, the partition dc_hip_populations_wide_pruned_dev uses; the rows
+ * of other blocks hold "none", so partial results merge by the per-row minimum of (d2 bits << 32 | index) (the contract
+ * of dc_hip_nearest_neighbors_segment_dev); a segment without a block gives "none" everywhere.  Flagged data (a
+ * non-finite or overflow-prone row, a NaN free energy, as for dc_hip_nearest_neighbors_wide_dev): the direct kernel
+ * answers behind the device-side gate, for a segment on the row block dc_hip_nearest_neighbors_segment_dev uses at these
+ * widths; the counters read (0, 0, 0).  dc_hip_wide_info_dev reads the counters of the call (the EVALUATED tile pairs,
+ * summed over its launches), dc_hip_wide_pruned_order_dev its order.
+ * Errors, all before a device is touched: segment >= n_segments > 0 and n_cols outside 65..256:
+ * DC_ERR_INVALID_ARGUMENT; a workspace smaller than dc_hip_wide_pruned_workspace_bytes (or none): DC_ERR_WORKSPACE;
+ * sizes: DC_ERR_TOO_LARGE as above; n_rows == 0: DC_OK. */
+DC_API int dc_hip_nearest_neighbors_wide_pruned_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* d_fe,
+                                                    size_t segment, size_t n_segments, uint32_t* d_nn_idx, float* d_nn_d2,
+                                                    uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
+                                                    void* stream);
 /* ---- ... and their cross form: query frames against a reference trajectory at 65..256 columns ------------------------
  * The wide sweep over a rectangle Q x R: the contract of the "cross sweeps" block above -- populations without a self
  * term, nn[q] the lexicographic minimum of (d2, j) over ALL j with no exclusion, nn_hd[q] the same over
