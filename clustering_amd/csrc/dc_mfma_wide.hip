@@ -173,11 +173,11 @@ int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols,
   hipLaunchKernelGGL(wide_extent_kernel, dim3((uint32_t)min_sz(1024, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s, d_coords,
                      n_rows, n_cols, hdr);
   hipLaunchKernelGGL(wide_prune_key_kernel, dim3((uint32_t)min_sz(4096, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s, d_coords,
-                     n_rows, n_cols, (const uint32_t*)hdr, keys, vals);
+                     n_rows, n_cols, (const uint32_t*)hdr, keys, vals, n_rows, 0u);
   if (sort_pairs_u32(keys, (uint32_t*)(p + P.off_keys_o), vals, perm, n_rows, p + P.off_sort, P.sort_bytes, s, kCellKeyBits) != 0)
     return -1;
   hipLaunchKernelGGL(wide_prune_rows_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, d_coords, n_rows, n_cols,
-                     (const uint32_t*)perm, P.blocks, coords_o, (float4*)(p + P.off_boxes), hdr);
+                     (const uint32_t*)perm, P.blocks, coords_o, (float4*)(p + P.off_boxes), hdr + kWideHdrOrder, kWideOrderMark);
   return wide_image_launches(coords_o, n_rows, n_cols, d_ws, s);
 }
 
@@ -210,7 +210,7 @@ int wide_pruned_args(const WidePrunedLayout& P, uint32_t n_rows, uint32_t n_cols
 int wide_pruned_scatter(const WidePrunedLayout& P, uint32_t n_rows, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
   char* p = (char*)d_ws;
   hipLaunchKernelGGL(wide_prune_scatter_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,
-                     (const uint32_t*)(p + P.off_perm), (const uint32_t*)(p + P.off_cnt), n_rows, n_rad, d_pops_first_row);
+                     (const uint32_t*)(p + P.off_perm), (const uint32_t*)(p + P.off_cnt), n_rows, n_rad, d_pops_first_row, n_rows);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace
@@ -359,6 +359,133 @@ int launch_nn_wide_against(const float* d_query, uint32_t n_query, const float* 
   X.q_fe = d_fe_query;
   X.fe = d_fe_query ? d_fe_ref : nullptr;
   return nn_wide<kAgainst>(X, n_query, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, s);
+}
+
+// ---- the pruned cross population sweep (dc_hip_populations_cross_wide_pruned_dev) -------------------------
+namespace {
+struct WideCrossPrunedLayout {
+  WideLayout L;                  // the head: what the unpruned cross sweeps lay out for n_query x n_ref
+  uint32_t blocks_r, blocks_q;   // blocks of kWideBlockRows positions: the reference's, the whole query array's
+  size_t off_perm_r, off_perm_q, off_keys, off_keys_o, off_vals, off_coords_r, off_coords_q, off_boxes_r, off_boxes_q, off_cnt,
+      off_sort, sort_bytes, total;
+};
+WideCrossPrunedLayout wide_cross_pruned_layout(size_t n_query, size_t n_ref, size_t n_cols) {
+  WideCrossPrunedLayout P;
+  P.L = wide_layout_against(n_query, n_ref, n_cols);
+  P.blocks_r = P.L.Tp / kWideBlockTiles;
+  P.blocks_q = P.L.Tqp / kWideBlockTiles;
+  const size_t n_max = n_query > n_ref ? n_query : n_ref;
+  const size_t words_r = align256(sizeof(uint32_t) * n_ref), words_q = align256(sizeof(uint32_t) * n_query);
+  const size_t words = align256(sizeof(uint32_t) * n_max);
+  P.off_perm_r = P.L.total;                 // [n_ref] position -> row of the reference
+  P.off_perm_q = P.off_perm_r + words_r;    // [i_to - i_from] position -> row of the query array
+  P.off_keys = P.off_perm_q + words_q;      // keys and values of one sort: the reference's, then the query range's
+  P.off_keys_o = P.off_keys + words;
+  P.off_vals = P.off_keys_o + words;
+  P.off_coords_r = P.off_vals + words;      // [n_ref][n_cols] the reference in its order
+  P.off_coords_q = align256(P.off_coords_r + sizeof(float) * n_ref * n_cols);   // [i_to - i_from][n_cols] the queries in theirs
+  P.off_boxes_r = align256(P.off_coords_q + sizeof(float) * n_query * n_cols);
+  P.off_boxes_q = align256(P.off_boxes_r + sizeof(float4) * P.blocks_r);
+  P.off_cnt = align256(P.off_boxes_q + sizeof(float4) * P.blocks_q);   // [kMaxRadiiPerLaunch][i_to - i_from] counts by query position
+  P.off_sort = align256(P.off_cnt + sizeof(uint32_t) * kMaxRadiiPerLaunch * n_query);
+  P.sort_bytes = sort_temp_bytes(n_max);
+  P.total = align256(P.off_sort + P.sort_bytes);
+  return P;
+}
+}  // namespace
+
+size_t wide_cross_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols) {
+  if (!wide_mfma_supports(n_cols) || n_query == 0 || n_ref == 0) return 0;
+  return wide_cross_pruned_layout(n_query, n_ref, n_cols).total;
+}
+
+int wide_cross_pruned_prepare(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                              uint32_t i_from, uint32_t i_to, void* d_ws, hipStream_t s) {
+  const WideCrossPrunedLayout P = wide_cross_pruned_layout(n_query, n_ref, n_cols);
+  const uint32_t n_q = i_to - i_from;
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  uint32_t* keys = (uint32_t*)(p + P.off_keys);
+  uint32_t* keys_o = (uint32_t*)(p + P.off_keys_o);
+  uint32_t* vals = (uint32_t*)(p + P.off_vals);
+  const float* q_range = d_query + (size_t)i_from * n_cols;
+  // one origin, one scale, M over every row of both arrays: the statistics of the unpruned cross sweep
+  if (wide_stats_against_launches(d_query, n_query, d_ref, n_ref, n_cols, d_ws, s) != 0) return -1;
+  if (hipMemsetD32Async((hipDeviceptr_t)(hdr + kWideHdrOrderLaidOut), (int)n_query, 1, s) != hipSuccess) return -1;
+  // one grid for both sets: the extent of the query range and the reference together, the cell from the reference's count
+  struct Side {
+    const float* rows;      // the first row a position can name ...
+    uint32_t n, row0;       // ... how many there are, and the number of the first in its array
+    const float* array;     // the array perm's rows index
+    size_t off_perm, off_coords, off_boxes;
+    uint32_t sign, mark;
+  } const sides[2] = {{d_ref, n_ref, 0u, d_ref, P.off_perm_r, P.off_coords_r, P.off_boxes_r, kWideHdrOrderRef, kWideOrderMarkRef},
+                      {q_range, n_q, i_from, d_query, P.off_perm_q, P.off_coords_q, P.off_boxes_q, kWideHdrOrderQuery, kWideOrderMarkQuery}};
+  for (const Side& side : sides)
+    hipLaunchKernelGGL(wide_extent_kernel, dim3((uint32_t)min_sz(1024, ((size_t)side.n + 255) / 256)), dim3(256), 0, s, side.rows,
+                       side.n, n_cols, hdr);
+  for (const Side& side : sides) {
+    uint32_t* perm = (uint32_t*)(p + side.off_perm);
+    hipLaunchKernelGGL(wide_prune_key_kernel, dim3((uint32_t)min_sz(4096, ((size_t)side.n + 255) / 256)), dim3(256), 0, s, side.rows,
+                       side.n, n_cols, (const uint32_t*)hdr, keys, vals, n_ref, side.row0);
+    if (sort_pairs_u32(keys, keys_o, vals, perm, side.n, p + P.off_sort, P.sort_bytes, s, kCellKeyBits) != 0) return -1;
+    hipLaunchKernelGGL(wide_prune_rows_kernel, dim3((side.n + 255u) / 256u), dim3(256), 0, s, side.array, side.n, n_cols,
+                       (const uint32_t*)perm, (side.n + kWideBlockRows - 1u) / kWideBlockRows, (float*)(p + side.off_coords),
+                       (float4*)(p + side.off_boxes), hdr + side.sign, side.mark);
+  }
+  return wide_image_against_launches(P.L, (const float*)(p + P.off_coords_q), n_q, (const float*)(p + P.off_coords_r), n_ref,
+                                     n_cols, d_ws, s);
+}
+
+int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                                 const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
+  if (i_from >= i_to || n_rad <= 0 || n_ref == 0) return 0;
+  const WideCrossPrunedLayout P = wide_cross_pruned_layout(n_query, n_ref, n_cols);
+  const uint32_t n_q = i_to - i_from;
+  char* p = (char*)d_ws;
+  uint32_t* cnt = (uint32_t*)(p + P.off_cnt);
+  if (hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (size_t)n_rad * n_q, s) != hipSuccess) return -1;
+  WideCrossPrunedArgs X{};
+  static_cast<WideArgs&>(X) = wide_args(P.L, (const float*)(p + P.off_coords_r), n_ref, n_cols, 0, n_q, d_ws,
+                                        (const float*)(p + P.off_coords_q), n_q);
+  X.rad2 = rad2;
+  X.n_rad = n_rad;
+  X.pops = cnt;
+  X.boxes = (const float4*)(p + P.off_boxes_r);
+  X.qboxes = (const float4*)(p + P.off_boxes_q);
+  X.seg = 0;
+  X.n_seg = 1;
+  float r2max = 0.0f;
+  for (int k = 0; k < n_rad; ++k) r2max = rad2.v[k] > r2max ? rad2.v[k] : r2max;
+  X.far2 = wide_prune_far2(r2max);
+  const dim3 grid(wide_grid_size((n_q + kWideBlockRows - 1u) / kWideBlockRows, wide_shares(P.blocks_r)));
+  sweep_timer_mark(0, true, s);
+  if (n_rad == 1)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, kAgainst, true>), grid, dim3(256), 0, s, X);
+  else if (n_rad <= 4)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 4, kAgainst, true>), grid, dim3(256), 0, s, X);
+  else
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, kAgainst, true>), grid, dim3(256), 0, s, X);
+  sweep_timer_mark(0, false, s);
+  hipLaunchKernelGGL(wide_prune_scatter_kernel, dim3((n_q + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,
+                     (const uint32_t*)(p + P.off_perm_q), (const uint32_t*)cnt, n_q, n_rad, d_pops_first_row, n_query);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n_ref, uint32_t n_cols, uint32_t* d_perm_q,
+                            uint32_t* d_perm_r, hipStream_t s) {
+  uint32_t tag[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  static_assert(kWideHdrOrderQuery == kWideHdrOrderRef + 3 && kWideHdrOrderLaidOut == kWideHdrOrderRef + 6, "seven words side by side");
+  if (hipMemcpyAsync(tag, (const char*)d_ws + 4 * kWideHdrOrderRef, sizeof(tag), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
+  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  if (tag[0] != kWideOrderMarkRef || tag[1] != n_ref || tag[2] != n_cols || tag[3] != kWideOrderMarkQuery ||
+      tag[4] != n_query_range || tag[5] != n_cols || tag[6] < n_query_range)
+    return 1;
+  const WideCrossPrunedLayout P = wide_cross_pruned_layout(tag[6], n_ref, n_cols);
+  if (hipMemcpyAsync(d_perm_q, (const char*)d_ws + P.off_perm_q, sizeof(uint32_t) * (size_t)n_query_range, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(d_perm_r, (const char*)d_ws + P.off_perm_r, sizeof(uint32_t) * (size_t)n_ref, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return -1;
+  return 0;
 }
 
 }  // namespace dc

@@ -99,4 +99,27 @@ int launch_nn_wide_against(const float* d_query, uint32_t n_query, const float* 
                            const float* d_fe_query, const float* d_fe_ref, uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx,
                            float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t stream);
 
+// ---- the pruned cross population sweep (dc_hip_populations_cross_wide_pruned_dev) -------------------------
+// The statistics of the cross form (one origin, one scale over both arrays), then ONE cell grid on columns 0 / 1 over the
+// query range and the reference together, its cell sized by the reference's row count; the reference and the query range
+// each sorted by those keys, gathered, boxed per block of 128 positions and imaged (A form and norms: reference, B form:
+// queries).  A workgroup owns (block of the query order, reference share), scans the reference's boxes against its query
+// box and runs the chains of the survivors; counts by query position, scattered to the rows behind the sweep.
+// bytes: the workspace of the unpruned cross sweeps at its head, then both orders, the sort's keys, both gathered sets, both
+// sets of boxes, the counts and the sort's scratch; 0 if the column count is not served or either set is empty; monotone
+// in either row count
+size_t wide_cross_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols);
+// on the stream, no host synchronisation; i_from < i_to <= n_query, n_ref > 0; returns 0 on success
+int wide_cross_pruned_prepare(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
+                              uint32_t i_from, uint32_t i_to, void* d_ws, hipStream_t stream);
+// the populations of the queries [i_from, i_to) -- the range the workspace was prepared for -- for up to kMaxRadiiPerLaunch
+// radii, WRITTEN to those rows of d_pops_first_row ([n_rad][n_query]; the other rows are the caller's); stands down on
+// flagged data, scatter included (the gated direct kernel answers).  Returns 0 on success.
+int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                                 const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t stream);
+// both orders the workspace holds, position -> row, copied to d_perm_q ([n_query_range], rows of the query array) and
+// d_perm_r ([n_ref]); 0 ok, 1 the workspace holds no cross order of that shape, -1 a HIP error (synchronises)
+int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n_ref, uint32_t n_cols, uint32_t* d_perm_q,
+                            uint32_t* d_perm_r, hipStream_t stream);
+
 }  // namespace dc

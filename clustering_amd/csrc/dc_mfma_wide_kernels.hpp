@@ -53,6 +53,9 @@
 // in three launches -- the blocks next to the query block, the blocks within the bound of its nearest neighbours, the
 // blocks within the bound of its lower-free-energy neighbours that hold a lower row (dc_wide_prune.hpp) --, the later
 // ones starting from the merged words of the earlier; the words are placed by position and name rows.
+// The pruned cross population sweep (dc_hip_populations_cross_wide_pruned_dev) is the pruned population
+// sweep over a rectangle: the query range and the reference each in an order of its own on ONE cell grid, a set of boxes
+// each; the kernel works in positions of the two orders, the scatter behind it writes rows of the query array.
 #pragma once
 #include "dc_mfma_kernels.hpp"
 #include "dc_mfma_wide.hpp"
@@ -79,6 +82,12 @@ static_assert(kWideHdrTiles > kHdrShift && kWideHdrTiles > kHdrScale + 4 && kWid
 // (words 8..11 of the 64-column header, here clear of the counters), and what order the workspace holds: mark, rows, columns
 constexpr uint32_t kWideHdrExt = 48, kWideHdrOrder = 52, kWideOrderMark = 0x57504F52u;
 static_assert(kWideHdrExt >= kWideHdrExact + 2 && 4 * (kWideHdrOrder + 3) <= kWideInfoBytes, "the pruned sweep's words: behind the counters, inside the info head");
+// ... and of the pruned cross sweep, words of their own: a self order never passes as a cross order, nor
+// the reverse (a preparation clears the whole header).  The reference's order: mark, rows, columns; behind it the
+// order of the query range: mark, rows of the range, columns; then the rows of the query array the workspace is laid out for
+constexpr uint32_t kWideHdrOrderRef = 56, kWideHdrOrderQuery = 59, kWideHdrOrderLaidOut = 62;
+constexpr uint32_t kWideOrderMarkRef = 0x57585052u, kWideOrderMarkQuery = 0x57585051u;
+static_assert(kWideHdrOrderRef >= kWideHdrOrder + 3 && 4 * (kWideHdrOrderLaidOut + 1) <= kWideInfoBytes, "the cross order's words: behind the self order's, inside the info head");
 constexpr float kWidePruneCellFrames = (float)kWideBlockRows;   // frames per cell of the order's grid: one block's worth
 constexpr uint32_t kWideListCap = 1024;   // surviving reference blocks a workgroup lists per scan round (4 KiB of LDS)
 static_assert(kWideListCap % 256 == 0, "a round: whole chunks of 64 boxes for each of the four waves");
@@ -406,11 +415,12 @@ __device__ __forceinline__ WidePruneGrid wide_prune_grid(const uint32_t* __restr
   return g;
 }
 // cell key and value of every row (against_key_kernel's arithmetic: the cells numbered column by column, every other
-// column downwards, key 0 for a non-finite row)
+// column downwards, key 0 for a non-finite row).  n_grid: the rows the cell edge is sized for (a self sweep: n_rows; the
+// cross sweep: the reference's, for both sets); row0: the number of coords' first row (the value of row i is row0 + i)
 __global__ __launch_bounds__(256) void wide_prune_key_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D,
                                                              const uint32_t* __restrict__ hdr, uint32_t* __restrict__ keys,
-                                                             uint32_t* __restrict__ vals) {
-  const WidePruneGrid g = wide_prune_grid(hdr, n_rows);
+                                                             uint32_t* __restrict__ vals, uint32_t n_grid, uint32_t row0) {
+  const WidePruneGrid g = wide_prune_grid(hdr, n_grid);
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_rows; i += gridDim.x * 256u) {
     const float x = coords[(size_t)i * D], y = coords[(size_t)i * D + 1];
     uint32_t key = 0;
@@ -420,15 +430,16 @@ __global__ __launch_bounds__(256) void wide_prune_key_kernel(const float* __rest
       key = bx * g.ny + ((bx & 1u) ? g.ny - 1u - by : by);
     }
     keys[i] = key;
-    vals[i] = i;
+    vals[i] = row0 + i;
   }
 }
 // The rows gathered into the order (coords_o: [n_rows][D]) and the box of every block of kWideBlockRows positions in the
-// (col 0, col 1) plane, from the original floats of its live rows; a workgroup takes two blocks.  Thread 0 signs the order.
+// (col 0, col 1) plane, from the original floats of its live rows; a workgroup takes two blocks.  Thread 0 signs the order
+// in the three header words at `sign`: mark, rows, columns.  (n_rows: the positions; perm may name rows of a longer array.)
 __global__ __launch_bounds__(256) void wide_prune_rows_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D,
                                                               const uint32_t* __restrict__ perm, uint32_t n_blocks,
                                                               float* __restrict__ coords_o, float4* __restrict__ boxes,
-                                                              uint32_t* __restrict__ hdr) {
+                                                              uint32_t* __restrict__ sign, uint32_t mark) {
   static_assert(kWideBlockRows == 128, "two waves per block of the order");
   __shared__ uint32_t s_frame[256];
   __shared__ float4 part[4];
@@ -461,20 +472,21 @@ __global__ __launch_bounds__(256) void wide_prune_rows_kernel(const float* __res
     boxes[2u * blockIdx.x + threadIdx.x] = make_float4(fminf(a.x, b.x), fmaxf(a.y, b.y), fminf(a.z, b.z), fmaxf(a.w, b.w));
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    hdr[kWideHdrOrder] = kWideOrderMark;
-    hdr[kWideHdrOrder + 1] = n_rows;
-    hdr[kWideHdrOrder + 2] = D;
+    sign[0] = mark;
+    sign[1] = n_rows;
+    sign[2] = D;
   }
 }
-// counts by position -> populations by row: pops[k][perm[p]] = cnt[k][p]; stands down with the sweep
+// counts by position -> populations by row: pops[k][perm[p]] = cnt[k][p]; stands down with the sweep.  pop_stride: the rows
+// of a radius in pops (a self sweep: n_rows; the cross sweep: the whole query array, of which the positions are a range)
 __global__ __launch_bounds__(256) void wide_prune_scatter_kernel(const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ perm,
                                                                  const uint32_t* __restrict__ cnt, uint32_t n_rows, int n_rad,
-                                                                 uint32_t* __restrict__ pops) {
+                                                                 uint32_t* __restrict__ pops, uint32_t pop_stride) {
   if (hdr[1] != 0) return;
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
   if (p >= n_rows) return;
   const uint32_t i = perm[p];
-  for (int k = 0; k < n_rad; ++k) pops[(size_t)k * n_rows + i] = cnt[(size_t)k * n_rows + p];
+  for (int k = 0; k < n_rad; ++k) pops[(size_t)k * pop_stride + i] = cnt[(size_t)k * n_rows + p];
 }
 // the pruned min-edge round: component and rank of every row, by position (the values stay component ids and ranks)
 __global__ __launch_bounds__(256) void wide_prune_gather_kernel(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ comp,
@@ -548,9 +560,9 @@ __global__ __launch_bounds__(256) void wide_nn_finish_pruned_kernel(const uint32
 // ... of a cross sweep: ONE origin and ONE scale over the queries and the reference together (column sums over both
 // sets, the mean over n_query + n_ref rows, header word 0 = the largest |x'|^2 of either set), then the A form and the
 // norms of the reference and the B form of the queries.  d_query == d_ref is an ordinary pair of sets.
-inline int wide_prepare_against_launches(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref,
-                                         uint32_t n_cols, void* d_ws, hipStream_t s) {
-  const WideLayout L = wide_layout_against(n_query, n_ref, n_cols);
+// ... its first half: header reset, statistics, scale
+inline int wide_stats_against_launches(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref,
+                                       uint32_t n_cols, void* d_ws, hipStream_t s) {
   char* p = (char*)d_ws;
   uint32_t* hdr = (uint32_t*)p;
   double* sums = (double*)(p + kWideOffSums);
@@ -570,14 +582,26 @@ inline int wide_prepare_against_launches(const float* d_query, uint32_t n_query,
     hipLaunchKernelGGL(wide_rowstats_kernel, dim3((uint32_t)min_sz(4096, ((size_t)side.n + 3) / 4)), dim3(256), 0, s, side.x,
                        side.n, n_cols, (const float*)means, hdr);
   hipLaunchKernelGGL(wide_scale_kernel, dim3(1), dim3(1), 0, s, hdr);
-  const size_t frags_r = (size_t)L.Tp * L.NM * 64, frags_q = (size_t)L.Tqp * L.NM * 64;
-  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags_r + 255) / 256)), dim3(256), 0, s, d_ref, n_ref, n_cols, L.NM,
-                     L.Tp, (const float*)means, (const uint32_t*)hdr, (uint4*)(p + L.off_img_a), (uint4*)nullptr,
-                     (float*)(p + L.off_norms));
-  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags_q + 255) / 256)), dim3(256), 0, s, d_query, n_query, n_cols, L.NM,
-                     L.Tqp, (const float*)means, (const uint32_t*)hdr, (uint4*)nullptr, (uint4*)(p + L.off_img_b),
-                     (float*)nullptr);
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// ... and its second, in a workspace laid out by L: the A form and the norms of the n_ref rows of d_ref, the B form of the
+// n_query rows of d_query (the pruned cross sweep: both gathered into their orders, the queries a range of the array L is for)
+inline int wide_image_against_launches(const WideLayout& L, const float* d_query, uint32_t n_query, const float* d_ref,
+                                       uint32_t n_ref, uint32_t n_cols, void* d_ws, hipStream_t s) {
+  char* p = (char*)d_ws;
+  const float* means = (const float*)(p + kWideOffMeans);
+  const uint32_t Tqp = wide_pad_tiles((n_query + 31u) / 32u);
+  const size_t frags_r = (size_t)L.Tp * L.NM * 64, frags_q = (size_t)Tqp * L.NM * 64;
+  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags_r + 255) / 256)), dim3(256), 0, s, d_ref, n_ref, n_cols, L.NM,
+                     L.Tp, means, (const uint32_t*)p, (uint4*)(p + L.off_img_a), (uint4*)nullptr, (float*)(p + L.off_norms));
+  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags_q + 255) / 256)), dim3(256), 0, s, d_query, n_query, n_cols, L.NM,
+                     Tqp, means, (const uint32_t*)p, (uint4*)nullptr, (uint4*)(p + L.off_img_b), (float*)nullptr);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+inline int wide_prepare_against_launches(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref,
+                                         uint32_t n_cols, void* d_ws, hipStream_t s) {
+  if (wide_stats_against_launches(d_query, n_query, d_ref, n_ref, n_cols, d_ws, s) != 0) return -1;
+  return wide_image_against_launches(wide_layout_against(n_query, n_ref, n_cols), d_query, n_query, d_ref, n_ref, n_cols, d_ws, s);
 }
 
 // ---- the sweep ------------------------------------------------------------------------------------------------------
@@ -636,8 +660,14 @@ struct WideNnPrunedArgs : WidePrunedArgs {
   const float* far2_hd;      // [blocks], read by ring 2
   const float2* fe_range;    // [blocks]: (least, largest) free energy of the block's live rows
 };
-template <bool PR, bool NN = false>
-using WideKernelArgs = std::conditional_t<PR, std::conditional_t<NN, WideNnPrunedArgs, WidePrunedArgs>, WideArgs>;
+// the pruned cross population instances: coords / img_a / norms / boxes are the REFERENCE gathered into its
+// order, q_coords / img_b the query range gathered into its own, n_query the rows of that range, i_from / i_to = 0 / n_query;
+// pops counts by query position.  A struct of its own, for the same reason.
+struct WideCrossPrunedArgs : WidePrunedArgs {
+  const float4* qboxes;      // [query blocks]: the box of every block of kWideBlockRows positions of the query order
+};
+template <bool PR, bool NN = false, bool CROSS = false>
+using WideKernelArgs = std::conditional_t<PR, std::conditional_t<NN, WideNnPrunedArgs, std::conditional_t<CROSS, WideCrossPrunedArgs, WidePrunedArgs>>, WideArgs>;
 
 // the deferred pairs of a wave, evaluated in the canonical order from the original coordinates, a pair per lane
 template <int MODE>
@@ -779,9 +809,14 @@ __device__ __attribute__((noinline)) void wide_nn_drain_pruned(const uint2* queu
 // A round without a survivor runs no chunk and fetches nothing.
 // The pruned neighbour instance is launched once per ring; its survivors are the blocks of that ring
 // (wide_nn_ring), rings 1 and 2 start the running minima from the merged words, and the words name rows.
+// The pruned cross population instances: two orders, two sets of boxes.  The query block is a block of
+// the QUERY order (its count bounds it, its box comes from X.qboxes), the scanned boxes and the listed blocks are the
+// reference's; rows, live[] and the drain speak of positions of the gathered query range [0, n_query) against positions
+// of the gathered reference, as the unpruned cross form speaks of rows; there is no segment.
 template <int MODE, int NR, SweepMode SM = kSelf, bool PR = false>
-__global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, MODE == kWideNn> X) {
-  static_assert(!PR || ((wide_counts(MODE) || MODE == kWideNn) && SM == kSelf), "the pruned form: self sweeps -- populations, the radius graph, neighbours");
+__global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, MODE == kWideNn, PR && SM == kAgainst> X) {
+  static_assert(!PR || ((wide_counts(MODE) || MODE == kWideNn) && SM == kSelf) || (MODE == kWidePop && SM == kAgainst && (NR == 1 || NR == 4 || NR == kMaxRadiiPerLaunch)),
+                "the pruned form: self sweeps -- populations, the radius graph, neighbours -- and the cross population sweep");
   if (X.hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
   __shared__ uint32_t list_s[PR ? kWideListCap : 1];                  // pruned: the surviving reference blocks of a round
   __shared__ unsigned long long mask_s[PR ? kWideListCap / 64 : 1];   // ... and the ballots they are compacted from
@@ -802,7 +837,9 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
   const uint32_t RB = X.Tp / kWideBlockTiles, Sy = wide_shares(RB);
   const WideUnit unit = wide_unit(blockIdx.x, Sy);
   uint32_t qb_of_unit = X.i_from / kWideBlockRows + unit.q_block;
-  if constexpr (PR) {   // every n_seg-th block of the order (64 bits: n_seg is any number)
+  // (the pruned cross form: i_from = 0, so this is the unit's block of the query order, bounded below by that order's
+  //  length -- the reference's block count RB says nothing about it)
+  if constexpr (PR && SM == kSelf) {   // every n_seg-th block of the order (64 bits: n_seg is any number)
     const unsigned long long q = X.seg + (unsigned long long)unit.q_block * X.n_seg;
     if (q >= RB) return;
     qb_of_unit = (uint32_t)q;
@@ -938,7 +975,10 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
   f32x16 acc[2][2];
   uint32_t n_eval = PR ? 0u : nblk;   // reference blocks this workgroup evaluates
   WideBox qbox{};
-  if constexpr (PR) {
+  if constexpr (PR && SM == kAgainst) {
+    const float4 b = X.qboxes[qb];
+    qbox = WideBox{b.x, b.y, b.z, b.w};
+  } else if constexpr (PR) {
     const float4 b = X.boxes[qb];
     qbox = WideBox{b.x, b.y, b.z, b.w};
   }

@@ -60,6 +60,10 @@ def _wide_against_bytes(n_q, n_ref, n_cols, n_radii=1):
     return capi.lib.dc_hip_cross_wide_workspace_bytes(n_q, n_ref, n_cols, n_radii)
 
 
+def _wide_against_pruned_bytes(n_q, n_ref, n_cols, n_radii=1):
+    return capi.lib.dc_hip_cross_wide_pruned_workspace_bytes(n_q, n_ref, n_cols, n_radii)
+
+
 class Workspace:
     """Device scratch of one kind of sweep (MFMA operand images); grown on demand, reused across calls.
     ``size`` is the library's byte count for a call's shape: get(*shape) asks it and returns (pointer, bytes)."""
@@ -86,6 +90,8 @@ _wide_workspaces = {}   # the matrix-core sweeps for rows of 65..256 columns, pe
 _wide_pruned_workspaces = {}   # ... of the pruned self population sweep (calculate_populations_wide_pruned), per device
 _wide_pruned_shapes = {}       # ... and the shape of the last call in each, which wide_pruned_order asks the order of
 _wide_against_workspaces = {}  # ... of their cross form (calculate_populations_against_wide, nearest_reference_wide), per device
+_wide_against_pruned_workspaces = {}   # ... of the pruned cross population sweep (calculate_populations_against_wide_pruned), per device
+_wide_against_pruned_shapes = {}       # ... and (rows of the query range, n_ref, n_cols) of the last call in each
 
 
 def _cached(cache, device, size):
@@ -121,6 +127,10 @@ def _wide_pruned_workspace(device):
 
 def _wide_against_workspace(device):
     return _cached(_wide_against_workspaces, device, _wide_against_bytes)
+
+
+def _wide_against_pruned_workspace(device):
+    return _cached(_wide_against_pruned_workspaces, device, _wide_against_pruned_bytes)
 
 
 def _variant(variant, stats_valid):
@@ -587,10 +597,76 @@ def wide_against_info(device):
     return int(t.value), int(m.value), int(e.value)
 
 
+# ---- ... the pruned cross population sweep (include/dc_density.h, the PRUNED wide cross sweep) -----------------------
+def calculate_populations_against_wide_pruned(queries, reference, radii, i_from=0, i_to=None, out=None):
+    """calculate_populations_against_wide without the block pairs that cannot hold a pair within the radii
+    (dc_hip_populations_cross_wide_pruned_dev): the same populations bit for bit.  The queries [i_from, i_to) and the
+    reference are put into one spatial order each, on one cell grid.  In a cached workspace of its own
+    (wide_against_pruned_info reads its counters, wide_against_pruned_order its two orders)."""
+    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
+    i_to = n_q if i_to is None else i_to
+    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    if out is None:
+        out = torch.empty((rad.size, n_q), dtype=torch.int32, device=queries.device)
+    assert out.shape == (rad.size, n_q) and out.dtype == torch.int32 and out.is_contiguous()
+    dev = queries.device
+    with torch.cuda.device(dev):
+        cache = _wide_against_pruned_workspace(dev)
+        ws, ws_bytes = cache.get(n_q, n_ref, n_cols, rad.size)
+        if ws_bytes == 0 and cache.buf is not None:   # (an empty side: the cached buffer then reports that nothing was swept)
+            ws, ws_bytes = _dev(cache.buf), int(cache.buf.numel())
+        rc = capi.lib.dc_hip_populations_cross_wide_pruned_dev(
+            _dev(queries), n_q, _dev(reference), n_ref, n_cols, rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size,
+            i_from, i_to, _dev(out), ws, ws_bytes, _stream_ptr())
+    capi.check(rc, "dc_hip_populations_cross_wide_pruned_dev")
+    _wide_against_pruned_shapes[str(dev)] = (max(i_to - i_from, 0), n_ref, n_cols)
+    return out
+
+
+def wide_against_pruned_info(device):
+    """(tiles, mfmas, exact_pairs) of the last calculate_populations_against_wide_pruned on this device, as
+    wide_against_info gives them; the tile pairs are the evaluated ones.  (0, 0, 0) when the direct kernel answered
+    (flagged data), nothing was swept, or no such sweep has run."""
+    ws = _wide_against_pruned_workspace(device)
+    if ws.buf is None:
+        return 0, 0, 0
+    t, m, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
+                   "dc_hip_wide_info_dev")
+    return int(t.value), int(m.value), int(e.value)
+
+
+def wide_against_pruned_order(device):
+    """both spatial orders of the last calculate_populations_against_wide_pruned on this device, position -> row:
+    (perm_q int32 [i_to - i_from], rows of the queries; perm_r int32 [n_ref]); block b of either order is its
+    positions 128 b .. 128 b + 127 (dc_hip_cross_wide_pruned_order_dev)."""
+    ws, shape = _wide_against_pruned_workspace(device), _wide_against_pruned_shapes.get(str(device))
+    if ws.buf is None or shape is None:
+        raise ValueError("no pruned wide cross sweep has run on this device")
+    perm_q = torch.empty(shape[0], dtype=torch.int32, device=device)
+    perm_r = torch.empty(shape[1], dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_cross_wide_pruned_order_dev(_dev(ws.buf), shape[0], shape[1], shape[2], _dev(perm_q),
+                                                               _dev(perm_r), _stream_ptr()),
+                   "dc_hip_cross_wide_pruned_order_dev")
+    return perm_q, perm_r
+
+
 def assign_frames_wide(queries, reference, radius, ref_states):
     """assign_frames for rows of 65..256 columns, every sweep on the matrix cores: calculate_populations_wide on the
     reference, calculate_populations_against_wide and nearest_reference_wide for the queries; the same four steps, the
     same state rule, the same dict, the same values."""
+    return _assign_frames_wide(queries, reference, radius, ref_states, False)
+
+
+def assign_frames_wide_pruned(queries, reference, radius, ref_states):
+    """assign_frames_wide with the populations of the queries through calculate_populations_against_wide_pruned: the same
+    dict, the same values.  (A function of its own: assign_frames_wide's parameter list is pinned.)"""
+    return _assign_frames_wide(queries, reference, radius, ref_states, True)
+
+
+def _assign_frames_wide(queries, reference, radius, ref_states, pruned_populations):
     n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
     dev = queries.device
     states_r = torch.as_tensor(np.ascontiguousarray(ref_states, dtype=np.int32), device=dev)
@@ -598,7 +674,8 @@ def assign_frames_wide(queries, reference, radius, ref_states):
     pops_ref = calculate_populations_wide(reference, [radius])[0].contiguous()
     max_pop = int(pops_ref.max().item()) if n_ref else 0
     fe_ref = calculate_free_energies(pops_ref)
-    pops_q = calculate_populations_against_wide(queries, reference, [radius])[0].contiguous()
+    pops_against = calculate_populations_against_wide_pruned if pruned_populations else calculate_populations_against_wide
+    pops_q = pops_against(queries, reference, [radius])[0].contiguous()
     fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
         torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
     nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference_wide(queries, reference, fe_q, fe_ref)

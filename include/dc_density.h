@@ -491,6 +491,34 @@ DC_API int dc_hip_nearest_neighbors_cross_wide_dev(const float* d_query, size_t 
                                                    const float* d_fe_ref, size_t i_from, size_t i_to,
                                                    uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                                                    float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
+/* ---- ... the PRUNED wide cross population sweep (65..256 columns) ----------------------------------------------------------
+ * dc_hip_populations_cross_wide_dev's populations bit for bit, without the block pairs that cannot hold a pair within
+ * the call's radii.  Statistics, origin and scale are those of the cross form.  ONE cell grid on columns 0 / 1 covers the
+ * queries [i_from, i_to) and the reference together (its cell sized by the reference's row count); the reference and the
+ * query range are each sorted by its keys, gathered and boxed per block of 128 positions, and a workgroup only runs the
+ * chains of the reference blocks whose box lies within 1.0001 x the launch's largest r^2 of its query block's.  Entry
+ * points of their own; no dc_variant value selects them.
+ * Arguments, refusals and contract are those of dc_hip_populations_cross_wide_dev: no self term; d_pops [n_radii][n_query]
+ * fully overwritten, zeros outside [i_from, i_to); radii in any order, more than 8 run one launch per 8, each pruned by
+ * its own largest radius; d_query == d_ref allowed; n_query == 0, n_ref == 0 or an empty range: DC_OK with zeros.
+ * Flagged data -- a non-finite or overflow-prone row in Q or in R -- is answered by the direct kernel behind the
+ * device-side gate, without a host synchronisation; the counters then read (0, 0, 0).
+ * n_cols outside 65..256: DC_ERR_INVALID_ARGUMENT; a workspace smaller than dc_hip_cross_wide_pruned_workspace_bytes:
+ * DC_ERR_WORKSPACE; n_ref + 1 and n_query must fit uint32: DC_ERR_TOO_LARGE -- all before a device is touched.
+ * dc_hip_cross_wide_pruned_workspace_bytes: 0 outside 65..256 columns and for an empty side, monotone in either row
+ * count, never below dc_hip_cross_wide_workspace_bytes.  The workspace keeps the info head of the wide sweeps:
+ * dc_hip_wide_info_dev reads the counters of the last call; its tile pairs are the EVALUATED ones.
+ * dc_hip_cross_wide_pruned_order_dev: both orders of the last call in that workspace, position -> row: d_perm_q
+ * [n_query_range = i_to - i_from] names rows of Q (query block b: positions 128 b .. 128 b + 127), d_perm_r [n_ref] rows
+ * of R.  A workspace that holds no cross order of that shape -- a self order included -- : DC_ERR_INVALID_ARGUMENT.
+ * Synchronises the stream. */
+DC_API size_t dc_hip_cross_wide_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_populations_cross_wide_pruned_dev(const float* d_query, size_t n_query, const float* d_ref, size_t n_ref,
+                                                    size_t n_cols, const float* radii, size_t n_radii, size_t i_from,
+                                                    size_t i_to, uint32_t* d_pops, void* d_ws, size_t ws_bytes,
+                                                    void* stream);
+DC_API int dc_hip_cross_wide_pruned_order_dev(const void* d_ws, size_t n_query_range, size_t n_ref, size_t n_cols,
+                                              uint32_t* d_perm_q, uint32_t* d_perm_r, void* stream);
 
 /* ---- ... and the radius graph on the wide self sweep (65..256 columns) --------------------------------------------------
  * The one-radius population sweep with a sink on its two decision points, the accumulator window and the exact drain.
