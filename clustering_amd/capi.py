@@ -52,6 +52,7 @@ SYMBOLS = (
     "dc_hip_radius_pairs_wide_pruned_dev", "dc_hip_radius_min_edge_wide_pruned_dev", "dc_hip_radius_forest_wide_pruned",
     "dc_hip_nearest_neighbors_wide_pruned_dev",
     "dc_hip_cross_wide_pruned_workspace_bytes", "dc_hip_populations_cross_wide_pruned_dev", "dc_hip_cross_wide_pruned_order_dev",
+    "dc_hip_nearest_neighbors_cross_wide_pruned_dev",
 )
 
 
@@ -225,6 +226,8 @@ def _load():
     lib.dc_hip_populations_cross_wide_pruned_dev.argtypes = lib.dc_hip_populations_cross_wide_dev.argtypes
     lib.dc_hip_cross_wide_pruned_order_dev.restype = i32
     lib.dc_hip_cross_wide_pruned_order_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp]
+    lib.dc_hip_nearest_neighbors_cross_wide_pruned_dev.restype = i32
+    lib.dc_hip_nearest_neighbors_cross_wide_pruned_dev.argtypes = lib.dc_hip_nearest_neighbors_cross_wide_dev.argtypes
     lib.dc_hip_free_energies_scaled_dev.restype = i32
     lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
     lib.dc_hip_populations_cross.restype = i32

@@ -472,6 +472,68 @@ int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_co
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---- the pruned cross neighbour sweep (dc_hip_nearest_neighbors_cross_wide_pruned_dev) --------------------
+// Behind wide_cross_pruned_prepare in the same workspace.  The sort's keys, keys_o and vals arrays (n_max words each) are
+// free once both orders stand: the first two hold the free energies of the reference and of the query range by position,
+// the third the words per block -- fe_min per reference block, then fe_max, far2_nn, far2_hd and the seed per query
+// block: blocks_r + 4 blocks_q <= 5 ceil(n_max / 128) words, inside n_max words from n_max = 6 on and inside the 256
+// bytes of align256 below.  A NaN free energy of either side flags the data (ring 2 rests on the ranges per block): the
+// gathers raise header word 1 on the stream, before the first sweep launch.  Then the launches of 4.24: seed, bounds, ring 1, bounds, ring 2, finish.
+int launch_nn_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, const float* d_fe_query, const float* d_fe_ref,
+                                uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                float* d_hd_d2, void* d_ws, hipStream_t s) {
+  if (i_from >= i_to || n_ref == 0) return 0;
+  const WideCrossPrunedLayout P = wide_cross_pruned_layout(n_query, n_ref, n_cols);
+  const uint32_t n_q = i_to - i_from, blocks_q = (n_q + kWideBlockRows - 1u) / kWideBlockRows;
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  float* fe_r = (float*)(p + P.off_keys);
+  float* fe_q = (float*)(p + P.off_keys_o);
+  float* fe_min_r = (float*)(p + P.off_vals);   // [blocks_r]
+  float* fe_max_q = fe_min_r + P.blocks_r;      // [blocks_q of the whole query array] each from here on
+  float* far2 = fe_max_q + P.blocks_q;          // [2]: nn, hd
+  uint32_t* seed = (uint32_t*)(far2 + 2 * (size_t)P.blocks_q);
+  WideCrossNnPrunedArgs X{};
+  static_cast<WideArgs&>(X) = wide_args(P.L, (const float*)(p + P.off_coords_r), n_ref, n_cols, 0, n_q, d_ws,
+                                        (const float*)(p + P.off_coords_q), n_q);
+  X.boxes = (const float4*)(p + P.off_boxes_r);
+  X.qboxes = (const float4*)(p + P.off_boxes_q);
+  X.seg = 0;
+  X.n_seg = 1;
+  X.perm = (const uint32_t*)(p + P.off_perm_r);
+  X.far2_nn = far2;
+  X.far2_hd = far2 + P.blocks_q;
+  X.fe_min_r = fe_min_r;
+  X.fe_max_q = fe_max_q;
+  X.seed = seed;
+  const uint32_t* perm_q = (const uint32_t*)(p + P.off_perm_q);
+  if (hipMemsetAsync(X.merge, 0xFF, sizeof(unsigned long long) * 2 * (size_t)n_q, s) != hipSuccess) return -1;
+  if (d_fe_query) {
+    // (the gathers and the seed kernel run on flagged data too: they read through the two orders and the boxes, which
+    //  wide_cross_pruned_prepare completes whatever the rows hold -- a preparation that stood down on flagged data would
+    //  have to gate them)
+    hipLaunchKernelGGL(wide_cross_nn_gather_kernel, dim3(P.blocks_r), dim3(128), 0, s, X.perm, d_fe_ref, n_ref, 0u, fe_r, fe_min_r, hdr);
+    hipLaunchKernelGGL(wide_cross_nn_gather_kernel, dim3(blocks_q), dim3(128), 0, s, perm_q, d_fe_query, n_q, 1u, fe_q, fe_max_q, hdr);
+    X.fe = fe_r;
+    X.q_fe = fe_q;
+  }
+  hipLaunchKernelGGL(wide_cross_seed_kernel, dim3(blocks_q), dim3(64), 0, s, X.qboxes, X.boxes, P.blocks_r, seed);
+  const dim3 grid(wide_grid_size(blocks_q, wide_shares(P.blocks_r)));
+  const uint32_t last_ring = d_fe_query ? kWideRing2 : kWideRing1;   // no ring 2 without free energies
+  sweep_timer_mark(1, true, s);
+  for (uint32_t ring = kWideRingSeed; ring <= last_ring; ++ring) {
+    if (ring != kWideRingSeed)
+      hipLaunchKernelGGL(wide_nn_bounds_kernel, dim3(blocks_q), dim3(128), 0, s, (const unsigned long long*)X.merge, n_q, ring - 1u,
+                         far2 + (size_t)(ring - 1u) * P.blocks_q);
+    X.ring = ring;
+    hipLaunchKernelGGL((wide_sweep_kernel<kWideNn, 1, kAgainst, true>), grid, dim3(256), 0, s, X);
+  }
+  sweep_timer_mark(1, false, s);
+  hipLaunchKernelGGL(wide_nn_finish_pruned_kernel, dim3((n_q + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,
+                     (const unsigned long long*)X.merge, perm_q, n_q, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n_ref, uint32_t n_cols, uint32_t* d_perm_q,
                             uint32_t* d_perm_r, hipStream_t s) {
   uint32_t tag[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};

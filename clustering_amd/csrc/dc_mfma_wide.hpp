@@ -117,6 +117,16 @@ int wide_cross_pruned_prepare(const float* d_query, uint32_t n_query, const floa
 // flagged data, scatter included (the gated direct kernel answers).  Returns 0 on success.
 int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
                                  const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t stream);
+// ---- the pruned cross neighbour sweep (dc_hip_nearest_neighbors_cross_wide_pruned_dev) --------------------
+// Behind wide_cross_pruned_prepare(.., i_from, i_to, ..) in the same workspace: nn / nn_hd of the queries [i_from, i_to)
+// against the reference, WRITTEN to those rows (outputs preset to "none" by the caller).  Three launches of the pruned
+// kAgainst neighbour instance -- the seed block of every query block (the reference block whose box centre is nearest,
+// dc_wide_prune.hpp), ring 1, ring 2 -- whose counters add up; d_fe_query == nullptr: nn only, two launches, the hd outputs
+// are not touched.  A NaN free energy flags the data (the gathers of the free energies raise the flag); on flagged data the
+// launches and the finish stand down (the gated direct kernel answers).  Uses the sort's key arrays of the layout, so its byte count is wide_cross_pruned_workspace_bytes.  Returns 0 on success.
+int launch_nn_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, const float* d_fe_query, const float* d_fe_ref,
+                                uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                float* d_hd_d2, void* d_ws, hipStream_t stream);
 // both orders the workspace holds, position -> row, copied to d_perm_q ([n_query_range], rows of the query array) and
 // d_perm_r ([n_ref]); 0 ok, 1 the workspace holds no cross order of that shape, -1 a HIP error (synchronises)
 int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n_ref, uint32_t n_cols, uint32_t* d_perm_q,

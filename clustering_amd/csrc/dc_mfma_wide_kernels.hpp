@@ -56,6 +56,9 @@
 // The pruned cross population sweep (dc_hip_populations_cross_wide_pruned_dev) is the pruned population
 // sweep over a rectangle: the query range and the reference each in an order of its own on ONE cell grid, a set of boxes
 // each; the kernel works in positions of the two orders, the scatter behind it writes rows of the query array.
+// The pruned cross neighbour sweep (dc_hip_nearest_neighbors_cross_wide_pruned_dev) joins the two: the
+// three launches of 4.24 on the two orders of 4.25, the seed of a query block being the one reference block whose box
+// centre is nearest to its own (wide_cross_seed_kernel).
 #pragma once
 #include "dc_mfma_kernels.hpp"
 #include "dc_mfma_wide.hpp"
@@ -557,6 +560,52 @@ __global__ __launch_bounds__(256) void wide_nn_finish_pruned_kernel(const uint32
   }
 }
 
+// the pruned cross neighbour sweep: the free energies of ONE side by position, and per block of its
+// order ONE end of their range over its live rows -- the least (the reference: want_max = 0; +inf for a block without a
+// live row) or the largest (the query range: want_max = 1; -inf), as wide_nn_gather_kernel writes them side by side.  A NaN
+// among them flags the data (header word 1, as wide_fe_flag_kernel does): ring 2 rests on these ends.
+// Not gated on header word 1 itself: it reads through perm, which the preparation completes whatever the data holds.
+__global__ __launch_bounds__(128) void wide_cross_nn_gather_kernel(const uint32_t* __restrict__ perm, const float* __restrict__ fe,
+                                                                   uint32_t n_rows, uint32_t want_max, float* __restrict__ fe_o,
+                                                                   float* __restrict__ fe_end, uint32_t* __restrict__ hdr) {
+  static_assert(kWideBlockRows == 128, "two waves per block of the order");
+  __shared__ float part[2];
+  const uint32_t p = blockIdx.x * kWideBlockRows + threadIdx.x;
+  const bool live = p < n_rows;
+  const float f = live ? fe[perm[p]] : 0.0f;
+  if (live) fe_o[p] = f;
+  if (__builtin_amdgcn_ballot_w64(f != f) != 0 && (threadIdx.x & 63u) == 0) atomicOr(hdr + 1, 1u);
+  float v = live ? f : (want_max ? -INFINITY : INFINITY);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float o = __shfl_xor(v, off, 64);
+    v = want_max ? fmaxf(v, o) : fminf(v, o);
+  }
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) fe_end[blockIdx.x] = want_max ? fmaxf(part[0], part[1]) : fminf(part[0], part[1]);
+}
+// ... and the seed of every query block (dc_wide_prune.hpp wide_cross_seed_key): one wave per query block, the least key
+// over the reference's boxes.  n_ref_blocks >= 1, so the seed is always a block of the reference.  Not gated on header
+// word 1 either: the preparation writes every box of both orders whatever the data holds (a non-finite row has key 0).
+__global__ __launch_bounds__(64) void wide_cross_seed_kernel(const float4* __restrict__ qboxes, const float4* __restrict__ boxes,
+                                                             uint32_t n_ref_blocks, uint32_t* __restrict__ seed) {
+  const float4 q = qboxes[blockIdx.x];
+  const WideBox qbox{q.x, q.y, q.z, q.w};
+  unsigned long long best = ~0ull;
+  for (uint32_t rb = threadIdx.x; rb < n_ref_blocks; rb += 64u) {
+    const float4 b = boxes[rb];
+    const unsigned long long key = wide_cross_seed_key(qbox, WideBox{b.x, b.y, b.z, b.w}, rb);
+    best = key < best ? key : best;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(best, off, 64);
+    best = o < best ? o : best;
+  }
+  if (threadIdx.x == 0) seed[blockIdx.x] = (uint32_t)best;
+}
+
 // ... of a cross sweep: ONE origin and ONE scale over the queries and the reference together (column sums over both
 // sets, the mean over n_query + n_ref rows, header word 0 = the largest |x'|^2 of either set), then the A form and the
 // norms of the reference and the B form of the queries.  d_query == d_ref is an ordinary pair of sets.
@@ -606,6 +655,18 @@ inline int wide_prepare_against_launches(const float* d_query, uint32_t n_query,
 
 // ---- the sweep ------------------------------------------------------------------------------------------------------
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// ON: a copy of v that the compiler cannot trace back to v (no instruction is emitted).  What is computed from the copy is
+// computed where it is used instead of once in front of the block loop, where it would hold a register across the whole
+// sweep -- for values that cost one instruction.  OFF: v itself, and the code of the instance is what it was.
+// This steers the register allocation of one compiler, it is no property of the language: after a change of the toolchain
+// compare the metadata of the instances again (scratch/wide_asm_diff.py prints .vgpr_count, .vgpr_spill_count and
+// .private_segment_fixed_size; DESIGN.md 4.26 has the figures to expect).
+template <bool ON>
+__device__ __forceinline__ uint32_t wide_fresh(uint32_t v) {
+  if constexpr (ON) asm volatile("" : "+v"(v));
+  return v;
+}
 
 // kWidePairs / kWideMinEdge (the radius graph): the one-radius population sweep with a sink on its two
 // decision points, the accumulator window and the exact drain; they count as kWidePop does
@@ -666,8 +727,19 @@ struct WideNnPrunedArgs : WidePrunedArgs {
 struct WideCrossPrunedArgs : WidePrunedArgs {
   const float4* qboxes;      // [query blocks]: the box of every block of kWideBlockRows positions of the query order
 };
+// the pruned cross neighbour instance: the operands of the pruned cross population instances (q_coords and
+// q_fe the query range GATHERED into its order, coords and fe the reference gathered into its own), the rings of the pruned
+// neighbour instance.  far2_nn / far2_hd are per QUERY block; fe_range is not read: the two ends it holds lie in two arrays,
+// the least per reference block and the largest per query block.  merge is indexed by the query's position, its hd half
+// n_query behind the nn half, and names the reference's ROW.  A struct of its own, for the same reason.
+struct WideCrossNnPrunedArgs : WideNnPrunedArgs {
+  const float4* qboxes;      // [query blocks]
+  const float* fe_min_r;     // [reference blocks], read by ring 2
+  const float* fe_max_q;     // [query blocks], read by ring 2
+  const uint32_t* seed;      // [query blocks]: the reference block of the seed launch
+};
 template <bool PR, bool NN = false, bool CROSS = false>
-using WideKernelArgs = std::conditional_t<PR, std::conditional_t<NN, WideNnPrunedArgs, std::conditional_t<CROSS, WideCrossPrunedArgs, WidePrunedArgs>>, WideArgs>;
+using WideKernelArgs = std::conditional_t<PR, std::conditional_t<NN, std::conditional_t<CROSS, WideCrossNnPrunedArgs, WideNnPrunedArgs>, std::conditional_t<CROSS, WideCrossPrunedArgs, WidePrunedArgs>>, WideArgs>;
 
 // the deferred pairs of a wave, evaluated in the canonical order from the original coordinates, a pair per lane
 template <int MODE>
@@ -801,6 +873,27 @@ __device__ __attribute__((noinline)) void wide_nn_drain_pruned(const uint2* queu
   __builtin_amdgcn_wave_barrier();
 }
 
+// ... of the pruned cross neighbour sweep: i is a position of the gathered reference, j one of the gathered
+// query range; the word lies at the query's position (the hd half n_query behind) and names the reference's row perm_r[i]
+__device__ __attribute__((noinline)) void wide_nn_drain_cross_pruned(const uint2* queue, uint32_t fill, const float* coords,
+                                                                     uint32_t n_query, uint32_t n_cols, uint32_t qrow0,
+                                                                     unsigned long long* merge, const uint32_t* perm_r,
+                                                                     const float* q_coords) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t e = lane; e < fill; e += 64u) {
+    const uint2 en = queue[e];
+    const uint32_t i = en.x, j = qrow0 + (en.y & 127u), flags = en.y >> 8;
+    const float d2 = dist2_canon_rt(q_coords + (size_t)j * n_cols, 1, coords + (size_t)i * n_cols, 1, (int)n_cols);
+    const unsigned long long w = ((unsigned long long)__float_as_uint(d2) << 32) | perm_r[i];
+    if (flags & 1u) atomicMin(&merge[j], w);
+    if (flags & 2u) atomicMin(&merge[(size_t)n_query + j], w);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
 // SM: kSelf -- queries and reference are the rows of one array: the diagonal pair leaves the sweep, populations get the
 // frame's own 1, a frame is not its own neighbour; kAgainst -- X.q_coords against X.coords: every pair counts.
 // PR: the pruned form.  A workgroup still owns (query block, share); it first scans the boxes of its share's blocks
@@ -813,10 +906,14 @@ __device__ __attribute__((noinline)) void wide_nn_drain_pruned(const uint2* queu
 // the QUERY order (its count bounds it, its box comes from X.qboxes), the scanned boxes and the listed blocks are the
 // reference's; rows, live[] and the drain speak of positions of the gathered query range [0, n_query) against positions
 // of the gathered reference, as the unpruned cross form speaks of rows; there is no segment.
+// The pruned cross neighbour instance is that form with the rings: the seed of a query block is the one
+// reference block X.seed names, the bounds and the largest free energy are the QUERY block's, the least free energy the
+// reference block's, the words lie by query position and name rows of the reference.
 template <int MODE, int NR, SweepMode SM = kSelf, bool PR = false>
 __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, MODE == kWideNn, PR && SM == kAgainst> X) {
-  static_assert(!PR || ((wide_counts(MODE) || MODE == kWideNn) && SM == kSelf) || (MODE == kWidePop && SM == kAgainst && (NR == 1 || NR == 4 || NR == kMaxRadiiPerLaunch)),
-                "the pruned form: self sweeps -- populations, the radius graph, neighbours -- and the cross population sweep");
+  static_assert(!PR || ((wide_counts(MODE) || MODE == kWideNn) && SM == kSelf) || (MODE == kWidePop && SM == kAgainst && (NR == 1 || NR == 4 || NR == kMaxRadiiPerLaunch)) ||
+                    (MODE == kWideNn && SM == kAgainst && NR == 1),
+                "the pruned form: self sweeps -- populations, the radius graph, neighbours -- and the cross population and neighbour sweeps");
   if (X.hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
   __shared__ uint32_t list_s[PR ? kWideListCap : 1];                  // pruned: the surviving reference blocks of a round
   __shared__ unsigned long long mask_s[PR ? kWideListCap / 64 : 1];   // ... and the ballots they are compacted from
@@ -826,6 +923,8 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
   __shared__ float min_s[4][2][2][32];   // neighbours: running minima (nn, nn_hd) per wave and query, exchanged per block
   __shared__ uint2 cr_s[kWideBlockRows];  // min edge: (component, rank) of the reference block's rows
   constexpr bool kCount = wide_counts(MODE);
+  // the pruned cross neighbour instance has no register to spare: 256 and 14 spilled without this, 0 spilled with it
+  constexpr bool kFresh = PR && MODE == kWideNn && SM == kAgainst;
   static_assert((MODE != kWidePairs && MODE != kWideMinEdge) || (NR == 1 && SM == kSelf), "the graph instances: one radius, self sweeps");
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, h = lane >> 5, c = lane & 31u;
   const uint32_t wq = wave & 1u, wr = wave >> 1;
@@ -890,7 +989,7 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
         // rings 1 and 2 start from the words of the launches before: a bound on the accumulator of the row a word names
         if (X.ring != kWideRingSeed && live[qt]) {
           m_nn[qt] = wide_nn_start(X.merge[jq[qt]], sc.s2, band);
-          m_hd[qt] = wide_nn_start(X.merge[(size_t)X.n_rows + jq[qt]], sc.s2, band);
+          m_hd[qt] = wide_nn_start(X.merge[(size_t)(SM == kAgainst ? n_q : X.n_rows) + jq[qt]], sc.s2, band);
         }
       }
     }
@@ -915,7 +1014,9 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
 
   // one pair per lane into the wave's queue (ok: this lane has one); drained before a push that might not fit
   auto drain = [&]() {
-    if constexpr (PR && MODE == kWideNn)
+    if constexpr (PR && MODE == kWideNn && SM == kAgainst)
+      wide_nn_drain_cross_pruned(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.merge, X.perm, q_coords);
+    else if constexpr (PR && MODE == kWideNn)
       wide_nn_drain_pruned(queue, fill, X.coords, n_q, D, qb * kWideBlockRows, X.merge, X.perm);
     else if constexpr (PR && MODE == kWidePairs)
       wide_pairs_drain_pruned(queue, fill, X.coords, D, qb * kWideBlockRows, X.rad2.v[0], X.pops, X.pairs, X.capacity, X.count,
@@ -984,12 +1085,17 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
   }
   // the neighbour instance: the bounds of the query block (wave-uniform; a ring reads what the launches before it wrote)
   float far2_nn = 0.0f, far2_hd = 0.0f, fe_max_q = 0.0f;
+  uint32_t seed_rb = 0u;   // the cross form: the reference block of the query block's seed launch
   if constexpr (PR && MODE == kWideNn) {
     if (X.ring >= kWideRing1) far2_nn = X.far2_nn[qb];
     if (X.ring == kWideRing2) {
       far2_hd = X.far2_hd[qb];
-      fe_max_q = X.fe_range[qb].y;
+      if constexpr (SM == kAgainst)
+        fe_max_q = X.fe_max_q[qb];
+      else
+        fe_max_q = X.fe_range[qb].y;
     }
+    if constexpr (SM == kAgainst) seed_rb = X.seed[qb];
   }
   uint32_t round0 = 0;
   do {
@@ -1003,7 +1109,11 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
         if (e < lim) {
           const uint32_t rb = y + (round0 + e) * Sy;
           const float4 b = X.boxes[rb];
-          if constexpr (MODE == kWideNn) {
+          if constexpr (MODE == kWideNn && SM == kAgainst) {
+            const float fe_min_r = (X.ring == kWideRing2) ? X.fe_min_r[rb] : 0.0f;
+            ok = wide_nn_ring(wide_cross_is_seed(seed_rb, rb), wide_box_gap2(qbox, WideBox{b.x, b.y, b.z, b.w}), far2_nn, far2_hd,
+                              fe_min_r, fe_max_q) == (int)X.ring;
+          } else if constexpr (MODE == kWideNn) {
             const float fe_min_r = (X.ring == kWideRing2) ? X.fe_range[rb].x : 0.0f;
             ok = wide_nn_ring(wide_nn_is_seed(qb, rb), wide_box_gap2(qbox, WideBox{b.x, b.y, b.z, b.w}), far2_nn, far2_hd, fe_min_r,
                               fe_max_q) == (int)X.ring;
@@ -1209,7 +1319,8 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
                   const float v = acc[rt][qt][g], fr = fe_s[(2 * wr + rt) * 32 + tile_row_local(g, (int)h)];
                   const uint32_t fl = ((v <= cut_nn) ? 1u : 0u) | (((fr < feq[qt]) & (v <= cut_hd)) ? 2u : 0u);
                   if ((__builtin_amdgcn_ballot_w64(fl != 0) & livemask[qt]) != 0) {
-                    const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)h);
+                    // (kFresh: the sixteen row offsets 4 h | k of a tile are otherwise kept in a register each, across the sweep)
+                    const uint32_t i = (rb * kWideBlockTiles + 2 * wr + rt) * 32 + tile_row_local(g, (int)wide_fresh<kFresh>(h));
                     push(fl != 0 && live[qt] && i < X.n_rows && (SM == kAgainst || i != jq[qt]), i, ((2 * wq + qt) * 32 + c) | (fl << 8));
                   }
                 }

@@ -52,6 +52,24 @@ DC_PRUNE_FN bool wide_nn_is_seed(unsigned query_block, unsigned ref_block) {
   return (ref_block >= query_block ? ref_block - query_block : query_block - ref_block) <= 1u;
 }
 
+// The cross form has two orders, so "the blocks next to the query block" do not exist: the seed of a query
+// block is ONE reference block, the one with a live row whose box centre is nearest to the query block's box centre in
+// the plane, the lowest block on a tie.  The key of a reference block: (bits of c2) << 32 | block, c2 = the two
+// differences of the centres 0.5f * (lo + hi), their squares, one sum; the seed is the block of the least key.  c2 >= +0
+// or a NaN, so its bits order as the numbers do; a block without a live row (lo > hi) gets the high word ~0 and loses to
+// every block with one.  Whatever the data, the least key names a block that was scanned.
+DC_PRUNE_FN unsigned long long wide_cross_seed_key(const WideBox& query, const WideBox& ref, unsigned ref_block) {
+  unsigned bits = 0xFFFFFFFFu;
+  if (!(ref.lo0 > ref.hi0) && !(ref.lo1 > ref.hi1)) {
+    const float dx = 0.5f * (query.lo0 + query.hi0) - 0.5f * (ref.lo0 + ref.hi0);
+    const float dy = 0.5f * (query.lo1 + query.hi1) - 0.5f * (ref.lo1 + ref.hi1);
+    const float c2 = dx * dx + dy * dy;
+    __builtin_memcpy(&bits, &c2, sizeof(bits));
+  }
+  return ((unsigned long long)bits << 32) | ref_block;
+}
+DC_PRUNE_FN bool wide_cross_is_seed(unsigned seed_of_query_block, unsigned ref_block) { return ref_block == seed_of_query_block; }
+
 // B: the largest exact d2 among the block's live rows so far (+inf: a row has none).  1.0001 as wide_prune_far2; below
 // the smallest normal float the relative bounds of the proof do not hold, so the bound never falls below it (B = 0, a
 // block of duplicates, keeps the blocks at gap 0: a duplicate of a lower row may sit in any of them)

@@ -623,8 +623,41 @@ def calculate_populations_against_wide_pruned(queries, reference, radii, i_from=
     return out
 
 
+def nearest_reference_wide_pruned(queries, reference, fe_query=None, fe_ref=None, i_from=0, i_to=None):
+    """nearest_reference_wide without the block pairs that cannot hold a nearest reference frame
+    (dc_hip_nearest_neighbors_cross_wide_pruned_dev): the same four arrays bit for bit.  A query block meets the reference
+    block nearest to it first, then the blocks within the bound of its nearest frames, then those within the bound of its
+    nearest frames of lower free energy.  In the cached workspace of calculate_populations_against_wide_pruned
+    (wide_against_pruned_info reads its counters, wide_against_pruned_order its two orders)."""
+    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
+    i_to = n_q if i_to is None else i_to
+    with_fe = fe_query is not None
+    if with_fe:
+        assert fe_ref is not None
+        for f, n in ((fe_query, n_q), (fe_ref, n_ref)):
+            assert f.is_cuda and f.dtype == torch.float32 and f.shape == (n,) and f.is_contiguous()
+    dev = queries.device
+    nn_idx = torch.empty(n_q, dtype=torch.int32, device=dev)
+    nn_d2 = torch.empty(n_q, dtype=torch.float32, device=dev)
+    hd_idx = torch.empty(n_q, dtype=torch.int32, device=dev) if with_fe else None
+    hd_d2 = torch.empty(n_q, dtype=torch.float32, device=dev) if with_fe else None
+    with torch.cuda.device(dev):
+        cache = _wide_against_pruned_workspace(dev)
+        ws, ws_bytes = cache.get(n_q, n_ref, n_cols, 1)
+        if ws_bytes == 0 and cache.buf is not None:   # (an empty side: the cached buffer then reports that nothing was swept)
+            ws, ws_bytes = _dev(cache.buf), int(cache.buf.numel())
+        rc = capi.lib.dc_hip_nearest_neighbors_cross_wide_pruned_dev(
+            _dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
+            _dev(fe_ref) if with_fe else None, i_from, i_to, _dev(nn_idx), _dev(nn_d2),
+            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None, ws, ws_bytes, _stream_ptr())
+    capi.check(rc, "dc_hip_nearest_neighbors_cross_wide_pruned_dev")
+    _wide_against_pruned_shapes[str(dev)] = (max(i_to - i_from, 0), n_ref, n_cols)
+    return nn_idx, nn_d2, hd_idx, hd_d2
+
+
 def wide_against_pruned_info(device):
-    """(tiles, mfmas, exact_pairs) of the last calculate_populations_against_wide_pruned on this device, as
+    """(tiles, mfmas, exact_pairs) of the last calculate_populations_against_wide_pruned / nearest_reference_wide_pruned
+    on this device (for the neighbour call: summed over its launches), as
     wide_against_info gives them; the tile pairs are the evaluated ones.  (0, 0, 0) when the direct kernel answered
     (flagged data), nothing was swept, or no such sweep has run."""
     ws = _wide_against_pruned_workspace(device)
@@ -638,7 +671,8 @@ def wide_against_pruned_info(device):
 
 
 def wide_against_pruned_order(device):
-    """both spatial orders of the last calculate_populations_against_wide_pruned on this device, position -> row:
+    """both spatial orders of the last calculate_populations_against_wide_pruned / nearest_reference_wide_pruned on this
+    device, position -> row:
     (perm_q int32 [i_to - i_from], rows of the queries; perm_r int32 [n_ref]); block b of either order is its
     positions 128 b .. 128 b + 127 (dc_hip_cross_wide_pruned_order_dev)."""
     ws, shape = _wide_against_pruned_workspace(device), _wide_against_pruned_shapes.get(str(device))
@@ -660,13 +694,15 @@ def assign_frames_wide(queries, reference, radius, ref_states):
     return _assign_frames_wide(queries, reference, radius, ref_states, False)
 
 
-def assign_frames_wide_pruned(queries, reference, radius, ref_states):
+def assign_frames_wide_pruned(queries, reference, radius, ref_states, pruned_neighbours=False):
     """assign_frames_wide with the populations of the queries through calculate_populations_against_wide_pruned: the same
-    dict, the same values.  (A function of its own: assign_frames_wide's parameter list is pinned.)"""
-    return _assign_frames_wide(queries, reference, radius, ref_states, True)
+    dict, the same values.  (A function of its own: assign_frames_wide's parameter list is pinned.)
+    pruned_neighbours=True: the nearest reference frames through nearest_reference_wide_pruned as well, as
+    assign_frames(..., pruned_neighbours=True) does below 65 columns."""
+    return _assign_frames_wide(queries, reference, radius, ref_states, True, pruned_neighbours)
 
 
-def _assign_frames_wide(queries, reference, radius, ref_states, pruned_populations):
+def _assign_frames_wide(queries, reference, radius, ref_states, pruned_populations, pruned_neighbours=False):
     n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
     dev = queries.device
     states_r = torch.as_tensor(np.ascontiguousarray(ref_states, dtype=np.int32), device=dev)
@@ -678,7 +714,8 @@ def _assign_frames_wide(queries, reference, radius, ref_states, pruned_populatio
     pops_q = pops_against(queries, reference, [radius])[0].contiguous()
     fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
         torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
-    nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference_wide(queries, reference, fe_q, fe_ref)
+    nearest = nearest_reference_wide_pruned if pruned_neighbours else nearest_reference_wide
+    nn_idx, nn_d2, hd_idx, hd_d2 = nearest(queries, reference, fe_q, fe_ref)
     none = n_ref + 1
     states = torch.zeros(n_q, dtype=torch.int32, device=dev)
     if n_ref:

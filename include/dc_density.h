@@ -519,6 +519,32 @@ DC_API int dc_hip_populations_cross_wide_pruned_dev(const float* d_query, size_t
                                                     void* stream);
 DC_API int dc_hip_cross_wide_pruned_order_dev(const void* d_ws, size_t n_query_range, size_t n_ref, size_t n_cols,
                                               uint32_t* d_perm_q, uint32_t* d_perm_r, void* stream);
+/* ---- ... and the PRUNED wide cross neighbour sweep (65..256 columns) --------------------------------------------------------
+ * dc_hip_nearest_neighbors_cross_wide_dev's four outputs bit for bit -- indices, d2 bits, "none" -- in the two orders and
+ * the workspace of dc_hip_populations_cross_wide_pruned_dev (dc_hip_cross_wide_pruned_workspace_bytes(n_query, n_ref,
+ * n_cols, 1)).  The call prepares both orders itself and trusts none left by an earlier call.  A query block of 128
+ * positions first meets ONE reference block, the one with a live row whose box centre is nearest to its own box centre in
+ * the (column 0, column 1) plane (the lowest block on a tie), then the blocks whose box lies within 1.0001 x the largest
+ * nn_d2 its rows have found, then those within 1.0001 x the largest hd_d2 that hold a row of lower free energy than one
+ * of its own.  Entry point of its own; no dc_variant value selects it.
+ * Arguments, refusals and contract are those of dc_hip_nearest_neighbors_cross_wide_dev: nn[q] the least (d2, ROW of R)
+ * over all j with no exclusion; nn_hd[q] the same over { j : fe_ref[j] < fe_query[q] }, compared as IEEE;
+ * d_fe_query == NULL: nn only (d_fe_ref, d_hd_idx, d_hd_d2 may be NULL and are not written, two launches instead of
+ * three); "none" = (n_ref + 1, FLT_MAX), also outside [i_from, i_to); outputs fully overwritten; d_query == d_ref
+ * allowed; n_query == 0, n_ref == 0 or an empty range: DC_OK with "none".
+ * Flagged data -- a non-finite or overflow-prone row in Q or in R, OR a NaN in fe_query[i_from, i_to) or fe_ref (the third
+ * launch rests on the least and largest free energy per block) -- is answered by the direct kernel behind the
+ * device-side gate, without a host synchronisation: the same IEEE comparison, so the results still equal the unpruned
+ * call's; the counters then read (0, 0, 0).
+ * n_cols outside 65..256: DC_ERR_INVALID_ARGUMENT; a workspace smaller than dc_hip_cross_wide_pruned_workspace_bytes (or
+ * none): DC_ERR_WORKSPACE; n_ref + 1 and n_query must fit uint32: DC_ERR_TOO_LARGE -- all before a device is touched.
+ * dc_hip_wide_info_dev reads the counters of the call (the EVALUATED tile pairs, summed over its launches; no block pair
+ * is counted twice), dc_hip_cross_wide_pruned_order_dev its two orders. */
+DC_API int dc_hip_nearest_neighbors_cross_wide_pruned_dev(const float* d_query, size_t n_query, const float* d_ref,
+                                                          size_t n_ref, size_t n_cols, const float* d_fe_query,
+                                                          const float* d_fe_ref, size_t i_from, size_t i_to,
+                                                          uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                                          float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ---- ... and the radius graph on the wide self sweep (65..256 columns) --------------------------------------------------
  * The one-radius population sweep with a sink on its two decision points, the accumulator window and the exact drain.
