@@ -53,7 +53,10 @@ SYMBOLS = (
     "dc_hip_nearest_neighbors_wide_pruned_dev",
     "dc_hip_cross_wide_pruned_workspace_bytes", "dc_hip_populations_cross_wide_pruned_dev", "dc_hip_cross_wide_pruned_order_dev",
     "dc_hip_nearest_neighbors_cross_wide_pruned_dev",
+    "dc_hip_neighbors_block_rows_wide", "dc_hip_neighbors_block_pack_wide_dev", "dc_hip_neighbors_block_unpack_wide_dev",
+    "dc_hip_wide_layout_status_dev", "dc_hip_session_open_flags", "dc_hip_session_wide",
 )
+SESSION_WIDE_SWEEPS = 0x1     # DC_SESSION_WIDE_SWEEPS (dc_hip_session_open_flags)
 
 
 class DensityLibraryError(RuntimeError):
@@ -228,6 +231,18 @@ def _load():
     lib.dc_hip_cross_wide_pruned_order_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp]
     lib.dc_hip_nearest_neighbors_cross_wide_pruned_dev.restype = i32
     lib.dc_hip_nearest_neighbors_cross_wide_pruned_dev.argtypes = lib.dc_hip_nearest_neighbors_cross_wide_dev.argtypes
+    lib.dc_hip_neighbors_block_rows_wide.restype = sz
+    lib.dc_hip_neighbors_block_rows_wide.argtypes = [sz, sz, sz]
+    lib.dc_hip_neighbors_block_pack_wide_dev.restype = i32
+    lib.dc_hip_neighbors_block_pack_wide_dev.argtypes = [vp, vp, vp, vp, sz, sz, sz, sz, vp, sz, vp, vp]
+    lib.dc_hip_neighbors_block_unpack_wide_dev.restype = i32
+    lib.dc_hip_neighbors_block_unpack_wide_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp]
+    lib.dc_hip_wide_layout_status_dev.restype = i32
+    lib.dc_hip_wide_layout_status_dev.argtypes = [vp, C.POINTER(C.c_int), vp]
+    lib.dc_hip_session_open_flags.restype = i32
+    lib.dc_hip_session_open_flags.argtypes = [vp, sz, sz, C.POINTER(C.c_int), i32, C.c_uint, C.POINTER(vp)]
+    lib.dc_hip_session_wide.restype = i32
+    lib.dc_hip_session_wide.argtypes = [vp]
     lib.dc_hip_free_energies_scaled_dev.restype = i32
     lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
     lib.dc_hip_populations_cross.restype = i32

@@ -491,6 +491,9 @@ int density_main(int argc, char** argv) {
       // back from RCCL to the host merge is correct and slow -- always said on stderr, every mode under -v
       if (dc_hip_session_merge_mode(session) == 2) std::cerr << "warning: " << dc_hip_session_merge_note(session) << std::endl;
       LOG("merge: %s\n", dc_hip_session_merge_note(session));
+      // ... and which sweeps (DC_SESSION_WIDE=1 puts a session of 65..256 columns on the pruned wide matrix-core sweeps)
+      LOG("sweeps: %s\n", dc_hip_session_wide(session) ? "pruned wide matrix-core sweeps (65..256 columns, DC_SESSION_WIDE=1)"
+                                                        : "the default sweeps of this column count");
     }
     return session;
   };

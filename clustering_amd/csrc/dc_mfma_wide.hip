@@ -337,6 +337,178 @@ int wide_pruned_order(const void* d_ws, uint32_t n_rows, uint32_t n_cols, uint32
   return 0;
 }
 
+// ---- neighbour blocks of a sharded run in the order of the pruned sweep (dc_hip_neighbors_block_*_wide_dev) --
+// Segment g of G owns the query blocks g, g + G, ... of the order; by LOCAL POSITION l its rows form a dense block an
+// all-gather can move: local block l / 128 is block (l / 128) G + g of the order, position p(l), row perm[p].  Flagged
+// data (the direct kernel answered on the reference's row block) uses the row block: chosen on the device from header
+// word 1, the word the sweep's gate read.  The layout header -- the last kWideBlockHdrRows entries of plane 0 -- says under
+// which layout a block was packed: mark | by position, positions, block size, segment count, deal (1: block b goes to
+// segment b mod G), and the 64-bit hash of the order.
+namespace {
+constexpr uint32_t kWideBlockHdrRows = 32, kWideBlockHdrWords = 7, kWideBlockMagic = 0x6E6E5700u;   // "nnW" | by_position
+constexpr uint32_t kWideBlockNoOrder = 2u;   // ... | the workspace holds no order of this shape: nothing packed, never unpacked
+
+__device__ __forceinline__ uint32_t wide_block_none(uint32_t c, uint32_t n_rows) {
+  return (c & 1u) ? __float_as_uint(FLT_MAX) : n_rows + 1u;
+}
+// 0: row blocks (flagged data), 1: by position, kWideBlockNoOrder: unflagged, but no order of n_rows x n_cols is signed
+__device__ __forceinline__ uint32_t wide_block_mode(const uint32_t* __restrict__ hdr, uint32_t n_rows, uint32_t n_cols) {
+  if (hdr[1] != 0u) return 0u;
+  const bool signed_here = hdr[kWideHdrOrder] == kWideOrderMark && hdr[kWideHdrOrder + 1] == n_rows && hdr[kWideHdrOrder + 2] == n_cols;
+  return signed_here ? 1u : kWideBlockNoOrder;
+}
+// word k < kWideBlockHdrWords of the header this workspace packs under
+__device__ __forceinline__ uint32_t wide_block_hdr_word(uint32_t k, uint32_t mode, const uint32_t* __restrict__ hdr, uint32_t n_rows,
+                                                        uint32_t G) {
+  const bool by_position = mode == 1u;
+  switch (k) {
+    case 0: return kWideBlockMagic | mode;
+    case 1: return n_rows;   // positions of the order (it has no pads) = rows of the row blocks
+    case 2: return by_position ? kWideBlockRows : 0u;
+    case 3: return G;
+    case 4: return by_position ? 1u : 0u;
+    case 5: return by_position ? hdr[kWideHdrOrderHash] : 0u;
+    case 6: return by_position ? hdr[kWideHdrOrderHash + 1] : 0u;
+    default: return 0u;
+  }
+}
+// wrap-around sum over the positions of a mixed (position, row) word: the same for every launch shape
+__global__ __launch_bounds__(256) void wide_order_hash_kernel(const uint32_t* __restrict__ perm, uint32_t n_rows,
+                                                              unsigned long long* __restrict__ hash) {
+  unsigned long long acc = 0ull;
+  for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < n_rows; p += gridDim.x * 256u) {
+    unsigned long long x = (((unsigned long long)p << 32) | perm[p]) * 0x9E3779B97F4A7C15ull;
+    x ^= x >> 29;
+    x *= 0xBF58476D1CE4E5B9ull;
+    acc += x ^ (x >> 32);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63u) == 0 && acc != 0ull) atomicAdd(hash, acc);
+}
+__global__ __launch_bounds__(256) void wide_block_pack_kernel(const uint32_t* __restrict__ nn_idx, const float* __restrict__ nn_d2,
+                                                              const uint32_t* __restrict__ hd_idx, const float* __restrict__ hd_d2,
+                                                              uint32_t n_rows, uint32_t n_cols, uint32_t seg, uint32_t G,
+                                                              uint32_t block_rows, const uint32_t* __restrict__ perm,
+                                                              const uint32_t* __restrict__ hdr, uint32_t* __restrict__ block) {
+  const uint32_t l = blockIdx.x * 256u + threadIdx.x;
+  if (l >= block_rows) return;
+  const uint32_t mode = wide_block_mode(hdr, n_rows, n_cols);
+  const uint32_t payload = block_rows - kWideBlockHdrRows;
+  if (l >= payload) {
+    const uint32_t k = l - payload;
+    block[l] = k < kWideBlockHdrWords ? wide_block_hdr_word(k, mode, hdr, n_rows, G) : 0u;
+    for (uint32_t c = 1; c < 4; ++c) block[c * (size_t)block_rows + l] = wide_block_none(c, n_rows);
+    return;
+  }
+  uint32_t i = 0xFFFFFFFFu;
+  if (mode == 1u) {
+    const unsigned long long p = ((unsigned long long)(l / kWideBlockRows) * G + seg) * kWideBlockRows + l % kWideBlockRows;
+    if (p < n_rows) i = perm[p];
+  } else if (mode == 0u) {
+    const uint32_t rng = n_rows / G, lo = seg * rng, hi = (seg == G - 1u) ? n_rows : lo + rng;
+    if (l < hi - lo) i = lo + l;
+  }
+  const bool live = i < n_rows;
+  block[0 * (size_t)block_rows + l] = live ? nn_idx[i] : wide_block_none(0, n_rows);
+  block[1 * (size_t)block_rows + l] = live ? __float_as_uint(nn_d2[i]) : wide_block_none(1, n_rows);
+  block[2 * (size_t)block_rows + l] = live ? hd_idx[i] : wide_block_none(2, n_rows);
+  block[3 * (size_t)block_rows + l] = live ? __float_as_uint(hd_d2[i]) : wide_block_none(3, n_rows);
+}
+// Every workgroup compares the G headers with the one this workspace packs under before it scatters anything: on a
+// mismatch nothing is written; workgroup 0 records the verdict of THIS unpack (dc_hip_wide_layout_status_dev).
+__global__ __launch_bounds__(256) void wide_block_unpack_kernel(const uint32_t* __restrict__ blocks /* [G][4][block_rows] */,
+                                                                uint32_t n_rows, uint32_t n_cols, uint32_t G, uint32_t block_rows,
+                                                                const uint32_t* __restrict__ perm, uint32_t* __restrict__ hdr,
+                                                                uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2,
+                                                                uint32_t* __restrict__ hd_idx, float* __restrict__ hd_d2) {
+  __shared__ uint32_t bad_s;
+  if (threadIdx.x == 0) bad_s = 0u;
+  __syncthreads();
+  const uint32_t mode = wide_block_mode(hdr, n_rows, n_cols);
+  const uint32_t payload = block_rows - kWideBlockHdrRows;
+  if (mode == kWideBlockNoOrder && threadIdx.x == 0) bad_s = 1u;
+  for (uint32_t e = threadIdx.x; e < kWideBlockHdrWords * G; e += 256u) {
+    const uint32_t r = e / kWideBlockHdrWords, k = e - kWideBlockHdrWords * r;
+    if (blocks[(size_t)r * 4u * block_rows + payload + k] != wide_block_hdr_word(k, mode, hdr, n_rows, G)) bad_s = 1u;
+  }
+  __syncthreads();
+  const uint32_t bad = bad_s;
+  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[kWideHdrLayoutBad] = bad;
+  if (bad != 0u) return;
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_rows) return;
+  uint32_t i, r, l;
+  if (mode == 1u) {
+    const uint32_t b = p / kWideBlockRows;
+    r = b % G;
+    l = (b / G) * kWideBlockRows + p % kWideBlockRows;
+    i = perm[p];
+    if (i >= n_rows) return;
+  } else {
+    const uint32_t rng = n_rows / G;
+    i = p;
+    r = rng ? min(p / rng, G - 1u) : G - 1u;
+    l = p - r * rng;
+  }
+  const uint32_t* b = blocks + (size_t)r * 4u * block_rows;
+  nn_idx[i] = b[l];
+  nn_d2[i] = __uint_as_float(b[(size_t)block_rows + l]);
+  hd_idx[i] = b[2 * (size_t)block_rows + l];
+  hd_d2[i] = __uint_as_float(b[3 * (size_t)block_rows + l]);
+}
+// the hash of the order the workspace holds, into its header (the sum starts from zero)
+int wide_order_hash(void* d_ws, uint32_t n_rows, uint32_t n_cols, hipStream_t s) {
+  const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
+  char* p = (char*)d_ws;
+  unsigned long long* hash = (unsigned long long*)(p + 4 * kWideHdrOrderHash);
+  if (hipMemsetAsync(hash, 0, sizeof(unsigned long long), s) != hipSuccess) return -1;
+  hipLaunchKernelGGL(wide_order_hash_kernel, dim3((uint32_t)min_sz(1024, ((size_t)n_rows + 255) / 256)), dim3(256), 0, s,
+                     (const uint32_t*)(p + P.off_perm), n_rows, hash);
+  return 0;
+}
+}  // namespace
+
+size_t wide_nn_block_rows(size_t n_rows, size_t n_cols, size_t n_segments) {
+  if (!wide_mfma_supports(n_cols) || n_segments == 0 || n_rows == 0) return 0;
+  const size_t row_block = n_rows - (n_segments - 1) * (n_rows / n_segments);   // the last (largest) row block
+  const size_t blocks = (n_rows + kWideBlockRows - 1) / kWideBlockRows;
+  const size_t most = (blocks + n_segments - 1) / n_segments;   // segment 0 owns the most blocks of the order
+  const size_t by_position = most * kWideBlockRows;
+  return (row_block > by_position ? row_block : by_position) + kWideBlockHdrRows;
+}
+
+int launch_nn_block_pack_wide(const uint32_t* d_nn_idx, const float* d_nn_d2, const uint32_t* d_hd_idx, const float* d_hd_d2,
+                              uint32_t n_rows, uint32_t n_cols, uint32_t segment, uint32_t n_segments, void* d_ws, uint32_t* d_block,
+                              hipStream_t s) {
+  const uint32_t rows = (uint32_t)wide_nn_block_rows(n_rows, n_cols, n_segments);
+  if (wide_order_hash(d_ws, n_rows, n_cols, s) != 0) return -1;
+  const char* p = (const char*)d_ws;
+  hipLaunchKernelGGL(wide_block_pack_kernel, dim3((rows + 255u) / 256u), dim3(256), 0, s, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, n_rows,
+                     n_cols, segment, n_segments, rows, (const uint32_t*)(p + wide_pruned_layout(n_rows, n_cols).off_perm),
+                     (const uint32_t*)p, d_block);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_nn_block_unpack_wide(const uint32_t* d_blocks, uint32_t n_rows, uint32_t n_cols, uint32_t n_segments, void* d_ws,
+                                uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, hipStream_t s) {
+  const uint32_t rows = (uint32_t)wide_nn_block_rows(n_rows, n_cols, n_segments);
+  if (wide_order_hash(d_ws, n_rows, n_cols, s) != 0) return -1;
+  char* p = (char*)d_ws;
+  hipLaunchKernelGGL(wide_block_unpack_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, d_blocks, n_rows, n_cols, n_segments,
+                     rows, (const uint32_t*)(p + wide_pruned_layout(n_rows, n_cols).off_perm), (uint32_t*)p, d_nn_idx, d_nn_d2,
+                     d_hd_idx, d_hd_d2);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int wide_layout_status(const void* d_ws, int* mismatch, hipStream_t s) {
+  uint32_t w = 0;
+  if (hipMemcpyAsync(&w, (const char*)d_ws + 4 * kWideHdrLayoutBad, sizeof(w), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
+  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  *mismatch = w != 0u ? 1 : 0;
+  return 0;
+}
+
 int wide_prepare_against(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
                          void* d_ws, hipStream_t s) {
   return wide_prepare_against_launches(d_query, n_query, d_ref, n_ref, n_cols, d_ws, s);

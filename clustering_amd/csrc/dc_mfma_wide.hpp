@@ -83,6 +83,24 @@ int launch_nn_wide_pruned(const float* d_fe, uint32_t n_rows, uint32_t n_cols, s
 // the three counters of the last sweep back to zero (a further round in a workspace that stays prepared)
 int wide_clear_counters(void* d_ws, hipStream_t stream);
 
+// ---- neighbour blocks of a sharded run in the order of that sweep (dc_hip_neighbors_block_*_wide_dev) -----
+// Behind a segment call of launch_nn_wide_pruned in the same workspace: the rows of the query blocks segment, segment +
+// n_segments, ... compacted by local position into [4][wide_nn_block_rows] (nn_idx, nn_d2 bits, hd_idx, hd_d2 bits; pads hold
+// "none"), the last 32 entries of plane 0 being the layout header; on flagged data the reference's row block instead,
+// decided on the device from the word the sweep's gate read.  No host synchronisation; return 0 on success.
+// rows of a block: the larger of the largest segment in positions and the largest row block, plus the header; 0 if the
+// column count is not served, for no rows and for no segments
+size_t wide_nn_block_rows(size_t n_rows, size_t n_cols, size_t n_segments);
+int launch_nn_block_pack_wide(const uint32_t* d_nn_idx, const float* d_nn_d2, const uint32_t* d_hd_idx, const float* d_hd_d2,
+                              uint32_t n_rows, uint32_t n_cols, uint32_t segment, uint32_t n_segments, void* d_ws, uint32_t* d_block,
+                              hipStream_t stream);
+// [n_segments][4][wide_nn_block_rows] -> the four arrays by row.  The kernel compares the headers of all blocks with the
+// layout of this workspace first; on a mismatch it writes nothing and leaves the verdict in the header (wide_layout_status)
+int launch_nn_block_unpack_wide(const uint32_t* d_blocks, uint32_t n_rows, uint32_t n_cols, uint32_t n_segments, void* d_ws,
+                                uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, hipStream_t stream);
+// the verdict of the last unpack in the workspace (1: refused); synchronises; 0 ok, -1 a HIP error
+int wide_layout_status(const void* d_ws, int* mismatch, hipStream_t stream);
+
 // ---- the cross form: query rows against a reference (dc_hip_*_cross_wide_dev) -----------------------------
 // The same kernel in its kAgainst instances: one origin and one scale over both sets, the A form and the norms of the
 // reference, the B form and the merge words of the queries; every pair counts (no self term, no exclusion).

@@ -91,6 +91,12 @@ static_assert(kWideHdrExt >= kWideHdrExact + 2 && 4 * (kWideHdrOrder + 3) <= kWi
 constexpr uint32_t kWideHdrOrderRef = 56, kWideHdrOrderQuery = 59, kWideHdrOrderLaidOut = 62;
 constexpr uint32_t kWideOrderMarkRef = 0x57585052u, kWideOrderMarkQuery = 0x57585051u;
 static_assert(kWideHdrOrderRef >= kWideHdrOrder + 3 && 4 * (kWideHdrOrderLaidOut + 1) <= kWideInfoBytes, "the cross order's words: behind the self order's, inside the info head");
+// ... and of the neighbour blocks of a sharded run (dc_hip_neighbors_block_*_wide_dev), behind the info
+// head: the verdict of the last unpack (1: the gathered blocks were packed under different layouts, nothing was unpacked)
+// and the 64-bit hash of the order, formed by the pack and by the unpack; a preparation clears both with the header
+constexpr uint32_t kWideHdrLayoutBad = 64, kWideHdrOrderHash = 66;
+static_assert(4 * kWideHdrLayoutBad >= kWideInfoBytes && kWideHdrOrderHash % 2 == 0 && 4 * (kWideHdrOrderHash + 2) <= kHdrBytes,
+              "the block words: behind the info head, the hash 64-bit aligned, inside the header");
 constexpr float kWidePruneCellFrames = (float)kWideBlockRows;   // frames per cell of the order's grid: one block's worth
 constexpr uint32_t kWideListCap = 1024;   // surviving reference blocks a workgroup lists per scan round (4 KiB of LDS)
 static_assert(kWideListCap % 256 == 0, "a round: whole chunks of 64 boxes for each of the four waves");

@@ -17,9 +17,15 @@
 // built, falls back to the reference's own merge: every partial is copied to the host, summed / minimised
 // there and written back to every device (density_clustering_cuda.cu:171-180, :311-326) -- slower, same
 // results.  DC_SESSION_MERGE=host / rccl forces one or the other (rccl: failing to get it is an error).
+//
+// A session opened with DC_SESSION_WIDE_SWEEPS (dc_hip_session_open_flags, or DC_SESSION_WIDE=1 for the hosts that call
+// dc_hip_session_open) runs, at 65..256 columns, the pruned wide matrix-core sweeps instead of the direct kernels: device g
+// of G takes segment g of G -- every G-th query block of the wide order -- of dc_hip_*_wide_pruned_dev, and the neighbour
+// blocks are packed and unpacked in that order (dc_hip_neighbors_block_*_wide_dev); the merges are the same.
 #include "../../include/dc_density.h"
 #include "dc_common.hpp"
 #include "dc_mfma.hpp"
+#include "dc_mfma_wide.hpp"
 #include "dc_forest_host.hpp"
 
 #include <rccl/rccl.h>   // types and enums only; the functions are resolved with dlsym
@@ -124,7 +130,10 @@ struct dc_hip_session {
   bool use_rccl = false;         // partials merge with RCCL collectives
   bool host_merge = false;       // ... or through the host (RCCL unavailable, or forced)
   bool have_fe = false;
+  bool wide = false;             // DC_SESSION_WIDE_SWEEPS at 65..256 columns: the pruned wide matrix-core sweeps answer
   size_t n_radii = 0;            // of the populations currently resident
+  // a wide session: the segments of a sweep -- 0, the whole call, for one device without RCCL, else one per device
+  size_t wide_segments() const { return (dev.size() > 1 || use_rccl) ? dev.size() : 0; }
   uint64_t tiles_pop = 0, tiles_nn = 0;
   std::string merge_note;        // why RCCL is not used although there are several devices
   std::string merge_line;        // dc_hip_session_merge_note: the merge in one line
@@ -283,10 +292,28 @@ int read_counters(dc_hip_session* s, bool pop) {
     if (!d.d_ws) continue;
     SESSION_HIP_TRY(hipSetDevice(d.device));
     uint64_t a = 0, b = 0;
-    if (int rc = dc_hip_workspace_counters_dev(d.d_ws, &a, &b, d.stream)) return rc;
+    if (s->wide) {   // the evaluated tile pairs of the last wide call in the workspace: the sweep that just ran
+      if (int rc = dc_hip_wide_info_dev(d.d_ws, &a, nullptr, nullptr, d.stream)) return rc;
+      b = a;
+    } else if (int rc = dc_hip_workspace_counters_dev(d.d_ws, &a, &b, d.stream)) {
+      return rc;
+    }
     total += pop ? a : b;
   }
   (pop ? s->tiles_pop : s->tiles_nn) = total;
+  return DC_OK;
+}
+
+// a wide session: the workspace of this device holds at least what the pruned wide sweeps ask for n_radii radii
+int wide_workspace(dc_hip_session* s, DevState& d, size_t n_radii) {
+  const size_t need = dc_hip_wide_pruned_workspace_bytes(s->n_rows, s->n_cols, n_radii);
+  if (d.d_ws && d.ws_bytes >= need) return DC_OK;
+  SESSION_HIP_TRY(hipStreamSynchronize(d.stream));
+  if (d.d_ws) (void)hipFree(d.d_ws);
+  d.d_ws = nullptr;
+  d.ws_bytes = 0;
+  SESSION_HIP_TRY(hipMalloc(&d.d_ws, need));
+  d.ws_bytes = need;
   return DC_OK;
 }
 
@@ -311,8 +338,18 @@ void dc_hip_session_close(dc_hip_session* s) {
 
 int dc_hip_session_open(const float* coords, size_t n_rows, size_t n_cols, const int* devices,
                         int n_devices, dc_hip_session** out) {
+  // DC_SESSION_WIDE=1: the hosts that open their session here (the command line, the C++ shim, dc_hip_density_all) get
+  // the wide sweeps
+  const char* wide = getenv("DC_SESSION_WIDE");
+  return dc_hip_session_open_flags(coords, n_rows, n_cols, devices, n_devices,
+                                   (wide && strcmp(wide, "1") == 0) ? DC_SESSION_WIDE_SWEEPS : 0u, out);
+}
+
+int dc_hip_session_open_flags(const float* coords, size_t n_rows, size_t n_cols, const int* devices,
+                              int n_devices, unsigned flags, dc_hip_session** out) {
   if (!out) return failf(DC_ERR_INVALID_ARGUMENT, "null session pointer");
   *out = nullptr;
+  if (flags & ~DC_SESSION_WIDE_SWEEPS) return failf(DC_ERR_INVALID_ARGUMENT, "unknown session flags 0x%x", flags & ~DC_SESSION_WIDE_SWEEPS);
   if (!coords && n_rows) return failf(DC_ERR_INVALID_ARGUMENT, "null coords");
   if (n_cols == 0) return failf(DC_ERR_INVALID_ARGUMENT, "n_cols must be >= 1");
   if (n_cols > dc::kMaxColsAny) return failf(DC_ERR_TOO_LARGE, "n_cols=%zu: at most %zu columns", n_cols, dc::kMaxColsAny);
@@ -361,6 +398,7 @@ int dc_hip_session_open(const float* coords, size_t n_rows, size_t n_cols, const
   dc_hip_session* s = new dc_hip_session();
   s->n_rows = n_rows;
   s->n_cols = n_cols;
+  s->wide = (flags & DC_SESSION_WIDE_SWEEPS) != 0 && dc::wide_mfma_supports(n_cols);
   s->dev.resize(n_devices);
   for (int g = 0; g < n_devices; ++g) {
     s->dev[g].device = devices ? devices[g] : g;
@@ -394,7 +432,7 @@ int dc_hip_session_open(const float* coords, size_t n_rows, size_t n_cols, const
     SESSION_HIP_TRY(hipStreamCreate(&d.stream));
     SESSION_HIP_TRY(hipMalloc((void**)&d.d_coords, std::max<size_t>(bytes, 4)));
     if (bytes) SESSION_HIP_TRY(hipMemcpyAsync(d.d_coords, coords, bytes, hipMemcpyHostToDevice, d.stream));
-    d.ws_bytes = dc_hip_workspace_bytes(n_rows, n_cols, 1);
+    d.ws_bytes = s->wide ? dc_hip_wide_pruned_workspace_bytes(n_rows, n_cols, 1) : dc_hip_workspace_bytes(n_rows, n_cols, 1);
     if (d.ws_bytes) SESSION_HIP_TRY(hipMalloc(&d.d_ws, d.ws_bytes));
     SESSION_HIP_TRY(hipStreamSynchronize(d.stream));
     return DC_OK;
@@ -456,6 +494,7 @@ int dc_hip_session_open(const float* coords, size_t n_rows, size_t n_cols, const
 
 int dc_hip_session_devices(const dc_hip_session* s) { return s ? (int)s->dev.size() : 0; }
 int dc_hip_session_uses_rccl(const dc_hip_session* s) { return (s && s->use_rccl) ? 1 : 0; }
+int dc_hip_session_wide(const dc_hip_session* s) { return (s && s->wide) ? 1 : 0; }
 int dc_hip_session_merge_mode(const dc_hip_session* s) {
   if (!s) return kMergeNone;
   return s->use_rccl ? kMergeRccl : (s->host_merge ? kMergeHost : kMergeNone);
@@ -483,6 +522,11 @@ int dc_hip_session_populations(dc_hip_session* s, const float* radii, size_t n_r
       d.pops_cap = 0;
       SESSION_HIP_TRY(hipMalloc((void**)&d.d_pops, sizeof(uint32_t) * n_radii * n));
       d.pops_cap = n_radii;
+    }
+    if (s->wide) {
+      if (int rc = wide_workspace(s, d, n_radii)) return rc;
+      return dc_hip_populations_wide_pruned_dev(d.d_coords, n, s->n_cols, radii, n_radii, (size_t)g, s->wide_segments(), d.d_pops,
+                                                d.d_ws, d.ws_bytes, d.stream);
     }
     // (the coordinates of a session never change: after the first sweep the header statistics stay valid)
     const int r = (G == 1) ? dc_hip_populations_dev(d.d_coords, n, s->n_cols, radii, n_radii, 0, n, d.d_pops, d.d_ws,
@@ -566,12 +610,26 @@ int dc_hip_session_nearest_neighbors(dc_hip_session* s, uint32_t* nn_idx, float*
   // of packed (d2, index) words
   const char* nn_mode = getenv("DC_SESSION_NN_MERGE");
   const bool gather = !(nn_mode && strcmp(nn_mode, "allreduce") == 0);
-  const size_t block_rows = dc_hip_neighbors_block_rows(n, s->n_cols, G);
+  const size_t block_rows = s->wide ? dc_hip_neighbors_block_rows_wide(n, s->n_cols, G) : dc_hip_neighbors_block_rows(n, s->n_cols, G);
   int rc = on_every_device(s, [&](int g) -> int {
     DevState& d = s->dev[g];
     if (!d.d_idx) SESSION_HIP_TRY(hipMalloc((void**)&d.d_idx, sizeof(uint32_t) * 2 * n));
     if (!d.d_d2) SESSION_HIP_TRY(hipMalloc((void**)&d.d_d2, sizeof(float) * 2 * n));
     int r;
+    if (s->wide) {
+      if ((r = wide_workspace(s, d, 1)) != DC_OK) return r;
+      r = dc_hip_nearest_neighbors_wide_pruned_dev(d.d_coords, n, s->n_cols, d.d_fe, (size_t)g, s->wide_segments(), d.d_idx, d.d_d2,
+                                                   d.d_idx + n, d.d_d2 + n, d.d_ws, d.ws_bytes, d.stream);
+      if (r != DC_OK || s->wide_segments() == 0) return r;
+      if (gather) {   // the rows of this device's blocks of the order as a dense block, by local position
+        if (!d.d_block) SESSION_HIP_TRY(hipMalloc((void**)&d.d_block, sizeof(uint32_t) * 4 * block_rows));
+        if (!d.d_blocks) SESSION_HIP_TRY(hipMalloc((void**)&d.d_blocks, sizeof(uint32_t) * 4 * block_rows * G));
+        return dc_hip_neighbors_block_pack_wide_dev(d.d_idx, d.d_d2, d.d_idx + n, d.d_d2 + n, n, s->n_cols, (size_t)g, G, d.d_ws,
+                                                    d.ws_bytes, d.d_block, d.stream);
+      }
+      if (!d.d_words) SESSION_HIP_TRY(hipMalloc((void**)&d.d_words, sizeof(unsigned long long) * 2 * n));
+      return dc_hip_neighbors_pack_dev(d.d_idx, d.d_d2, d.d_idx + n, d.d_d2 + n, n, d.d_words, d.stream);
+    }
     if (G == 1 && !s->use_rccl) {
       r = dc_hip_nearest_neighbors_dev(d.d_coords, n, s->n_cols, d.d_fe, 0, n, d.d_idx, d.d_d2, d.d_idx + n,
                                        d.d_d2 + n, d.d_ws, d.ws_bytes, d.variant(), d.stream);
@@ -613,6 +671,9 @@ int dc_hip_session_nearest_neighbors(dc_hip_session* s, uint32_t* nn_idx, float*
     }
     rc = on_every_device(s, [&](int g) -> int {
       DevState& d = s->dev[g];
+      if (s->wide)
+        return dc_hip_neighbors_block_unpack_wide_dev(d.d_blocks, n, s->n_cols, G, d.d_ws, d.ws_bytes, d.d_idx, d.d_d2, d.d_idx + n,
+                                                      d.d_d2 + n, d.stream);
       return dc_hip_neighbors_block_unpack_dev(d.d_blocks, n, s->n_cols, G, d.d_ws, d.ws_bytes, DC_VARIANT_AUTO, d.d_idx,
                                                d.d_d2, d.d_idx + n, d.d_d2 + n, d.stream);
     });
@@ -670,9 +731,14 @@ int dc_hip_session_radius_pairs(dc_hip_session* s, float r2, uint32_t* pairs, si
   hipError_t e = hipMalloc((void**)&d_count, sizeof(unsigned long long));
   if (e == hipSuccess && capacity) e = hipMalloc((void**)&d_pairs, sizeof(uint32_t) * 2 * capacity);
   if (e != hipSuccess) rc = failf(DC_ERR_HIP, "radius pairs setup: %s", hipGetErrorString(e));
-  if (rc == DC_OK)
+  if (rc == DC_OK && s->wide) {
+    if ((rc = wide_workspace(s, d, 1)) == DC_OK)
+      rc = dc_hip_radius_pairs_wide_pruned_dev(d.d_coords, n, s->n_cols, r2, d.d_pops, d_pairs, capacity, d_count, d.d_ws,
+                                               d.ws_bytes, d.stream);
+  } else if (rc == DC_OK) {
     rc = dc_hip_radius_pairs_dev(d.d_coords, n, s->n_cols, r2, d.d_pops, d_pairs, capacity, d_count, d.d_ws,
                                  d.ws_bytes, d.stream);
+  }
   if (rc == DC_OK) {
     e = hipMemcpyAsync(count, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
@@ -712,7 +778,7 @@ int dc_hip_session_radius_forest(dc_hip_session* s, float r2, const uint32_t* ra
     if (!d.d_words) SESSION_HIP_TRY(hipMalloc((void**)&d.d_words, sizeof(unsigned long long) * 2 * n));
     SESSION_HIP_TRY(hipMemcpyAsync(d.d_rank, rank, sizeof(uint32_t) * n, hipMemcpyHostToDevice, d.stream));
     SESSION_HIP_TRY(hipStreamSynchronize(d.stream));
-    return DC_OK;
+    return s->wide ? wide_workspace(s, d, 1) : DC_OK;
   });
   if (rc != DC_OK) return rc;
   std::vector<unsigned long long> best(n);
@@ -723,6 +789,9 @@ int dc_hip_session_radius_forest(dc_hip_session* s, float r2, const uint32_t* ra
       DevState& d = s->dev[g];
       SESSION_HIP_TRY(hipMemcpyAsync(d.d_comp, forest.comp.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, d.stream));
       // (G devices: each sees the pairs of its own segment's queries; every pair is seen from both ends)
+      if (s->wide)   // (every round prepares the order again: DESIGN.md 4.27)
+        return dc_hip_radius_min_edge_wide_pruned_dev(d.d_coords, n, s->n_cols, r2, d.d_comp, d.d_rank, (size_t)g, s->wide_segments(),
+                                                      d.d_words, d.d_pops, d.d_ws, d.ws_bytes, d.stream);
       return dc_hip_radius_min_edge_segment_dev(d.d_coords, n, s->n_cols, r2, d.d_comp, d.d_rank, (size_t)g,
                                                 G > 1 ? G : 0, d.d_words, d.d_pops, d.d_ws, d.ws_bytes, d.stream);
     });

@@ -1078,6 +1078,67 @@ def unpack_neighbor_blocks(coords, blocks, n_segments, variant="auto", out=None,
     return out
 
 
+# ---- ... and the blocks of a sharded run of the pruned WIDE neighbour sweep (65..256 columns) ---------------------------
+def neighbor_block_rows_wide(n_rows, n_cols, n_segments):
+    """rows of one rank's block in the wide order (dc_hip_neighbors_block_rows_wide): the larger of the largest segment in
+    positions and the largest row block, plus the 32 header entries"""
+    return int(capi.lib.dc_hip_neighbors_block_rows_wide(n_rows, n_cols, n_segments))
+
+
+def pack_neighbor_block_wide(coords, nn_idx, nn_d2, hd_idx, hd_d2, segment, n_segments, out=None):
+    """The results of this segment's blocks of the order as a dense block int32 [4, block_rows]
+    (dc_hip_neighbors_block_pack_wide_dev); call right after nearest_neighbors_wide_pruned(coords, fe, segment, n_segments)
+    on the same device: the order and the flag of its data are read from the workspace of the pruned wide sweeps."""
+    n_rows, n_cols = _check_coords(coords)
+    rows = neighbor_block_rows_wide(n_rows, n_cols, n_segments)
+    if out is None:
+        out = torch.empty((4, rows), dtype=torch.int32, device=coords.device)
+    assert out.shape == (4, rows) and out.dtype == torch.int32 and out.is_contiguous()
+    with torch.cuda.device(coords.device):
+        ws, ws_bytes = _wide_pruned_workspace(coords.device).get(n_rows, n_cols, 1)
+        rc = capi.lib.dc_hip_neighbors_block_pack_wide_dev(_dev(nn_idx), _dev(nn_d2), _dev(hd_idx), _dev(hd_d2), n_rows, n_cols,
+                                                           segment, n_segments, ws, ws_bytes, _dev(out), _stream_ptr())
+    capi.check(rc, "dc_hip_neighbors_block_pack_wide_dev")
+    return out
+
+
+def wide_layout_status(device):
+    """True if the last dc_hip_neighbors_block_unpack_wide_dev in this device's workspace of the pruned wide sweeps REFUSED
+    its blocks (nothing was unpacked) -- dc_hip_wide_layout_status_dev; synchronises"""
+    ws = _wide_pruned_workspace(device)
+    if ws.buf is None:
+        return False
+    bad = C.c_int(0)
+    with torch.cuda.device(device):
+        capi.check(capi.lib.dc_hip_wide_layout_status_dev(_dev(ws.buf), C.byref(bad), _stream_ptr()),
+                   "dc_hip_wide_layout_status_dev")
+    return bool(bad.value)
+
+
+def unpack_neighbor_blocks_wide(coords, blocks, n_segments, out=None, check=True):
+    """blocks int32 [n_segments, 4, block_rows] gathered from all ranks -> (nn_idx, nn_d2, hd_idx, hd_d2) by frame
+    (dc_hip_neighbors_block_unpack_wide_dev), in the workspace of the pruned wide sweeps of this device, which must hold
+    the order the blocks were packed by.  The kernel compares the layout headers itself and writes nothing on a mismatch;
+    check=True asks for its verdict right away (one synchronisation) and raises, check=False leaves that to the caller
+    (wide_layout_status) -- the arrays handed out then hold what they held before (zeros if made here)."""
+    n_rows, n_cols = _check_coords(coords)
+    dev = coords.device
+    rows = neighbor_block_rows_wide(n_rows, n_cols, n_segments)
+    assert blocks.is_contiguous() and blocks.dtype == torch.int32 and blocks.numel() == n_segments * 4 * rows
+    if out is None:
+        buf = (torch.empty if check else torch.zeros)((4, n_rows), dtype=torch.int32, device=dev)
+        out = (buf[0], buf[1].view(torch.float32), buf[2], buf[3].view(torch.float32))
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _wide_pruned_workspace(dev).get(n_rows, n_cols, 1)
+        rc = capi.lib.dc_hip_neighbors_block_unpack_wide_dev(_dev(blocks), n_rows, n_cols, n_segments, ws, ws_bytes,
+                                                             _dev(out[0]), _dev(out[1]), _dev(out[2]), _dev(out[3]),
+                                                             _stream_ptr())
+    capi.check(rc, "dc_hip_neighbors_block_unpack_wide_dev")
+    if check and n_rows and wide_layout_status(dev):
+        raise RuntimeError("neighbour blocks of the ranks were packed under different layouts")
+    return out
+
+
 def compute_sigma2(nn_d2):
     """compute_sigma2 (density_clustering.cpp:334-343)."""
     out = C.c_double(0.0)
@@ -1093,7 +1154,9 @@ class Session:
     results of several devices merged on the devices over RCCL.  This is the path the C++ shim and the
     command line take; tests use it to compare the resident flow with the call-by-call one."""
 
-    def __init__(self, coords_host, n_devices=0, devices=None):
+    def __init__(self, coords_host, n_devices=0, devices=None, wide=False):
+        """wide=True: dc_hip_session_open_flags(DC_SESSION_WIDE_SWEEPS) -- at 65..256 columns the pruned wide matrix-core
+        sweeps answer; wide=False: dc_hip_session_open (which the environment's DC_SESSION_WIDE=1 turns into the same)"""
         c = np.ascontiguousarray(coords_host, dtype=np.float32)
         assert c.ndim == 2
         self.n_rows, self.n_cols = c.shape
@@ -1102,8 +1165,13 @@ class Session:
         if devices is not None:
             devs = (C.c_int * len(devices))(*devices)
             n_devices = len(devices)
-        capi.check(capi.lib.dc_hip_session_open(c.ctypes.data_as(C.c_void_p), self.n_rows, self.n_cols, devs,
-                                                n_devices, C.byref(self._h)), "dc_hip_session_open")
+        if wide:
+            capi.check(capi.lib.dc_hip_session_open_flags(c.ctypes.data_as(C.c_void_p), self.n_rows, self.n_cols, devs,
+                                                          n_devices, capi.SESSION_WIDE_SWEEPS, C.byref(self._h)),
+                       "dc_hip_session_open_flags")
+        else:
+            capi.check(capi.lib.dc_hip_session_open(c.ctypes.data_as(C.c_void_p), self.n_rows, self.n_cols, devs,
+                                                    n_devices, C.byref(self._h)), "dc_hip_session_open")
 
     def close(self):
         if self._h:
@@ -1122,6 +1190,11 @@ class Session:
     @property
     def n_devices(self):
         return int(capi.lib.dc_hip_session_devices(self._h))
+
+    @property
+    def wide(self):
+        """True if the session runs the pruned wide sweeps (the flag, and 65..256 columns): dc_hip_session_wide"""
+        return bool(capi.lib.dc_hip_session_wide(self._h))
 
     @property
     def uses_rccl(self):

@@ -463,6 +463,35 @@ DC_API int dc_hip_nearest_neighbors_wide_pruned_dev(const float* d_coords, size_
                                                     size_t segment, size_t n_segments, uint32_t* d_nn_idx, float* d_nn_d2,
                                                     uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
                                                     void* stream);
+/* ---- ... the neighbour blocks of a sharded run of it (the all-gather merge, 65..256 columns) ------------------------------
+ * The contract of dc_hip_neighbors_block_*_dev in the order of the pruned wide sweep.  Rank g of G packs, right behind its
+ * dc_hip_nearest_neighbors_wide_pruned_dev(segment g, G) and in the same workspace, the rows of the query blocks b = g
+ * (mod G) of the order, 128 positions each, by local position into d_block [4][block_rows] uint32: nn_idx, nn_d2 bits,
+ * hd_idx, hd_d2 bits; pad entries hold "none" = (n_rows + 1, FLT_MAX).  block_rows =
+ * dc_hip_neighbors_block_rows_wide(n_rows, n_cols, G): the larger of the largest segment in positions and the largest
+ * row block of the reference's partition (n_rows / G rows, the last rank takes the remainder), plus 32.  The last 32
+ * entries of plane 0 are the layout header: mark | by-position flag, positions, block size 128, segment count, deal,
+ * and a 64-bit hash of the order (words 0..6; the rest 0).  Flagged data, which the sweep answered from the direct
+ * kernel on the reference's row block: row blocks -- pack and unpack decide on the device from the word the sweep's gate
+ * left in the workspace, without a host synchronisation.
+ * The unpack takes d_blocks [G][4][block_rows], the blocks of all ranks in rank order, in a workspace that holds the
+ * same order (every rank of a run derives it from the same rows), and writes the four arrays by row.  Its kernel first
+ * compares the G headers with the layout of its own workspace: on a mismatch it writes NOTHING and records the verdict in
+ * the workspace, where dc_hip_wide_layout_status_dev reads it (*mismatch = 1; synchronises the stream); the verdict is
+ * that of the last unpack, a clean one reads 0.
+ * Errors, all before a device is touched: segment >= n_segments, n_segments == 0 and n_cols outside 65..256:
+ * DC_ERR_INVALID_ARGUMENT; a workspace smaller than dc_hip_wide_pruned_workspace_bytes(n_rows, n_cols, 1) (or none):
+ * DC_ERR_WORKSPACE; sizes: DC_ERR_TOO_LARGE as above; n_rows == 0: DC_OK.  dc_hip_neighbors_block_rows_wide is 0 outside
+ * 65..256 columns, for no rows and for no segments. */
+DC_API size_t dc_hip_neighbors_block_rows_wide(size_t n_rows, size_t n_cols, size_t n_segments);
+DC_API int dc_hip_neighbors_block_pack_wide_dev(const uint32_t* d_nn_idx, const float* d_nn_d2, const uint32_t* d_hd_idx,
+                                                const float* d_hd_d2, size_t n_rows, size_t n_cols, size_t segment,
+                                                size_t n_segments, void* d_ws, size_t ws_bytes, uint32_t* d_block,
+                                                void* stream);
+DC_API int dc_hip_neighbors_block_unpack_wide_dev(const uint32_t* d_blocks, size_t n_rows, size_t n_cols, size_t n_segments,
+                                                  void* d_ws, size_t ws_bytes, uint32_t* d_nn_idx, float* d_nn_d2,
+                                                  uint32_t* d_hd_idx, float* d_hd_d2, void* stream);
+DC_API int dc_hip_wide_layout_status_dev(const void* d_ws, int* mismatch, void* stream);
 /* ---- ... and their cross form: query frames against a reference trajectory at 65..256 columns ------------------------
  * The wide sweep over a rectangle Q x R: the contract of the "cross sweeps" block above -- populations without a self
  * term, nn[q] the lexicographic minimum of (d2, j) over ALL j with no exclusion, nn_hd[q] the same over
@@ -701,6 +730,21 @@ typedef struct dc_hip_session dc_hip_session;
  * The calling thread's current device is restored by every session entry point. */
 DC_API int dc_hip_session_open(const float* coords, size_t n_rows, size_t n_cols, const int* devices,
                                int n_devices, dc_hip_session** session);
+/* dc_hip_session_open with flags.  DC_SESSION_WIDE_SWEEPS: a session of 65..256 columns runs the pruned matrix-core
+ * sweeps of those widths instead of the direct kernels -- populations: dc_hip_populations_wide_pruned_dev; neighbours:
+ * dc_hip_nearest_neighbors_wide_pruned_dev, several devices merging by the all-gather of
+ * dc_hip_neighbors_block_pack_wide_dev blocks (DC_SESSION_NN_MERGE=allreduce: by the minimum of packed words); pair
+ * list: dc_hip_radius_pairs_wide_pruned_dev on device 0; forest: a dc_hip_radius_min_edge_wide_pruned_dev round per
+ * device -- device g of G taking segment g of G.  Same results, same rules for every call; dc_hip_session_counters
+ * then reports the evaluated tile pairs of dc_hip_wide_info_dev, summed over the devices (0 on flagged data).  Outside
+ * 65..256 columns the flag changes nothing.  Unknown bits: DC_ERR_INVALID_ARGUMENT.
+ * dc_hip_session_open is flags = 0, unless the environment holds DC_SESSION_WIDE=1, which sets DC_SESSION_WIDE_SWEEPS
+ * (hosts that open their session through it -- the command line, the C++ shim, dc_hip_density_all). */
+#define DC_SESSION_WIDE_SWEEPS 0x1u
+DC_API int dc_hip_session_open_flags(const float* coords, size_t n_rows, size_t n_cols, const int* devices,
+                                     int n_devices, unsigned flags, dc_hip_session** session);
+/* 1: the session runs the wide sweeps (the flag is set and 65 <= n_cols <= 256); else 0 */
+DC_API int dc_hip_session_wide(const dc_hip_session* session);
 DC_API void dc_hip_session_close(dc_hip_session* session);
 DC_API int dc_hip_session_devices(const dc_hip_session* session);      /* number of devices */
 DC_API int dc_hip_session_uses_rccl(const dc_hip_session* session);    /* 1 if partials merge over RCCL */
