@@ -44,21 +44,34 @@ dim3 wide_grid(uint32_t i_from, uint32_t i_to, uint32_t Tp) {
   return dim3(wide_grid_size(q_blocks, wide_shares(Tp / kWideBlockTiles)));
 }
 
+// the counting instance of a launch of n_rad radii -- one, up to four, up to kMaxRadiiPerLaunch --, timed as a population sweep
+template <SweepMode SM, bool PR>
+void launch_pop_instance(const WideKernelArgs<PR, false, PR && SM == kAgainst>& X, int n_rad, dim3 grid, hipStream_t s) {
+  sweep_timer_mark(0, true, s);
+  if (n_rad == 1)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, SM, PR>), grid, dim3(256), 0, s, X);
+  else if (n_rad <= 4)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 4, SM, PR>), grid, dim3(256), 0, s, X);
+  else
+    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, SM, PR>), grid, dim3(256), 0, s, X);
+  sweep_timer_mark(0, false, s);
+}
+// the largest fl32(r^2) of a launch: what the pruning rule of the pruned sweeps starts from
+float largest_radius2(const Rad2& rad2, int n_rad) {
+  float r2max = 0.0f;
+  for (int k = 0; k < n_rad; ++k) r2max = rad2.v[k] > r2max ? rad2.v[k] : r2max;
+  return r2max;
+}
+// a segment count as the kernels take it: clamped to 32 bits
+uint32_t segments_u32(size_t n_segments) { return (uint32_t)(n_segments < 0xFFFFFFFFull ? n_segments : 0xFFFFFFFFull); }
+
 // the counting sweep of the queries X.i_from .. X.i_to, for the rows of one array (kSelf) or against a reference
 template <SweepMode SM>
 void pop_wide(WideArgs X, const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, hipStream_t s) {
   X.rad2 = rad2;
   X.n_rad = n_rad;
   X.pops = d_pops_first_row;
-  const dim3 grid = wide_grid(X.i_from, X.i_to, X.Tp);
-  sweep_timer_mark(0, true, s);
-  if (n_rad == 1)
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, SM>), grid, dim3(256), 0, s, X);
-  else if (n_rad <= 4)
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 4, SM>), grid, dim3(256), 0, s, X);
-  else
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, SM>), grid, dim3(256), 0, s, X);
-  sweep_timer_mark(0, false, s);
+  launch_pop_instance<SM, false>(X, n_rad, wide_grid(X.i_from, X.i_to, X.Tp), s);
 }
 
 // ... and the neighbour sweep (X.fe / X.q_fe set by the caller); n_q: the rows of the query array, whose merge words
@@ -196,10 +209,8 @@ int wide_pruned_args(const WidePrunedLayout& P, uint32_t n_rows, uint32_t n_cols
   X.pops = cnt;
   X.boxes = (const float4*)(p + P.off_boxes);
   X.seg = (uint32_t)segment;
-  X.n_seg = (uint32_t)(n_segments < 0xFFFFFFFFull ? n_segments : 0xFFFFFFFFull);
-  float r2max = 0.0f;
-  for (int k = 0; k < n_rad; ++k) r2max = rad2.v[k] > r2max ? rad2.v[k] : r2max;
-  X.far2 = wide_prune_far2(r2max);
+  X.n_seg = segments_u32(n_segments);
+  X.far2 = wide_prune_far2(largest_radius2(rad2, n_rad));
   X.perm = (const uint32_t*)(p + P.off_perm);
   const uint32_t q_blocks = (uint32_t)((P.blocks - segment + n_segments - 1) / n_segments);
   *grid = dim3(wide_grid_size(q_blocks, wide_shares(P.blocks)));
@@ -223,14 +234,7 @@ int launch_pop_wide_pruned(uint32_t n_rows, uint32_t n_cols, size_t segment, siz
   WidePrunedArgs X;
   dim3 grid;
   if (wide_pruned_args(P, n_rows, n_cols, segment, n_segments, rad2, n_rad, d_ws, s, &X, &grid) != 0) return -1;
-  sweep_timer_mark(0, true, s);
-  if (n_rad == 1)
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, kSelf, true>), grid, dim3(256), 0, s, X);
-  else if (n_rad <= 4)
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 4, kSelf, true>), grid, dim3(256), 0, s, X);
-  else
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, kSelf, true>), grid, dim3(256), 0, s, X);
-  sweep_timer_mark(0, false, s);
+  launch_pop_instance<kSelf, true>(X, n_rad, grid, s);
   return wide_pruned_scatter(P, n_rows, n_rad, d_pops_first_row, d_ws, s);
 }
 
@@ -297,7 +301,7 @@ int launch_nn_wide_pruned(const float* d_fe, uint32_t n_rows, uint32_t n_cols, s
   X.fe = fe_o;
   X.boxes = (const float4*)(p + P.off_boxes);
   X.seg = (uint32_t)segment;
-  X.n_seg = (uint32_t)(n_segments < 0xFFFFFFFFull ? n_segments : 0xFFFFFFFFull);
+  X.n_seg = segments_u32(n_segments);
   X.perm = (const uint32_t*)(p + P.off_perm);
   X.far2_nn = far2;
   X.far2_hd = far2 + P.blocks;
@@ -627,18 +631,9 @@ int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_co
   X.qboxes = (const float4*)(p + P.off_boxes_q);
   X.seg = 0;
   X.n_seg = 1;
-  float r2max = 0.0f;
-  for (int k = 0; k < n_rad; ++k) r2max = rad2.v[k] > r2max ? rad2.v[k] : r2max;
-  X.far2 = wide_prune_far2(r2max);
-  const dim3 grid(wide_grid_size((n_q + kWideBlockRows - 1u) / kWideBlockRows, wide_shares(P.blocks_r)));
-  sweep_timer_mark(0, true, s);
-  if (n_rad == 1)
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, kAgainst, true>), grid, dim3(256), 0, s, X);
-  else if (n_rad <= 4)
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 4, kAgainst, true>), grid, dim3(256), 0, s, X);
-  else
-    hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, kAgainst, true>), grid, dim3(256), 0, s, X);
-  sweep_timer_mark(0, false, s);
+  X.far2 = wide_prune_far2(largest_radius2(rad2, n_rad));
+  launch_pop_instance<kAgainst, true>(X, n_rad, dim3(wide_grid_size((n_q + kWideBlockRows - 1u) / kWideBlockRows, wide_shares(P.blocks_r))),
+                                      s);
   hipLaunchKernelGGL(wide_prune_scatter_kernel, dim3((n_q + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,
                      (const uint32_t*)(p + P.off_perm_q), (const uint32_t*)cnt, n_q, n_rad, d_pops_first_row, n_query);
   return hipGetLastError() == hipSuccess ? 0 : -1;

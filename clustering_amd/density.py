@@ -6,6 +6,7 @@ clustering_amd.distributed, torch.distributed.  All compute goes through
 libdcdensity.so; nothing in this package computes distances on the CPU or in torch.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -32,43 +33,29 @@ def _dev(t):
     return C.c_void_p(t.data_ptr())
 
 
-def _self_bytes(n_rows, n_cols, n_radii=1):
-    return capi.lib.dc_hip_workspace_bytes(n_rows, n_cols, n_radii)
-
-
-def _cross_bytes(n_q, n_ref, n_cols):
-    return capi.lib.dc_hip_cross_workspace_bytes(n_q, n_ref, n_cols)
-
-
-def _cross_pruned_bytes(n_q, n_ref, n_cols):
-    return capi.lib.dc_hip_cross_workspace_bytes_for(n_q, n_ref, n_cols, capi.VARIANT_CROSS_PRUNED)
-
-
-def _nearest_pruned_bytes(n_q, n_ref, n_cols):
-    return capi.lib.dc_hip_nearest_cross_pruned_workspace_bytes(n_q, n_ref, n_cols)
-
-
-def _wide_bytes(n_rows, n_cols, n_radii=1):
-    return capi.lib.dc_hip_wide_workspace_bytes(n_rows, n_cols, n_radii)
-
-
-def _wide_pruned_bytes(n_rows, n_cols, n_radii=1):
-    return capi.lib.dc_hip_wide_pruned_workspace_bytes(n_rows, n_cols, n_radii)
-
-
-def _wide_against_bytes(n_q, n_ref, n_cols, n_radii=1):
-    return capi.lib.dc_hip_cross_wide_workspace_bytes(n_q, n_ref, n_cols, n_radii)
-
-
-def _wide_against_pruned_bytes(n_q, n_ref, n_cols, n_radii=1):
-    return capi.lib.dc_hip_cross_wide_pruned_workspace_bytes(n_q, n_ref, n_cols, n_radii)
+# The cached workspaces, by kind: the library's byte count for a call's shape -- (n_rows, n_cols[, n_radii]) for the self
+# sweeps, (n_q, n_ref, n_cols[, n_radii]) for the sweeps against a reference.  A new kind of sweep is one more row.
+_SIZES = {
+    "self": capi.lib.dc_hip_workspace_bytes,
+    "cross": lambda n_q, n_ref, n_cols, n_radii=1: capi.lib.dc_hip_cross_workspace_bytes(n_q, n_ref, n_cols),
+    # ... of variant="cross_pruned" (the larger layout of its two orders)
+    "cross_pruned": lambda n_q, n_ref, n_cols, n_radii=1: capi.lib.dc_hip_cross_workspace_bytes_for(
+        n_q, n_ref, n_cols, capi.VARIANT_CROSS_PRUNED),
+    # ... of nearest_reference(pruned=True)
+    "nearest_pruned": lambda n_q, n_ref, n_cols, n_radii=1: capi.lib.dc_hip_nearest_cross_pruned_workspace_bytes(n_q, n_ref, n_cols),
+    # the matrix-core sweeps for rows of 65..256 columns, their pruned form, their cross form and its pruned form
+    "wide": capi.lib.dc_hip_wide_workspace_bytes,
+    "wide_pruned": capi.lib.dc_hip_wide_pruned_workspace_bytes,
+    "wide_against": capi.lib.dc_hip_cross_wide_workspace_bytes,
+    "wide_against_pruned": capi.lib.dc_hip_cross_wide_pruned_workspace_bytes,
+}
 
 
 class Workspace:
     """Device scratch of one kind of sweep (MFMA operand images); grown on demand, reused across calls.
     ``size`` is the library's byte count for a call's shape: get(*shape) asks it and returns (pointer, bytes)."""
 
-    def __init__(self, device, size=_self_bytes):
+    def __init__(self, device, size=_SIZES["self"]):
         self.device = device
         self.size = size
         self.buf = None
@@ -82,55 +69,38 @@ class Workspace:
         return _dev(self.buf), int(self.buf.numel())
 
 
-_workspaces = {}        # self sweeps, per device
-_cross_workspaces = {}  # sweeps against a reference, per device
-_cross_pruned_workspaces = {}  # ... of variant="cross_pruned" (the larger layout of its two orders), per device
-_nearest_pruned_workspaces = {}  # ... of nearest_reference(pruned=True), per device
-_wide_workspaces = {}   # the matrix-core sweeps for rows of 65..256 columns, per device
-_wide_pruned_workspaces = {}   # ... of the pruned self population sweep (calculate_populations_wide_pruned), per device
-_wide_pruned_shapes = {}       # ... and the shape of the last call in each, which wide_pruned_order asks the order of
-_wide_against_workspaces = {}  # ... of their cross form (calculate_populations_against_wide, nearest_reference_wide), per device
-_wide_against_pruned_workspaces = {}   # ... of the pruned cross population sweep (calculate_populations_against_wide_pruned), per device
-_wide_against_pruned_shapes = {}       # ... and (rows of the query range, n_ref, n_cols) of the last call in each
+_caches = {kind: {} for kind in _SIZES}   # kind -> device -> Workspace
+_shapes = {kind: {} for kind in _SIZES}   # kind -> device -> the shape of the last call that passed capi.check (the pruned
+#                                           wide kinds record it: their order readers ask the library for that shape)
 
 
-def _cached(cache, device, size):
+def _cached(kind, device):
     key = str(device)
-    if key not in cache:
-        cache[key] = Workspace(device, size)
-    return cache[key]
+    if key not in _caches[kind]:
+        _caches[kind][key] = Workspace(device, _SIZES[kind])
+    return _caches[kind][key]
 
 
-def _workspace(device):
-    return _cached(_workspaces, device, _self_bytes)
+def _get(kind, device, *shape):
+    """(pointer, bytes) of the cached workspace of one kind for a call's shape.  A cross-wide call with an empty side needs
+    no workspace; it gets the cached buffer, if there is one, so that the info reader of its kind reports that nothing was
+    swept rather than the call before."""
+    cache = _cached(kind, device)
+    ws, ws_bytes = cache.get(*shape)
+    if ws_bytes == 0 and cache.buf is not None and kind in ("wide_against", "wide_against_pruned"):
+        return _dev(cache.buf), int(cache.buf.numel())
+    return ws, ws_bytes
 
 
-def _cross_workspace(device):
-    return _cached(_cross_workspaces, device, _cross_bytes)
-
-
-def _cross_pruned_workspace(device):
-    return _cached(_cross_pruned_workspaces, device, _cross_pruned_bytes)
-
-
-def _nearest_pruned_workspace(device):
-    return _cached(_nearest_pruned_workspaces, device, _nearest_pruned_bytes)
-
-
-def _wide_workspace(device):
-    return _cached(_wide_workspaces, device, _wide_bytes)
-
-
-def _wide_pruned_workspace(device):
-    return _cached(_wide_pruned_workspaces, device, _wide_pruned_bytes)
-
-
-def _wide_against_workspace(device):
-    return _cached(_wide_against_workspaces, device, _wide_against_bytes)
-
-
-def _wide_against_pruned_workspace(device):
-    return _cached(_wide_against_pruned_workspaces, device, _wide_against_pruned_bytes)
+# (the names tests and tools reach into: lookups into the registry)
+_workspace = functools.partial(_cached, "self")
+_cross_workspace = functools.partial(_cached, "cross")
+_cross_pruned_workspace = functools.partial(_cached, "cross_pruned")
+_wide_workspace = functools.partial(_cached, "wide")
+_wide_pruned_workspace = functools.partial(_cached, "wide_pruned")
+_wide_against_pruned_workspace = functools.partial(_cached, "wide_against_pruned")
+_cross_pruned_workspaces = _caches["cross_pruned"]
+_nearest_pruned_workspaces = _caches["nearest_pruned"]
 
 
 def _variant(variant, stats_valid):
@@ -156,6 +126,45 @@ def _ascending(rad, out):
     return np.ascontiguousarray(rad[order]), torch.empty_like(out), torch.from_numpy(order).to(out.device)
 
 
+def _populations(fn, kind, device, head, sizes, radii, span, out, variant=None, ascending=False):
+    """One population call of the library function ``fn`` in the cached workspace of ``kind``.  head: the leading C
+    arguments (the arrays and their sizes); sizes: the shape the workspace is sized for, the rows of the result first;
+    span: the row range or the segment; variant: the C ``variant`` argument of the calls that take one.  Only the narrow
+    calls reorder their radii (ascending=True); the others pass the caller's order.  -> int32 [n_radii, sizes[0]]"""
+    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    if out is None:
+        out = torch.empty((rad.size, sizes[0]), dtype=torch.int32, device=device)
+    assert out.shape == (rad.size, sizes[0]) and out.dtype == torch.int32 and out.is_contiguous()
+    rad_call, dst, order = _ascending(rad, out) if ascending else (rad, out, None)
+    with torch.cuda.device(device):
+        ws, ws_bytes = _get(kind, device, *sizes, rad.size)
+        rc = getattr(capi.lib, fn)(*head, rad_call.ctypes.data_as(C.POINTER(C.c_float)), rad.size, *span, _dev(dst), ws, ws_bytes,
+                                   *(() if variant is None else (variant,)), _stream_ptr())
+    capi.check(rc, fn)
+    if order is not None:
+        out[order] = dst
+    return out
+
+
+def _neighbors(fn, kind, coords, fe, span, variant=None):
+    """One self-neighbour call of ``fn`` in the cached workspace of ``kind``, like _populations; a row range may leave its
+    end open (None: n_rows).  -> (nn_idx int32, nn_d2 float32, hd_idx int32, hd_d2 float32), each [n_rows]"""
+    n_rows, n_cols = _check_coords(coords)
+    span = (span[0], n_rows if span[1] is None else span[1])
+    assert fe.is_cuda and fe.dtype == torch.float32 and fe.shape == (n_rows,) and fe.is_contiguous()
+    dev = coords.device
+    nn_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    hd_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    nn_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    hd_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _get(kind, dev, n_rows, n_cols, 1)
+        rc = getattr(capi.lib, fn)(_dev(coords), n_rows, n_cols, _dev(fe), *span, _dev(nn_idx), _dev(nn_d2), _dev(hd_idx),
+                                   _dev(hd_d2), ws, ws_bytes, *(() if variant is None else (variant,)), _stream_ptr())
+    capi.check(rc, fn)
+    return nn_idx, nn_d2, hd_idx, hd_d2
+
+
 def calculate_populations_partial(coords, radii, i_from=0, i_to=None, variant="auto", out=None, stats_valid=False):
     """Per-GPU partial of calculate_populations (density_clustering_cuda.cu:45-137).
 
@@ -165,21 +174,8 @@ def calculate_populations_partial(coords, radii, i_from=0, i_to=None, variant="a
     zero outside [i_from, i_to).
     """
     n_rows, n_cols = _check_coords(coords)
-    i_to = n_rows if i_to is None else i_to
-    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
-    if out is None:
-        out = torch.empty((rad.size, n_rows), dtype=torch.int32, device=coords.device)
-    assert out.shape == (rad.size, n_rows) and out.dtype == torch.int32 and out.is_contiguous()
-    rad_call, dst, order = _ascending(rad, out)
-    with torch.cuda.device(coords.device):
-        ws, ws_bytes = _workspace(coords.device).get(n_rows, n_cols, rad.size)
-        rc = capi.lib.dc_hip_populations_dev(
-            _dev(coords), n_rows, n_cols, rad_call.ctypes.data_as(C.POINTER(C.c_float)), rad.size,
-            i_from, i_to, _dev(dst), ws, ws_bytes, _variant(variant, stats_valid), _stream_ptr())
-    capi.check(rc, "dc_hip_populations_dev")
-    if order is not None:
-        out[order] = dst
-    return out
+    return _populations("dc_hip_populations_dev", "self", coords.device, (_dev(coords), n_rows, n_cols), (n_rows, n_cols), radii,
+                        (i_from, n_rows if i_to is None else i_to), out, _variant(variant, stats_valid), ascending=True)
 
 
 def calculate_populations_segment(coords, radii, segment, n_segments, variant="auto", out=None, stats_valid=False):
@@ -188,39 +184,15 @@ def calculate_populations_segment(coords, radii, segment, n_segments, variant="a
     that merge by summation over the segments (a one-radius pruned sweep is symmetric -- it credits both frames
     of a pair -- so a segment's counts cover all rows; the other sweeps leave zeros outside the segment)."""
     n_rows, n_cols = _check_coords(coords)
-    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
-    if out is None:
-        out = torch.empty((rad.size, n_rows), dtype=torch.int32, device=coords.device)
-    assert out.shape == (rad.size, n_rows) and out.dtype == torch.int32 and out.is_contiguous()
-    rad_call, dst, order = _ascending(rad, out)
-    with torch.cuda.device(coords.device):
-        ws, ws_bytes = _workspace(coords.device).get(n_rows, n_cols, rad.size)
-        rc = capi.lib.dc_hip_populations_segment_dev(
-            _dev(coords), n_rows, n_cols, rad_call.ctypes.data_as(C.POINTER(C.c_float)), rad.size,
-            segment, n_segments, _dev(dst), ws, ws_bytes, _variant(variant, stats_valid), _stream_ptr())
-    capi.check(rc, "dc_hip_populations_segment_dev")
-    if order is not None:
-        out[order] = dst
-    return out
+    return _populations("dc_hip_populations_segment_dev", "self", coords.device, (_dev(coords), n_rows, n_cols), (n_rows, n_cols),
+                        radii, (segment, n_segments), out, _variant(variant, stats_valid), ascending=True)
 
 
 def nearest_neighbors_segment(coords, fe, segment, n_segments, variant="auto", stats_valid=False):
     """Neighbours of one segment of a sharded run (dc_hip_nearest_neighbors_segment_dev); the rows of
     other segments hold (n_rows+1, FLT_MAX)."""
-    n_rows, n_cols = _check_coords(coords)
-    assert fe.is_cuda and fe.dtype == torch.float32 and fe.shape == (n_rows,) and fe.is_contiguous()
-    dev = coords.device
-    nn_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    hd_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    nn_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    hd_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _workspace(dev).get(n_rows, n_cols, 1)
-        rc = capi.lib.dc_hip_nearest_neighbors_segment_dev(
-            _dev(coords), n_rows, n_cols, _dev(fe), segment, n_segments, _dev(nn_idx), _dev(nn_d2),
-            _dev(hd_idx), _dev(hd_d2), ws, ws_bytes, _variant(variant, stats_valid), _stream_ptr())
-    capi.check(rc, "dc_hip_nearest_neighbors_segment_dev")
-    return nn_idx, nn_d2, hd_idx, hd_d2
+    return _neighbors("dc_hip_nearest_neighbors_segment_dev", "self", coords, fe, (segment, n_segments),
+                      _variant(variant, stats_valid))
 
 
 def calculate_free_energies(pops):
@@ -240,21 +212,7 @@ def nearest_neighbors_partial(coords, fe, i_from=0, i_to=None, variant="auto", s
 
     -> (nn_idx int32, nn_d2 float32, hd_idx int32, hd_d2 float32), each [n_rows]; rows outside the
     range hold the reference's "none" value (n_rows+1, FLT_MAX)."""
-    n_rows, n_cols = _check_coords(coords)
-    i_to = n_rows if i_to is None else i_to
-    assert fe.is_cuda and fe.dtype == torch.float32 and fe.shape == (n_rows,) and fe.is_contiguous()
-    dev = coords.device
-    nn_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    hd_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    nn_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    hd_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _workspace(dev).get(n_rows, n_cols, 1)
-        rc = capi.lib.dc_hip_nearest_neighbors_dev(
-            _dev(coords), n_rows, n_cols, _dev(fe), i_from, i_to, _dev(nn_idx), _dev(nn_d2),
-            _dev(hd_idx), _dev(hd_d2), ws, ws_bytes, _variant(variant, stats_valid), _stream_ptr())
-    capi.check(rc, "dc_hip_nearest_neighbors_dev")
-    return nn_idx, nn_d2, hd_idx, hd_d2
+    return _neighbors("dc_hip_nearest_neighbors_dev", "self", coords, fe, (i_from, i_to), _variant(variant, stats_valid))
 
 
 # ---- matrix-core sweeps for rows of 65..256 columns (include/dc_density.h "wide" sweeps) ---------------------------
@@ -263,45 +221,19 @@ def calculate_populations_wide(coords, radii, i_from=0, i_to=None, out=None):
     the same populations bit for bit, one matrix-core chain per tile pair for all radii (up to 8 per launch), radii in
     any order, in a cached workspace of its own (wide_sweep_info reads its counters).  Other column counts raise."""
     n_rows, n_cols = _check_coords(coords)
-    i_to = n_rows if i_to is None else i_to
-    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
-    if out is None:
-        out = torch.empty((rad.size, n_rows), dtype=torch.int32, device=coords.device)
-    assert out.shape == (rad.size, n_rows) and out.dtype == torch.int32 and out.is_contiguous()
-    with torch.cuda.device(coords.device):
-        ws, ws_bytes = _wide_workspace(coords.device).get(n_rows, n_cols, rad.size)
-        rc = capi.lib.dc_hip_populations_wide_dev(
-            _dev(coords), n_rows, n_cols, rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size, i_from, i_to, _dev(out),
-            ws, ws_bytes, _stream_ptr())
-    capi.check(rc, "dc_hip_populations_wide_dev")
-    return out
+    return _populations("dc_hip_populations_wide_dev", "wide", coords.device, (_dev(coords), n_rows, n_cols), (n_rows, n_cols),
+                        radii, (i_from, n_rows if i_to is None else i_to), out)
 
 
 def nearest_neighbors_wide(coords, fe, i_from=0, i_to=None):
     """nearest_neighbors_partial for rows of 65..256 columns on the matrix cores (dc_hip_nearest_neighbors_wide_dev).
     -> (nn_idx int32, nn_d2 float32, hd_idx int32, hd_d2 float32), each [n_rows]; "none" is (n_rows+1, FLT_MAX)."""
-    n_rows, n_cols = _check_coords(coords)
-    i_to = n_rows if i_to is None else i_to
-    assert fe.is_cuda and fe.dtype == torch.float32 and fe.shape == (n_rows,) and fe.is_contiguous()
-    dev = coords.device
-    nn_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    hd_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    nn_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    hd_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _wide_workspace(dev).get(n_rows, n_cols, 1)
-        rc = capi.lib.dc_hip_nearest_neighbors_wide_dev(
-            _dev(coords), n_rows, n_cols, _dev(fe), i_from, i_to, _dev(nn_idx), _dev(nn_d2), _dev(hd_idx), _dev(hd_d2),
-            ws, ws_bytes, _stream_ptr())
-    capi.check(rc, "dc_hip_nearest_neighbors_wide_dev")
-    return nn_idx, nn_d2, hd_idx, hd_d2
+    return _neighbors("dc_hip_nearest_neighbors_wide_dev", "wide", coords, fe, (i_from, i_to))
 
 
-def wide_sweep_info(device):
-    """(tiles, mfmas, exact_pairs): 32x32 frame-pair tiles evaluated, MFMA instructions issued and frame pairs sent
-    to the exact path by the last wide sweep on this device (dc_hip_wide_info_dev); (0, 0, 0) when the direct
-    kernels answered (flagged data), nothing was swept, or no wide sweep has run."""
-    ws = _wide_workspace(device)
+def _wide_info(kind, device):
+    """(tiles, mfmas, exact_pairs) from the head of this device's workspace of ``kind`` (dc_hip_wide_info_dev)"""
+    ws = _cached(kind, device)
     if ws.buf is None:
         return 0, 0, 0
     t, m, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
@@ -309,6 +241,13 @@ def wide_sweep_info(device):
         capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
                    "dc_hip_wide_info_dev")
     return int(t.value), int(m.value), int(e.value)
+
+
+def wide_sweep_info(device):
+    """(tiles, mfmas, exact_pairs): 32x32 frame-pair tiles evaluated, MFMA instructions issued and frame pairs sent
+    to the exact path by the last wide sweep on this device (dc_hip_wide_info_dev); (0, 0, 0) when the direct
+    kernels answered (flagged data), nothing was swept, or no wide sweep has run."""
+    return _wide_info("wide", device)
 
 
 # ---- ... the pruned self population sweep (include/dc_density.h, the PRUNED wide sweep) ------------------------------
@@ -318,17 +257,9 @@ def calculate_populations_wide_pruned(coords, radii, segment=0, n_segments=0, ou
     otherwise the query blocks segment, segment + n_segments, ... of the spatial order (wide_pruned_order): final counts
     for their rows, zeros elsewhere.  In a cached workspace of its own (wide_pruned_info reads its counters)."""
     n_rows, n_cols = _check_coords(coords)
-    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
-    if out is None:
-        out = torch.empty((rad.size, n_rows), dtype=torch.int32, device=coords.device)
-    assert out.shape == (rad.size, n_rows) and out.dtype == torch.int32 and out.is_contiguous()
-    with torch.cuda.device(coords.device):
-        ws, ws_bytes = _wide_pruned_workspace(coords.device).get(n_rows, n_cols, rad.size)
-        rc = capi.lib.dc_hip_populations_wide_pruned_dev(
-            _dev(coords), n_rows, n_cols, rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size, segment, n_segments,
-            _dev(out), ws, ws_bytes, _stream_ptr())
-    capi.check(rc, "dc_hip_populations_wide_pruned_dev")
-    _wide_pruned_shapes[str(coords.device)] = (n_rows, n_cols)
+    out = _populations("dc_hip_populations_wide_pruned_dev", "wide_pruned", coords.device, (_dev(coords), n_rows, n_cols),
+                       (n_rows, n_cols), radii, (segment, n_segments), out)
+    _shapes["wide_pruned"][str(coords.device)] = (n_rows, n_cols)
     return out
 
 
@@ -338,41 +269,22 @@ def nearest_neighbors_wide_pruned(coords, fe, segment=0, n_segments=0):
     (segment is not read); otherwise the query blocks segment, segment + n_segments, ... of the order
     (wide_pruned_order): final results on their rows, "none" elsewhere.  In the cached workspace of the pruned wide
     sweeps (wide_pruned_info reads its counters, wide_pruned_order its order)."""
-    n_rows, n_cols = _check_coords(coords)
-    assert fe.is_cuda and fe.dtype == torch.float32 and fe.shape == (n_rows,) and fe.is_contiguous()
-    dev = coords.device
-    nn_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    hd_idx = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    nn_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    hd_d2 = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _wide_pruned_workspace(dev).get(n_rows, n_cols, 1)
-        rc = capi.lib.dc_hip_nearest_neighbors_wide_pruned_dev(
-            _dev(coords), n_rows, n_cols, _dev(fe), segment, n_segments, _dev(nn_idx), _dev(nn_d2), _dev(hd_idx), _dev(hd_d2),
-            ws, ws_bytes, _stream_ptr())
-    capi.check(rc, "dc_hip_nearest_neighbors_wide_pruned_dev")
-    _wide_pruned_shapes[str(dev)] = (n_rows, n_cols)
-    return nn_idx, nn_d2, hd_idx, hd_d2
+    out = _neighbors("dc_hip_nearest_neighbors_wide_pruned_dev", "wide_pruned", coords, fe, (segment, n_segments))
+    _shapes["wide_pruned"][str(coords.device)] = tuple(coords.shape)
+    return out
 
 
 def wide_pruned_info(device):
     """(tiles, mfmas, exact_pairs) of the last calculate_populations_wide_pruned on this device, as wide_sweep_info
     gives them; the tile pairs are the evaluated ones.  (0, 0, 0) when the direct kernel answered (flagged data), the
     segment held no block, or no such sweep has run."""
-    ws = _wide_pruned_workspace(device)
-    if ws.buf is None:
-        return 0, 0, 0
-    t, m, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    with torch.cuda.device(device):
-        capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
-                   "dc_hip_wide_info_dev")
-    return int(t.value), int(m.value), int(e.value)
+    return _wide_info("wide_pruned", device)
 
 
 def wide_pruned_order(device):
     """the spatial order of the last calculate_populations_wide_pruned on this device: int32 [n_rows], position -> row
     (block b of the order: positions 128 b .. 128 b + 127) (dc_hip_wide_pruned_order_dev)."""
-    ws, shape = _wide_pruned_workspace(device), _wide_pruned_shapes.get(str(device))
+    ws, shape = _cached("wide_pruned", device), _shapes["wide_pruned"].get(str(device))
     if ws.buf is None or shape is None:
         raise ValueError("no pruned wide sweep has run on this device")
     perm = torch.empty(shape[0], dtype=torch.int32, device=device)
@@ -391,6 +303,39 @@ def _check_pair(queries, reference):
     return n_q, n_ref, n_cols
 
 
+def _populations_against(fn, kind, queries, reference, sizes, radii, i_from, i_to, out, variant=None, ascending=False):
+    """_populations for the query frames [i_from, i_to) in a reference; sizes: (n_q, n_ref, n_cols), checked by the caller"""
+    n_q, n_ref, n_cols = sizes
+    return _populations(fn, kind, queries.device, (_dev(queries), n_q, _dev(reference), n_ref, n_cols), sizes, radii,
+                        (i_from, n_q if i_to is None else i_to), out, variant, ascending)
+
+
+def _nearest(fn, kind, queries, reference, sizes, fe_query, fe_ref, i_from, i_to, variant=None):
+    """One cross-neighbour call of ``fn`` in the cached workspace of ``kind``; sizes: (n_q, n_ref, n_cols), checked by the
+    caller.  -> (nn_idx int32, nn_d2 float32, hd_idx, hd_d2), each [n_q]; without free energies hd_idx / hd_d2 are None"""
+    n_q, n_ref, n_cols = sizes
+    i_to = n_q if i_to is None else i_to
+    with_fe = fe_query is not None
+    if with_fe:
+        assert fe_ref is not None
+        for f, n in ((fe_query, n_q), (fe_ref, n_ref)):
+            assert f.is_cuda and f.dtype == torch.float32 and f.shape == (n,) and f.is_contiguous()
+    dev = queries.device
+    nn_idx = torch.empty(n_q, dtype=torch.int32, device=dev)
+    nn_d2 = torch.empty(n_q, dtype=torch.float32, device=dev)
+    hd_idx = torch.empty(n_q, dtype=torch.int32, device=dev) if with_fe else None
+    hd_d2 = torch.empty(n_q, dtype=torch.float32, device=dev) if with_fe else None
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _get(kind, dev, n_q, n_ref, n_cols, 1)
+        rc = getattr(capi.lib, fn)(
+            _dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
+            _dev(fe_ref) if with_fe else None, i_from, i_to, _dev(nn_idx), _dev(nn_d2),
+            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None, ws, ws_bytes,
+            *(() if variant is None else (variant,)), _stream_ptr())
+    capi.check(rc, fn)
+    return nn_idx, nn_d2, hd_idx, hd_d2
+
+
 def calculate_populations_against(queries, reference, radii, i_from=0, i_to=None, variant="auto", out=None):
     """Populations of the query frames in the reference trajectory (dc_hip_populations_cross_dev):
     pops[r][q] = #{ j : d2(Q_q, R_j) < r^2 } -- no self term, so a copy of reference frame j gets pop_R(j).
@@ -398,23 +343,9 @@ def calculate_populations_against(queries, reference, radii, i_from=0, i_to=None
     -> torch.int32 [n_radii, n_q] in the order of ``radii``, zero outside [i_from, i_to).
     variant="cross_pruned" (n_cols <= 64): the matrix-core sweep with tile-pair pruning, in a workspace of its own
     (evaluated_tiles_against reads its counters); the same results."""
-    n_q, n_ref, n_cols = _check_pair(queries, reference)
-    i_to = n_q if i_to is None else i_to
-    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
-    if out is None:
-        out = torch.empty((rad.size, n_q), dtype=torch.int32, device=queries.device)
-    assert out.shape == (rad.size, n_q) and out.dtype == torch.int32 and out.is_contiguous()
-    rad_call, dst, order = _ascending(rad, out)
-    with torch.cuda.device(queries.device):
-        cache = _cross_pruned_workspace if variant == "cross_pruned" else _cross_workspace
-        ws, ws_bytes = cache(queries.device).get(n_q, n_ref, n_cols)
-        rc = capi.lib.dc_hip_populations_cross_dev(
-            _dev(queries), n_q, _dev(reference), n_ref, n_cols, rad_call.ctypes.data_as(C.POINTER(C.c_float)),
-            rad.size, i_from, i_to, _dev(dst), ws, ws_bytes, capi.VARIANTS[variant], _stream_ptr())
-    capi.check(rc, "dc_hip_populations_cross_dev")
-    if order is not None:
-        out[order] = dst
-    return out
+    return _populations_against("dc_hip_populations_cross_dev", "cross_pruned" if variant == "cross_pruned" else "cross", queries,
+                                reference, _check_pair(queries, reference), radii, i_from, i_to, out, capi.VARIANTS[variant],
+                                ascending=True)
 
 
 def calculate_free_energies_against(pops, max_pop):
@@ -439,30 +370,12 @@ def nearest_reference(queries, reference, fe_query=None, fe_ref=None, i_from=0, 
     if pruned and variant != "auto":
         raise ValueError(f"nearest_reference(pruned=True) takes variant='auto', not {variant!r}: the pruned sweep is "
                          "an entry point of its own")
-    n_q, n_ref, n_cols = _check_pair(queries, reference)
-    i_to = n_q if i_to is None else i_to
-    with_fe = fe_query is not None
-    if with_fe:
-        assert fe_ref is not None
-        for f, n in ((fe_query, n_q), (fe_ref, n_ref)):
-            assert f.is_cuda and f.dtype == torch.float32 and f.shape == (n,) and f.is_contiguous()
-    dev = queries.device
-    nn_idx = torch.empty(n_q, dtype=torch.int32, device=dev)
-    nn_d2 = torch.empty(n_q, dtype=torch.float32, device=dev)
-    hd_idx = torch.empty(n_q, dtype=torch.int32, device=dev) if with_fe else None
-    hd_d2 = torch.empty(n_q, dtype=torch.float32, device=dev) if with_fe else None
-    args = (_dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
-            _dev(fe_ref) if with_fe else None, i_from, i_to, _dev(nn_idx), _dev(nn_d2),
-            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None)
-    with torch.cuda.device(dev):
-        if pruned:
-            ws, ws_bytes = _nearest_pruned_workspace(dev).get(n_q, n_ref, n_cols)
-            rc = capi.lib.dc_hip_nearest_neighbors_cross_pruned_dev(*args, ws, ws_bytes, _stream_ptr())
-        else:
-            ws, ws_bytes = _cross_workspace(dev).get(n_q, n_ref, n_cols)
-            rc = capi.lib.dc_hip_nearest_neighbors_cross_dev(*args, ws, ws_bytes, capi.VARIANTS[variant], _stream_ptr())
-    capi.check(rc, "dc_hip_nearest_neighbors_cross_pruned_dev" if pruned else "dc_hip_nearest_neighbors_cross_dev")
-    return nn_idx, nn_d2, hd_idx, hd_d2
+    sizes = _check_pair(queries, reference)
+    if pruned:
+        return _nearest("dc_hip_nearest_neighbors_cross_pruned_dev", "nearest_pruned", queries, reference, sizes, fe_query, fe_ref,
+                        i_from, i_to)
+    return _nearest("dc_hip_nearest_neighbors_cross_dev", "cross", queries, reference, sizes, fe_query, fe_ref, i_from, i_to,
+                    capi.VARIANTS[variant])
 
 
 def evaluated_tiles_nearest_reference(device):
@@ -470,7 +383,7 @@ def evaluated_tiles_nearest_reference(device):
     the launch of the last nearest_reference(..., pruned=True) on this device (dc_hip_nearest_cross_pruned_info_dev).
     (0, 0, 0) after a call the pruned kernel did not answer: flagged data, a reference beyond 2^24 positions, nothing
     to sweep."""
-    ws = _nearest_pruned_workspace(device)
+    ws = _cached("nearest_pruned", device)
     if ws.buf is None:
         return 0, 0, 0
     t, m, n = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
@@ -479,6 +392,29 @@ def evaluated_tiles_nearest_reference(device):
                                                                  _stream_ptr()),
                    "dc_hip_nearest_cross_pruned_info_dev")
     return int(t.value), int(m.value), int(n.value)
+
+
+def _assign_frames(queries, reference, radius, ref_states, sizes, pops_self, pops_against, nearest):
+    """the four steps of assign_frames with the three sweeps it is given -> its dict"""
+    n_q, n_ref, _ = sizes
+    dev = queries.device
+    states_r = torch.as_tensor(np.ascontiguousarray(ref_states, dtype=np.int32), device=dev)
+    assert states_r.shape == (n_ref,)
+    pops_ref = pops_self(reference, [radius])[0].contiguous()
+    max_pop = int(pops_ref.max().item()) if n_ref else 0
+    fe_ref = calculate_free_energies(pops_ref)
+    pops_q = pops_against(queries, reference, [radius])[0].contiguous()
+    fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
+        torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
+    nn_idx, nn_d2, hd_idx, hd_d2 = nearest(queries, reference, fe_q, fe_ref)
+    none = n_ref + 1
+    states = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    if n_ref:
+        pick = torch.where(hd_idx != none, hd_idx, nn_idx)
+        ok = pick != none
+        states[ok] = states_r[pick[ok].long()]
+    return {"states": states, "pops_ref": pops_ref, "max_pop": max_pop, "fe_ref": fe_ref, "pops": pops_q, "fe": fe_q,
+            "nn_idx": nn_idx, "nn_d2": nn_d2, "hd_idx": hd_idx, "hd_d2": hd_d2}
 
 
 def assign_frames(queries, reference, radius, ref_states, variant="auto", pruned_neighbours=False):
@@ -493,42 +429,14 @@ def assign_frames(queries, reference, radius, ref_states, variant="auto", pruned
     neighbours of step 3 run on "auto".  pruned_neighbours=True: step 3 runs the pruned neighbour sweep
     (nearest_reference(pruned=True); the variant must then be "auto" or "cross_pruned").  The two can be combined; the
     results are the same either way."""
-    n_q, n_ref, n_cols = _check_pair(queries, reference)
-    pop_variant = variant
-    if variant == "cross_pruned":
-        variant = "auto"
-    dev = queries.device
-    states_r = torch.as_tensor(np.ascontiguousarray(ref_states, dtype=np.int32), device=dev)
-    assert states_r.shape == (n_ref,)
-    pops_ref = calculate_populations_partial(reference, [radius], variant=variant)[0].contiguous()
-    max_pop = int(pops_ref.max().item()) if n_ref else 0
-    fe_ref = calculate_free_energies(pops_ref)
-    pops_q = calculate_populations_against(queries, reference, [radius], variant=pop_variant)[0].contiguous()
-    fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
-        torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
-    nn_idx, nn_d2, hd_idx, hd_d2 = nearest_reference(queries, reference, fe_q, fe_ref, variant=variant,
-                                                     pruned=pruned_neighbours)
-    none = n_ref + 1
-    states = torch.zeros(n_q, dtype=torch.int32, device=dev)
-    if n_ref:
-        pick = torch.where(hd_idx != none, hd_idx, nn_idx)
-        ok = pick != none
-        states[ok] = states_r[pick[ok].long()]
-    return {"states": states, "pops_ref": pops_ref, "max_pop": max_pop, "fe_ref": fe_ref, "pops": pops_q, "fe": fe_q,
-            "nn_idx": nn_idx, "nn_d2": nn_d2, "hd_idx": hd_idx, "hd_d2": hd_d2}
+    other = "auto" if variant == "cross_pruned" else variant
+    return _assign_frames(queries, reference, radius, ref_states, _check_pair(queries, reference),
+                          functools.partial(calculate_populations_partial, variant=other),
+                          functools.partial(calculate_populations_against, variant=variant),
+                          functools.partial(nearest_reference, variant=other, pruned=pruned_neighbours))
 
 
 # ---- the cross sweeps for rows of 65..256 columns on the matrix cores (include/dc_density.h, the wide sweeps' cross form) ----
-def _wide_against_ws(device, *shape):
-    """(pointer, bytes) for a cross-wide call.  A call with an empty side needs no workspace; it gets the cached buffer, if
-    there is one, so that wide_against_info reports that nothing was swept rather than the call before."""
-    cache = _wide_against_workspace(device)
-    ws, ws_bytes = cache.get(*shape)
-    if ws_bytes == 0 and cache.buf is not None:
-        return _dev(cache.buf), int(cache.buf.numel())
-    return ws, ws_bytes
-
-
 def _check_pair_wide(queries, reference):
     """_check_pair, the column count (refused here as the library refuses it: 65..256) first"""
     for t in (queries, reference):
@@ -542,84 +450,41 @@ def calculate_populations_against_wide(queries, reference, radii, i_from=0, i_to
     (dc_hip_populations_cross_wide_dev): the same populations bit for bit -- no self term -- with one matrix-core chain
     per tile pair for all radii (up to 8 per launch), radii in any order, in a cached workspace of its own
     (wide_against_info reads its counters).  Other column counts raise."""
-    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
-    i_to = n_q if i_to is None else i_to
-    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
-    if out is None:
-        out = torch.empty((rad.size, n_q), dtype=torch.int32, device=queries.device)
-    assert out.shape == (rad.size, n_q) and out.dtype == torch.int32 and out.is_contiguous()
-    with torch.cuda.device(queries.device):
-        ws, ws_bytes = _wide_against_ws(queries.device, n_q, n_ref, n_cols, rad.size)
-        rc = capi.lib.dc_hip_populations_cross_wide_dev(
-            _dev(queries), n_q, _dev(reference), n_ref, n_cols, rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size,
-            i_from, i_to, _dev(out), ws, ws_bytes, _stream_ptr())
-    capi.check(rc, "dc_hip_populations_cross_wide_dev")
-    return out
+    return _populations_against("dc_hip_populations_cross_wide_dev", "wide_against", queries, reference,
+                                _check_pair_wide(queries, reference), radii, i_from, i_to, out)
 
 
 def nearest_reference_wide(queries, reference, fe_query=None, fe_ref=None, i_from=0, i_to=None):
     """nearest_reference(variant="direct") for rows of 65..256 columns on the matrix cores
     (dc_hip_nearest_neighbors_cross_wide_dev).  -> (nn_idx int32, nn_d2 float32, hd_idx, hd_d2), each [n_q]; "none" is
     (n_ref + 1, FLT_MAX).  Without free energies hd_idx / hd_d2 are None.  Other column counts raise."""
-    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
-    i_to = n_q if i_to is None else i_to
-    with_fe = fe_query is not None
-    if with_fe:
-        assert fe_ref is not None
-        for f, n in ((fe_query, n_q), (fe_ref, n_ref)):
-            assert f.is_cuda and f.dtype == torch.float32 and f.shape == (n,) and f.is_contiguous()
-    dev = queries.device
-    nn_idx = torch.empty(n_q, dtype=torch.int32, device=dev)
-    nn_d2 = torch.empty(n_q, dtype=torch.float32, device=dev)
-    hd_idx = torch.empty(n_q, dtype=torch.int32, device=dev) if with_fe else None
-    hd_d2 = torch.empty(n_q, dtype=torch.float32, device=dev) if with_fe else None
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _wide_against_ws(dev, n_q, n_ref, n_cols, 1)
-        rc = capi.lib.dc_hip_nearest_neighbors_cross_wide_dev(
-            _dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
-            _dev(fe_ref) if with_fe else None, i_from, i_to, _dev(nn_idx), _dev(nn_d2),
-            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None, ws, ws_bytes, _stream_ptr())
-    capi.check(rc, "dc_hip_nearest_neighbors_cross_wide_dev")
-    return nn_idx, nn_d2, hd_idx, hd_d2
+    return _nearest("dc_hip_nearest_neighbors_cross_wide_dev", "wide_against", queries, reference,
+                    _check_pair_wide(queries, reference), fe_query, fe_ref, i_from, i_to)
 
 
 def wide_against_info(device):
     """(tiles, mfmas, exact_pairs) of the last calculate_populations_against_wide / nearest_reference_wide on this
     device, as wide_sweep_info gives them for the self sweeps (dc_hip_wide_info_dev on the cross sweeps' own workspace);
     (0, 0, 0) when the direct kernels answered (flagged data), nothing was swept, or no such sweep has run."""
-    ws = _wide_against_workspace(device)
-    if ws.buf is None:
-        return 0, 0, 0
-    t, m, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    with torch.cuda.device(device):
-        capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
-                   "dc_hip_wide_info_dev")
-    return int(t.value), int(m.value), int(e.value)
+    return _wide_info("wide_against", device)
 
 
 # ---- ... the pruned cross population sweep (include/dc_density.h, the PRUNED wide cross sweep) -----------------------
+def _record_against_pruned(queries, sizes, i_from, i_to):
+    """(rows of the query range, n_ref, n_cols) of a pruned wide cross call that passed: what its order reader asks for"""
+    n_q, n_ref, n_cols = sizes
+    _shapes["wide_against_pruned"][str(queries.device)] = (max((n_q if i_to is None else i_to) - i_from, 0), n_ref, n_cols)
+
+
 def calculate_populations_against_wide_pruned(queries, reference, radii, i_from=0, i_to=None, out=None):
     """calculate_populations_against_wide without the block pairs that cannot hold a pair within the radii
     (dc_hip_populations_cross_wide_pruned_dev): the same populations bit for bit.  The queries [i_from, i_to) and the
     reference are put into one spatial order each, on one cell grid.  In a cached workspace of its own
     (wide_against_pruned_info reads its counters, wide_against_pruned_order its two orders)."""
-    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
-    i_to = n_q if i_to is None else i_to
-    rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
-    if out is None:
-        out = torch.empty((rad.size, n_q), dtype=torch.int32, device=queries.device)
-    assert out.shape == (rad.size, n_q) and out.dtype == torch.int32 and out.is_contiguous()
-    dev = queries.device
-    with torch.cuda.device(dev):
-        cache = _wide_against_pruned_workspace(dev)
-        ws, ws_bytes = cache.get(n_q, n_ref, n_cols, rad.size)
-        if ws_bytes == 0 and cache.buf is not None:   # (an empty side: the cached buffer then reports that nothing was swept)
-            ws, ws_bytes = _dev(cache.buf), int(cache.buf.numel())
-        rc = capi.lib.dc_hip_populations_cross_wide_pruned_dev(
-            _dev(queries), n_q, _dev(reference), n_ref, n_cols, rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size,
-            i_from, i_to, _dev(out), ws, ws_bytes, _stream_ptr())
-    capi.check(rc, "dc_hip_populations_cross_wide_pruned_dev")
-    _wide_against_pruned_shapes[str(dev)] = (max(i_to - i_from, 0), n_ref, n_cols)
+    sizes = _check_pair_wide(queries, reference)
+    out = _populations_against("dc_hip_populations_cross_wide_pruned_dev", "wide_against_pruned", queries, reference, sizes, radii,
+                               i_from, i_to, out)
+    _record_against_pruned(queries, sizes, i_from, i_to)
     return out
 
 
@@ -629,30 +494,11 @@ def nearest_reference_wide_pruned(queries, reference, fe_query=None, fe_ref=None
     block nearest to it first, then the blocks within the bound of its nearest frames, then those within the bound of its
     nearest frames of lower free energy.  In the cached workspace of calculate_populations_against_wide_pruned
     (wide_against_pruned_info reads its counters, wide_against_pruned_order its two orders)."""
-    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
-    i_to = n_q if i_to is None else i_to
-    with_fe = fe_query is not None
-    if with_fe:
-        assert fe_ref is not None
-        for f, n in ((fe_query, n_q), (fe_ref, n_ref)):
-            assert f.is_cuda and f.dtype == torch.float32 and f.shape == (n,) and f.is_contiguous()
-    dev = queries.device
-    nn_idx = torch.empty(n_q, dtype=torch.int32, device=dev)
-    nn_d2 = torch.empty(n_q, dtype=torch.float32, device=dev)
-    hd_idx = torch.empty(n_q, dtype=torch.int32, device=dev) if with_fe else None
-    hd_d2 = torch.empty(n_q, dtype=torch.float32, device=dev) if with_fe else None
-    with torch.cuda.device(dev):
-        cache = _wide_against_pruned_workspace(dev)
-        ws, ws_bytes = cache.get(n_q, n_ref, n_cols, 1)
-        if ws_bytes == 0 and cache.buf is not None:   # (an empty side: the cached buffer then reports that nothing was swept)
-            ws, ws_bytes = _dev(cache.buf), int(cache.buf.numel())
-        rc = capi.lib.dc_hip_nearest_neighbors_cross_wide_pruned_dev(
-            _dev(queries), n_q, _dev(reference), n_ref, n_cols, _dev(fe_query) if with_fe else None,
-            _dev(fe_ref) if with_fe else None, i_from, i_to, _dev(nn_idx), _dev(nn_d2),
-            _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None, ws, ws_bytes, _stream_ptr())
-    capi.check(rc, "dc_hip_nearest_neighbors_cross_wide_pruned_dev")
-    _wide_against_pruned_shapes[str(dev)] = (max(i_to - i_from, 0), n_ref, n_cols)
-    return nn_idx, nn_d2, hd_idx, hd_d2
+    sizes = _check_pair_wide(queries, reference)
+    out = _nearest("dc_hip_nearest_neighbors_cross_wide_pruned_dev", "wide_against_pruned", queries, reference, sizes, fe_query,
+                   fe_ref, i_from, i_to)
+    _record_against_pruned(queries, sizes, i_from, i_to)
+    return out
 
 
 def wide_against_pruned_info(device):
@@ -660,14 +506,7 @@ def wide_against_pruned_info(device):
     on this device (for the neighbour call: summed over its launches), as
     wide_against_info gives them; the tile pairs are the evaluated ones.  (0, 0, 0) when the direct kernel answered
     (flagged data), nothing was swept, or no such sweep has run."""
-    ws = _wide_against_pruned_workspace(device)
-    if ws.buf is None:
-        return 0, 0, 0
-    t, m, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    with torch.cuda.device(device):
-        capi.check(capi.lib.dc_hip_wide_info_dev(_dev(ws.buf), C.byref(t), C.byref(m), C.byref(e), _stream_ptr()),
-                   "dc_hip_wide_info_dev")
-    return int(t.value), int(m.value), int(e.value)
+    return _wide_info("wide_against_pruned", device)
 
 
 def wide_against_pruned_order(device):
@@ -675,7 +514,7 @@ def wide_against_pruned_order(device):
     device, position -> row:
     (perm_q int32 [i_to - i_from], rows of the queries; perm_r int32 [n_ref]); block b of either order is its
     positions 128 b .. 128 b + 127 (dc_hip_cross_wide_pruned_order_dev)."""
-    ws, shape = _wide_against_pruned_workspace(device), _wide_against_pruned_shapes.get(str(device))
+    ws, shape = _cached("wide_against_pruned", device), _shapes["wide_against_pruned"].get(str(device))
     if ws.buf is None or shape is None:
         raise ValueError("no pruned wide cross sweep has run on this device")
     perm_q = torch.empty(shape[0], dtype=torch.int32, device=device)
@@ -691,7 +530,8 @@ def assign_frames_wide(queries, reference, radius, ref_states):
     """assign_frames for rows of 65..256 columns, every sweep on the matrix cores: calculate_populations_wide on the
     reference, calculate_populations_against_wide and nearest_reference_wide for the queries; the same four steps, the
     same state rule, the same dict, the same values."""
-    return _assign_frames_wide(queries, reference, radius, ref_states, False)
+    return _assign_frames(queries, reference, radius, ref_states, _check_pair_wide(queries, reference), calculate_populations_wide,
+                          calculate_populations_against_wide, nearest_reference_wide)
 
 
 def assign_frames_wide_pruned(queries, reference, radius, ref_states, pruned_neighbours=False):
@@ -699,31 +539,9 @@ def assign_frames_wide_pruned(queries, reference, radius, ref_states, pruned_nei
     dict, the same values.  (A function of its own: assign_frames_wide's parameter list is pinned.)
     pruned_neighbours=True: the nearest reference frames through nearest_reference_wide_pruned as well, as
     assign_frames(..., pruned_neighbours=True) does below 65 columns."""
-    return _assign_frames_wide(queries, reference, radius, ref_states, True, pruned_neighbours)
-
-
-def _assign_frames_wide(queries, reference, radius, ref_states, pruned_populations, pruned_neighbours=False):
-    n_q, n_ref, n_cols = _check_pair_wide(queries, reference)
-    dev = queries.device
-    states_r = torch.as_tensor(np.ascontiguousarray(ref_states, dtype=np.int32), device=dev)
-    assert states_r.shape == (n_ref,)
-    pops_ref = calculate_populations_wide(reference, [radius])[0].contiguous()
-    max_pop = int(pops_ref.max().item()) if n_ref else 0
-    fe_ref = calculate_free_energies(pops_ref)
-    pops_against = calculate_populations_against_wide_pruned if pruned_populations else calculate_populations_against_wide
-    pops_q = pops_against(queries, reference, [radius])[0].contiguous()
-    fe_q = calculate_free_energies_against(pops_q, max_pop) if max_pop else \
-        torch.full((n_q,), float("inf"), dtype=torch.float32, device=dev)
-    nearest = nearest_reference_wide_pruned if pruned_neighbours else nearest_reference_wide
-    nn_idx, nn_d2, hd_idx, hd_d2 = nearest(queries, reference, fe_q, fe_ref)
-    none = n_ref + 1
-    states = torch.zeros(n_q, dtype=torch.int32, device=dev)
-    if n_ref:
-        pick = torch.where(hd_idx != none, hd_idx, nn_idx)
-        ok = pick != none
-        states[ok] = states_r[pick[ok].long()]
-    return {"states": states, "pops_ref": pops_ref, "max_pop": max_pop, "fe_ref": fe_ref, "pops": pops_q, "fe": fe_q,
-            "nn_idx": nn_idx, "nn_d2": nn_d2, "hd_idx": hd_idx, "hd_d2": hd_d2}
+    return _assign_frames(queries, reference, radius, ref_states, _check_pair_wide(queries, reference), calculate_populations_wide,
+                          calculate_populations_against_wide_pruned,
+                          nearest_reference_wide_pruned if pruned_neighbours else nearest_reference_wide)
 
 
 def evaluated_tiles(device):
@@ -877,10 +695,10 @@ def radius_pairs_wide(coords, r2, capacity=None):
     sizes the buffer unless a capacity is given.  Rows with inf / NaN have no partners (population 1; the direct kernel
     answers such data).  In the cached workspace of the wide sweeps (wide_sweep_info reads its counters).  Other column
     counts raise."""
-    return _radius_pairs_wide("dc_hip_radius_pairs_wide_dev", _wide_workspace, coords, r2, capacity)
+    return _radius_pairs_wide("dc_hip_radius_pairs_wide_dev", "wide", coords, r2, capacity)
 
 
-def _radius_pairs_wide(fn, workspace, coords, r2, capacity):
+def _radius_pairs_wide(fn, kind, coords, r2, capacity):
     n_rows, n_cols = _check_coords_wide(coords)
     dev = coords.device
     pops = torch.empty(n_rows, dtype=torch.int32, device=dev)
@@ -888,7 +706,7 @@ def _radius_pairs_wide(fn, workspace, coords, r2, capacity):
 
     def sweep(pairs, cap):
         with torch.cuda.device(dev):
-            ws, ws_bytes = workspace(dev).get(n_rows, n_cols, 1)
+            ws, ws_bytes = _get(kind, dev, n_rows, n_cols, 1)
             rc = getattr(capi.lib, fn)(_dev(coords), n_rows, n_cols, float(r2), _dev(pops),
                                        _dev(pairs) if pairs is not None else None, cap,
                                        _dev(count), ws, ws_bytes, _stream_ptr())
@@ -900,7 +718,7 @@ def _radius_pairs_wide(fn, workspace, coords, r2, capacity):
     pairs = torch.empty((max(capacity, 1), 2), dtype=torch.int32, device=dev)
     n = sweep(pairs, capacity)
     if n > capacity:
-        return _radius_pairs_wide(fn, workspace, coords, r2, n)
+        return _radius_pairs_wide(fn, kind, coords, r2, n)
     return pairs[:n].to(torch.int64), pops
 
 
@@ -910,10 +728,10 @@ def radius_min_edge_wide(coords, r2, comp, rank, segment=0, n_segments=0):
     id, -1 (all ones) if none; pops int32 [n_rows]).  n_segments > 0: what the queries of one row block of a sharded
     run see (partials merge by unsigned minimum / summation), array-equal to radius_min_edge of that segment.  Other
     column counts raise."""
-    return _radius_min_edge_wide("dc_hip_radius_min_edge_wide_dev", _wide_workspace, coords, r2, comp, rank, segment, n_segments)
+    return _radius_min_edge_wide("dc_hip_radius_min_edge_wide_dev", "wide", coords, r2, comp, rank, segment, n_segments)
 
 
-def _radius_min_edge_wide(fn, workspace, coords, r2, comp, rank, segment, n_segments):
+def _radius_min_edge_wide(fn, kind, coords, r2, comp, rank, segment, n_segments):
     n_rows, n_cols = _check_coords_wide(coords)
     dev = coords.device
     for t in (comp, rank):
@@ -921,7 +739,7 @@ def _radius_min_edge_wide(fn, workspace, coords, r2, comp, rank, segment, n_segm
     best = torch.empty(n_rows, dtype=torch.int64, device=dev)
     pops = torch.empty(n_rows, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        ws, ws_bytes = workspace(dev).get(n_rows, n_cols, 1)
+        ws, ws_bytes = _get(kind, dev, n_rows, n_cols, 1)
         rc = getattr(capi.lib, fn)(_dev(coords), n_rows, n_cols, float(r2), _dev(comp), _dev(rank), segment, n_segments,
                                    _dev(best), _dev(pops), ws, ws_bytes, _stream_ptr())
     capi.check(rc, fn)
@@ -955,8 +773,8 @@ def radius_pairs_wide_pruned(coords, r2, capacity=None):
     (dc_hip_radius_pairs_wide_pruned_dev): the same set of pairs -- in no order within a pair -- and the same
     populations.  In the cached workspace of the pruned wide sweeps (wide_pruned_info reads its counters,
     wide_pruned_order its order)."""
-    out = _radius_pairs_wide("dc_hip_radius_pairs_wide_pruned_dev", _wide_pruned_workspace, coords, r2, capacity)
-    _wide_pruned_shapes[str(coords.device)] = tuple(coords.shape)
+    out = _radius_pairs_wide("dc_hip_radius_pairs_wide_pruned_dev", "wide_pruned", coords, r2, capacity)
+    _shapes["wide_pruned"][str(coords.device)] = tuple(coords.shape)
     return out
 
 
@@ -965,9 +783,9 @@ def radius_min_edge_wide_pruned(coords, r2, comp, rank, segment=0, n_segments=0)
     == 0) is array-equal to it; n_segments > 0: what the queries of the blocks segment, segment + n_segments, ... of
     the spatial order see (partials merge by unsigned minimum / summation; pops are non-zero only on the rows of those
     blocks).  wide_pruned_info and wide_pruned_order as above."""
-    out = _radius_min_edge_wide("dc_hip_radius_min_edge_wide_pruned_dev", _wide_pruned_workspace, coords, r2, comp, rank,
+    out = _radius_min_edge_wide("dc_hip_radius_min_edge_wide_pruned_dev", "wide_pruned", coords, r2, comp, rank,
                                 segment, n_segments)
-    _wide_pruned_shapes[str(coords.device)] = tuple(coords.shape)
+    _shapes["wide_pruned"][str(coords.device)] = tuple(coords.shape)
     return out
 
 
@@ -1008,21 +826,57 @@ def neighbor_block_rows(n_rows, n_cols, n_segments):
     return int(capi.lib.dc_hip_neighbors_block_rows(n_rows, n_cols, n_segments))
 
 
-def pack_neighbor_block(coords, nn_idx, nn_d2, hd_idx, hd_d2, segment, n_segments, variant="auto", out=None):
-    """The results of this segment's own rows as a dense block int32 [4, block_rows] (dc_hip_neighbors_block_pack_dev);
-    call right after nearest_neighbors_segment on the same device (its ordering is read from the workspace)."""
+def _pack_block(fn, kind, rows, coords, results, segment, n_segments, out, variant=None):
+    """One block pack call of ``fn`` in the cached workspace of ``kind``; rows: the block's rows -> int32 [4, rows]"""
     n_rows, n_cols = _check_coords(coords)
-    rows = neighbor_block_rows(n_rows, n_cols, n_segments)
+    rows = rows(n_rows, n_cols, n_segments)
     if out is None:
         out = torch.empty((4, rows), dtype=torch.int32, device=coords.device)
     assert out.shape == (4, rows) and out.dtype == torch.int32 and out.is_contiguous()
     with torch.cuda.device(coords.device):
-        ws, ws_bytes = _workspace(coords.device).get(n_rows, n_cols, 1)
-        rc = capi.lib.dc_hip_neighbors_block_pack_dev(_dev(nn_idx), _dev(nn_d2), _dev(hd_idx), _dev(hd_d2), n_rows, n_cols,
-                                                      segment, n_segments, ws, ws_bytes, capi.VARIANTS[variant],
-                                                      _dev(out), _stream_ptr())
-    capi.check(rc, "dc_hip_neighbors_block_pack_dev")
+        ws, ws_bytes = _get(kind, coords.device, n_rows, n_cols, 1)
+        rc = getattr(capi.lib, fn)(*[_dev(t) for t in results], n_rows, n_cols, segment, n_segments, ws, ws_bytes,
+                                   *(() if variant is None else (variant,)), _dev(out), _stream_ptr())
+    capi.check(rc, fn)
     return out
+
+
+def _unpack_blocks(fn, kind, rows, coords, blocks, n_segments, out, check, variant=None, no_workspace=None):
+    """One block unpack call of ``fn`` in the cached workspace of ``kind``; no_workspace: what check=True does first for a
+    shape without one.  -> (the four arrays, bytes of the workspace)"""
+    n_rows, n_cols = _check_coords(coords)
+    dev = coords.device
+    rows = rows(n_rows, n_cols, n_segments)
+    assert blocks.is_contiguous() and blocks.dtype == torch.int32 and blocks.numel() == n_segments * 4 * rows
+    if out is None:
+        buf = (torch.empty if check else torch.zeros)((4, n_rows), dtype=torch.int32, device=dev)   # (one fill, not four)
+        out = (buf[0], buf[1].view(torch.float32), buf[2], buf[3].view(torch.float32))
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _get(kind, dev, n_rows, n_cols, 1)
+        if check and not ws_bytes and no_workspace:
+            no_workspace(blocks.view(n_segments, 4, rows))
+        rc = getattr(capi.lib, fn)(_dev(blocks), n_rows, n_cols, n_segments, ws, ws_bytes, *(() if variant is None else (variant,)),
+                                   _dev(out[0]), _dev(out[1]), _dev(out[2]), _dev(out[3]), _stream_ptr())
+    capi.check(rc, fn)
+    return out, ws_bytes
+
+
+def _layout_status(fn, kind, device):
+    """the verdict word of the last block unpack in this device's workspace of ``kind``, read by ``fn``; synchronises"""
+    ws = _cached(kind, device)
+    if ws.buf is None:
+        return False
+    bad = C.c_int(0)
+    with torch.cuda.device(device):
+        capi.check(getattr(capi.lib, fn)(_dev(ws.buf), C.byref(bad), _stream_ptr()), fn)
+    return bool(bad.value)
+
+
+def pack_neighbor_block(coords, nn_idx, nn_d2, hd_idx, hd_d2, segment, n_segments, variant="auto", out=None):
+    """The results of this segment's own rows as a dense block int32 [4, block_rows] (dc_hip_neighbors_block_pack_dev);
+    call right after nearest_neighbors_segment on the same device (its ordering is read from the workspace)."""
+    return _pack_block("dc_hip_neighbors_block_pack_dev", "self", neighbor_block_rows, coords, (nn_idx, nn_d2, hd_idx, hd_d2),
+                       segment, n_segments, out, capi.VARIANTS[variant])
 
 
 BLOCK_HEADER_ROWS = 32    # the last entries of plane 0 of a block: its layout header (dc_mfma.hip nn_block_pack_kernel)
@@ -1040,14 +894,7 @@ def check_neighbor_block_layout(blocks):
 def layout_status(device):
     """True if the last dc_hip_neighbors_block_unpack_dev in this device's workspace REFUSED its blocks (their layout headers
     differed: nothing was unpacked) -- dc_hip_workspace_layout_status_dev; synchronises"""
-    ws = _workspace(device)
-    if ws.buf is None:
-        return False
-    bad = C.c_int(0)
-    with torch.cuda.device(device):
-        capi.check(capi.lib.dc_hip_workspace_layout_status_dev(_dev(ws.buf), C.byref(bad), _stream_ptr()),
-                   "dc_hip_workspace_layout_status_dev")
-    return bool(bad.value)
+    return _layout_status("dc_hip_workspace_layout_status_dev", "self", device)
 
 
 def unpack_neighbor_blocks(coords, blocks, n_segments, variant="auto", out=None, check=True):
@@ -1057,23 +904,11 @@ def unpack_neighbor_blocks(coords, blocks, n_segments, variant="auto", out=None,
     the caller: layout_status() BEFORE the next call into the workspace -- the verdict word describes the last unpack only,
     the next unpack or sweep replaces it -- and on a mismatch the returned arrays hold whatever they held before (zeros
     here: a refused unpack must not hand out uninitialised memory as neighbours)."""
-    n_rows, n_cols = _check_coords(coords)
-    dev = coords.device
-    rows = neighbor_block_rows(n_rows, n_cols, n_segments)
-    assert blocks.is_contiguous() and blocks.dtype == torch.int32 and blocks.numel() == n_segments * 4 * rows
-    if out is None:
-        buf = (torch.empty if check else torch.zeros)((4, n_rows), dtype=torch.int32, device=dev)   # (one fill, not four)
-        out = (buf[0], buf[1].view(torch.float32), buf[2], buf[3].view(torch.float32))
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _workspace(dev).get(n_rows, n_cols, 1)
-        if check and not ws_bytes:   # (no workspace for the kernel to flag in -- shapes without a matrix-core sweep: compared here)
-            check_neighbor_block_layout(blocks.view(n_segments, 4, rows))
-        rc = capi.lib.dc_hip_neighbors_block_unpack_dev(_dev(blocks), n_rows, n_cols, n_segments, ws, ws_bytes,
-                                                        capi.VARIANTS[variant], _dev(out[0]), _dev(out[1]), _dev(out[2]),
-                                                        _dev(out[3]), _stream_ptr())
-    capi.check(rc, "dc_hip_neighbors_block_unpack_dev")
-    if check and ws_bytes and layout_status(dev):
-        check_neighbor_block_layout(blocks.view(n_segments, 4, rows))   # (raises, with the headers in the message)
+    # (no workspace for the kernel to flag in -- shapes without a matrix-core sweep: the headers are compared here)
+    out, ws_bytes = _unpack_blocks("dc_hip_neighbors_block_unpack_dev", "self", neighbor_block_rows, coords, blocks, n_segments, out,
+                                   check, capi.VARIANTS[variant], no_workspace=check_neighbor_block_layout)
+    if check and ws_bytes and layout_status(coords.device):
+        check_neighbor_block_layout(blocks.view(n_segments, 4, -1))   # (raises, with the headers in the message)
         raise RuntimeError("neighbour blocks of the ranks were packed under different layouts")
     return out
 
@@ -1089,30 +924,14 @@ def pack_neighbor_block_wide(coords, nn_idx, nn_d2, hd_idx, hd_d2, segment, n_se
     """The results of this segment's blocks of the order as a dense block int32 [4, block_rows]
     (dc_hip_neighbors_block_pack_wide_dev); call right after nearest_neighbors_wide_pruned(coords, fe, segment, n_segments)
     on the same device: the order and the flag of its data are read from the workspace of the pruned wide sweeps."""
-    n_rows, n_cols = _check_coords(coords)
-    rows = neighbor_block_rows_wide(n_rows, n_cols, n_segments)
-    if out is None:
-        out = torch.empty((4, rows), dtype=torch.int32, device=coords.device)
-    assert out.shape == (4, rows) and out.dtype == torch.int32 and out.is_contiguous()
-    with torch.cuda.device(coords.device):
-        ws, ws_bytes = _wide_pruned_workspace(coords.device).get(n_rows, n_cols, 1)
-        rc = capi.lib.dc_hip_neighbors_block_pack_wide_dev(_dev(nn_idx), _dev(nn_d2), _dev(hd_idx), _dev(hd_d2), n_rows, n_cols,
-                                                           segment, n_segments, ws, ws_bytes, _dev(out), _stream_ptr())
-    capi.check(rc, "dc_hip_neighbors_block_pack_wide_dev")
-    return out
+    return _pack_block("dc_hip_neighbors_block_pack_wide_dev", "wide_pruned", neighbor_block_rows_wide, coords,
+                       (nn_idx, nn_d2, hd_idx, hd_d2), segment, n_segments, out)
 
 
 def wide_layout_status(device):
     """True if the last dc_hip_neighbors_block_unpack_wide_dev in this device's workspace of the pruned wide sweeps REFUSED
     its blocks (nothing was unpacked) -- dc_hip_wide_layout_status_dev; synchronises"""
-    ws = _wide_pruned_workspace(device)
-    if ws.buf is None:
-        return False
-    bad = C.c_int(0)
-    with torch.cuda.device(device):
-        capi.check(capi.lib.dc_hip_wide_layout_status_dev(_dev(ws.buf), C.byref(bad), _stream_ptr()),
-                   "dc_hip_wide_layout_status_dev")
-    return bool(bad.value)
+    return _layout_status("dc_hip_wide_layout_status_dev", "wide_pruned", device)
 
 
 def unpack_neighbor_blocks_wide(coords, blocks, n_segments, out=None, check=True):
@@ -1121,20 +940,9 @@ def unpack_neighbor_blocks_wide(coords, blocks, n_segments, out=None, check=True
     the order the blocks were packed by.  The kernel compares the layout headers itself and writes nothing on a mismatch;
     check=True asks for its verdict right away (one synchronisation) and raises, check=False leaves that to the caller
     (wide_layout_status) -- the arrays handed out then hold what they held before (zeros if made here)."""
-    n_rows, n_cols = _check_coords(coords)
-    dev = coords.device
-    rows = neighbor_block_rows_wide(n_rows, n_cols, n_segments)
-    assert blocks.is_contiguous() and blocks.dtype == torch.int32 and blocks.numel() == n_segments * 4 * rows
-    if out is None:
-        buf = (torch.empty if check else torch.zeros)((4, n_rows), dtype=torch.int32, device=dev)
-        out = (buf[0], buf[1].view(torch.float32), buf[2], buf[3].view(torch.float32))
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _wide_pruned_workspace(dev).get(n_rows, n_cols, 1)
-        rc = capi.lib.dc_hip_neighbors_block_unpack_wide_dev(_dev(blocks), n_rows, n_cols, n_segments, ws, ws_bytes,
-                                                             _dev(out[0]), _dev(out[1]), _dev(out[2]), _dev(out[3]),
-                                                             _stream_ptr())
-    capi.check(rc, "dc_hip_neighbors_block_unpack_wide_dev")
-    if check and n_rows and wide_layout_status(dev):
+    out, _ = _unpack_blocks("dc_hip_neighbors_block_unpack_wide_dev", "wide_pruned", neighbor_block_rows_wide, coords, blocks,
+                            n_segments, out, check)
+    if check and coords.shape[0] and wide_layout_status(coords.device):
         raise RuntimeError("neighbour blocks of the ranks were packed under different layouts")
     return out
 

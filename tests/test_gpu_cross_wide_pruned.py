@@ -355,3 +355,38 @@ def test_at_most_one_percent_of_the_evaluated_pairs_go_to_the_exact_path(dens, n
     (tiles, mfmas, exact), _, _, _ = check(dens, Q, R, d2, std_radii(n_cols))
     print(f"D={n_cols}: {tiles} tile pairs, {exact} exact pairs = {100.0 * exact / (1024 * tiles):.4f} % of the evaluated pairs")
     assert exact <= 0.01 * 1024 * tiles
+
+
+def test_every_counter_and_order_reader_answers_from_the_workspace_of_its_own_kind(dens):
+    """The four wide kinds keep a cached workspace each: a call of one kind must show in that kind's reader alone.  300 rows
+    (three blocks of 128, the last one partial: the smallest shape with more than one block) and 200 queries against them,
+    65 columns.  A call that sweeps nothing -- an empty row range; for the pruned self sweep segment 3 of 4, which owns no
+    block of three -- turns its own reader to (0, 0, 0) and leaves the other three as they were."""
+    import torch
+    n_q, n_r, D = 200, 300, 65
+    Q, R = crossref.sets(D, n_q, n_r, seed=43)
+    q, r = gpu(Q), gpu(R)
+    radii = [crossref.radius(D)]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    readers = {"wide": dens.wide_sweep_info, "wide pruned": dens.wide_pruned_info, "against wide": dens.wide_against_info,
+               "against wide pruned": dens.wide_against_pruned_info}
+    sweeps = {"wide": lambda *span: dens.calculate_populations_wide(r, radii, *span),
+              "wide pruned": lambda *span: dens.calculate_populations_wide_pruned(r, radii, *span),
+              "against wide": lambda *span: dens.calculate_populations_against_wide(q, r, radii, *span),
+              "against wide pruned": lambda *span: dens.calculate_populations_against_wide_pruned(q, r, radii, *span)}
+    nothing = {"wide": (0, 0), "wide pruned": (3, 4), "against wide": (0, 0), "against wide pruned": (0, 0)}
+    for kind, sweep in sweeps.items():
+        sweep()
+    state = {kind: read(dev) for kind, read in readers.items()}
+    print(state)
+    for kind, (tiles, mfmas, _) in state.items():
+        assert tiles > 0 and mfmas == cw.nm_for(D) * tiles, (kind, "the matrix-core sweep answered")
+    perm = dens.wide_pruned_order(dev)
+    perm_q, perm_r = dens.wide_against_pruned_order(dev)
+    assert sorted(perm.tolist()) == list(range(n_r)), "the self order: a permutation of the 300 rows"
+    assert sorted(perm_q.tolist()) == list(range(n_q)) and sorted(perm_r.tolist()) == list(range(n_r)), "the cross orders: 200 and 300"
+    for kind, sweep in sweeps.items():
+        got = sweep(*nothing[kind])
+        assert int(got.abs().sum()) == 0, (kind, "nothing swept, nothing counted")
+        state[kind] = (0, 0, 0)
+        assert {k: read(dev) for k, read in readers.items()} == state, f"after the empty {kind} call"
