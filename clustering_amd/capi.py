@@ -55,6 +55,9 @@ SYMBOLS = (
     "dc_hip_nearest_neighbors_cross_wide_pruned_dev",
     "dc_hip_neighbors_block_rows_wide", "dc_hip_neighbors_block_pack_wide_dev", "dc_hip_neighbors_block_unpack_wide_dev",
     "dc_hip_wide_layout_status_dev", "dc_hip_session_open_flags", "dc_hip_session_wide",
+    "dc_hip_reference_wide_workspace_bytes", "dc_hip_reference_wide_open_dev", "dc_hip_reference_wide_close",
+    "dc_hip_reference_wide_set_free_energies_dev", "dc_hip_reference_wide_stage_dev", "dc_hip_reference_wide_populations_dev",
+    "dc_hip_reference_wide_nearest_dev", "dc_hip_reference_wide_info_dev", "dc_hip_reference_wide_order_dev",
 )
 SESSION_WIDE_SWEEPS = 0x1     # DC_SESSION_WIDE_SWEEPS (dc_hip_session_open_flags)
 
@@ -243,6 +246,25 @@ def _load():
     lib.dc_hip_session_open_flags.argtypes = [vp, sz, sz, C.POINTER(C.c_int), i32, C.c_uint, C.POINTER(vp)]
     lib.dc_hip_session_wide.restype = i32
     lib.dc_hip_session_wide.argtypes = [vp]
+    lib.dc_hip_reference_wide_workspace_bytes.restype = sz
+    lib.dc_hip_reference_wide_workspace_bytes.argtypes = [sz, sz, sz]
+    lib.dc_hip_reference_wide_open_dev.restype = i32
+    lib.dc_hip_reference_wide_open_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, C.POINTER(vp)]
+    lib.dc_hip_reference_wide_close.restype = None
+    lib.dc_hip_reference_wide_close.argtypes = [vp]
+    lib.dc_hip_reference_wide_set_free_energies_dev.restype = i32
+    lib.dc_hip_reference_wide_set_free_energies_dev.argtypes = [vp, vp, vp]
+    lib.dc_hip_reference_wide_stage_dev.restype = i32
+    lib.dc_hip_reference_wide_stage_dev.argtypes = [vp, vp, sz, vp]
+    lib.dc_hip_reference_wide_populations_dev.restype = i32
+    lib.dc_hip_reference_wide_populations_dev.argtypes = [vp, C.POINTER(C.c_float), sz, vp, vp]
+    lib.dc_hip_reference_wide_nearest_dev.restype = i32
+    lib.dc_hip_reference_wide_nearest_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.dc_hip_reference_wide_info_dev.restype = i32
+    lib.dc_hip_reference_wide_info_dev.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
+    lib.dc_hip_reference_wide_order_dev.restype = i32
+    lib.dc_hip_reference_wide_order_dev.argtypes = [vp, vp, vp, vp]
     lib.dc_hip_free_energies_scaled_dev.restype = i32
     lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
     lib.dc_hip_populations_cross.restype = i32

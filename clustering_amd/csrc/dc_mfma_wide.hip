@@ -613,11 +613,11 @@ int wide_cross_pruned_prepare(const float* d_query, uint32_t n_query, const floa
                                      n_cols, d_ws, s);
 }
 
-int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
-                                 const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
-  if (i_from >= i_to || n_rad <= 0 || n_ref == 0) return 0;
-  const WideCrossPrunedLayout P = wide_cross_pruned_layout(n_query, n_ref, n_cols);
-  const uint32_t n_q = i_to - i_from;
+namespace {
+// the launch in a workspace whose places P names: the n_q gathered query rows against the gathered reference, the counts
+// scattered to rows of a population array of n_query rows per radius
+int pop_wide_cross_pruned(const WideCrossPrunedLayout& P, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t n_q,
+                          const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
   char* p = (char*)d_ws;
   uint32_t* cnt = (uint32_t*)(p + P.off_cnt);
   if (hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (size_t)n_rad * n_q, s) != hipSuccess) return -1;
@@ -638,6 +638,14 @@ int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_co
                      (const uint32_t*)(p + P.off_perm_q), (const uint32_t*)cnt, n_q, n_rad, d_pops_first_row, n_query);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+}  // namespace
+
+int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                                 const Rad2& rad2, int n_rad, uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
+  if (i_from >= i_to || n_rad <= 0 || n_ref == 0) return 0;
+  return pop_wide_cross_pruned(wide_cross_pruned_layout(n_query, n_ref, n_cols), n_query, n_ref, n_cols, i_to - i_from, rad2, n_rad,
+                               d_pops_first_row, d_ws, s);
+}
 
 // ---- the pruned cross neighbour sweep (dc_hip_nearest_neighbors_cross_wide_pruned_dev) --------------------
 // Behind wide_cross_pruned_prepare in the same workspace.  The sort's keys, keys_o and vals arrays (n_max words each) are
@@ -646,19 +654,25 @@ int launch_pop_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_co
 // block: blocks_r + 4 blocks_q <= 5 ceil(n_max / 128) words, inside n_max words from n_max = 6 on and inside the 256
 // bytes of align256 below.  A NaN free energy of either side flags the data (ring 2 rests on the ranges per block): the
 // gathers raise header word 1 on the stream, before the first sweep launch.  Then the launches of 4.24: seed, bounds, ring 1, bounds, ring 2, finish.
-int launch_nn_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, const float* d_fe_query, const float* d_fe_ref,
-                                uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
-                                float* d_hd_d2, void* d_ws, hipStream_t s) {
-  if (i_from >= i_to || n_ref == 0) return 0;
-  const WideCrossPrunedLayout P = wide_cross_pruned_layout(n_query, n_ref, n_cols);
-  const uint32_t n_q = i_to - i_from, blocks_q = (n_q + kWideBlockRows - 1u) / kWideBlockRows;
+namespace {
+// where the free-energy words of a neighbour sweep lie: the free energies of either side by position, the least per
+// reference block, and [4][P.blocks_q] words per query block -- the largest free energy, far2 nn, far2 hd, the seed
+struct WideCrossNnPlaces {
+  size_t off_fe_r, off_fe_q, off_fe_min_r, off_qwords;
+  size_t off_flag_q;     // the header word a NaN among the queries' free energies raises (bytes)
+  bool ref_resident;     // the reference's words stand (the resident reference gathered them when they were set)
+};
+// the launches in a workspace whose places P and N name: the n_q gathered query rows against the gathered reference
+int nn_wide_cross_pruned(const WideCrossPrunedLayout& P, const WideCrossNnPlaces& N, uint32_t n_ref, uint32_t n_cols, uint32_t n_q,
+                         const float* d_fe_query, const float* d_fe_ref, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                         float* d_hd_d2, void* d_ws, hipStream_t s) {
+  const uint32_t blocks_q = (n_q + kWideBlockRows - 1u) / kWideBlockRows;
   char* p = (char*)d_ws;
-  uint32_t* hdr = (uint32_t*)p;
-  float* fe_r = (float*)(p + P.off_keys);
-  float* fe_q = (float*)(p + P.off_keys_o);
-  float* fe_min_r = (float*)(p + P.off_vals);   // [blocks_r]
-  float* fe_max_q = fe_min_r + P.blocks_r;      // [blocks_q of the whole query array] each from here on
-  float* far2 = fe_max_q + P.blocks_q;          // [2]: nn, hd
+  float* fe_r = (float*)(p + N.off_fe_r);
+  float* fe_q = (float*)(p + N.off_fe_q);
+  float* fe_min_r = (float*)(p + N.off_fe_min_r);   // [blocks_r]
+  float* fe_max_q = (float*)(p + N.off_qwords);     // [blocks_q of the whole query array] each from here on
+  float* far2 = fe_max_q + P.blocks_q;              // [2]: nn, hd
   uint32_t* seed = (uint32_t*)(far2 + 2 * (size_t)P.blocks_q);
   WideCrossNnPrunedArgs X{};
   static_cast<WideArgs&>(X) = wide_args(P.L, (const float*)(p + P.off_coords_r), n_ref, n_cols, 0, n_q, d_ws,
@@ -679,11 +693,16 @@ int launch_nn_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_col
     // (the gathers and the seed kernel run on flagged data too: they read through the two orders and the boxes, which
     //  wide_cross_pruned_prepare completes whatever the rows hold -- a preparation that stood down on flagged data would
     //  have to gate them)
-    hipLaunchKernelGGL(wide_cross_nn_gather_kernel, dim3(P.blocks_r), dim3(128), 0, s, X.perm, d_fe_ref, n_ref, 0u, fe_r, fe_min_r, hdr);
-    hipLaunchKernelGGL(wide_cross_nn_gather_kernel, dim3(blocks_q), dim3(128), 0, s, perm_q, d_fe_query, n_q, 1u, fe_q, fe_max_q, hdr);
+    if (!N.ref_resident)
+      hipLaunchKernelGGL(wide_cross_nn_gather_kernel, dim3(P.blocks_r), dim3(128), 0, s, X.perm, d_fe_ref, n_ref, 0u, fe_r, fe_min_r,
+                         (uint32_t*)p + 1);
+    hipLaunchKernelGGL(wide_cross_nn_gather_kernel, dim3(blocks_q), dim3(128), 0, s, perm_q, d_fe_query, n_q, 1u, fe_q, fe_max_q,
+                       (uint32_t*)(p + N.off_flag_q));
     X.fe = fe_r;
     X.q_fe = fe_q;
   }
+  // (the resident reference: word 1 of this sweep from its flags, those of the free energies just gathered among them)
+  if (N.ref_resident) hipLaunchKernelGGL(wide_res_arm_kernel, dim3(1), dim3(64), 0, s, (uint32_t*)p, d_fe_query ? 1u : 0u);
   hipLaunchKernelGGL(wide_cross_seed_kernel, dim3(blocks_q), dim3(64), 0, s, X.qboxes, X.boxes, P.blocks_r, seed);
   const dim3 grid(wide_grid_size(blocks_q, wide_shares(P.blocks_r)));
   const uint32_t last_ring = d_fe_query ? kWideRing2 : kWideRing1;   // no ring 2 without free energies
@@ -700,6 +719,16 @@ int launch_nn_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_col
                      (const unsigned long long*)X.merge, perm_q, n_q, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+}  // namespace
+
+int launch_nn_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, const float* d_fe_query, const float* d_fe_ref,
+                                uint32_t i_from, uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                float* d_hd_d2, void* d_ws, hipStream_t s) {
+  if (i_from >= i_to || n_ref == 0) return 0;
+  const WideCrossPrunedLayout P = wide_cross_pruned_layout(n_query, n_ref, n_cols);
+  const WideCrossNnPlaces N{P.off_keys, P.off_keys_o, P.off_vals, P.off_vals + sizeof(float) * P.blocks_r, 4, false};
+  return nn_wide_cross_pruned(P, N, n_ref, n_cols, i_to - i_from, d_fe_query, d_fe_ref, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, d_ws, s);
+}
 
 int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n_ref, uint32_t n_cols, uint32_t* d_perm_q,
                             uint32_t* d_perm_r, hipStream_t s) {
@@ -715,6 +744,205 @@ int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n
       hipMemcpyAsync(d_perm_r, (const char*)d_ws + P.off_perm_r, sizeof(uint32_t) * (size_t)n_ref, hipMemcpyDeviceToDevice, s) != hipSuccess)
     return -1;
   return 0;
+}
+
+// ---- the resident reference of the pruned cross sweeps (dc_hip_reference_wide_*) --------------------------
+// The preparation of wide_cross_pruned_prepare in two halves: the reference's, once, under statistics that do not depend
+// on a batch (dc_mfma_wide_kernels.hpp, "the resident reference"), and a batch's.  The sweeps are launch_pop_wide_cross_pruned
+// and launch_nn_wide_cross_pruned as they stand, in a workspace of three regions:
+//   resident (n_ref, n_cols):    A image, norms, the reference's order, its gathered rows, its boxes; its free energies by
+//                                position, their least per block, and a copy by row for the direct kernel
+//   batch (max_batch, n_cols):   B image, merge words, the batch's order, its gathered rows, its boxes, the counts; the
+//                                queries' free energies by position and the four words per query block
+//   scratch (the larger count):  keys, sorted keys, values and the sort's own bytes -- the reference's sort once, then a
+//                                batch's; nothing that outlives a sort lies here
+namespace {
+struct WideReferenceLayout {
+  WideCrossPrunedLayout P;   // the places of the pruned cross sweep (P.L: the images, norms and merge words)
+  WideCrossNnPlaces N;       // ... and of its free-energy words
+  size_t off_fe_row;         // [n_ref] the reference's free energies by row
+  size_t resident_begin, resident_end, batch_begin, batch_end;   // scratch: batch_end .. P.total
+};
+WideReferenceLayout wide_reference_layout(size_t n_ref, size_t n_cols, size_t max_batch) {
+  WideReferenceLayout R;
+  WideCrossPrunedLayout& P = R.P;
+  WideLayout& L = P.L;
+  L.T = (uint32_t)((n_ref + 31) / 32);
+  L.Tp = wide_pad_tiles(L.T);
+  L.Tq = (uint32_t)((max_batch + 31) / 32);
+  L.Tqp = wide_pad_tiles(L.Tq);
+  L.NM = (uint32_t)nm_for((int)n_cols);
+  P.blocks_r = L.Tp / kWideBlockTiles;
+  P.blocks_q = L.Tqp / kWideBlockTiles;
+  const size_t tile_bytes = (size_t)16 * 64 * L.NM;
+  const size_t n_max = max_batch > n_ref ? max_batch : n_ref;
+  size_t at = kWideOffImages;
+  auto take = [&at](size_t bytes) {
+    const size_t off = at;
+    at = align256(at + bytes);
+    return off;
+  };
+  R.resident_begin = at;
+  L.off_img_a = take(tile_bytes * L.Tp);
+  L.off_norms = take(sizeof(float) * 32 * (size_t)L.Tp);
+  P.off_perm_r = take(sizeof(uint32_t) * n_ref);
+  P.off_coords_r = take(sizeof(float) * n_ref * n_cols);
+  P.off_boxes_r = take(sizeof(float4) * P.blocks_r);
+  R.N.off_fe_r = take(sizeof(float) * n_ref);
+  R.N.off_fe_min_r = take(sizeof(float) * P.blocks_r);
+  R.off_fe_row = take(sizeof(float) * n_ref);
+  R.resident_end = R.batch_begin = at;
+  L.off_img_b = take(tile_bytes * L.Tqp);
+  L.off_merge = take(sizeof(unsigned long long) * 2 * max_batch);
+  P.off_perm_q = take(sizeof(uint32_t) * max_batch);
+  P.off_coords_q = take(sizeof(float) * max_batch * n_cols);
+  P.off_boxes_q = take(sizeof(float4) * P.blocks_q);
+  P.off_cnt = take(sizeof(uint32_t) * kMaxRadiiPerLaunch * max_batch);
+  R.N.off_fe_q = take(sizeof(float) * max_batch);
+  R.N.off_qwords = take(sizeof(uint32_t) * 4 * P.blocks_q);
+  R.batch_end = at;
+  P.off_keys = take(sizeof(uint32_t) * n_max);
+  P.off_keys_o = take(sizeof(uint32_t) * n_max);
+  P.off_vals = take(sizeof(uint32_t) * n_max);
+  P.sort_bytes = sort_temp_bytes(n_max);
+  P.off_sort = take(P.sort_bytes);
+  P.total = L.total = at;
+  R.N.off_flag_q = 4 * kWideHdrResFlagFeQuery;
+  R.N.ref_resident = true;
+  return R;
+}
+// one side's rows in the workspace's grid order: sort by the keys in the scratch, gather, box, sign
+int wide_reference_order(const WideReferenceLayout& R, const float* d_rows, uint32_t n, uint32_t n_cols, size_t off_perm,
+                         size_t off_coords, size_t off_boxes, uint32_t sign, uint32_t mark, void* d_ws, hipStream_t s) {
+  char* p = (char*)d_ws;
+  uint32_t* perm = (uint32_t*)(p + off_perm);
+  if (sort_pairs_u32((uint32_t*)(p + R.P.off_keys), (uint32_t*)(p + R.P.off_keys_o), (uint32_t*)(p + R.P.off_vals), perm, n,
+                     p + R.P.off_sort, R.P.sort_bytes, s, kCellKeyBits) != 0)
+    return -1;
+  hipLaunchKernelGGL(wide_prune_rows_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, d_rows, n, n_cols, (const uint32_t*)perm,
+                     (n + kWideBlockRows - 1u) / kWideBlockRows, (float*)(p + off_coords), (float4*)(p + off_boxes),
+                     (uint32_t*)p + sign, mark);
+  return 0;
+}
+}  // namespace
+
+size_t wide_reference_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_batch) {
+  if (!wide_mfma_supports(n_cols) || n_ref == 0 || max_batch == 0) return 0;
+  return wide_reference_layout(n_ref, n_cols, max_batch).P.total;
+}
+
+int wide_reference_open(const float* d_ref, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws, hipStream_t s) {
+  const WideReferenceLayout R = wide_reference_layout(n_ref, n_cols, max_batch);
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  const float* means = (const float*)(p + kWideOffMeans);
+  // statistics of the reference alone (wide_stats_launches without the free energies and with the resident scale)
+  if (hipMemsetAsync(d_ws, 0, kWideOffImages, s) != hipSuccess) return -1;
+  const size_t elems = (size_t)n_ref * n_cols;
+  hipLaunchKernelGGL(wide_colsum_kernel, dim3((uint32_t)min_sz(1024, (elems + 255) / 256)), dim3(256), 0, s, d_ref, n_ref, n_cols,
+                     (double*)(p + kWideOffSums));
+  hipLaunchKernelGGL(wide_mean_kernel, dim3(1), dim3(256), 0, s, (const double*)(p + kWideOffSums), (size_t)n_ref, n_cols,
+                     (float*)(p + kWideOffMeans));
+  hipLaunchKernelGGL(wide_rowstats_kernel, dim3((uint32_t)min_sz(4096, ((size_t)n_ref + 3) / 4)), dim3(256), 0, s, d_ref, n_ref,
+                     n_cols, means, hdr);
+  hipLaunchKernelGGL(wide_res_scale_kernel, dim3(1), dim3(1), 0, s, hdr);
+  if (hipMemsetD32Async((hipDeviceptr_t)(hdr + kWideHdrOrderLaidOut), (int)max_batch, 1, s) != hipSuccess) return -1;
+  // the grid: the reference's extent, the cell from its count; its order, gathered rows, boxes, A image and norms
+  hipLaunchKernelGGL(wide_extent_kernel, dim3((uint32_t)min_sz(1024, ((size_t)n_ref + 255) / 256)), dim3(256), 0, s, d_ref, n_ref,
+                     n_cols, hdr);
+  hipLaunchKernelGGL(wide_prune_key_kernel, dim3((uint32_t)min_sz(4096, ((size_t)n_ref + 255) / 256)), dim3(256), 0, s, d_ref, n_ref,
+                     n_cols, (const uint32_t*)hdr, (uint32_t*)(p + R.P.off_keys), (uint32_t*)(p + R.P.off_vals), n_ref, 0u);
+  if (wide_reference_order(R, d_ref, n_ref, n_cols, R.P.off_perm_r, R.P.off_coords_r, R.P.off_boxes_r, kWideHdrOrderRef,
+                           kWideOrderMarkRef, d_ws, s) != 0)
+    return -1;
+  const WideLayout& L = R.P.L;
+  const size_t frags = (size_t)L.Tp * L.NM * 64;
+  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags + 255) / 256)), dim3(256), 0, s, (const float*)(p + R.P.off_coords_r),
+                     n_ref, n_cols, L.NM, L.Tp, means, (const uint32_t*)p, (uint4*)(p + L.off_img_a), (uint4*)nullptr,
+                     (float*)(p + L.off_norms));
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int wide_reference_set_free_energies(const float* d_fe_ref, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws,
+                                     hipStream_t s) {
+  const WideReferenceLayout R = wide_reference_layout(n_ref, n_cols, max_batch);
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  float* fe_row = (float*)(p + R.off_fe_row);
+  if (hipMemcpyAsync(fe_row, d_fe_ref, sizeof(float) * (size_t)n_ref, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
+  if (hipMemsetD32Async((hipDeviceptr_t)(hdr + kWideHdrResFlagFeRef), 0, 1, s) != hipSuccess) return -1;
+  hipLaunchKernelGGL(wide_cross_nn_gather_kernel, dim3(R.P.blocks_r), dim3(128), 0, s, (const uint32_t*)(p + R.P.off_perm_r),
+                     (const float*)fe_row, n_ref, 0u, (float*)(p + R.N.off_fe_r), (float*)(p + R.N.off_fe_min_r),
+                     hdr + kWideHdrResFlagFeRef);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+const float* wide_reference_fe_by_row(const void* d_ws, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch) {
+  return (const float*)((const char*)d_ws + wide_reference_layout(n_ref, n_cols, max_batch).off_fe_row);
+}
+
+int wide_reference_stage(const float* d_query, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws,
+                         hipStream_t s) {
+  const WideReferenceLayout R = wide_reference_layout(n_ref, n_cols, max_batch);
+  char* p = (char*)d_ws;
+  uint32_t* hdr = (uint32_t*)p;
+  const float* means = (const float*)(p + kWideOffMeans);
+  hipLaunchKernelGGL(wide_res_batch_reset_kernel, dim3(1), dim3(64), 0, s, hdr);
+  if (n_query == 0) return hipGetLastError() == hipSuccess ? 0 : -1;
+  hipLaunchKernelGGL(wide_res_gate_kernel, dim3((uint32_t)min_sz(4096, ((size_t)n_query + 3) / 4)), dim3(256), 0, s, d_query, n_query,
+                     n_cols, means, hdr, (uint32_t*)(p + R.P.off_keys), (uint32_t*)(p + R.P.off_vals), n_ref);
+  if (wide_reference_order(R, d_query, n_query, n_cols, R.P.off_perm_q, R.P.off_coords_q, R.P.off_boxes_q, kWideHdrOrderQuery,
+                           kWideOrderMarkQuery, d_ws, s) != 0)
+    return -1;
+  const WideLayout& L = R.P.L;
+  const uint32_t Tqp = wide_pad_tiles((n_query + 31u) / 32u);
+  const size_t frags = (size_t)Tqp * L.NM * 64;
+  hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags + 255) / 256)), dim3(256), 0, s, (const float*)(p + R.P.off_coords_q),
+                     n_query, n_cols, L.NM, Tqp, means, (const uint32_t*)p, (uint4*)nullptr, (uint4*)(p + L.off_img_b), (float*)nullptr);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int wide_reference_arm(void* d_ws, hipStream_t s) {
+  hipLaunchKernelGGL(wide_res_arm_kernel, dim3(1), dim3(64), 0, s, (uint32_t*)d_ws, 0u);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_pop_wide_reference(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, const Rad2& rad2, int n_rad,
+                              uint32_t* d_pops_first_row, void* d_ws, hipStream_t s) {
+  if (n_query == 0 || n_rad <= 0) return 0;
+  return pop_wide_cross_pruned(wide_reference_layout(n_ref, n_cols, max_batch).P, n_query, n_ref, n_cols, n_query, rad2, n_rad,
+                               d_pops_first_row, d_ws, s);
+}
+
+int launch_nn_wide_reference(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, const float* d_fe_query,
+                             uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t s) {
+  if (n_query == 0) return 0;
+  const WideReferenceLayout R = wide_reference_layout(n_ref, n_cols, max_batch);
+  if (hipMemsetD32Async((hipDeviceptr_t)((uint32_t*)d_ws + kWideHdrResFlagFeQuery), 0, 1, s) != hipSuccess) return -1;
+  return nn_wide_cross_pruned(R.P, R.N, n_ref, n_cols, n_query, d_fe_query, nullptr, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, d_ws, s);
+}
+
+int wide_reference_info(const void* d_ws, uint64_t* tiles, uint64_t* mfmas, uint64_t* exact_pairs, uint32_t* answered, hipStream_t s) {
+  uint32_t h[kWideHdrResAnswered + 1];
+  if (hipMemcpyAsync(h, d_ws, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
+  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  if (tiles) *tiles = ((uint64_t)h[kWideHdrTiles + 1] << 32) | h[kWideHdrTiles];
+  if (mfmas) *mfmas = ((uint64_t)h[kWideHdrMfma + 1] << 32) | h[kWideHdrMfma];
+  if (exact_pairs) *exact_pairs = ((uint64_t)h[kWideHdrExact + 1] << 32) | h[kWideHdrExact];
+  if (answered) *answered = h[kWideHdrResAnswered];
+  return 0;
+}
+
+int wide_reference_order_copy(const void* d_ws, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch,
+                              uint32_t* d_perm_q, uint32_t* d_perm_r, hipStream_t s) {
+  const WideReferenceLayout R = wide_reference_layout(n_ref, n_cols, max_batch);
+  const char* p = (const char*)d_ws;
+  if (d_perm_q && n_query &&
+      hipMemcpyAsync(d_perm_q, p + R.P.off_perm_q, sizeof(uint32_t) * (size_t)n_query, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return -1;
+  if (d_perm_r && hipMemcpyAsync(d_perm_r, p + R.P.off_perm_r, sizeof(uint32_t) * (size_t)n_ref, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return -1;
+  return hipStreamSynchronize(s) == hipSuccess ? 0 : -1;
 }
 
 }  // namespace dc

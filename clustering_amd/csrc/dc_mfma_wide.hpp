@@ -150,4 +150,36 @@ int launch_nn_wide_cross_pruned(uint32_t n_query, uint32_t n_ref, uint32_t n_col
 int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n_ref, uint32_t n_cols, uint32_t* d_perm_q,
                             uint32_t* d_perm_r, hipStream_t stream);
 
+// ---- the resident reference of the pruned cross sweeps (dc_hip_reference_wide_*) --------------------------
+// The reference prepared once under statistics of its own (origin: its column means; scale: that of four times its
+// largest |x - mean|^2; grid: its extent), a batch of at most max_batch queries staged against it in one pass (the gate:
+// a row that is non-finite or beyond the scale's extent flags the batch, which the gated direct kernels then answer),
+// and the two pruned cross sweeps in that workspace, in any order and any number of times per staged batch.  Everything
+// runs on the stream without host synchronisation, except the two readers.  All return 0 on success.
+// bytes: a resident region sized by (n_ref, n_cols), a batch region sized by (max_batch, n_cols), the sort's scratch sized
+// by the larger count; 0 if the column count is not served or a count is zero; monotone in each argument
+size_t wide_reference_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_batch);
+int wide_reference_open(const float* d_ref, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws, hipStream_t stream);
+// the reference's free energies: copied by row (what the direct kernel reads), gathered by position, the least per block;
+// a NaN among them raises a word of its own, which only a neighbour sweep with free energies reads
+int wide_reference_set_free_energies(const float* d_fe_ref, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws,
+                                     hipStream_t stream);
+const float* wide_reference_fe_by_row(const void* d_ws, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch);
+// the batch half: gate and keys, order, gathered rows, boxes, B image (n_query <= max_batch; 0: only the batch's words are cleared)
+int wide_reference_stage(const float* d_query, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws,
+                         hipStream_t stream);
+// in front of a population sweep: header word 1 from the reference's and the batch's flags, the counters from zero
+// (launch_nn_wide_reference does the same itself, with the free energies' flags)
+int wide_reference_arm(void* d_ws, hipStream_t stream);
+// launch_pop_wide_cross_pruned / launch_nn_wide_cross_pruned of the staged batch (d_fe_query == nullptr: nn only)
+int launch_pop_wide_reference(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, const Rad2& rad2, int n_rad,
+                              uint32_t* d_pops_first_row, void* d_ws, hipStream_t stream);
+int launch_nn_wide_reference(uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, const float* d_fe_query,
+                             uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, hipStream_t stream);
+// the counters of the last sweep and who answered it; both orders, position -> row (a null pointer is skipped); synchronise
+int wide_reference_info(const void* d_ws, uint64_t* tiles, uint64_t* mfmas, uint64_t* exact_pairs, uint32_t* answered,
+                        hipStream_t stream);
+int wide_reference_order_copy(const void* d_ws, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch,
+                              uint32_t* d_perm_q, uint32_t* d_perm_r, hipStream_t stream);
+
 }  // namespace dc

@@ -268,8 +268,8 @@ __global__ void wide_fe_flag_kernel(const float* __restrict__ fe, uint32_t n_row
   if (__builtin_amdgcn_ballot_w64(nan) != 0 && (threadIdx.x & 63u) == 0) atomicOr(hdr + 1, 1u);
 }
 
-__global__ void wide_scale_kernel(uint32_t* __restrict__ hdr) {
-  const float M = __uint_as_float(hdr[0]);
+// the scale of the extent M into the header (M itself: word 0 is the caller's)
+__device__ __forceinline__ void wide_write_scale(uint32_t* __restrict__ hdr, float M) {
   hdr[kHdrMused] = __float_as_uint(M);
   const ScaleExp e = pick_scale_nn(M);
   hdr[kHdrScale + 0] = __float_as_uint(e.c);
@@ -278,6 +278,7 @@ __global__ void wide_scale_kernel(uint32_t* __restrict__ hdr) {
   hdr[kHdrScale + 3] = (uint32_t)e.a;
   hdr[kHdrScale + 4] = (uint32_t)e.rounded;
 }
+__global__ void wide_scale_kernel(uint32_t* __restrict__ hdr) { wide_write_scale(hdr, __uint_as_float(hdr[0])); }
 
 // Both operand images in the slot layout of dc_mfma_kernels.hpp (slot_value): one thread writes the 16-byte fragment of
 // one lane of one MFMA of one tile, reference side (A form) and query side (B form: the pieces of -2x'', and in the
@@ -423,6 +424,16 @@ __device__ __forceinline__ WidePruneGrid wide_prune_grid(const uint32_t* __restr
   g.ny = (uint32_t)fminf(e1 / g.cell, 4000.0f) + 1u;
   return g;
 }
+// the cell key of a row from its columns 0 / 1, clamped to the grid: a row outside the extent gets an edge cell
+__device__ __forceinline__ uint32_t wide_prune_key(const WidePruneGrid& g, float x, float y) {
+  uint32_t key = 0;
+  if (fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX) {
+    const uint32_t bx = (uint32_t)fminf(fmaxf((x - g.lo0) / g.cell, 0.0f), 4000.0f);
+    const uint32_t by = min((uint32_t)fminf(fmaxf((y - g.lo1) / g.cell, 0.0f), 4000.0f), g.ny - 1u);
+    key = bx * g.ny + ((bx & 1u) ? g.ny - 1u - by : by);
+  }
+  return key;
+}
 // cell key and value of every row (against_key_kernel's arithmetic: the cells numbered column by column, every other
 // column downwards, key 0 for a non-finite row).  n_grid: the rows the cell edge is sized for (a self sweep: n_rows; the
 // cross sweep: the reference's, for both sets); row0: the number of coords' first row (the value of row i is row0 + i)
@@ -431,14 +442,7 @@ __global__ __launch_bounds__(256) void wide_prune_key_kernel(const float* __rest
                                                              uint32_t* __restrict__ vals, uint32_t n_grid, uint32_t row0) {
   const WidePruneGrid g = wide_prune_grid(hdr, n_grid);
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_rows; i += gridDim.x * 256u) {
-    const float x = coords[(size_t)i * D], y = coords[(size_t)i * D + 1];
-    uint32_t key = 0;
-    if (fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX) {
-      const uint32_t bx = (uint32_t)fminf(fmaxf((x - g.lo0) / g.cell, 0.0f), 4000.0f);
-      const uint32_t by = min((uint32_t)fminf(fmaxf((y - g.lo1) / g.cell, 0.0f), 4000.0f), g.ny - 1u);
-      key = bx * g.ny + ((bx & 1u) ? g.ny - 1u - by : by);
-    }
-    keys[i] = key;
+    keys[i] = wide_prune_key(g, coords[(size_t)i * D], coords[(size_t)i * D + 1]);
     vals[i] = row0 + i;
   }
 }
@@ -569,18 +573,19 @@ __global__ __launch_bounds__(256) void wide_nn_finish_pruned_kernel(const uint32
 // the pruned cross neighbour sweep: the free energies of ONE side by position, and per block of its
 // order ONE end of their range over its live rows -- the least (the reference: want_max = 0; +inf for a block without a
 // live row) or the largest (the query range: want_max = 1; -inf), as wide_nn_gather_kernel writes them side by side.  A NaN
-// among them flags the data (header word 1, as wide_fe_flag_kernel does): ring 2 rests on these ends.
+// among them raises *flag (the cross calls: header word 1, as wide_fe_flag_kernel does; the resident reference: a word
+// per side): ring 2 rests on these ends.
 // Not gated on header word 1 itself: it reads through perm, which the preparation completes whatever the data holds.
 __global__ __launch_bounds__(128) void wide_cross_nn_gather_kernel(const uint32_t* __restrict__ perm, const float* __restrict__ fe,
                                                                    uint32_t n_rows, uint32_t want_max, float* __restrict__ fe_o,
-                                                                   float* __restrict__ fe_end, uint32_t* __restrict__ hdr) {
+                                                                   float* __restrict__ fe_end, uint32_t* __restrict__ flag) {
   static_assert(kWideBlockRows == 128, "two waves per block of the order");
   __shared__ float part[2];
   const uint32_t p = blockIdx.x * kWideBlockRows + threadIdx.x;
   const bool live = p < n_rows;
   const float f = live ? fe[perm[p]] : 0.0f;
   if (live) fe_o[p] = f;
-  if (__builtin_amdgcn_ballot_w64(f != f) != 0 && (threadIdx.x & 63u) == 0) atomicOr(hdr + 1, 1u);
+  if (__builtin_amdgcn_ballot_w64(f != f) != 0 && (threadIdx.x & 63u) == 0) atomicOr(flag, 1u);
   float v = live ? f : (want_max ? -INFINITY : INFINITY);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -657,6 +662,104 @@ inline int wide_prepare_against_launches(const float* d_query, uint32_t n_query,
                                          uint32_t n_cols, void* d_ws, hipStream_t s) {
   if (wide_stats_against_launches(d_query, n_query, d_ref, n_ref, n_cols, d_ws, s) != 0) return -1;
   return wide_image_against_launches(wide_layout_against(n_query, n_ref, n_cols), d_query, n_query, d_ref, n_ref, n_cols, d_ws, s);
+}
+
+// ---- the resident reference of the pruned cross sweeps (dc_hip_reference_wide_*) -----------------------
+// The reference is prepared once: origin = ITS column means, extent of columns 0 / 1 = ITS extent, and the scale that of
+//   M_res = 4 M_ref,   M_ref = the largest |x - mean|^2 of the reference as wide_rowstats_kernel forms it,
+// in header word 0 and kHdrMused, where M stands: a query up to twice as far from the origin as the farthest reference
+// frame is inside.  The band holds as it stands: it asks only that M bounds the norm of every row of BOTH operands, which
+// the reference meets with room (M_ref <= M_res) and every batch that passes wide_res_gate_kernel by that kernel's test.
+// The factor is a power of two: the exponent of pick_scale_nn moves by exactly one, the scale stays a power of two.
+// Header words of the resident form (behind the block words; a preparation of another form clears them with the header):
+// the flags are kept apart, and word 1 -- the word every gate reads -- is formed from them in front of every sweep.
+constexpr uint32_t kWideHdrResFlagRef = 72;       // the reference holds a non-finite / overflow-prone row, or 4 M_ref is beyond kNormLimit
+constexpr uint32_t kWideHdrResFlagFeRef = 73;     // a NaN among the reference's free energies
+constexpr uint32_t kWideHdrResFlagBatch = 74;     // the staged batch holds a row that is non-finite or beyond M_res
+constexpr uint32_t kWideHdrResFlagFeQuery = 75;   // a NaN among the free energies of the last neighbour sweep's queries
+constexpr uint32_t kWideHdrResAnswered = 76;      // who answered the last sweep: 0 the matrix cores, 1..3 the direct kernels (dc_density.h)
+constexpr uint32_t kWideHdrResMref = 77;          // M_ref (float bits)
+static_assert(kWideHdrResFlagRef >= kWideHdrOrderHash + 2 && 4 * (kWideHdrResMref + 1) <= kHdrBytes, "the resident words: behind the block words, inside the header");
+
+// behind the reference's statistics (word 0 = M_ref, word 1 = its flag): M_res and its scale; the flag moves to its own word
+__global__ void wide_res_scale_kernel(uint32_t* __restrict__ hdr) {
+  const float M_ref = __uint_as_float(hdr[0]), M_res = 4.0f * M_ref;
+  const bool flagged = hdr[1] != 0u || !(M_res <= kNormLimit);
+  hdr[kWideHdrResMref] = __float_as_uint(M_ref);
+  hdr[kWideHdrResFlagRef] = flagged ? 1u : 0u;
+  const float M = (M_res <= kNormLimit) ? M_res : M_ref;   // (a flagged reference is never swept: any finite scale serves)
+  hdr[0] = __float_as_uint(M);
+  hdr[1] = flagged ? 1u : 0u;
+  wide_write_scale(hdr, M);
+}
+
+// in front of a batch: what belongs to the batch before -- the counters, the signature of the query order, its two flags,
+// who answered -- is cleared; the means, M_res, the scale, the extent and the reference's order stay
+__global__ void wide_res_batch_reset_kernel(uint32_t* __restrict__ hdr) {
+  const uint32_t t = threadIdx.x;
+  if (t < 6u) hdr[kWideHdrTiles + t] = 0u;
+  if (t < 3u) hdr[kWideHdrOrderQuery + t] = 0u;
+  if (t == 0u) {
+    hdr[kWideHdrResFlagBatch] = 0u;
+    hdr[kWideHdrResFlagFeQuery] = 0u;
+    hdr[kWideHdrResAnswered] = 0u;
+    hdr[1] = hdr[kWideHdrResFlagRef];
+  }
+}
+
+// The gate of a batch, its ONE pass over the rows: a wave per row, the columns across its lanes (the resident means in
+// registers, four per lane).  |x - mean|^2 as wide_rowstats_kernel forms it against the resident means; the batch's flag
+// is raised by a row that is non-finite, beyond kNormLimit or beyond M_res (header word 0).  Columns 0 / 1 of the row are
+// in lanes 0 / 1: lane 0 writes the row's cell key on the reference's grid (clamped) and its value for the sort.
+// Stands in for a column-sum pass, a statistics pass, an extent pass and a key pass over the batch.  No LDS.
+__global__ __launch_bounds__(256) void wide_res_gate_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D,
+                                                            const float* __restrict__ means, uint32_t* __restrict__ hdr,
+                                                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                            uint32_t n_grid) {
+  static_assert(kWideMaxCols <= 4 * 64 && kWideMinCols > 64, "four columns per lane at most; lanes 0 / 1 hold columns 0 / 1");
+  const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+  const float M_res = __uint_as_float(hdr[0]);
+  const WidePruneGrid g = wide_prune_grid(hdr, n_grid);
+  float mu[4];
+#pragma unroll
+  for (uint32_t q = 0; q < 4u; ++q) mu[q] = (lane + 64u * q < D) ? means[lane + 64u * q] : 0.0f;
+  bool bad = false;
+  for (uint32_t row = wave; row < n_rows; row += n_waves) {
+    const float* x = coords + (size_t)row * D;
+    double nrm = 0.0;
+    float first = 0.0f;
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q)
+      if (lane + 64u * q < D) {
+        const float xk = x[lane + 64u * q];
+        if (q == 0u) first = xk;
+        const float v = xk - mu[q];
+        nrm += (double)v * (double)v;
+      }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nrm += __shfl_xor(nrm, off, 64);
+    const float nf = (float)nrm * (1.0f + 4.0e-7f);
+    bad = bad | !(nf <= kNormLimit) | !(nf <= M_res);
+    const float c0 = __shfl(first, 0, 64), c1 = __shfl(first, 1, 64);
+    if (lane == 0) {
+      keys[row] = wide_prune_key(g, c0, c1);
+      vals[row] = row;
+    }
+  }
+  if (lane == 0 && bad) atomicOr(hdr + kWideHdrResFlagBatch, 1u);
+}
+
+// in front of every sweep of a staged batch: word 1 from the resident flags -- the free energies' only for a neighbour
+// sweep that reads them (with_fe) --, who answers, and the counters of this sweep from zero
+__global__ void wide_res_arm_kernel(uint32_t* __restrict__ hdr, uint32_t with_fe) {
+  const uint32_t t = threadIdx.x;
+  if (t < 6u) hdr[kWideHdrTiles + t] = 0u;
+  if (t == 0u) {
+    const bool ref = hdr[kWideHdrResFlagRef] != 0u, batch = hdr[kWideHdrResFlagBatch] != 0u;
+    const bool fe = with_fe != 0u && (hdr[kWideHdrResFlagFeRef] | hdr[kWideHdrResFlagFeQuery]) != 0u;
+    hdr[1] = (ref || batch || fe) ? 1u : 0u;
+    hdr[kWideHdrResAnswered] = ref ? 1u : (batch ? 2u : (fe ? 3u : 0u));
+  }
 }
 
 // ---- the sweep ------------------------------------------------------------------------------------------------------

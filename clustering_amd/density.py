@@ -544,6 +544,150 @@ def assign_frames_wide_pruned(queries, reference, radius, ref_states, pruned_nei
                           nearest_reference_wide_pruned if pruned_neighbours else nearest_reference_wide)
 
 
+class Reference:
+    """A resident reference for the pruned wide cross sweeps (dc_hip_reference_wide_*, 65..256 columns): the reference
+    is prepared once, here; every batch of at most ``max_batch`` queries then pays for itself alone.
+
+        with Reference(reference, max_batch=20000, radius=r, ref_states=states) as ref:
+            for batch in batches:
+                out = ref.assign(batch)            # the dict of assign_frames_wide_pruned, the same values
+
+    or step by step: stage(queries), then populations(radii) and nearest(fe_query) in any order, any number of times.
+    The results are those of calculate_populations_against_wide / nearest_reference_wide bit for bit.  The object keeps
+    the reference tensor and the staged batch alive and allocates its workspace through torch on the reference's device.
+    With ``radius`` and ``ref_states`` the construction runs calculate_populations_wide_pruned on the reference ONCE and keeps
+    pops_ref, max_pop and fe_ref (set as the reference's free energies): what assign() needs of the reference."""
+
+    def __init__(self, reference, max_batch, radius=None, ref_states=None):
+        self._h = None
+        self._n_ref, self._n_cols = _check_coords(reference)
+        if not 65 <= self._n_cols <= 256:
+            raise ValueError(f"n_cols={self._n_cols}: the wide matrix-core sweeps take 65..256 columns")
+        self._max_batch = int(max_batch)
+        if self._n_ref < 1 or self._max_batch < 1:
+            raise ValueError(f"a reference of {self._n_ref} rows, batches of {self._max_batch}: both must be positive")
+        if (radius is None) != (ref_states is None):
+            raise ValueError("radius and ref_states go together")
+        states = None if ref_states is None else np.ascontiguousarray(ref_states, dtype=np.int32)
+        if states is not None and states.shape != (self._n_ref,):
+            raise ValueError(f"ref_states must hold one state per reference row ({self._n_ref}), got shape {states.shape}")
+        self._ref, self._queries, self._fe_ref = reference, None, None
+        self.device = reference.device
+        need = int(capi.lib.dc_hip_reference_wide_workspace_bytes(self._n_ref, self._n_cols, self._max_batch))
+        self._ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            capi.check(capi.lib.dc_hip_reference_wide_open_dev(_dev(reference), self._n_ref, self._n_cols, self._max_batch,
+                                                               _dev(self._ws), need, _stream_ptr(), C.byref(h)),
+                       "dc_hip_reference_wide_open_dev")
+        self._h = h
+        self.radius, self.pops_ref, self.max_pop, self.fe_ref, self._states_r = radius, None, None, None, None
+        if radius is not None:
+            self._states_r = torch.as_tensor(states, device=self.device)
+            self.pops_ref = calculate_populations_wide_pruned(reference, [radius])[0].contiguous()
+            self.max_pop = int(self.pops_ref.max().item())
+            self.fe_ref = calculate_free_energies(self.pops_ref)
+            self.set_free_energies(self.fe_ref)
+
+    n_ref = property(lambda self: self._n_ref)
+    n_cols = property(lambda self: self._n_cols)
+    max_batch = property(lambda self: self._max_batch)
+
+    def close(self):
+        if self._h is not None:
+            capi.lib.dc_hip_reference_wide_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def _call(self, fn, *args):
+        if self._h is None:
+            raise ValueError("the reference is closed")
+        with torch.cuda.device(self.device):
+            capi.check(getattr(capi.lib, fn)(self._h, *args, _stream_ptr()), fn)
+
+    def set_free_energies(self, fe_ref):
+        """fe_ref: float32 CUDA [n_ref]; read by this call (the library keeps a copy in its workspace)"""
+        assert fe_ref.is_cuda and fe_ref.dtype == torch.float32 and fe_ref.shape == (self._n_ref,) and fe_ref.is_contiguous()
+        self._call("dc_hip_reference_wide_set_free_energies_dev", _dev(fe_ref))
+        self._fe_ref = fe_ref
+
+    def stage(self, queries):
+        """the batch every sweep until the next stage() speaks of: float32 CUDA [n_q <= max_batch, n_cols]"""
+        n_q, n_cols = _check_coords(queries)
+        if n_cols != self._n_cols or queries.device != self.device:
+            raise ValueError("queries and reference need the same n_cols and the same device")
+        self._call("dc_hip_reference_wide_stage_dev", _dev(queries), n_q)
+        self._queries = queries
+
+    def populations(self, radii):
+        """-> int32 [n_radii, n_q] of the staged batch, in the order of ``radii``"""
+        if self._queries is None:
+            raise ValueError("no batch is staged")
+        rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+        out = torch.empty((rad.size, self._queries.shape[0]), dtype=torch.int32, device=self.device)
+        self._call("dc_hip_reference_wide_populations_dev", rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size, _dev(out))
+        return out
+
+    def nearest(self, fe_query=None):
+        """-> (nn_idx int32, nn_d2 float32, hd_idx, hd_d2) of the staged batch; without fe_query hd_idx / hd_d2 are None"""
+        if self._queries is None:
+            raise ValueError("no batch is staged")
+        n_q, with_fe = self._queries.shape[0], fe_query is not None
+        if with_fe:
+            assert fe_query.is_cuda and fe_query.dtype == torch.float32 and fe_query.shape == (n_q,) and fe_query.is_contiguous()
+        nn_idx = torch.empty(n_q, dtype=torch.int32, device=self.device)
+        nn_d2 = torch.empty(n_q, dtype=torch.float32, device=self.device)
+        hd_idx = torch.empty(n_q, dtype=torch.int32, device=self.device) if with_fe else None
+        hd_d2 = torch.empty(n_q, dtype=torch.float32, device=self.device) if with_fe else None
+        self._call("dc_hip_reference_wide_nearest_dev", _dev(fe_query) if with_fe else None, _dev(nn_idx), _dev(nn_d2),
+                   _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None)
+        return nn_idx, nn_d2, hd_idx, hd_d2
+
+    def info(self):
+        """(tiles, mfmas, exact_pairs, answered, reference_preparations) of the last sweep (dc_hip_reference_wide_info_dev)"""
+        t, m, e, a, r = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+        self._call("dc_hip_reference_wide_info_dev", C.byref(t), C.byref(m), C.byref(e), C.byref(a), C.byref(r))
+        return int(t.value), int(m.value), int(e.value), int(a.value), int(r.value)
+
+    def order(self):
+        """(perm_q int32 [n_q of the staged batch] or None before a stage, perm_r int32 [n_ref]), position -> row"""
+        perm_q = None if self._queries is None else torch.empty(self._queries.shape[0], dtype=torch.int32, device=self.device)
+        perm_r = torch.empty(self._n_ref, dtype=torch.int32, device=self.device)
+        self._call("dc_hip_reference_wide_order_dev", None if perm_q is None else _dev(perm_q), _dev(perm_r))
+        return perm_q, perm_r
+
+    def assign(self, queries):
+        """assign_frames_wide_pruned(queries, reference, radius, ref_states, pruned_neighbours=True) without its work on
+        the reference: any number of rows, in chunks of max_batch.  -> the same dict, the same values."""
+        if self.radius is None:
+            raise ValueError("assign() needs the radius and ref_states given at construction")
+        n_q, _ = _check_coords(queries)
+        none, parts = self._n_ref + 1, []
+        for lo in range(0, max(n_q, 1), self._max_batch):
+            chunk = queries[lo:lo + self._max_batch]
+            self.stage(chunk)
+            pops = self.populations([self.radius])[0].contiguous()
+            fe = calculate_free_energies_against(pops, self.max_pop) if self.max_pop else \
+                torch.full((chunk.shape[0],), float("inf"), dtype=torch.float32, device=self.device)
+            nn_idx, nn_d2, hd_idx, hd_d2 = self.nearest(fe)
+            states = torch.zeros(chunk.shape[0], dtype=torch.int32, device=self.device)
+            pick = torch.where(hd_idx != none, hd_idx, nn_idx)
+            ok = pick != none
+            states[ok] = self._states_r[pick[ok].long()]
+            parts.append({"states": states, "pops": pops, "fe": fe, "nn_idx": nn_idx, "nn_d2": nn_d2, "hd_idx": hd_idx, "hd_d2": hd_d2})
+        out = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        out.update(pops_ref=self.pops_ref, max_pop=self.max_pop, fe_ref=self.fe_ref)
+        return out
+
+
 def evaluated_tiles(device):
     """(pop_tiles, nn_tiles): 32x32 frame-pair tiles evaluated by the last pruned sweeps on this device's
     workspace.  The header is rebuilt by every sweep, so read it right after the sweep of interest
