@@ -58,6 +58,9 @@ SYMBOLS = (
     "dc_hip_reference_wide_workspace_bytes", "dc_hip_reference_wide_open_dev", "dc_hip_reference_wide_close",
     "dc_hip_reference_wide_set_free_energies_dev", "dc_hip_reference_wide_stage_dev", "dc_hip_reference_wide_populations_dev",
     "dc_hip_reference_wide_nearest_dev", "dc_hip_reference_wide_info_dev", "dc_hip_reference_wide_order_dev",
+    "dc_hip_reference_workspace_bytes", "dc_hip_reference_open_dev", "dc_hip_reference_close",
+    "dc_hip_reference_set_free_energies_dev", "dc_hip_reference_stage_dev", "dc_hip_reference_populations_dev",
+    "dc_hip_reference_nearest_dev", "dc_hip_reference_info_dev", "dc_hip_reference_order_dev",
 )
 SESSION_WIDE_SWEEPS = 0x1     # DC_SESSION_WIDE_SWEEPS (dc_hip_session_open_flags)
 
@@ -265,6 +268,25 @@ def _load():
                                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     lib.dc_hip_reference_wide_order_dev.restype = i32
     lib.dc_hip_reference_wide_order_dev.argtypes = [vp, vp, vp, vp]
+    lib.dc_hip_reference_workspace_bytes.restype = sz
+    lib.dc_hip_reference_workspace_bytes.argtypes = [sz, sz, sz]
+    lib.dc_hip_reference_open_dev.restype = i32
+    lib.dc_hip_reference_open_dev.argtypes = [vp, sz, sz, sz, C.c_float, vp, sz, vp, C.POINTER(vp)]
+    lib.dc_hip_reference_close.restype = None
+    lib.dc_hip_reference_close.argtypes = [vp]
+    lib.dc_hip_reference_set_free_energies_dev.restype = i32
+    lib.dc_hip_reference_set_free_energies_dev.argtypes = [vp, vp, vp]
+    lib.dc_hip_reference_stage_dev.restype = i32
+    lib.dc_hip_reference_stage_dev.argtypes = [vp, vp, sz, vp]
+    lib.dc_hip_reference_populations_dev.restype = i32
+    lib.dc_hip_reference_populations_dev.argtypes = [vp, C.POINTER(C.c_float), sz, vp, vp]
+    lib.dc_hip_reference_nearest_dev.restype = i32
+    lib.dc_hip_reference_nearest_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.dc_hip_reference_info_dev.restype = i32
+    lib.dc_hip_reference_info_dev.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
+    lib.dc_hip_reference_order_dev.restype = i32
+    lib.dc_hip_reference_order_dev.argtypes = [vp, i32, vp, vp, vp]
     lib.dc_hip_free_energies_scaled_dev.restype = i32
     lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
     lib.dc_hip_populations_cross.restype = i32

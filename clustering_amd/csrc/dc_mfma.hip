@@ -3,6 +3,7 @@
 #include "dc_mfma_kernels.hpp"
 #include "dc_against.hpp"
 #include "dc_against_nn.hpp"
+#include "dc_against_ref.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -909,6 +910,8 @@ __global__ __launch_bounds__(64) void pop_cross_kernel(
 }
 
 #include "dc_prep.hpp"
+#include "dc_reference_layout.hpp"
+#include "dc_reference.hpp"
 
 }  // namespace
 
@@ -2352,6 +2355,212 @@ int launch_nn_cross_pruned(const float* d_query, uint32_t n_q, const float* d_re
                         (const float*)(p + NL.off_meta), (unsigned long long*)(p + NL.off_merge64), W.T_r, W.T_q, n_ref, W.hdr};
   nn_against_sweep(A, n_cols, d_nn_idx, d_nn_d2, have_fe ? d_hd_idx : nullptr, have_fe ? d_hd_d2 : nullptr, stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---- the resident reference of the two pruned cross sweeps (dc_hip_reference_*) ---------------------------
+// The preparation of launch_pop_cross_pruned and launch_nn_cross_pruned in two halves: the reference's, once, under
+// statistics that do not depend on a batch (dc_reference.hpp), and a batch's, in reference_stage.  Both orders of a batch
+// are built there: a sweep prepares nothing, whichever comes first and however often it runs.
+namespace {
+struct ReferenceWs {
+  ReferenceLayout L;
+  char* p;
+  uint32_t* hdr;
+  SortBufs sort;
+  template <class T>
+  T* at(size_t off) const { return reinterpret_cast<T*>(p + off); }
+};
+ReferenceWs reference_ws(void* d_ws, size_t n_ref, size_t n_cols, size_t max_batch) {
+  ReferenceWs W;
+  W.L = reference_layout(n_ref, n_cols, max_batch);
+  W.p = (char*)d_ws;
+  W.hdr = (uint32_t*)d_ws;
+  W.sort = sort_bufs(d_ws, W.L, W.L.off_sort, W.L.sort_bytes);
+  return W;
+}
+void reference_arm(const ReferenceWs& W, uint32_t which, bool with_fe, hipStream_t s) {
+  hipLaunchKernelGGL(ref_arm_kernel, dim3(1), dim3(64), 0, s, W.hdr, which, with_fe ? 1u : 0u);
+}
+// the sort of n (key, value) pairs into perm, then in that order the tile boxes and (coords_o != nullptr) the rows
+int reference_order(const ReferenceWs& W, const SortBufs& sort, const float* d_set, uint32_t n, uint32_t n_cols, unsigned key_bits,
+                    uint32_t* perm, uint32_t T, float* coords_o, float4* boxes, hipStream_t s) {
+  if (sort.run(perm, n, s, key_bits)) return -3;
+  hipLaunchKernelGGL(against_rows_kernel, dim3((32u * T + 255) / 256), dim3(256), 0, s, d_set, n_cols, (const uint32_t*)perm, T,
+                     coords_o, boxes);
+  return 0;
+}
+// the neighbour side of R: cell order (d_fe == nullptr, the form a handle is opened in) or (cell, free energy) order
+int reference_nn_side(const ReferenceWs& W, const float* d_ref, const float* d_fe, uint32_t n_ref, uint32_t n_cols, hipStream_t s) {
+  const ReferenceLayout& L = W.L;
+  const dim3 blk(256);
+  const bool have_fe = d_fe != nullptr;
+  uint32_t* fe_hdr = W.hdr + kRefFeRefHdr;   // (fe_key_kernel's view: word 1 the NaN flag, words 12 / 13 the range)
+  hipLaunchKernelGGL(ref_fe_reset_kernel, dim3(1), dim3(1), 0, s, W.hdr, kRefFeRefHdr);
+  if (have_fe)
+    hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>((n_ref + 255) / 256, 256u)), blk, 0, s, d_fe, n_ref, (uint32_t*)nullptr,
+                       (uint32_t*)nullptr, fe_hdr);
+  const unsigned cell_bits = cell_key_bits(n_ref, kNnCellFrames);
+  const unsigned key_bits = (cell_bits + 9u <= 24u) ? 24u : 32u;
+  const unsigned fe_bits = have_fe ? std::min(key_bits - cell_bits, 16u) : 0u;
+  uint32_t* perm = W.at<uint32_t>(L.nn.off_perm_r);
+  float4* boxes = W.at<float4>(L.nn.off_box_r);
+  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_r + 255) / 256, 1024u)), blk, 0, s, d_ref, n_cols,
+                     (const uint32_t*)W.hdr, n_ref, cell_frames(true), 0u, n_ref, W.sort.keys_in, W.sort.vals_in, perm, 32u * L.T_r);
+  if (have_fe)
+    hipLaunchKernelGGL(against_fe_key_kernel, dim3(std::min<uint32_t>((n_ref + 255) / 256, 1024u)), blk, 0, s, W.sort.keys_in,
+                       (const uint32_t*)W.sort.vals_in, n_ref, d_fe, (const uint32_t*)fe_hdr, (uint32_t)fe_bits);
+  if (int rc = reference_order(W, W.sort, d_ref, n_ref, n_cols, cell_bits + fe_bits, perm, L.T_r, W.at<float>(L.nn.off_coords_r), boxes, s))
+    return rc;
+  hipLaunchKernelGGL(against_fe_rows_kernel, dim3((32u * L.T_r + 255) / 256), blk, 0, s, d_fe, (const uint32_t*)perm, L.T_r,
+                     W.at<float>(have_fe ? L.off_fe_c : L.off_fe_c_none), W.at<float2>(have_fe ? L.off_ferange : L.off_ferange_none));
+  hipLaunchKernelGGL(against_meta_kernel, dim3(1), blk, 0, s, (const uint32_t*)W.hdr, n_ref, cell_frames(true), (const float4*)boxes,
+                     L.T_r, W.at<float>(L.off_meta));
+  reference_arm(W, 1u, false, s);   // (the neighbour scale in words 20..24 for the image builder)
+  image(d_ref, 32u * L.T_r, n_cols, L.NM, L.T_r, perm, 2, W.at<void>(L.nn.off_img_r), nullptr, W.p, s);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+}  // namespace
+
+bool reference_takes(size_t n_ref, size_t n_cols) { return cross_pruned_takes(n_ref, n_cols); }
+
+size_t reference_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_batch) {
+  if (!mfma_supports(n_cols) || n_ref == 0 || max_batch == 0) return 0;
+  return reference_layout(n_ref, n_cols, max_batch).total;
+}
+
+int reference_open(const float* d_ref, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, float r2max, void* d_ws,
+                   hipStream_t s) {
+  const ReferenceWs W = reference_ws(d_ws, n_ref, n_cols, max_batch);
+  const ReferenceLayout& L = W.L;
+  // statistics of the reference alone: cross_prepare's launches over one set, then M_res and both scales
+  if (hipMemsetAsync(d_ws, 0, kRefOffArrays, s) != hipSuccess) return -1;
+  const uint32_t blocks = (uint32_t)std::min<size_t>(512, ((size_t)n_ref * n_cols + 255) / 256);
+  hipLaunchKernelGGL(colsum_kernel, dim3(blocks), dim3(256), 0, s, d_ref, n_ref, n_cols, (double*)(W.p + kHdrSums));
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, s, (const double*)(W.p + kHdrSums), n_ref, n_cols, (float*)(W.p + kHdrMeans));
+  hipLaunchKernelGGL(rowstats_kernel, dim3(std::min<uint32_t>((n_ref + 255) / 256, 512u)), dim3(256), 0, s, d_ref, n_ref, n_cols,
+                     (const float*)(W.p + kHdrMeans), W.hdr, 0u);
+  hipLaunchKernelGGL(ref_scale_kernel, dim3(1), dim3(1), 0, s, W.hdr, r2max, n_cols);
+  // the population side: R in the cell order of the population grid, its rows, boxes, A image and norms at the population scale
+  uint32_t* perm = W.at<uint32_t>(L.pop.off_perm_r);
+  hipLaunchKernelGGL(against_key_kernel, dim3(std::min<uint32_t>((32u * L.T_r + 255) / 256, 1024u)), dim3(256), 0, s, d_ref, n_cols,
+                     (const uint32_t*)W.hdr, n_ref, cell_frames(false), 0u, n_ref, W.sort.keys_in, W.sort.vals_in, perm, 32u * L.T_r);
+  if (int rc = reference_order(W, W.sort, d_ref, n_ref, n_cols, cell_key_bits(n_ref, kPopCellFrames), perm, L.T_r,
+                               W.at<float>(L.pop.off_coords_r), W.at<float4>(L.pop.off_box_r), s))
+    return rc;
+  reference_arm(W, 0u, false, s);   // (the population scale in words 20..24 for the image builder)
+  image(d_ref, 32u * L.T_r, n_cols, L.NM, L.T_r, perm, 0, W.at<void>(L.pop.off_img_r), W.at<void>(L.pop.off_norm_r), W.p, s);
+  // the neighbour side in its cell-only form, which also leaves the +inf words of a sweep without free energies
+  return reference_nn_side(W, d_ref, nullptr, n_ref, n_cols, s);
+}
+
+int reference_set_free_energies(const float* d_ref, const float* d_fe_ref, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch,
+                                void* d_ws, hipStream_t s) {
+  const ReferenceWs W = reference_ws(d_ws, n_ref, n_cols, max_batch);
+  float* fe_row = W.at<float>(W.L.off_fe_row);
+  if (hipMemcpyAsync(fe_row, d_fe_ref, sizeof(float) * (size_t)n_ref, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
+  return reference_nn_side(W, d_ref, fe_row, n_ref, n_cols, s);
+}
+
+const float* reference_fe_by_row(const void* d_ws, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch) {
+  return (const float*)((const char*)d_ws + reference_layout(n_ref, n_cols, max_batch).off_fe_row);
+}
+
+int reference_stage(const float* d_query, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws,
+                    hipStream_t s) {
+  const ReferenceWs W = reference_ws(d_ws, n_ref, n_cols, max_batch);
+  const ReferenceLayout& L = W.L;
+  // what belongs to the batch before: its flag; the means, M_res, the scales, the grid and the reference's sides stay
+  if (hipMemsetD32Async((hipDeviceptr_t)(W.hdr + kRefFlagBatch), 0, 1, s) != hipSuccess) return -1;
+  if (n_query == 0) return 0;
+  const uint32_t T_q = (n_query + 31u) / 32u;
+  hipLaunchKernelGGL(ref_gate_kernel, dim3(std::min<uint32_t>((32u * T_q + 255) / 256, 1024u)), dim3(256), 0, s, d_query, n_query,
+                     n_cols, (const float*)(W.p + kHdrMeans), W.hdr, n_ref, cell_frames(false), cell_frames(true), W.sort.keys_in,
+                     W.sort.vals_in, W.at<uint32_t>(L.off_keys_nn), W.at<uint32_t>(L.off_vals_nn), W.at<uint32_t>(L.pop.off_perm_q),
+                     W.at<uint32_t>(L.nn.off_perm_q), 32u * T_q);
+  // either order: the sort (the neighbour grid's keys wait in the batch region for theirs), the boxes, the B image at that
+  // sweep's scale
+  SortBufs sort_nn = W.sort;
+  sort_nn.keys_in = W.at<uint32_t>(L.off_keys_nn);
+  sort_nn.vals_in = W.at<uint32_t>(L.off_vals_nn);
+  struct Side {
+    const ReferenceSide& S;
+    const SortBufs& sort;
+    unsigned key_bits;
+    uint32_t which;
+  } const sides[2] = {{L.pop, W.sort, cell_key_bits(n_ref, kPopCellFrames), 0u}, {L.nn, sort_nn, cell_key_bits(n_ref, kNnCellFrames), 1u}};
+  for (const Side& side : sides) {
+    uint32_t* perm = W.at<uint32_t>(side.S.off_perm_q);
+    if (int rc = reference_order(W, side.sort, d_query, n_query, n_cols, side.key_bits, perm, T_q, nullptr, W.at<float4>(side.S.off_box_q), s))
+      return rc;
+    reference_arm(W, side.which, false, s);
+    image(d_query, 32u * T_q, n_cols, L.NM, T_q, perm, 1, W.at<void>(side.S.off_img_q), W.at<void>(side.S.off_norm_q), W.p, s);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_pop_reference(const float* d_query, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch,
+                         const float* rad2, int n_rad, uint32_t* d_pops, void* d_ws, hipStream_t s) {
+  if (n_query == 0 || n_rad <= 0) return 0;
+  const ReferenceWs W = reference_ws(d_ws, n_ref, n_cols, max_batch);
+  const ReferenceSide& S = W.L.pop;
+  reference_arm(W, 0u, false, s);
+  const AgainstArgs A{d_query, W.at<const uint4>(S.off_img_r), W.at<const float>(S.off_norm_r), W.at<const float4>(S.off_box_r),
+                      W.at<const float>(S.off_coords_r), W.at<const uint4>(S.off_img_q), W.at<const float>(S.off_norm_q),
+                      W.at<const uint32_t>(S.off_perm_q), W.at<const float4>(S.off_box_q), W.L.T_r, (n_query + 31u) / 32u, n_query,
+                      (const uint32_t*)W.hdr, (unsigned long long*)(W.p + 8)};
+  // one radius at a time on the one preparation, whose scale serves the largest the handle was opened for
+  for (int r = 0; r < n_rad; ++r) pop_against_sweep(A, n_cols, one_radius(rad2[r]), d_pops + (size_t)r * n_query, s);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_nn_reference(const float* d_query, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch,
+                        const float* d_fe_query, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
+                        void* d_ws, hipStream_t s) {
+  if (n_query == 0) return 0;
+  const ReferenceWs W = reference_ws(d_ws, n_ref, n_cols, max_batch);
+  const ReferenceLayout& L = W.L;
+  const ReferenceSide& S = L.nn;
+  const bool have_fe = d_fe_query != nullptr;
+  // a NaN among the queries' free energies flags this sweep (fe_key_kernel raises its word; the range is not used)
+  hipLaunchKernelGGL(ref_fe_reset_kernel, dim3(1), dim3(1), 0, s, W.hdr, kRefFeQueryHdr);
+  if (have_fe)
+    hipLaunchKernelGGL(fe_key_kernel, dim3(std::min<uint32_t>((n_query + 255) / 256, 256u)), dim3(256), 0, s, d_fe_query, n_query,
+                       (uint32_t*)nullptr, (uint32_t*)nullptr, W.hdr + kRefFeQueryHdr);
+  reference_arm(W, 1u, have_fe, s);
+  const NnAgainstArgs A{d_query, d_fe_query, W.at<const uint4>(S.off_img_r), W.at<const uint32_t>(S.off_perm_r),
+                        W.at<const float4>(S.off_box_r), W.at<const float2>(have_fe ? L.off_ferange : L.off_ferange_none),
+                        W.at<const float>(have_fe ? L.off_fe_c : L.off_fe_c_none), W.at<const float>(S.off_coords_r),
+                        W.at<const uint4>(S.off_img_q), W.at<const float>(S.off_norm_q), W.at<const uint32_t>(S.off_perm_q),
+                        W.at<const float4>(S.off_box_q), W.at<const float>(L.off_meta), W.at<unsigned long long>(L.off_merge64),
+                        L.T_r, (n_query + 31u) / 32u, n_ref, W.hdr};
+  nn_against_sweep(A, n_cols, d_nn_idx, d_nn_d2, have_fe ? d_hd_idx : nullptr, have_fe ? d_hd_d2 : nullptr, s);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int reference_info(const void* d_ws, uint64_t* tiles, uint64_t* mfmas, uint32_t* shares, uint32_t* answered, hipStream_t s) {
+  uint32_t h[kRefOffArrays / 4];
+  if (hipMemcpyAsync(h, d_ws, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
+  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  auto u64 = [&h](uint32_t w) { return ((uint64_t)h[w + 1] << 32) | h[w]; };
+  // (the arm kernel zeroes the counters of both sweeps: the sum is the last sweep's)
+  if (tiles) *tiles = u64(2) + u64(4);
+  if (mfmas) *mfmas = u64(kHdrMfmaPop) + u64(kHdrMfmaNn);
+  if (shares) *shares = h[kHdrShares];
+  if (answered) *answered = h[kRefAnswered];
+  return 0;
+}
+
+int reference_order_copy(const void* d_ws, int which, uint32_t n_query, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch,
+                         uint32_t* d_perm_q, uint32_t* d_perm_r, hipStream_t s) {
+  const ReferenceLayout L = reference_layout(n_ref, n_cols, max_batch);
+  const ReferenceSide& S = which ? L.nn : L.pop;
+  const char* p = (const char*)d_ws;
+  if (d_perm_q && n_query &&
+      hipMemcpyAsync(d_perm_q, p + S.off_perm_q, sizeof(uint32_t) * (size_t)n_query, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return -1;
+  if (d_perm_r && hipMemcpyAsync(d_perm_r, p + S.off_perm_r, sizeof(uint32_t) * (size_t)n_ref, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return -1;
+  return hipStreamSynchronize(s) == hipSuccess ? 0 : -1;
 }
 
 // ---- DC_VARIANT_MFMA32: the fp32-input MFMA instance (dc_mfma32.hpp) ---------------------------------------------

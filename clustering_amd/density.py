@@ -558,6 +558,8 @@ class Reference:
     With ``radius`` and ``ref_states`` the construction runs calculate_populations_wide_pruned on the reference ONCE and keeps
     pops_ref, max_pop and fe_ref (set as the reference's free energies): what assign() needs of the reference."""
 
+    _api = "dc_hip_reference_wide_"   # the entry points' common prefix
+
     def __init__(self, reference, max_batch, radius=None, ref_states=None):
         self._h = None
         self._n_ref, self._n_cols = _check_coords(reference)
@@ -595,7 +597,7 @@ class Reference:
 
     def close(self):
         if self._h is not None:
-            capi.lib.dc_hip_reference_wide_close(self._h)
+            getattr(capi.lib, self._api + "close")(self._h)
             self._h = None
 
     def __enter__(self):
@@ -611,12 +613,12 @@ class Reference:
         if self._h is None:
             raise ValueError("the reference is closed")
         with torch.cuda.device(self.device):
-            capi.check(getattr(capi.lib, fn)(self._h, *args, _stream_ptr()), fn)
+            capi.check(getattr(capi.lib, self._api + fn)(self._h, *args, _stream_ptr()), self._api + fn)
 
     def set_free_energies(self, fe_ref):
         """fe_ref: float32 CUDA [n_ref]; read by this call (the library keeps a copy in its workspace)"""
         assert fe_ref.is_cuda and fe_ref.dtype == torch.float32 and fe_ref.shape == (self._n_ref,) and fe_ref.is_contiguous()
-        self._call("dc_hip_reference_wide_set_free_energies_dev", _dev(fe_ref))
+        self._call("set_free_energies_dev", _dev(fe_ref))
         self._fe_ref = fe_ref
 
     def stage(self, queries):
@@ -624,7 +626,7 @@ class Reference:
         n_q, n_cols = _check_coords(queries)
         if n_cols != self._n_cols or queries.device != self.device:
             raise ValueError("queries and reference need the same n_cols and the same device")
-        self._call("dc_hip_reference_wide_stage_dev", _dev(queries), n_q)
+        self._call("stage_dev", _dev(queries), n_q)
         self._queries = queries
 
     def populations(self, radii):
@@ -633,7 +635,7 @@ class Reference:
             raise ValueError("no batch is staged")
         rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
         out = torch.empty((rad.size, self._queries.shape[0]), dtype=torch.int32, device=self.device)
-        self._call("dc_hip_reference_wide_populations_dev", rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size, _dev(out))
+        self._call("populations_dev", rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size, _dev(out))
         return out
 
     def nearest(self, fe_query=None):
@@ -647,21 +649,21 @@ class Reference:
         nn_d2 = torch.empty(n_q, dtype=torch.float32, device=self.device)
         hd_idx = torch.empty(n_q, dtype=torch.int32, device=self.device) if with_fe else None
         hd_d2 = torch.empty(n_q, dtype=torch.float32, device=self.device) if with_fe else None
-        self._call("dc_hip_reference_wide_nearest_dev", _dev(fe_query) if with_fe else None, _dev(nn_idx), _dev(nn_d2),
+        self._call("nearest_dev", _dev(fe_query) if with_fe else None, _dev(nn_idx), _dev(nn_d2),
                    _dev(hd_idx) if with_fe else None, _dev(hd_d2) if with_fe else None)
         return nn_idx, nn_d2, hd_idx, hd_d2
 
     def info(self):
         """(tiles, mfmas, exact_pairs, answered, reference_preparations) of the last sweep (dc_hip_reference_wide_info_dev)"""
         t, m, e, a, r = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
-        self._call("dc_hip_reference_wide_info_dev", C.byref(t), C.byref(m), C.byref(e), C.byref(a), C.byref(r))
+        self._call("info_dev", C.byref(t), C.byref(m), C.byref(e), C.byref(a), C.byref(r))
         return int(t.value), int(m.value), int(e.value), int(a.value), int(r.value)
 
     def order(self):
         """(perm_q int32 [n_q of the staged batch] or None before a stage, perm_r int32 [n_ref]), position -> row"""
         perm_q = None if self._queries is None else torch.empty(self._queries.shape[0], dtype=torch.int32, device=self.device)
         perm_r = torch.empty(self._n_ref, dtype=torch.int32, device=self.device)
-        self._call("dc_hip_reference_wide_order_dev", None if perm_q is None else _dev(perm_q), _dev(perm_r))
+        self._call("order_dev", None if perm_q is None else _dev(perm_q), _dev(perm_r))
         return perm_q, perm_r
 
     def assign(self, queries):
@@ -686,6 +688,71 @@ class Reference:
         out = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
         out.update(pops_ref=self.pops_ref, max_pop=self.max_pop, fe_ref=self.fe_ref)
         return out
+
+
+class NarrowReference(Reference):
+    """A resident reference for the pruned cross sweeps of rows of 1..64 columns (dc_hip_reference_*): Reference's
+    methods, for calculate_populations_against(variant="cross_pruned") and nearest_reference(pruned=True).
+
+        with NarrowReference(reference, max_batch=100000, radius=r, ref_states=states) as ref:
+            for batch in batches:
+                out = ref.assign(batch)   # the dict of assign_frames(variant="cross_pruned", pruned_neighbours=True)
+
+    ``max_radius`` (default: ``radius``) is the largest radius any populations() call will use: the reference's operand
+    image is built at the scale of that radius, and a larger one is refused.  With ``radius`` and ``ref_states`` the
+    construction runs calculate_populations_partial (variant "auto") on the reference ONCE and keeps pops_ref, max_pop
+    and fe_ref (set as the reference's free energies).  info() -> (tiles, mfmas, shares, answered,
+    reference_preparations); order(which): 0 the population sweep's orders, 1 the neighbour sweep's."""
+    _api = "dc_hip_reference_"
+
+    def __init__(self, reference, max_batch, max_radius=None, radius=None, ref_states=None):
+        self._h = None
+        self._n_ref, self._n_cols = _check_coords(reference)
+        if not 1 <= self._n_cols <= 64:
+            raise ValueError(f"n_cols={self._n_cols}: the resident reference of the pruned cross sweeps takes 1..64 columns")
+        self._max_batch = int(max_batch)
+        if self._n_ref < 1 or self._max_batch < 1:
+            raise ValueError(f"a reference of {self._n_ref} rows, batches of {self._max_batch}: both must be positive")
+        if (radius is None) != (ref_states is None):
+            raise ValueError("radius and ref_states go together")
+        max_radius = radius if max_radius is None else max_radius
+        if max_radius is None:
+            raise ValueError("max_radius (or radius) is needed: the population scale is fixed when the reference is opened")
+        states = None if ref_states is None else np.ascontiguousarray(ref_states, dtype=np.int32)
+        if states is not None and states.shape != (self._n_ref,):
+            raise ValueError(f"ref_states must hold one state per reference row ({self._n_ref}), got shape {states.shape}")
+        self._ref, self._queries, self._fe_ref = reference, None, None
+        self.device = reference.device
+        self.max_radius = float(max_radius)
+        need = int(capi.lib.dc_hip_reference_workspace_bytes(self._n_ref, self._n_cols, self._max_batch))
+        self._ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            capi.check(capi.lib.dc_hip_reference_open_dev(_dev(reference), self._n_ref, self._n_cols, self._max_batch,
+                                                          self.max_radius, _dev(self._ws), need, _stream_ptr(), C.byref(h)),
+                       "dc_hip_reference_open_dev")
+        self._h = h
+        self.radius, self.pops_ref, self.max_pop, self.fe_ref, self._states_r = radius, None, None, None, None
+        if radius is not None:
+            self._states_r = torch.as_tensor(states, device=self.device)
+            self.pops_ref = calculate_populations_partial(reference, [radius], variant="auto")[0].contiguous()
+            self.max_pop = int(self.pops_ref.max().item())
+            self.fe_ref = calculate_free_energies(self.pops_ref)
+            self.set_free_energies(self.fe_ref)
+
+    def info(self):
+        """(tiles, mfmas, shares, answered, reference_preparations) of the last sweep (dc_hip_reference_info_dev)"""
+        t, m, n, a, r = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._call("info_dev", C.byref(t), C.byref(m), C.byref(n), C.byref(a), C.byref(r))
+        return int(t.value), int(m.value), int(n.value), int(a.value), int(r.value)
+
+    def order(self, which=0):
+        """(perm_q int32 [n_q of the staged batch] or None before a stage, perm_r int32 [n_ref]), position -> row, of the
+        population sweep (which = 0) or of the neighbour sweep (which = 1)"""
+        perm_q = None if self._queries is None else torch.empty(self._queries.shape[0], dtype=torch.int32, device=self.device)
+        perm_r = torch.empty(self._n_ref, dtype=torch.int32, device=self.device)
+        self._call("order_dev", int(which), None if perm_q is None else _dev(perm_q), _dev(perm_r))
+        return perm_q, perm_r
 
 
 def evaluated_tiles(device):

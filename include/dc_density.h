@@ -395,6 +395,71 @@ DC_API int dc_hip_nearest_neighbors_cross_pruned_dev(const float* d_query, size_
 DC_API int dc_hip_nearest_cross_pruned_info_dev(const void* d_ws, uint64_t* nn_tiles, uint64_t* nn_mfma,
                                                 uint32_t* n_shares, void* stream);
 
+/* ---- ... and a RESIDENT REFERENCE for the two pruned cross sweeps (1..64 columns) ---------------------------------------
+ * DC_VARIANT_CROSS_PRUNED of dc_hip_populations_cross_dev and dc_hip_nearest_neighbors_cross_pruned_dev for a caller who
+ * streams batches of queries against ONE reference: the reference is prepared once, when it is opened -- origin, both
+ * scales, grid, and per sweep its order, its gathered rows, boxes and operand image --, and a batch pays for itself alone.
+ * The statistics cannot depend on a batch: the origin is the column mean of the reference, the grid its extent in columns
+ * 0 / 1 (a query outside it lands in an edge cell; its tile's box is still formed from its own floats), and the scales are
+ * those of FOUR TIMES the reference's largest |x - mean|^2: a query up to twice as far from the origin as the farthest
+ * reference frame runs on the matrix cores.
+ * The handle is a small host object.  It BORROWS d_ref and d_ws until it is closed, and d_query from
+ * dc_hip_reference_stage_dev until the last sweep of that batch: all must stay valid and unchanged for that long.
+ * d_fe_ref and d_fe_query are read by the call they are given to and not kept.  Calls on one handle are ordered by the
+ * caller: on one stream, or with synchronisation between them.  Nothing here synchronises with the host but the two readers.
+ *   workspace_bytes  a region sized by (n_ref, n_cols) that stays, one sized by (max_batch, n_cols) that a batch
+ *                    rewrites, and the sort's scratch; 0 outside 1..64 columns or for a zero count; monotone in each argument
+ *   open             prepares the reference (the population side once per handle: `reference_preparations` of the info
+ *                    call counts its runs).  max_radius: the largest radius any population call on this handle will use,
+ *                    any number >= 0, +inf allowed; the population scale -- and the resident operand image -- are those
+ *                    of fl32(max_radius^2).  The neighbour side of the reference is prepared in its form without free energies
+ *   set_free_energies  fe_ref[n_ref], as dc_hip_nearest_neighbors_cross_dev takes it: a copy by row is kept, and the
+ *                    neighbour side of the reference is prepared again, ordered by (cell, free energy); may be called
+ *                    again with new values
+ *   stage            the batch: ONE pass over its rows (the gate, and the cell keys on both grids), then per sweep its
+ *                    order, boxes and operand image.  n_query <= max_batch; n_query == 0 stages an empty batch, whose
+ *                    sweeps return DC_OK and write nothing
+ *   populations      d_pops[n_radii][n_query] = dc_hip_populations_cross_dev's over the whole batch, bit for bit: strict <,
+ *                    no self term, radii (host pointer) in any order.  A radius whose fl32(r * r) exceeds fl32(max_radius^2)
+ *                    is refused before the device is touched
+ *   nearest          the four arrays of dc_hip_nearest_neighbors_cross_dev over the whole batch, bit for bit: the least
+ *                    (d2, ROW of R); "none" = (n_ref + 1, FLT_MAX); d_fe_query == NULL: nn only, the hd outputs may be NULL
+ *                    and are not written
+ * The two sweeps of a staged batch run in either order and any number of times without a second preparation.
+ * Flagged data is answered by the direct kernels behind the device-side gate, without a host synchronisation, with the
+ * same results; the counters then read zero.  `answered` of the info call says who answered the LAST sweep:
+ *   0 the matrix cores;  1 the direct kernels, the reference holds a non-finite or overflow-prone row;  2 the direct
+ *   kernels, the staged batch holds a row that is non-finite or farther from the origin than the scales allow;  3 the
+ *   direct kernel, a NaN in fe_ref or in d_fe_query (the neighbour sweep with free energies only: populations, and
+ *   neighbours without free energies, stay on the matrix cores).
+ * A flag lasts as long as what raised it: the batch's until the next stage, the free energies' until they are set again
+ * (fe_ref) or until the next neighbour sweep (d_fe_query).
+ * info (tiles: 32x32 tile pairs evaluated, mfmas: MFMA instructions issued, shares: the reference shares of a neighbour
+ * sweep's launch, 0 after a population sweep -- all of the last sweep; any pointer may be NULL) and order (which: 0 the
+ * population sweep's orders, 1 the neighbour sweep's; d_perm_q[n_query of the staged batch], d_perm_r[n_ref], position ->
+ * row; either may be NULL) SYNCHRONISE.
+ * Refusals, all before a device is touched, dc_hip_last_error names the function: n_cols outside 1..64, n_ref == 0,
+ * max_batch == 0, a max_radius that is NaN or negative, a NULL array, handle or `out`, n_query > max_batch, a sweep before
+ * any stage, d_fe_query before free energies were set, a radius beyond max_radius, `which` other than 0 / 1:
+ * DC_ERR_INVALID_ARGUMENT; n_ref + 1 or max_batch beyond uint32, either count times n_cols beyond the element arithmetic
+ * (as the cross calls check them), or a reference whose padded order exceeds 2^24 positions (the per-call entry points
+ * keep serving it): DC_ERR_TOO_LARGE; a workspace smaller than dc_hip_reference_workspace_bytes, or none:
+ * DC_ERR_WORKSPACE.  On a refusal of open *out is NULL. */
+typedef struct dc_reference dc_reference;
+DC_API size_t dc_hip_reference_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_batch);
+DC_API int dc_hip_reference_open_dev(const float* d_ref, size_t n_ref, size_t n_cols, size_t max_batch, float max_radius,
+                                     void* d_ws, size_t ws_bytes, void* stream, dc_reference** out);
+DC_API void dc_hip_reference_close(dc_reference* reference);
+DC_API int dc_hip_reference_set_free_energies_dev(dc_reference* reference, const float* d_fe_ref, void* stream);
+DC_API int dc_hip_reference_stage_dev(dc_reference* reference, const float* d_query, size_t n_query, void* stream);
+DC_API int dc_hip_reference_populations_dev(dc_reference* reference, const float* radii, size_t n_radii, uint32_t* d_pops,
+                                            void* stream);
+DC_API int dc_hip_reference_nearest_dev(dc_reference* reference, const float* d_fe_query, uint32_t* d_nn_idx, float* d_nn_d2,
+                                        uint32_t* d_hd_idx, float* d_hd_d2, void* stream);
+DC_API int dc_hip_reference_info_dev(dc_reference* reference, uint64_t* tiles, uint64_t* mfmas, uint32_t* shares,
+                                     uint32_t* answered, uint32_t* reference_preparations, void* stream);
+DC_API int dc_hip_reference_order_dev(dc_reference* reference, int which, uint32_t* d_perm_q, uint32_t* d_perm_r, void* stream);
+
 /* ---- matrix-core sweeps for rows of 65..256 columns ("wide" sweeps) ----------------------------------------------
  * Every-pair self sweeps on the f16 matrix cores whose K axis streams through LDS, with the results of
  * dc_hip_populations_dev / dc_hip_nearest_neighbors_dev bit for bit (classifier + guard band + canonical re-check;
