@@ -61,6 +61,9 @@ SYMBOLS = (
     "dc_hip_reference_workspace_bytes", "dc_hip_reference_open_dev", "dc_hip_reference_close",
     "dc_hip_reference_set_free_energies_dev", "dc_hip_reference_stage_dev", "dc_hip_reference_populations_dev",
     "dc_hip_reference_nearest_dev", "dc_hip_reference_info_dev", "dc_hip_reference_order_dev",
+    "dc_hip_assign_workspace_bytes", "dc_hip_assign_open_dev", "dc_hip_assign_open_wide_dev", "dc_hip_assign_close",
+    "dc_hip_assign_batch_dev",
+    "dc_hip_assigner_open", "dc_hip_assigner_reference", "dc_hip_assigner_path", "dc_hip_assigner_assign", "dc_hip_assigner_close",
 )
 SESSION_WIDE_SWEEPS = 0x1     # DC_SESSION_WIDE_SWEEPS (dc_hip_session_open_flags)
 
@@ -287,6 +290,26 @@ def _load():
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     lib.dc_hip_reference_order_dev.restype = i32
     lib.dc_hip_reference_order_dev.argtypes = [vp, i32, vp, vp, vp]
+    lib.dc_hip_assign_workspace_bytes.restype = sz
+    lib.dc_hip_assign_workspace_bytes.argtypes = [sz, sz]
+    lib.dc_hip_assign_open_dev.restype = i32
+    lib.dc_hip_assign_open_dev.argtypes = [vp, vp, C.c_uint32, C.c_float, vp, sz, vp, C.POINTER(vp)]
+    lib.dc_hip_assign_open_wide_dev.restype = i32
+    lib.dc_hip_assign_open_wide_dev.argtypes = lib.dc_hip_assign_open_dev.argtypes
+    lib.dc_hip_assign_close.restype = None
+    lib.dc_hip_assign_close.argtypes = [vp]
+    lib.dc_hip_assign_batch_dev.restype = i32
+    lib.dc_hip_assign_batch_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.dc_hip_assigner_open.restype = i32
+    lib.dc_hip_assigner_open.argtypes = [vp, sz, sz, vp, C.c_float, sz, i32, C.POINTER(vp)]
+    lib.dc_hip_assigner_reference.restype = i32
+    lib.dc_hip_assigner_reference.argtypes = [vp, vp, vp, C.POINTER(C.c_uint32)]
+    lib.dc_hip_assigner_path.restype = i32
+    lib.dc_hip_assigner_path.argtypes = [vp]
+    lib.dc_hip_assigner_assign.restype = i32
+    lib.dc_hip_assigner_assign.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.dc_hip_assigner_close.restype = None
+    lib.dc_hip_assigner_close.argtypes = [vp]
     lib.dc_hip_free_energies_scaled_dev.restype = i32
     lib.dc_hip_free_energies_scaled_dev.argtypes = [vp, sz, C.c_uint32, vp, vp]
     lib.dc_hip_populations_cross.restype = i32

@@ -1,4 +1,4 @@
-// clustering_cli.cpp -- `clustering density` on MI355X.
+// clustering_cli.cpp -- `clustering density` and `clustering assign` on MI355X.
 //
 // Re-creates the density mode of the reference's command line (clustering.cpp:141-193 options,
 // density_clustering.cpp:559-825 control flow) on top of libdcdensity.so, with the reference's
@@ -711,21 +711,145 @@ int density_main(int argc, char** argv) {
   return EXIT_SUCCESS;
 }
 
+// ---- the assign mode: new frames to the states of a clustered reference (dc_hip_assigner_*) ---------------------
+const char* kAssignHelp =
+    "clustering assign: \n"
+    "assign new frames to the states of an already clustered reference trajectory.\n"
+    "every new frame gets its population inside the hypersphere among the reference\n"
+    "frames, its free energy on the reference's scale, its nearest reference frame,\n"
+    "its nearest reference frame of lower free energy, and the state of the latter\n"
+    "(of the former if there is none; 0 if the reference is out of reach).\n\n"
+    "options:\n"
+    "  -h [ --help ]                   show this help.\n"
+    "  -f [ --file ] arg               input (required): coordinates of the reference\n"
+    "                                  (space separated ASCII or NumPy .npy).\n"
+    "  -s [ --states ] arg             input (required): state of every reference frame,\n"
+    "                                  one per line.\n"
+    "  -q [ --query ] arg              input (required): coordinates of the new frames.\n"
+    "  -r [ --radius ] arg             parameter (required): hypersphere radius.\n"
+    "  -o [ --output ] arg             output (required): state of every new frame.\n"
+    "  -p [ --population ] arg         output (optional): population per new frame.\n"
+    "  -d [ --free-energy ] arg        output (optional): free energy per new frame.\n"
+    "  -b [ --nearest-neighbors ] arg  output (optional): nearest reference frames.\n"
+    "  --batch arg (=100000)           new frames per batch on the GPU.\n"
+    "  -v [ --verbose ]                verbose mode: print runtime information to STDOUT.\n";
+
+int assign_main(int argc, char** argv) {
+  std::string file, states_file, query, output, population, free_energy, nn;
+  bool has_radius = false;
+  float radius = 0.0f;
+  std::size_t batch = 100000;
+  std::map<std::string, std::string> longnames = {
+      {"--file", "-f"}, {"--states", "-s"}, {"--query", "-q"}, {"--radius", "-r"}, {"--output", "-o"}, {"--population", "-p"},
+      {"--free-energy", "-d"}, {"--nearest-neighbors", "-b"}, {"--verbose", "-v"}, {"--help", "-h"}};
+  for (int i = 2; i < argc; ++i) {
+    std::string a = argv[i];
+    if (longnames.count(a)) a = longnames[a];
+    auto need = [&](const char* what) -> const char* {
+      if (i + 1 >= argc) die(std::string("\nerror parsing arguments:\n\nthe required argument for option '") + what + "' is missing\n");
+      return argv[++i];
+    };
+    if (a == "-h") {
+      std::cout << kAssignHelp << std::endl;
+      std::exit(EXIT_SUCCESS);
+    } else if (a == "-f") file = need("--file");
+    else if (a == "-s") states_file = need("--states");
+    else if (a == "-q") query = need("--query");
+    else if (a == "-r") {
+      radius = std::strtof(need("--radius"), nullptr);
+      has_radius = true;
+    } else if (a == "-o") output = need("--output");
+    else if (a == "-p") population = need("--population");
+    else if (a == "-d") free_energy = need("--free-energy");
+    else if (a == "-b") nn = need("--nearest-neighbors");
+    else if (a == "--batch") {
+      const long long v = std::strtoll(need("--batch"), nullptr, 10);
+      if (v < 1) die("error: --batch needs a positive number of frames");
+      batch = (std::size_t)v;
+    } else if (a == "-v") g_verbose = true;
+    else die("\nerror parsing arguments:\n\nunrecognised option '" + a + "'\n\n" + kAssignHelp);
+  }
+  auto required = [&](bool given, const char* name) {
+    if (!given) die(std::string("\nerror parsing arguments:\n\nthe option '") + name + "' is required but missing\n\n" + kAssignHelp);
+  };
+  required(!file.empty(), "--file");
+  required(!states_file.empty(), "--states");
+  required(!query.empty(), "--query");
+  required(has_radius, "--radius");
+  required(!output.empty(), "--output");
+  const int n_gpus = Clustering::Density::CUDA::get_num_gpus();   // (no GPU: says so and exits, as the density mode does)
+  const std::string header = provenance_header(argc, argv);
+  Comments cm = {{"clustering_radius", radius}};
+  LOG("\n%s\n~~~ using for parallization: HIP (device 0 of %d GPU%s)\n", header.c_str(), n_gpus, n_gpus == 1 ? "" : "s");
+
+  std::vector<float> ref, queries;
+  std::size_t n_ref = 0, n_cols = 0, n_query = 0, n_cols_q = 0;
+  read_coords(file, ref, n_ref, n_cols);
+  if (n_ref == 0) die("error: no frames in '" + file + "'");
+  LOG("    reading reference states: %s\n", states_file.c_str());
+  const std::vector<std::size_t> states_in = read_single_column<std::size_t>(states_file);
+  if (states_in.size() != n_ref) die("error: state file does not match the number of reference frames");
+  std::vector<std::int32_t> states_ref(n_ref);
+  for (std::size_t i = 0; i < n_ref; ++i) {
+    if (states_in[i] > (std::size_t)INT32_MAX) die("error: state ids must fit 31 bits");
+    states_ref[i] = (std::int32_t)states_in[i];
+  }
+  read_coords(query, queries, n_query, n_cols_q);
+  if (n_query == 0) die("error: no frames in '" + query + "'");
+  if (n_cols_q != n_cols) die("error: reference and new frames differ in their number of columns");
+
+  LOG("~~~ preparing the reference\n    using radius: %g\n", radius);
+  dc_assigner* assigner = nullptr;
+  must(dc_hip_assigner_open(ref.data(), n_ref, n_cols, states_ref.data(), radius, std::min(batch, n_query), 0, &assigner),
+       "preparing the reference");
+  static const char* const kPaths[] = {"the resident reference of 1..64 columns", "the resident reference of 65..256 columns",
+                                       "the per-call cross sweeps"};
+  std::uint32_t max_pop = 0;
+  must(dc_hip_assigner_reference(assigner, nullptr, nullptr, &max_pop), "reading the reference");
+  LOG("    served by: %s\n    max_pop of the reference: %u\n", kPaths[dc_hip_assigner_path(assigner)], max_pop);
+
+  LOG("~~~ assigning %zu frames\n", n_query);
+  std::vector<std::int32_t> states(n_query);
+  std::vector<std::uint32_t> pops(n_query), nn_idx(n_query), hd_idx(n_query);
+  std::vector<float> fe(n_query), nn_d2(n_query), hd_d2(n_query);
+  must(dc_hip_assigner_assign(assigner, queries.data(), n_query, states.data(), pops.data(), fe.data(), nn_idx.data(),
+                              nn_d2.data(), hd_idx.data(), hd_d2.data()),
+       "assigning the frames");
+  dc_hip_assigner_close(assigner);
+  if (!population.empty()) {
+    LOG("    storing population in: %s\n", population.c_str());
+    write_pops(population, pops.data(), n_query, header, cm);
+  }
+  if (!free_energy.empty()) {
+    LOG("    storing free energy in: %s\n", free_energy.c_str());
+    write_fes(free_energy, fe.data(), n_query, header, cm);
+  }
+  if (!nn.empty()) {
+    LOG("    storing nearest neighbors in: %s\n", nn.c_str());
+    write_neighborhood(nn, n_query, nn_idx.data(), nn_d2.data(), hd_idx.data(), hd_d2.data(), header, cm);
+  }
+  LOG("    storing states in: %s\n", output.c_str());
+  write_clustered_trajectory(output, std::vector<std::size_t>(states.begin(), states.end()), header, cm);
+  return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   const std::string general_help = std::string("clustering ") + kVersion +
-      "\n\nmodes:\n  density: run density clustering (pop / free energy / nearest neighbours on the GPU)\n\n"
+      "\n\nmodes:\n  density: run density clustering (pop / free energy / nearest neighbours on the GPU)\n"
+      "  assign:  assign new frames to the states of a clustered reference trajectory\n\n"
       "usage:\n  clustering density --option1 --option2 ...\n\nfor a list of available options:\n"
-      "  clustering density -h\n\nthis binary is parallized with HIP (MI355X)\n\n";
+      "  clustering density -h\n  clustering assign -h\n\nthis binary is parallized with HIP (MI355X)\n\n";
   if (argc <= 2) {
     std::cerr << general_help;
     return EXIT_FAILURE;
   }
   const std::string mode(argv[1]);
+  if (mode == "assign") return assign_main(argc, argv);
   if (mode != "density") {
     std::cerr << "\nerror: unrecognized mode '" << mode << "'\n\n"
-              << "(this build provides the density mode only; the other modes of moldyn/Clustering\n"
+              << "(this build provides the density and assign modes only; the other modes of moldyn/Clustering\n"
               << " -- network, mpp, coring, noise, filter, stats -- are CPU post-processing tools)\n\n"
               << general_help;
     return EXIT_FAILURE;

@@ -559,6 +559,8 @@ class Reference:
     pops_ref, max_pop and fe_ref (set as the reference's free energies): what assign() needs of the reference."""
 
     _api = "dc_hip_reference_wide_"   # the entry points' common prefix
+    _assign_open = "dc_hip_assign_open_wide_dev"   # ... and the assigner's open for this kind of handle
+    _assign_h = _assign_ws = None     # the assigner of assign_device(), built on first use
 
     def __init__(self, reference, max_batch, radius=None, ref_states=None):
         self._h = None
@@ -596,6 +598,9 @@ class Reference:
     max_batch = property(lambda self: self._max_batch)
 
     def close(self):
+        if self._assign_h is not None:
+            capi.lib.dc_hip_assign_close(self._assign_h)
+            self._assign_h = None
         if self._h is not None:
             getattr(capi.lib, self._api + "close")(self._h)
             self._h = None
@@ -690,6 +695,49 @@ class Reference:
         return out
 
 
+    def _assigner(self):
+        """the dc_assign of this handle (dc_hip_assign_open[_wide]_dev), from radius, ref_states and max_pop; built once"""
+        if self.radius is None:
+            raise ValueError("assign_device() needs the radius and ref_states given at construction")
+        if self._h is None:
+            raise ValueError("the reference is closed")
+        if self._assign_h is None:
+            need = int(capi.lib.dc_hip_assign_workspace_bytes(self._n_ref, self._max_batch))
+            self._assign_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+            h = C.c_void_p()
+            with torch.cuda.device(self.device):
+                capi.check(getattr(capi.lib, self._assign_open)(self._h, _dev(self._states_r), int(self.max_pop), float(self.radius),
+                                                                _dev(self._assign_ws), need, _stream_ptr(), C.byref(h)),
+                           self._assign_open)
+            self._assign_h = h
+        return self._assign_h
+
+    def assign_device(self, queries):
+        """assign() in one library call per chunk of max_batch rows (dc_hip_assign_batch_dev): the same dict, the same
+        values, and no host synchronisation anywhere -- the free energies come from a table filled when the assigner is
+        built (on the first call), the state pick is a kernel.  The call returns with its work queued on the current
+        stream; the batch can be queued behind the one before it."""
+        n_q, n_cols = _check_coords(queries)
+        if n_cols != self._n_cols or queries.device != self.device:
+            raise ValueError("queries and reference need the same n_cols and the same device")
+        a = self._assigner()
+        i32 = dict(dtype=torch.int32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        out = {"states": torch.empty(n_q, **i32), "pops": torch.empty(n_q, **i32), "fe": torch.empty(n_q, **f32),
+               "nn_idx": torch.empty(n_q, **i32), "nn_d2": torch.empty(n_q, **f32), "hd_idx": torch.empty(n_q, **i32),
+               "hd_d2": torch.empty(n_q, **f32)}
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr()
+            for lo in range(0, n_q, self._max_batch):
+                n = min(self._max_batch, n_q - lo)
+                capi.check(capi.lib.dc_hip_assign_batch_dev(a, C.c_void_p(queries.data_ptr() + 4 * lo * n_cols), n,
+                                                            *(C.c_void_p(t.data_ptr() + 4 * lo) for t in out.values()), stream),
+                           "dc_hip_assign_batch_dev")
+                self._queries = queries[lo:lo + n]   # (what the handle has staged now)
+        out.update(pops_ref=self.pops_ref, max_pop=self.max_pop, fe_ref=self.fe_ref)
+        return out
+
+
 class NarrowReference(Reference):
     """A resident reference for the pruned cross sweeps of rows of 1..64 columns (dc_hip_reference_*): Reference's
     methods, for calculate_populations_against(variant="cross_pruned") and nearest_reference(pruned=True).
@@ -704,6 +752,7 @@ class NarrowReference(Reference):
     and fe_ref (set as the reference's free energies).  info() -> (tiles, mfmas, shares, answered,
     reference_preparations); order(which): 0 the population sweep's orders, 1 the neighbour sweep's."""
     _api = "dc_hip_reference_"
+    _assign_open = "dc_hip_assign_open_dev"
 
     def __init__(self, reference, max_batch, max_radius=None, radius=None, ref_states=None):
         self._h = None
@@ -753,6 +802,73 @@ class NarrowReference(Reference):
         perm_r = torch.empty(self._n_ref, dtype=torch.int32, device=self.device)
         self._call("order_dev", int(which), None if perm_q is None else _dev(perm_q), _dev(perm_r))
         return perm_q, perm_r
+
+
+class Assigner:
+    """The host-pointer assigner (dc_hip_assigner_*): what `clustering assign` and a C / C++ host run.  The library owns
+    the device memory: it uploads ``reference_host`` [n_ref, n_cols] and ``ref_states`` [n_ref], runs the reference's
+    self sweep at ``radius`` once, and opens the resident reference of the width.
+
+        with Assigner(reference_host, ref_states, radius, max_batch=100000) as a:
+            out = a.assign(queries_host)      # dict of numpy arrays: the values of assign_frames[_wide_pruned]
+
+    ``path``: 0 the narrow handle (1..64 columns), 1 the wide handle (65..256), 2 the per-call cross entry points (any
+    other width, or a reference the narrow handle refuses as too large)."""
+
+    def __init__(self, reference_host, ref_states, radius, max_batch, device=0):
+        self._h = None
+        ref = np.ascontiguousarray(reference_host, dtype=np.float32)
+        states = np.ascontiguousarray(ref_states, dtype=np.int32)
+        if ref.ndim != 2 or states.shape != (ref.shape[0],):
+            raise ValueError("reference_host must be [n_ref, n_cols] and ref_states hold one state per reference row")
+        self.n_ref, self.n_cols = ref.shape
+        h = C.c_void_p()
+        capi.check(capi.lib.dc_hip_assigner_open(ref.ctypes.data_as(C.c_void_p), self.n_ref, self.n_cols,
+                                                 states.ctypes.data_as(C.c_void_p), float(radius), int(max_batch), int(device),
+                                                 C.byref(h)), "dc_hip_assigner_open")
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            capi.lib.dc_hip_assigner_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    @property
+    def path(self):
+        return int(capi.lib.dc_hip_assigner_path(self._h))
+
+    def reference(self):
+        """(pops_ref uint32 [n_ref], fe_ref float32 [n_ref], max_pop) of the reference's self sweep"""
+        pops, fe, top = np.empty(self.n_ref, np.uint32), np.empty(self.n_ref, np.float32), C.c_uint32(0)
+        capi.check(capi.lib.dc_hip_assigner_reference(self._h, pops.ctypes.data_as(C.c_void_p), fe.ctypes.data_as(C.c_void_p),
+                                                      C.byref(top)), "dc_hip_assigner_reference")
+        return pops, fe, int(top.value)
+
+    def assign(self, queries_host):
+        """-> dict of numpy arrays [n_q]: states int32, pops uint32, fe float32, nn_idx uint32, nn_d2 float32, hd_idx
+        uint32, hd_d2 float32; any number of rows"""
+        if self._h is None:
+            raise ValueError("the assigner is closed")
+        q = np.ascontiguousarray(queries_host, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.n_cols:
+            raise ValueError("queries and reference need the same n_cols")
+        n_q = q.shape[0]
+        out = {"states": np.empty(n_q, np.int32), "pops": np.empty(n_q, np.uint32), "fe": np.empty(n_q, np.float32),
+               "nn_idx": np.empty(n_q, np.uint32), "nn_d2": np.empty(n_q, np.float32), "hd_idx": np.empty(n_q, np.uint32),
+               "hd_d2": np.empty(n_q, np.float32)}
+        capi.check(capi.lib.dc_hip_assigner_assign(self._h, q.ctypes.data_as(C.c_void_p), n_q,
+                                                   *(v.ctypes.data_as(C.c_void_p) for v in out.values())),
+                   "dc_hip_assigner_assign")
+        return out
 
 
 def evaluated_tiles(device):

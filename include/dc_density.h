@@ -770,6 +770,75 @@ DC_API int dc_hip_wide_info_dev(const void* d_ws, uint64_t* tiles, uint64_t* mfm
 DC_API int dc_hip_free_energies_scaled_dev(const uint32_t* d_pops, size_t n, uint32_t max_pop, float* d_fe,
                                            void* stream);
 
+/* ---- ASSIGNER: new frames to the states of a clustered reference, on either resident reference --------------------------
+ * One call per batch for the job the two resident references exist for: every query's population in the reference at one
+ * radius, its free energy on the reference's scale, its nearest reference frame, its nearest reference frame of lower
+ * free energy, and its state: states_ref[hd] if hd exists, else states_ref[nn], else 0 (unassigned).  The values are those
+ * of the handle's populations / dc_hip_free_energies_scaled_dev(max_pop) / the handle's nearest, bit for bit.
+ * The free energies come from a table: a query's population against the reference is at most n_ref, so
+ * table[p] = (float)-log((double)((float)p * (1.0f / (float)max_pop))), p = 0 .. n_ref, filled ONCE by the host libm when
+ * the assigner is opened, holds every value dc_hip_free_energies_scaled_dev can give (+inf at 0, negative above max_pop).
+ * A batch therefore needs no hand-off to the host: dc_hip_assign_batch_dev is five stream-ordered steps -- the handle's
+ * stage, its populations, the table look-up, its nearest, the state pick -- and NOTHING in it synchronises with the host,
+ * flagged batches included (the handles answer those behind their device-side gate).  A batch can be queued behind the one
+ * before it and beside its own upload.
+ * The assigner is a small host object.  It BORROWS the reference handle (which must hold its free energies and stay open)
+ * and d_ws until it is closed, and d_query as the handle's stage does: until the batch's last step has run.  d_states_ref
+ * is read by open (a copy is kept in the workspace) and not kept.  The table's host copy lives in the assigner until close,
+ * so that its upload needs no synchronisation.  Calls on one assigner, and other calls on its handle, are ordered by the
+ * caller: on one stream, or with synchronisation between them (a batch re-stages the handle).
+ *   workspace_bytes  the table [n_ref + 1], the states [n_ref] and six arrays [max_batch] for the outputs a caller leaves
+ *                    NULL; 0 for a zero count; monotone in each argument.  max_batch is the handle's
+ *   open             max_pop: the scale of the free energies (the maximum of the reference's own populations); radius: the
+ *                    one radius of every batch
+ *   batch            n_query <= max_batch of the handle; 0 rows: DC_OK, nothing written.  d_states [n_query] is required;
+ *                    d_pops, d_fe, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2 [n_query] may each be NULL.  "none" is
+ *                    (n_ref + 1, FLT_MAX).  The table index is clamped to n_ref
+ * Refusals of open, all before a device is touched, dc_hip_last_error names the function, *out is NULL: a NULL handle,
+ * array or `out`, a handle whose free energies were never set, max_pop == 0, a radius that is NaN or negative, a radius
+ * whose fl32(r * r) exceeds the narrow handle's fl32(max_radius^2): DC_ERR_INVALID_ARGUMENT; a workspace smaller than
+ * dc_hip_assign_workspace_bytes(n_ref, max_batch of the handle), or none: DC_ERR_WORKSPACE.  Of batch: a NULL assigner,
+ * d_query or d_states, n_query > max_batch: DC_ERR_INVALID_ARGUMENT. */
+typedef struct dc_assign dc_assign;
+DC_API size_t dc_hip_assign_workspace_bytes(size_t n_ref, size_t max_batch);
+DC_API int dc_hip_assign_open_dev(dc_reference* reference, const int32_t* d_states_ref, uint32_t max_pop, float radius,
+                                  void* d_ws, size_t ws_bytes, void* stream, dc_assign** out);
+DC_API int dc_hip_assign_open_wide_dev(dc_reference_wide* reference, const int32_t* d_states_ref, uint32_t max_pop,
+                                       float radius, void* d_ws, size_t ws_bytes, void* stream, dc_assign** out);
+DC_API void dc_hip_assign_close(dc_assign* assign);
+DC_API int dc_hip_assign_batch_dev(dc_assign* assign, const float* d_query, size_t n_query, int32_t* d_states,
+                                   uint32_t* d_pops, float* d_fe, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                   float* d_hd_d2, void* stream);
+
+/* ---- ... and its host-pointer form, for C / C++ hosts and `clustering assign` -----------------------------------------------
+ * All pointers are HOST pointers; the assigner owns its device memory, its streams and its pinned batch slots.  A
+ * dc_assigner is used by one host thread at a time; the calling thread's current device is restored by every call.
+ *   open       uploads the reference [n_ref][n_cols] and its states, runs the reference's self sweep at `radius` once
+ *              (dc_hip_populations_dev under DC_VARIANT_AUTO; dc_hip_populations_wide_pruned_dev at 65..256 columns),
+ *              dc_hip_free_energies_dev, then opens the resident reference of the width (max_batch, and for the narrow
+ *              one max_radius = radius), sets its free energies and opens the assigner above.  ANY width is served: rows
+ *              wider than 256 columns, and a reference the narrow handle refuses as too large, go through the per-call
+ *              entry points (dc_hip_populations_cross_dev / dc_hip_nearest_neighbors_cross_dev, DC_VARIANT_AUTO) with the
+ *              same table and pick kernels; that path makes no stream-order promise.  Synchronises
+ *   reference  the self sweep's populations [n_ref], free energies [n_ref] and maximum; any pointer may be NULL
+ *   path       0 the narrow handle, 1 the wide handle, 2 the per-call cross entry points (-1 for a NULL assigner)
+ *   assign     any n_query, in chunks of max_batch through two batch slots: the upload of chunk k + 1 and the download of
+ *              chunk k - 1 run on a copy stream, ordered by events, beside the sweeps of chunk k.  `states` [n_query] is
+ *              required, the six other arrays [n_query] may be NULL; 0 rows: DC_OK.  Returns when every output is written.
+ *              DC_ASSIGN_OVERLAP=0 (environment, read once per process: a measurement switch) puts copies and sweeps on
+ *              one stream; the results are the same
+ * Refusals of open, before a device is touched, *out is NULL: a NULL array or `out`, n_ref, n_cols or max_batch == 0, a
+ * radius that is NaN or negative: DC_ERR_INVALID_ARGUMENT; counts beyond the cross calls' limits: DC_ERR_TOO_LARGE; then no
+ * device: DC_ERR_NO_DEVICE; a device ordinal out of range: DC_ERR_INVALID_ARGUMENT. */
+typedef struct dc_assigner dc_assigner;
+DC_API int dc_hip_assigner_open(const float* ref, size_t n_ref, size_t n_cols, const int32_t* states_ref, float radius,
+                                size_t max_batch, int device, dc_assigner** out);
+DC_API int dc_hip_assigner_reference(const dc_assigner* assigner, uint32_t* pops_ref, float* fe_ref, uint32_t* max_pop);
+DC_API int dc_hip_assigner_path(const dc_assigner* assigner);
+DC_API int dc_hip_assigner_assign(dc_assigner* assigner, const float* queries, size_t n_query, int32_t* states,
+                                  uint32_t* pops, float* fe, uint32_t* nn_idx, float* nn_d2, uint32_t* hd_idx, float* hd_d2);
+DC_API void dc_hip_assigner_close(dc_assigner* assigner);
+
 /* ---------------------------------------------------------------------------------------
  * host-pointer entry points (mirror the reference's per-GPU host functions)
  * ------------------------------------------------------------------------------------- */
