@@ -47,6 +47,8 @@ SYMBOLS = (
     "dc_hip_nearest_cross_pruned_info_dev",
     "dc_hip_wide_workspace_bytes", "dc_hip_populations_wide_dev", "dc_hip_nearest_neighbors_wide_dev", "dc_hip_wide_info_dev",
     "dc_hip_cross_wide_workspace_bytes", "dc_hip_populations_cross_wide_dev", "dc_hip_nearest_neighbors_cross_wide_dev",
+    "dc_hip_xwide_workspace_bytes", "dc_hip_populations_xwide_dev", "dc_hip_nearest_neighbors_xwide_dev",
+    "dc_hip_cross_xwide_workspace_bytes", "dc_hip_populations_cross_xwide_dev", "dc_hip_nearest_neighbors_cross_xwide_dev",
     "dc_hip_radius_pairs_wide_dev", "dc_hip_radius_min_edge_wide_dev", "dc_hip_radius_forest_wide",
     "dc_hip_wide_pruned_workspace_bytes", "dc_hip_populations_wide_pruned_dev", "dc_hip_wide_pruned_order_dev",
     "dc_hip_radius_pairs_wide_pruned_dev", "dc_hip_radius_min_edge_wide_pruned_dev", "dc_hip_radius_forest_wide_pruned",
@@ -212,6 +214,14 @@ def _load():
     lib.dc_hip_populations_cross_wide_dev.argtypes = [vp, sz, vp, sz, sz, C.POINTER(C.c_float), sz, sz, sz, vp, vp, sz, vp]
     lib.dc_hip_nearest_neighbors_cross_wide_dev.restype = i32
     lib.dc_hip_nearest_neighbors_cross_wide_dev.argtypes = [vp, sz, vp, sz, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]
+    for xwide, wide in (("dc_hip_xwide_workspace_bytes", "dc_hip_wide_workspace_bytes"),
+                        ("dc_hip_populations_xwide_dev", "dc_hip_populations_wide_dev"),
+                        ("dc_hip_nearest_neighbors_xwide_dev", "dc_hip_nearest_neighbors_wide_dev"),
+                        ("dc_hip_cross_xwide_workspace_bytes", "dc_hip_cross_wide_workspace_bytes"),
+                        ("dc_hip_populations_cross_xwide_dev", "dc_hip_populations_cross_wide_dev"),
+                        ("dc_hip_nearest_neighbors_cross_xwide_dev", "dc_hip_nearest_neighbors_cross_wide_dev")):
+        getattr(lib, xwide).restype = getattr(lib, wide).restype     # (257..1024 columns: the lists of their namesakes)
+        getattr(lib, xwide).argtypes = getattr(lib, wide).argtypes
     lib.dc_hip_radius_pairs_wide_dev.restype = i32
     lib.dc_hip_radius_pairs_wide_dev.argtypes = [vp, sz, sz, C.c_float, vp, vp, sz, vp, vp, sz, vp]
     lib.dc_hip_radius_min_edge_wide_dev.restype = i32

@@ -1,5 +1,6 @@
 // dc_mfma_wide.hip -- host side of the matrix-core sweeps for rows of 65..256 columns: workspace, preparation and
-// launches (kernels: dc_mfma_wide_kernels.hpp).
+// launches (kernels: dc_mfma_wide_kernels.hpp).  The unpruned self and cross sweeps also serve 257..1024 columns, in the
+// layout of those widths (dc_hip_*_xwide_dev).
 #include "dc_mfma_wide_kernels.hpp"
 
 namespace dc {
@@ -11,6 +12,16 @@ size_t wide_workspace_bytes(size_t n_rows, size_t n_cols) {
 
 size_t wide_against_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols) {
   if (!wide_mfma_supports(n_cols) || n_query == 0 || n_ref == 0) return 0;
+  return wide_layout_against(n_query, n_ref, n_cols).total;
+}
+
+size_t xwide_workspace_bytes(size_t n_rows, size_t n_cols) {
+  if (!xwide_mfma_supports(n_cols) || n_rows == 0) return 0;
+  return wide_layout(n_rows, n_cols).total;
+}
+
+size_t xwide_against_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols) {
+  if (!xwide_mfma_supports(n_cols) || n_query == 0 || n_ref == 0) return 0;
   return wide_layout_against(n_query, n_ref, n_cols).total;
 }
 
@@ -39,10 +50,23 @@ WideArgs wide_args(const WideLayout& L, const float* d_ref, uint32_t n_ref, uint
   return X;
 }
 
-dim3 wide_grid(uint32_t i_from, uint32_t i_to, uint32_t Tp) {
+dim3 wide_grid(uint32_t i_from, uint32_t i_to, uint32_t Tp, WideGroup grp = kWideGroup88) {
   const uint32_t q_blocks = (i_to + kWideBlockRows - 1) / kWideBlockRows - i_from / kWideBlockRows;
-  return dim3(wide_grid_size(q_blocks, wide_shares(Tp / kWideBlockTiles)));
+  return dim3(wide_grid_size(q_blocks, wide_shares(Tp / kWideBlockTiles, grp), grp));
 }
+
+// The group of the unit map at 257..1024 columns: 8 x 8 like every other launch -- the smaller groups
+// measured there were not faster by more than the spread of the runs, and moved no L2 hit rate.  -DDC_XWIDE_GROUP_Q=q -DDC_XWIDE_GROUP_S=s builds the unpruned instances of another shape
+// for these widths, which is how that measurement was made (scratch/xwide_unit_ab.py); the default build holds none.
+#ifndef DC_XWIDE_GROUP_Q
+#define DC_XWIDE_GROUP_Q 8
+#define DC_XWIDE_GROUP_S 8
+#endif
+constexpr WideGroup kXWideGroup{DC_XWIDE_GROUP_Q, DC_XWIDE_GROUP_S};
+constexpr bool kXWideOwnGroup = kXWideGroup.gq != 8u || kXWideGroup.gs != 8u;
+static_assert(kXWideGroup.gq >= 1 && kXWideGroup.gq <= 8 && (kXWideGroup.gq & (kXWideGroup.gq - 1)) == 0 && kXWideGroup.gs >= 1 &&
+                  kXWideGroup.gs <= 8 && (kXWideGroup.gs & (kXWideGroup.gs - 1)) == 0,
+              "a group: powers of two up to 8 x 8");
 
 // the counting instance of a launch of n_rad radii -- one, up to four, up to kMaxRadiiPerLaunch --, timed as a population sweep
 template <SweepMode SM, bool PR>
@@ -71,6 +95,21 @@ void pop_wide(WideArgs X, const Rad2& rad2, int n_rad, uint32_t* d_pops_first_ro
   X.rad2 = rad2;
   X.n_rad = n_rad;
   X.pops = d_pops_first_row;
+  if constexpr (kXWideOwnGroup) {
+    if (X.n_cols > kWideMaxCols) {
+      constexpr uint32_t Q = kXWideGroup.gq, S = kXWideGroup.gs;
+      const dim3 grid = wide_grid(X.i_from, X.i_to, X.Tp, kXWideGroup);
+      sweep_timer_mark(0, true, s);
+      if (n_rad == 1)
+        hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 1, SM, false, Q, S>), grid, dim3(256), 0, s, X);
+      else if (n_rad <= 4)
+        hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, 4, SM, false, Q, S>), grid, dim3(256), 0, s, X);
+      else
+        hipLaunchKernelGGL((wide_sweep_kernel<kWidePop, kMaxRadiiPerLaunch, SM, false, Q, S>), grid, dim3(256), 0, s, X);
+      sweep_timer_mark(0, false, s);
+      return;
+    }
+  }
   launch_pop_instance<SM, false>(X, n_rad, wide_grid(X.i_from, X.i_to, X.Tp), s);
 }
 
@@ -80,9 +119,13 @@ template <SweepMode SM>
 int nn_wide(const WideArgs& X, uint32_t n_q, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
             hipStream_t s) {
   if (hipMemsetAsync(X.merge, 0xFF, sizeof(unsigned long long) * 2 * (size_t)n_q, s) != hipSuccess) return -1;
-  const dim3 grid = wide_grid(X.i_from, X.i_to, X.Tp);
+  const bool own_group = kXWideOwnGroup && X.n_cols > kWideMaxCols;
+  const dim3 grid = wide_grid(X.i_from, X.i_to, X.Tp, own_group ? kXWideGroup : kWideGroup88);
   sweep_timer_mark(1, true, s);
-  hipLaunchKernelGGL((wide_sweep_kernel<kWideNn, 1, SM>), grid, dim3(256), 0, s, X);
+  if (own_group)
+    hipLaunchKernelGGL((wide_sweep_kernel<kWideNn, 1, SM, false, kXWideGroup.gq, kXWideGroup.gs>), grid, dim3(256), 0, s, X);
+  else
+    hipLaunchKernelGGL((wide_sweep_kernel<kWideNn, 1, SM>), grid, dim3(256), 0, s, X);
   sweep_timer_mark(1, false, s);
   hipLaunchKernelGGL(wide_nn_finish_kernel, dim3((X.i_to - X.i_from + 255) / 256), dim3(256), 0, s, (const uint32_t*)X.hdr,
                      (const unsigned long long*)X.merge, n_q, X.i_from, X.i_to, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2);

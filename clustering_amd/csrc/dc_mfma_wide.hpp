@@ -14,6 +14,17 @@ inline bool wide_mfma_supports(size_t n_cols) { return n_cols >= kWideMinCols &&
 size_t wide_workspace_bytes(size_t n_rows, size_t n_cols);
 constexpr size_t kWideInfoBytes = 256;   // the head of the workspace dc_hip_wide_info_dev reads (header words 40..45)
 
+// ---- rows of 257..1024 columns (dc_hip_*_xwide_dev) --------------------------------------------------------
+// The unpruned self and cross sweeps below serve these widths as they stand: the chain streams along K and takes its
+// length at run time.  What differs is the workspace -- the sums and means regions behind the header hold kXWideMaxCols
+// entries, so the images start further back -- and with it the byte counts; wide_prepare, launch_*_wide_mfma,
+// wide_prepare_against and launch_*_wide_against read the layout of the width they are given.
+constexpr size_t kXWideMinCols = kWideMaxCols + 1, kXWideMaxCols = 1024;
+inline bool xwide_mfma_supports(size_t n_cols) { return n_cols >= kXWideMinCols && n_cols <= kXWideMaxCols; }
+// as wide_workspace_bytes / wide_against_workspace_bytes: 0 if the column count is not served or a set is empty
+size_t xwide_workspace_bytes(size_t n_rows, size_t n_cols);
+size_t xwide_against_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols);
+
 // statistics, scale and operand images of d_coords in the workspace (d_fe: the neighbour call's free energies, a NaN
 // among them flags the data like a non-finite row); returns 0 on success
 int wide_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, void* d_ws,

@@ -79,6 +79,12 @@ constexpr uint32_t kWideHdrTiles = 40, kWideHdrMfma = 42, kWideHdrExact = 44;   
 constexpr size_t kWideOffSums = kHdrBytes;                             // [256] double: column sums
 constexpr size_t kWideOffMeans = kWideOffSums + 8 * kWideMaxCols;      // [256] float: column means
 constexpr size_t kWideOffImages = kWideOffMeans + 4 * kWideMaxCols;    // 4096
+// The layout is a function of the maximum width of the family a column count belongs to: up to kWideMaxCols the regions
+// above, byte for byte; beyond (257..1024 columns) [1024] doubles and [1024] floats, the images at 13 312
+inline size_t wide_head_cols(size_t n_cols) { return n_cols <= kWideMaxCols ? kWideMaxCols : kXWideMaxCols; }
+inline size_t wide_off_means(size_t n_cols) { return kWideOffSums + 8 * wide_head_cols(n_cols); }
+inline size_t wide_off_images(size_t n_cols) { return wide_off_means(n_cols) + 4 * wide_head_cols(n_cols); }
+static_assert(kHdrBytes + 12 * kXWideMaxCols == 13312, "the images of the 257..1024 layout start at byte 13 312");
 static_assert(4 * (kWideHdrExact + 2) <= kWideInfoBytes && kWideInfoBytes <= kHdrBytes, "counters inside the info head");
 static_assert(kWideHdrTiles > kHdrShift && kWideHdrTiles > kHdrScale + 4 && kWideHdrTiles % 2 == 0, "counters clear of the shared header words, 64-bit aligned");
 // the pruned population sweep: extent of columns 0 / 1 as ~key(min0), key(max0), ~key(min1), key(max1)
@@ -114,21 +120,29 @@ static_assert(kWideListCap % 256 == 0, "a round: whole chunks of 64 boxes for ea
 // (XCD, share slot) pairs of a group are n shares x 64 / n further query blocks, so every XCD has work at every size.
 constexpr uint32_t kWideShares = 64;        // reference shares at most: share s owns the reference blocks s, s + n_shares, ...
 constexpr uint32_t kWideShareBlocks = 8;    // reference blocks a share holds at least (while there are that many)
-__host__ __device__ inline uint32_t wide_shares(uint32_t ref_blocks) {
+// The group: gq query blocks x gs share slots side by side on an XCD (powers of two, at most 8 each).  8 x 8 is the map
+// above and what every launch passes; other shapes exist for the measurement of DESIGN.md 4.31 (deep K: do fewer blocks
+// per group keep the operands in L2?).  With gs share slots per XCD a launch has 8 gs of them, which caps its shares.
+struct WideGroup {
+  uint32_t gq, gs;
+};
+constexpr WideGroup kWideGroup88{8u, 8u};
+__host__ __device__ inline uint32_t wide_shares(uint32_t ref_blocks, WideGroup grp = kWideGroup88) {
   uint32_t s = 1;
-  while (2u * s <= kWideShares && 2u * s * kWideShareBlocks <= ref_blocks) s *= 2u;
+  while (2u * s <= 8u * grp.gs && 2u * s * kWideShareBlocks <= ref_blocks) s *= 2u;
   return s;
 }
+static_assert(8u * kWideGroup88.gs == kWideShares, "the 8 x 8 group hands out kWideShares share slots");
 struct WideUnit {
   uint32_t q_block, share;
 };
-__host__ __device__ inline WideUnit wide_unit(uint32_t id, uint32_t n_shares) {
-  const uint32_t xcd = id & 7u, slot = id >> 3, g = xcd * 8u + ((slot >> 3) & 7u), mult = kWideShares / n_shares;
-  return WideUnit{((slot >> 6) * 8u + (slot & 7u)) * mult + g / n_shares, g % n_shares};
+__host__ __device__ inline WideUnit wide_unit(uint32_t id, uint32_t n_shares, WideGroup grp = kWideGroup88) {
+  const uint32_t xcd = id & 7u, slot = id >> 3, g = xcd * grp.gs + ((slot / grp.gq) % grp.gs), mult = 8u * grp.gs / n_shares;
+  return WideUnit{((slot / (grp.gq * grp.gs)) * grp.gq + (slot % grp.gq)) * mult + g / n_shares, g % n_shares};
 }
-inline uint32_t wide_grid_size(uint32_t q_blocks, uint32_t n_shares) {
-  const uint32_t per_group = 8u * (kWideShares / n_shares);   // query blocks of 512 consecutive workgroups
-  return 8u * 64u * ((q_blocks + per_group - 1u) / per_group);
+inline uint32_t wide_grid_size(uint32_t q_blocks, uint32_t n_shares, WideGroup grp = kWideGroup88) {
+  const uint32_t per_group = grp.gq * (8u * grp.gs / n_shares);   // query blocks of 8 gq gs consecutive workgroups
+  return 8u * grp.gq * grp.gs * ((q_blocks + per_group - 1u) / per_group);
 }
 
 struct WideLayout {
@@ -146,7 +160,7 @@ inline WideLayout wide_layout_against(size_t n_query, size_t n_ref, size_t n_col
   L.Tqp = wide_pad_tiles(L.Tq);
   L.NM = (uint32_t)nm_for((int)n_cols);
   const size_t tile_bytes = (size_t)16 * 64 * L.NM;
-  L.off_img_a = kWideOffImages;
+  L.off_img_a = wide_off_images(n_cols);
   L.off_img_b = align256(L.off_img_a + tile_bytes * L.Tp);
   L.off_norms = align256(L.off_img_b + tile_bytes * L.Tqp);
   L.off_merge = align256(L.off_norms + sizeof(float) * 32 * (size_t)L.Tp);
@@ -189,6 +203,8 @@ __host__ __device__ inline float wide_cut_ratio(const WideBand& b) {
 // that row's real d2 <= d2_c / (1 - u)^(D+1) <= d2_c (1 + 1.6e-5) at D <= 256, and its accumulator is at most
 // S d2 (1 + kappa) + e0 by the band: m0 is that, rounded up.  Every reference whose canonical sum is <= d2_c has an
 // accumulator <= m0 <= cut(m0) as well, so all that could beat or tie the word are still raised.
+// (The constant 2.0e-5 below holds at D <= 256 only: at 1024 columns (1 - u)^-(D+1) - 1 is 6.1e-5.  The pruned sweeps stop
+//  at kWideMaxCols, and the unpruned sweeps of 257..1024 columns, DESIGN.md 4.31, never call this.)
 __device__ __forceinline__ float wide_nn_start(unsigned long long word, float S, const WideBand& b) {
   if (word == ~0ull) return INFINITY;
   const float d2c = __uint_as_float((uint32_t)(word >> 32));
@@ -196,13 +212,13 @@ __device__ __forceinline__ float wide_nn_start(unsigned long long word, float S,
   return m + fabsf(m) * kWideRoundMargin;
 }
 
-// ---- statistics, scale, images: the instances of dc_mfma.hip's passes for up to kWideMaxCols columns ------------------
+// ---- statistics, scale, images: the instances of dc_mfma.hip's passes for up to kXWideMaxCols columns -----------------
 // (the partial sums meet in atomics, in an order that follows the scheduling: the float means, and with them M, the images
 //  and the number of pairs in the band, may differ in the last bit from run to run of one call -- any origin near the mean
 //  serves, the band covers it, the results are exact either way; only the exact-pair counter is not reproducible)
 __global__ void wide_colsum_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D, double* __restrict__ sums) {
-  __shared__ double part[kWideMaxCols];
-  if (threadIdx.x < (uint32_t)kWideMaxCols) part[threadIdx.x] = 0.0;
+  __shared__ double part[kXWideMaxCols];
+  for (uint32_t k = threadIdx.x; k < D; k += blockDim.x) part[k] = 0.0;
   __syncthreads();
   const uint32_t nthreads = gridDim.x * blockDim.x;
   const uint32_t used = (nthreads / D) * D;   // stride is a multiple of D: fixed column
@@ -223,15 +239,15 @@ __global__ void wide_colsum_kernel(const float* __restrict__ coords, uint32_t n_
     atomicAdd(&part[id % D], s0 + s1);
   }
   __syncthreads();
-  if (threadIdx.x < D) atomicAdd(&sums[threadIdx.x], part[threadIdx.x]);
+  for (uint32_t k = threadIdx.x; k < D; k += blockDim.x) atomicAdd(&sums[k], part[k]);   // every column, whatever the block holds
 }
 
 __global__ void wide_mean_kernel(const double* __restrict__ sums, size_t n_rows, uint32_t D, float* __restrict__ means) {
-  const uint32_t k = threadIdx.x;
-  if (k >= D) return;
-  float muf = (float)(sums[k] / (double)n_rows);
-  if (!(fabsf(muf) <= FLT_MAX)) muf = 0.0f;
-  means[k] = muf;
+  for (uint32_t k = threadIdx.x; k < D; k += blockDim.x) {
+    float muf = (float)(sums[k] / (double)n_rows);
+    if (!(fabsf(muf) <= FLT_MAX)) muf = 0.0f;
+    means[k] = muf;
+  }
 }
 
 // max |x'|^2 (word 0) and the non-finite / overflow flag (word 1); one wave per row, the columns across its lanes.
@@ -349,9 +365,9 @@ inline int wide_stats_launches(const float* d_coords, uint32_t n_rows, uint32_t 
   char* p = (char*)d_ws;
   uint32_t* hdr = (uint32_t*)p;
   double* sums = (double*)(p + kWideOffSums);
-  float* means = (float*)(p + kWideOffMeans);
+  float* means = (float*)(p + wide_off_means(n_cols));
   // header, counters of the last sweep, column sums
-  if (hipMemsetAsync(d_ws, 0, kWideOffImages, s) != hipSuccess) return -1;
+  if (hipMemsetAsync(d_ws, 0, wide_off_images(n_cols), s) != hipSuccess) return -1;
   const size_t elems = (size_t)n_rows * n_cols;
   const uint32_t sum_blocks = (uint32_t)min_sz(1024, (elems + 255) / 256);
   hipLaunchKernelGGL(wide_colsum_kernel, dim3(sum_blocks), dim3(256), 0, s, d_coords, n_rows, n_cols, sums);
@@ -369,7 +385,7 @@ inline int wide_image_launches(const float* d_coords, uint32_t n_rows, uint32_t 
   char* p = (char*)d_ws;
   const size_t frags = (size_t)L.Tp * L.NM * 64;
   hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags + 255) / 256)), dim3(256), 0, s, d_coords, n_rows, n_cols, L.NM,
-                     L.Tp, (const float*)(p + kWideOffMeans), (const uint32_t*)p, (uint4*)(p + L.off_img_a),
+                     L.Tp, (const float*)(p + wide_off_means(n_cols)), (const uint32_t*)p, (uint4*)(p + L.off_img_a),
                      (uint4*)(p + L.off_img_b), (float*)(p + L.off_norms));
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -626,8 +642,8 @@ inline int wide_stats_against_launches(const float* d_query, uint32_t n_query, c
   char* p = (char*)d_ws;
   uint32_t* hdr = (uint32_t*)p;
   double* sums = (double*)(p + kWideOffSums);
-  float* means = (float*)(p + kWideOffMeans);
-  if (hipMemsetAsync(d_ws, 0, kWideOffImages, s) != hipSuccess) return -1;
+  float* means = (float*)(p + wide_off_means(n_cols));
+  if (hipMemsetAsync(d_ws, 0, wide_off_images(n_cols), s) != hipSuccess) return -1;
   struct Side {
     const float* x;
     uint32_t n;
@@ -649,7 +665,7 @@ inline int wide_stats_against_launches(const float* d_query, uint32_t n_query, c
 inline int wide_image_against_launches(const WideLayout& L, const float* d_query, uint32_t n_query, const float* d_ref,
                                        uint32_t n_ref, uint32_t n_cols, void* d_ws, hipStream_t s) {
   char* p = (char*)d_ws;
-  const float* means = (const float*)(p + kWideOffMeans);
+  const float* means = (const float*)(p + wide_off_means(n_cols));
   const uint32_t Tqp = wide_pad_tiles((n_query + 31u) / 32u);
   const size_t frags_r = (size_t)L.Tp * L.NM * 64, frags_q = (size_t)Tqp * L.NM * 64;
   hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags_r + 255) / 256)), dim3(256), 0, s, d_ref, n_ref, n_cols, L.NM,
@@ -1018,7 +1034,8 @@ __device__ __attribute__((noinline)) void wide_nn_drain_cross_pruned(const uint2
 // The pruned cross neighbour instance is that form with the rings: the seed of a query block is the one
 // reference block X.seed names, the bounds and the largest free energy are the QUERY block's, the least free energy the
 // reference block's, the words lie by query position and name rows of the reference.
-template <int MODE, int NR, SweepMode SM = kSelf, bool PR = false>
+// GQ x GS: the group of the unit map (8 x 8 in every instance the library launches; see WideGroup).
+template <int MODE, int NR, SweepMode SM = kSelf, bool PR = false, uint32_t GQ = 8u, uint32_t GS = 8u>
 __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, MODE == kWideNn, PR && SM == kAgainst> X) {
   static_assert(!PR || ((wide_counts(MODE) || MODE == kWideNn) && SM == kSelf) || (MODE == kWidePop && SM == kAgainst && (NR == 1 || NR == 4 || NR == kMaxRadiiPerLaunch)) ||
                     (MODE == kWideNn && SM == kAgainst && NR == 1),
@@ -1042,8 +1059,10 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
   const float* const q_fe = (SM == kAgainst) ? X.q_fe : X.fe;
   const uint32_t n_q = (SM == kAgainst) ? X.n_query : X.n_rows;
   const bool has_fe = SM == kSelf || q_fe != nullptr;
-  const uint32_t RB = X.Tp / kWideBlockTiles, Sy = wide_shares(RB);
-  const WideUnit unit = wide_unit(blockIdx.x, Sy);
+  constexpr WideGroup kGroup{GQ, GS};
+  static_assert(!PR || (GQ == 8u && GS == 8u), "the pruned forms run on the 8 x 8 map");
+  const uint32_t RB = X.Tp / kWideBlockTiles, Sy = wide_shares(RB, kGroup);
+  const WideUnit unit = wide_unit(blockIdx.x, Sy, kGroup);
   uint32_t qb_of_unit = X.i_from / kWideBlockRows + unit.q_block;
   // (the pruned cross form: i_from = 0, so this is the unit's block of the query order, bounded below by that order's
   //  length -- the reference's block count RB says nothing about it)

@@ -48,6 +48,9 @@ _SIZES = {
     "wide_pruned": capi.lib.dc_hip_wide_pruned_workspace_bytes,
     "wide_against": capi.lib.dc_hip_cross_wide_workspace_bytes,
     "wide_against_pruned": capi.lib.dc_hip_cross_wide_pruned_workspace_bytes,
+    # ... and the unpruned self and cross sweeps for rows of 257..1024 columns (a layout of their own)
+    "xwide": capi.lib.dc_hip_xwide_workspace_bytes,
+    "xwide_against": capi.lib.dc_hip_cross_xwide_workspace_bytes,
 }
 
 
@@ -87,7 +90,7 @@ def _get(kind, device, *shape):
     swept rather than the call before."""
     cache = _cached(kind, device)
     ws, ws_bytes = cache.get(*shape)
-    if ws_bytes == 0 and cache.buf is not None and kind in ("wide_against", "wide_against_pruned"):
+    if ws_bytes == 0 and cache.buf is not None and kind in ("wide_against", "wide_against_pruned", "xwide_against"):
         return _dev(cache.buf), int(cache.buf.numel())
     return ws, ws_bytes
 
@@ -248,6 +251,29 @@ def wide_sweep_info(device):
     to the exact path by the last wide sweep on this device (dc_hip_wide_info_dev); (0, 0, 0) when the direct
     kernels answered (flagged data), nothing was swept, or no wide sweep has run."""
     return _wide_info("wide", device)
+
+
+# ---- ... and for rows of 257..1024 columns (include/dc_density.h, the "extra-wide" sweeps) ---------------------------
+def calculate_populations_xwide(coords, radii, i_from=0, i_to=None, out=None):
+    """calculate_populations_wide for rows of 257..1024 columns (dc_hip_populations_xwide_dev): the same kernel over a
+    longer chain, the same populations bit for bit as variant="direct", in a cached workspace of its own kind
+    (xwide_sweep_info reads its counters).  Other column counts raise."""
+    n_rows, n_cols = _check_coords(coords)
+    return _populations("dc_hip_populations_xwide_dev", "xwide", coords.device, (_dev(coords), n_rows, n_cols), (n_rows, n_cols),
+                        radii, (i_from, n_rows if i_to is None else i_to), out)
+
+
+def nearest_neighbors_xwide(coords, fe, i_from=0, i_to=None):
+    """nearest_neighbors_wide for rows of 257..1024 columns (dc_hip_nearest_neighbors_xwide_dev).
+    -> (nn_idx int32, nn_d2 float32, hd_idx int32, hd_d2 float32), each [n_rows]; "none" is (n_rows+1, FLT_MAX)."""
+    return _neighbors("dc_hip_nearest_neighbors_xwide_dev", "xwide", coords, fe, (i_from, i_to))
+
+
+def xwide_sweep_info(device):
+    """(tiles, mfmas, exact_pairs) of the last calculate_populations_xwide / nearest_neighbors_xwide on this device, as
+    wide_sweep_info gives them; (0, 0, 0) when the direct kernels answered (flagged data), nothing was swept, or no such
+    sweep has run."""
+    return _wide_info("xwide", device)
 
 
 # ---- ... the pruned self population sweep (include/dc_density.h, the PRUNED wide sweep) ------------------------------
@@ -467,6 +493,43 @@ def wide_against_info(device):
     device, as wide_sweep_info gives them for the self sweeps (dc_hip_wide_info_dev on the cross sweeps' own workspace);
     (0, 0, 0) when the direct kernels answered (flagged data), nothing was swept, or no such sweep has run."""
     return _wide_info("wide_against", device)
+
+
+# ---- ... and for rows of 257..1024 columns (include/dc_density.h, the "extra-wide" sweeps) ---------------------------
+def _check_pair_xwide(queries, reference):
+    """_check_pair, the column count (refused here as the library refuses it: 257..1024) first"""
+    for t in (queries, reference):
+        if isinstance(t, torch.Tensor) and t.dim() == 2 and not 257 <= t.shape[1] <= 1024:
+            raise ValueError(f"n_cols={t.shape[1]}: the extra-wide matrix-core sweeps take 257..1024 columns")
+    return _check_pair(queries, reference)
+
+
+def calculate_populations_against_xwide(queries, reference, radii, i_from=0, i_to=None, out=None):
+    """calculate_populations_against_wide for rows of 257..1024 columns (dc_hip_populations_cross_xwide_dev), in a cached
+    workspace of its own kind (xwide_against_info reads its counters).  Other column counts raise."""
+    return _populations_against("dc_hip_populations_cross_xwide_dev", "xwide_against", queries, reference,
+                                _check_pair_xwide(queries, reference), radii, i_from, i_to, out)
+
+
+def nearest_reference_xwide(queries, reference, fe_query=None, fe_ref=None, i_from=0, i_to=None):
+    """nearest_reference_wide for rows of 257..1024 columns (dc_hip_nearest_neighbors_cross_xwide_dev).  Without free
+    energies hd_idx / hd_d2 are None.  Other column counts raise."""
+    return _nearest("dc_hip_nearest_neighbors_cross_xwide_dev", "xwide_against", queries, reference,
+                    _check_pair_xwide(queries, reference), fe_query, fe_ref, i_from, i_to)
+
+
+def xwide_against_info(device):
+    """(tiles, mfmas, exact_pairs) of the last calculate_populations_against_xwide / nearest_reference_xwide on this
+    device, as wide_against_info gives them."""
+    return _wide_info("xwide_against", device)
+
+
+def assign_frames_xwide(queries, reference, radius, ref_states):
+    """assign_frames for rows of 257..1024 columns, every sweep on the matrix cores: calculate_populations_xwide on the
+    reference, calculate_populations_against_xwide and nearest_reference_xwide for the queries; the same dict, the same
+    values."""
+    return _assign_frames(queries, reference, radius, ref_states, _check_pair_xwide(queries, reference), calculate_populations_xwide,
+                          calculate_populations_against_xwide, nearest_reference_xwide)
 
 
 # ---- ... the pruned cross population sweep (include/dc_density.h, the PRUNED wide cross sweep) -----------------------

@@ -585,6 +585,34 @@ DC_API int dc_hip_nearest_neighbors_cross_wide_dev(const float* d_query, size_t 
                                                    const float* d_fe_ref, size_t i_from, size_t i_to,
                                                    uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                                                    float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
+/* ---- ... and the same sweeps for rows of 257..1024 columns ("extra-wide") ---------------------------------------------------
+ * The unpruned self and cross sweeps above at 257..1024 columns: the same kernels (their chain streams along K and takes
+ * its length at run time), the same contracts, results bit-identical to DC_VARIANT_DIRECT -- beyond 400 columns that is
+ * the column-chunked direct kernel, which also answers flagged data behind the device-side gate.  Every entry point takes
+ * the argument list of its _wide_ namesake and refuses in the same order, naming itself; n_cols outside 257..1024:
+ * DC_ERR_INVALID_ARGUMENT.  The workspace has a layout of its own (column sums and means for 1024 columns behind the
+ * header, the operand images from byte 13 312 on; about 6 KB per row and image at 1024 columns), so a workspace of one
+ * family never serves the other: dc_hip_xwide_workspace_bytes / dc_hip_cross_xwide_workspace_bytes are 0 outside
+ * 257..1024 columns, for no rows and for an empty side, and monotone in the row counts.  The info head is that of the
+ * wide sweeps: dc_hip_wide_info_dev reads the counters of the last call.  No pruned form, no session and no resident
+ * reference exists at these widths; no dc_variant value selects them. */
+DC_API size_t dc_hip_xwide_workspace_bytes(size_t n_rows, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_populations_xwide_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* radii,
+                                        size_t n_radii, size_t i_from, size_t i_to, uint32_t* d_pops, void* d_ws,
+                                        size_t ws_bytes, void* stream);
+DC_API int dc_hip_nearest_neighbors_xwide_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* d_fe,
+                                              size_t i_from, size_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+                                              uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
+                                              void* stream);
+DC_API size_t dc_hip_cross_xwide_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_populations_cross_xwide_dev(const float* d_query, size_t n_query, const float* d_ref, size_t n_ref,
+                                              size_t n_cols, const float* radii, size_t n_radii, size_t i_from,
+                                              size_t i_to, uint32_t* d_pops, void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_nearest_neighbors_cross_xwide_dev(const float* d_query, size_t n_query, const float* d_ref,
+                                                    size_t n_ref, size_t n_cols, const float* d_fe_query,
+                                                    const float* d_fe_ref, size_t i_from, size_t i_to,
+                                                    uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                                    float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
 /* ---- ... the PRUNED wide cross population sweep (65..256 columns) ----------------------------------------------------------
  * dc_hip_populations_cross_wide_dev's populations bit for bit, without the block pairs that cannot hold a pair within
  * the call's radii.  Statistics, origin and scale are those of the cross form.  ONE cell grid on columns 0 / 1 covers the
