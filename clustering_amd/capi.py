@@ -262,44 +262,21 @@ def _load():
     lib.dc_hip_session_open_flags.argtypes = [vp, sz, sz, C.POINTER(C.c_int), i32, C.c_uint, C.POINTER(vp)]
     lib.dc_hip_session_wide.restype = i32
     lib.dc_hip_session_wide.argtypes = [vp]
-    lib.dc_hip_reference_wide_workspace_bytes.restype = sz
-    lib.dc_hip_reference_wide_workspace_bytes.argtypes = [sz, sz, sz]
-    lib.dc_hip_reference_wide_open_dev.restype = i32
-    lib.dc_hip_reference_wide_open_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, C.POINTER(vp)]
-    lib.dc_hip_reference_wide_close.restype = None
-    lib.dc_hip_reference_wide_close.argtypes = [vp]
-    lib.dc_hip_reference_wide_set_free_energies_dev.restype = i32
-    lib.dc_hip_reference_wide_set_free_energies_dev.argtypes = [vp, vp, vp]
-    lib.dc_hip_reference_wide_stage_dev.restype = i32
-    lib.dc_hip_reference_wide_stage_dev.argtypes = [vp, vp, sz, vp]
-    lib.dc_hip_reference_wide_populations_dev.restype = i32
-    lib.dc_hip_reference_wide_populations_dev.argtypes = [vp, C.POINTER(C.c_float), sz, vp, vp]
-    lib.dc_hip_reference_wide_nearest_dev.restype = i32
-    lib.dc_hip_reference_wide_nearest_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.dc_hip_reference_wide_info_dev.restype = i32
-    lib.dc_hip_reference_wide_info_dev.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
-    lib.dc_hip_reference_wide_order_dev.restype = i32
-    lib.dc_hip_reference_wide_order_dev.argtypes = [vp, vp, vp, vp]
-    lib.dc_hip_reference_workspace_bytes.restype = sz
-    lib.dc_hip_reference_workspace_bytes.argtypes = [sz, sz, sz]
-    lib.dc_hip_reference_open_dev.restype = i32
-    lib.dc_hip_reference_open_dev.argtypes = [vp, sz, sz, sz, C.c_float, vp, sz, vp, C.POINTER(vp)]
-    lib.dc_hip_reference_close.restype = None
-    lib.dc_hip_reference_close.argtypes = [vp]
-    lib.dc_hip_reference_set_free_energies_dev.restype = i32
-    lib.dc_hip_reference_set_free_energies_dev.argtypes = [vp, vp, vp]
-    lib.dc_hip_reference_stage_dev.restype = i32
-    lib.dc_hip_reference_stage_dev.argtypes = [vp, vp, sz, vp]
-    lib.dc_hip_reference_populations_dev.restype = i32
-    lib.dc_hip_reference_populations_dev.argtypes = [vp, C.POINTER(C.c_float), sz, vp, vp]
-    lib.dc_hip_reference_nearest_dev.restype = i32
-    lib.dc_hip_reference_nearest_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.dc_hip_reference_info_dev.restype = i32
-    lib.dc_hip_reference_info_dev.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
-                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
-    lib.dc_hip_reference_order_dev.restype = i32
-    lib.dc_hip_reference_order_dev.argtypes = [vp, i32, vp, vp, vp]
+    # the two resident reference handles (wide: 65..256 columns, narrow: 1..64): one list per step, and the three that differ
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    for api, open_extra, third_counter, order_extra in (("dc_hip_reference_wide_", [], u64p, []),
+                                                        ("dc_hip_reference_", [C.c_float], u32p, [i32])):
+        for step, restype, argtypes in (("workspace_bytes", sz, [sz, sz, sz]),
+                                        ("open_dev", i32, [vp, sz, sz, sz] + open_extra + [vp, sz, vp, C.POINTER(vp)]),
+                                        ("close", None, [vp]),
+                                        ("set_free_energies_dev", i32, [vp, vp, vp]),
+                                        ("stage_dev", i32, [vp, vp, sz, vp]),
+                                        ("populations_dev", i32, [vp, C.POINTER(C.c_float), sz, vp, vp]),
+                                        ("nearest_dev", i32, [vp, vp, vp, vp, vp, vp, vp]),
+                                        ("info_dev", i32, [vp, u64p, u64p, third_counter, u32p, u32p, vp]),
+                                        ("order_dev", i32, [vp] + order_extra + [vp, vp, vp])):
+            getattr(lib, api + step).restype = restype
+            getattr(lib, api + step).argtypes = argtypes
     lib.dc_hip_assign_workspace_bytes.restype = sz
     lib.dc_hip_assign_workspace_bytes.argtypes = [sz, sz]
     lib.dc_hip_assign_open_dev.restype = i32

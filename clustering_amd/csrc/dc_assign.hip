@@ -1,7 +1,7 @@
 // dc_assign.hip -- assigning new frames to a clustered reference (include/dc_density.h "assigner").
 //   dc_hip_assign_*    device level: one batch = stage, populations at the radius, free energies by table, nearest,
-//                      state pick -- five stream-ordered steps on a resident reference handle of either width, driven
-//                      through a table of three function pointers per handle kind
+//                      state pick -- five stream-ordered steps on a resident reference handle of either kind (the one
+//                      struct and the shared bodies of dc_assign.hpp), or on the per-call cross entry points
 //   dc_hip_assigner_*  host level: owns the reference, its self sweep, the handle and two batch slots; uploads and
 //                      downloads on a copy stream beside the sweeps
 // Two kernels live here, both a row per lane; every sweep is the library's.
@@ -55,24 +55,8 @@ __global__ void assign_pick_kernel(const uint32_t* __restrict__ nn_idx, const ui
 
 constexpr uint32_t kThreads = 256;
 
-// the three steps a batch takes of whatever holds the reference
-struct HandleOps {
-  int (*stage)(void* h, const float* d_query, size_t n_query, void* stream);
-  int (*populations)(void* h, const float* radii, size_t n_radii, uint32_t* d_pops, void* stream);
-  int (*nearest)(void* h, const float* d_fe_query, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
-                 void* stream);
-};
-
-template <class H, int (*Stage)(H*, const float*, size_t, void*), int (*Pops)(H*, const float*, size_t, uint32_t*, void*),
-          int (*Near)(H*, const float*, uint32_t*, float*, uint32_t*, float*, void*)>
-HandleOps ops_of() {
-  return {[](void* h, const float* q, size_t n, void* s) { return Stage((H*)h, q, n, s); },
-          [](void* h, const float* r, size_t n, uint32_t* p, void* s) { return Pops((H*)h, r, n, p, s); },
-          [](void* h, const float* f, uint32_t* a, float* b, uint32_t* c, float* d, void* s) { return Near((H*)h, f, a, b, c, d, s); }};
-}
-
 // a reference no handle takes (rows wider than 256 columns, or beyond the narrow handle's 2^24 positions): the per-call
-// cross entry points under DC_VARIANT_AUTO behind the same three steps
+// cross entry points under DC_VARIANT_AUTO behind the three steps a batch takes of a handle
 struct CrossRef {
   const float* d_ref = nullptr;
   const float* d_fe_ref = nullptr;
@@ -82,15 +66,15 @@ struct CrossRef {
   const float* d_query = nullptr;
   size_t n_query = 0;
 };
-int cross_stage(CrossRef* c, const float* d_query, size_t n_query, void*) {
+int cross_stage(CrossRef* c, const float* d_query, size_t n_query) {
   c->d_query = d_query, c->n_query = n_query;
   return DC_OK;
 }
-int cross_populations(CrossRef* c, const float* radii, size_t n_radii, uint32_t* d_pops, void* stream) {
+int cross_populations(const CrossRef* c, const float* radii, size_t n_radii, uint32_t* d_pops, void* stream) {
   return dc_hip_populations_cross_dev(c->d_query, c->n_query, c->d_ref, c->n_ref, c->n_cols, radii, n_radii, 0, c->n_query, d_pops,
                                       c->d_ws, c->ws_bytes, DC_VARIANT_AUTO, stream);
 }
-int cross_nearest(CrossRef* c, const float* d_fe_query, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
+int cross_nearest(const CrossRef* c, const float* d_fe_query, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2,
                   void* stream) {
   return dc_hip_nearest_neighbors_cross_dev(c->d_query, c->n_query, c->d_ref, c->n_ref, c->n_cols, d_fe_query, c->d_fe_ref, 0,
                                             c->n_query, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, c->d_ws, c->ws_bytes, DC_VARIANT_AUTO,
@@ -114,8 +98,8 @@ struct AssignLayout {
 }  // namespace
 
 struct dc_assign {
-  HandleOps ops{};
-  void* handle = nullptr;        // borrowed: dc_reference*, dc_reference_wide* or CrossRef*
+  dc::ReferenceHandle* ref = nullptr;   // borrowed: the handle of either kind that holds the reference, or
+  CrossRef* cross = nullptr;            // ... where no handle takes it
   size_t n_ref = 0, max_batch = 0;
   float radius = 0.0f;
   float* h_table = nullptr;      // the table's host copy: pinned, alive until close (its upload is asynchronous)
@@ -127,7 +111,9 @@ struct dc_assign {
 
 namespace {
 
-int assign_open(const char* fn, const HandleOps& ops, void* handle, const dc::ReferenceFacts& f, const int32_t* d_states_ref,
+// f: a resident reference as its assigner sees it -- the counts, whether its free energies were set, the largest
+// fl32(r * r) a population call takes: *ref, or a description of *cross
+int assign_open(const char* fn, dc::ReferenceHandle* ref, CrossRef* cross, const dc::ReferenceHandle& f, const int32_t* d_states_ref,
                 uint32_t max_pop, float radius, void* d_ws, size_t ws_bytes, void* stream, dc_assign** out) {
   if (!f.has_fe) return failf(DC_ERR_INVALID_ARGUMENT, "%s: the reference's free energies were never set", fn);
   if (max_pop == 0) return failf(DC_ERR_INVALID_ARGUMENT, "%s: max_pop must be positive", fn);
@@ -141,7 +127,7 @@ int assign_open(const char* fn, const HandleOps& ops, void* handle, const dc::Re
   hipStream_t s = (hipStream_t)stream;
   const AssignLayout lay(f.n_ref, f.max_batch);
   dc_assign* a = new dc_assign;
-  a->ops = ops, a->handle = handle, a->n_ref = f.n_ref, a->max_batch = f.max_batch, a->radius = radius;
+  a->ref = ref, a->cross = cross, a->n_ref = f.n_ref, a->max_batch = f.max_batch, a->radius = radius;
   const size_t n_table = f.n_ref + 1;
   a->table.resize(n_table);
   dc::fe_table(a->table, max_pop);
@@ -168,6 +154,15 @@ int assign_open(const char* fn, const HandleOps& ops, void* handle, const dc::Re
   return DC_OK;
 }
 
+// dc_hip_assign_open[_wide]_dev
+int assign_open_on(const char* fn, dc::ReferenceHandle* ref, const int32_t* d_states_ref, uint32_t max_pop, float radius, void* d_ws,
+                   size_t ws_bytes, void* stream, dc_assign** out) {
+  if (!out) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer (out)", fn);
+  *out = nullptr;
+  if (!ref) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer (reference)", fn);
+  return assign_open(fn, ref, nullptr, *ref, d_states_ref, max_pop, radius, d_ws, ws_bytes, stream, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -179,24 +174,12 @@ size_t dc_hip_assign_workspace_bytes(size_t n_ref, size_t max_batch) {
 
 int dc_hip_assign_open_dev(dc_reference* ref, const int32_t* d_states_ref, uint32_t max_pop, float radius, void* d_ws,
                            size_t ws_bytes, void* stream, dc_assign** out) {
-  const char* fn = "dc_hip_assign_open_dev";
-  if (!out) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer (out)", fn);
-  *out = nullptr;
-  if (!ref) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer (reference)", fn);
-  static const HandleOps ops =
-      ops_of<dc_reference, dc_hip_reference_stage_dev, dc_hip_reference_populations_dev, dc_hip_reference_nearest_dev>();
-  return assign_open(fn, ops, ref, dc::reference_facts(ref), d_states_ref, max_pop, radius, d_ws, ws_bytes, stream, out);
+  return assign_open_on("dc_hip_assign_open_dev", dc::handle(ref), d_states_ref, max_pop, radius, d_ws, ws_bytes, stream, out);
 }
 
 int dc_hip_assign_open_wide_dev(dc_reference_wide* ref, const int32_t* d_states_ref, uint32_t max_pop, float radius, void* d_ws,
                                 size_t ws_bytes, void* stream, dc_assign** out) {
-  const char* fn = "dc_hip_assign_open_wide_dev";
-  if (!out) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer (out)", fn);
-  *out = nullptr;
-  if (!ref) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer (reference)", fn);
-  static const HandleOps ops = ops_of<dc_reference_wide, dc_hip_reference_wide_stage_dev, dc_hip_reference_wide_populations_dev,
-                                      dc_hip_reference_wide_nearest_dev>();
-  return assign_open(fn, ops, ref, dc::reference_facts(ref), d_states_ref, max_pop, radius, d_ws, ws_bytes, stream, out);
+  return assign_open_on("dc_hip_assign_open_wide_dev", dc::handle(ref), d_states_ref, max_pop, radius, d_ws, ws_bytes, stream, out);
 }
 
 void dc_hip_assign_close(dc_assign* a) {
@@ -221,10 +204,14 @@ int dc_hip_assign_batch_dev(dc_assign* a, const float* d_query, size_t n_query, 
   uint32_t* hd_idx = d_hd_idx ? d_hd_idx : a->d_scratch[4];
   float* hd_d2 = d_hd_d2 ? d_hd_d2 : (float*)a->d_scratch[5];
   const uint32_t n = (uint32_t)n_query, n_ref = (uint32_t)a->n_ref, blocks = (n + kThreads - 1) / kThreads;
-  if (int rc = a->ops.stage(a->handle, d_query, n_query, stream)) return rc;
-  if (int rc = a->ops.populations(a->handle, &a->radius, 1, pops, stream)) return rc;
+  dc::ReferenceHandle* r = a->ref;
+  if (int rc = r ? dc::handle_stage(*r->kind, r, d_query, n_query, stream) : cross_stage(a->cross, d_query, n_query)) return rc;
+  if (int rc = r ? dc::handle_populations(*r->kind, r, &a->radius, 1, pops, stream) : cross_populations(a->cross, &a->radius, 1, pops, stream))
+    return rc;
   assign_fe_kernel<<<blocks, kThreads, 0, s>>>(pops, n, a->d_table, n_ref, fe);
-  if (int rc = a->ops.nearest(a->handle, fe, nn_idx, nn_d2, hd_idx, hd_d2, stream)) return rc;
+  if (int rc = r ? dc::handle_nearest(*r->kind, r, fe, nn_idx, nn_d2, hd_idx, hd_d2, stream)
+                 : cross_nearest(a->cross, fe, nn_idx, nn_d2, hd_idx, hd_d2, stream))
+    return rc;
   assign_pick_kernel<<<blocks, kThreads, 0, s>>>(nn_idx, hd_idx, a->d_states_ref, n, n_ref, d_states);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return failf(DC_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
@@ -280,8 +267,7 @@ struct dc_assigner {
   uint32_t max_pop = 0;
   hipStream_t compute = nullptr, copy = nullptr;   // (one stream under DC_ASSIGN_OVERLAP=0)
   std::vector<void*> bufs;                         // device memory, freed at close
-  dc_reference* narrow = nullptr;
-  dc_reference_wide* wide = nullptr;
+  dc::ReferenceHandle* ref = nullptr;              // the handle of paths 0 (narrow) and 1 (wide)
   CrossRef cross;
   dc_assign* assign = nullptr;
   std::vector<uint32_t> pops_ref;
@@ -339,34 +325,29 @@ int assigner_build(dc_assigner* a, const float* ref, const int32_t* states_ref) 
   const size_t aws = dc_hip_assign_workspace_bytes(n_ref, max_batch);
   DC_ASSIGN_TRY(dev_alloc(a, &d_aws, aws));
   a->path = wide ? 1 : (n_cols <= 64 ? 0 : 2);
-  if (a->path == 0) {
-    const size_t hws = dc_hip_reference_workspace_bytes(n_ref, n_cols, max_batch);
+  if (a->path != 2) {
+    const dc::ReferenceKind& k = wide ? dc::kReferenceWide : dc::kReferenceNarrow;
+    const size_t hws = (wide ? dc_hip_reference_wide_workspace_bytes : dc_hip_reference_workspace_bytes)(n_ref, n_cols, max_batch);
     DC_ASSIGN_TRY(dev_alloc(a, &d_hws, hws));
-    const int rc = dc_hip_reference_open_dev((const float*)d_ref, n_ref, n_cols, max_batch, a->radius, d_hws, hws, s, &a->narrow);
-    if (rc == DC_ERR_TOO_LARGE)
-      a->path = 2;   // (a reference beyond the handle's 2^24 positions: the per-call entry points serve it)
+    const int rc = dc::handle_open(k, (const float*)d_ref, n_ref, n_cols, max_batch, wide ? INFINITY : a->radius, d_hws, hws, s, &a->ref);
+    if (rc == DC_ERR_TOO_LARGE && !wide)
+      a->path = 2;   // (a reference beyond the narrow handle's 2^24 positions: the per-call entry points serve it)
     else if (rc)
       return rc;
   }
-  if (a->path == 0) {
-    if (int rc = dc_hip_reference_set_free_energies_dev(a->narrow, (const float*)d_fe, s)) return rc;
-    if (int rc = dc_hip_assign_open_dev(a->narrow, (const int32_t*)d_states, a->max_pop, a->radius, d_aws, aws, s, &a->assign)) return rc;
-  } else if (a->path == 1) {
-    const size_t hws = dc_hip_reference_wide_workspace_bytes(n_ref, n_cols, max_batch);
-    DC_ASSIGN_TRY(dev_alloc(a, &d_hws, hws));
-    if (int rc = dc_hip_reference_wide_open_dev((const float*)d_ref, n_ref, n_cols, max_batch, d_hws, hws, s, &a->wide)) return rc;
-    if (int rc = dc_hip_reference_wide_set_free_energies_dev(a->wide, (const float*)d_fe, s)) return rc;
-    if (int rc = dc_hip_assign_open_wide_dev(a->wide, (const int32_t*)d_states, a->max_pop, a->radius, d_aws, aws, s, &a->assign))
+  if (a->path != 2) {
+    if (int rc = dc::handle_set_free_energies(*a->ref->kind, a->ref, (const float*)d_fe, s)) return rc;
+    if (int rc = assign_open_on(wide ? "dc_hip_assign_open_wide_dev" : "dc_hip_assign_open_dev", a->ref, (const int32_t*)d_states, a->max_pop,
+                                a->radius, d_aws, aws, s, &a->assign))
       return rc;
   } else {
     CrossRef& c = a->cross;
     c.d_ref = (const float*)d_ref, c.d_fe_ref = (const float*)d_fe, c.n_ref = n_ref, c.n_cols = n_cols;
     c.ws_bytes = dc_hip_cross_workspace_bytes(max_batch, n_ref, n_cols);
     if (c.ws_bytes) DC_ASSIGN_TRY(dev_alloc(a, &c.d_ws, c.ws_bytes));
-    static const HandleOps ops = ops_of<CrossRef, cross_stage, cross_populations, cross_nearest>();
-    dc::ReferenceFacts f;
+    dc::ReferenceHandle f;
     f.n_ref = n_ref, f.n_cols = n_cols, f.max_batch = max_batch, f.has_fe = true, f.r2max = INFINITY;
-    if (int rc = assign_open(fn, ops, &c, f, (const int32_t*)d_states, a->max_pop, a->radius, d_aws, aws, s, &a->assign)) return rc;
+    if (int rc = assign_open(fn, nullptr, &c, f, (const int32_t*)d_states, a->max_pop, a->radius, d_aws, aws, s, &a->assign)) return rc;
   }
   for (Slot& sl : a->slot) {
     DC_ASSIGN_TRY(hipHostMalloc((void**)&sl.h_query, std::max<size_t>(sizeof(float) * max_batch * n_cols, 4), hipHostMallocDefault));
@@ -495,8 +476,7 @@ void dc_hip_assigner_close(dc_assigner* a) {
   if (a->compute) (void)hipStreamSynchronize(a->compute);
   if (a->copy) (void)hipStreamSynchronize(a->copy);
   dc_hip_assign_close(a->assign);
-  dc_hip_reference_close(a->narrow);
-  dc_hip_reference_wide_close(a->wide);
+  delete a->ref;
   for (Slot& sl : a->slot) {
     if (sl.h_query) (void)hipHostFree(sl.h_query);
     if (sl.h_out) (void)hipHostFree(sl.h_out);

@@ -624,34 +624,47 @@ class Reference:
     _api = "dc_hip_reference_wide_"   # the entry points' common prefix
     _assign_open = "dc_hip_assign_open_wide_dev"   # ... and the assigner's open for this kind of handle
     _assign_h = _assign_ws = None     # the assigner of assign_device(), built on first use
+    _cols = (65, 256, "the wide matrix-core sweeps take 65..256 columns")   # the widths of this kind, and its refusal
 
     def __init__(self, reference, max_batch, radius=None, ref_states=None):
+        self._init(reference, max_batch, radius, ref_states)
+
+    def _open_args(self, radius, max_radius):
+        """what this kind's open call takes between max_batch and the workspace"""
+        return ()
+
+    def _self_populations(self, reference, radius):
+        return calculate_populations_wide_pruned(reference, [radius])
+
+    def _init(self, reference, max_batch, radius, ref_states, max_radius=None):
+        """the construction of either kind: _cols, _open_args and _self_populations are what a kind supplies"""
         self._h = None
         self._n_ref, self._n_cols = _check_coords(reference)
-        if not 65 <= self._n_cols <= 256:
-            raise ValueError(f"n_cols={self._n_cols}: the wide matrix-core sweeps take 65..256 columns")
+        if not self._cols[0] <= self._n_cols <= self._cols[1]:
+            raise ValueError(f"n_cols={self._n_cols}: {self._cols[2]}")
         self._max_batch = int(max_batch)
         if self._n_ref < 1 or self._max_batch < 1:
             raise ValueError(f"a reference of {self._n_ref} rows, batches of {self._max_batch}: both must be positive")
         if (radius is None) != (ref_states is None):
             raise ValueError("radius and ref_states go together")
+        open_args = self._open_args(radius, max_radius)
         states = None if ref_states is None else np.ascontiguousarray(ref_states, dtype=np.int32)
         if states is not None and states.shape != (self._n_ref,):
             raise ValueError(f"ref_states must hold one state per reference row ({self._n_ref}), got shape {states.shape}")
         self._ref, self._queries, self._fe_ref = reference, None, None
         self.device = reference.device
-        need = int(capi.lib.dc_hip_reference_wide_workspace_bytes(self._n_ref, self._n_cols, self._max_batch))
+        need = int(getattr(capi.lib, self._api + "workspace_bytes")(self._n_ref, self._n_cols, self._max_batch))
         self._ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            capi.check(capi.lib.dc_hip_reference_wide_open_dev(_dev(reference), self._n_ref, self._n_cols, self._max_batch,
-                                                               _dev(self._ws), need, _stream_ptr(), C.byref(h)),
-                       "dc_hip_reference_wide_open_dev")
+            capi.check(getattr(capi.lib, self._api + "open_dev")(_dev(reference), self._n_ref, self._n_cols, self._max_batch,
+                                                                 *open_args, _dev(self._ws), need, _stream_ptr(), C.byref(h)),
+                       self._api + "open_dev")
         self._h = h
         self.radius, self.pops_ref, self.max_pop, self.fe_ref, self._states_r = radius, None, None, None, None
         if radius is not None:
             self._states_r = torch.as_tensor(states, device=self.device)
-            self.pops_ref = calculate_populations_wide_pruned(reference, [radius])[0].contiguous()
+            self.pops_ref = self._self_populations(reference, radius)[0].contiguous()
             self.max_pop = int(self.pops_ref.max().item())
             self.fe_ref = calculate_free_energies(self.pops_ref)
             self.set_free_energies(self.fe_ref)
@@ -816,41 +829,20 @@ class NarrowReference(Reference):
     reference_preparations); order(which): 0 the population sweep's orders, 1 the neighbour sweep's."""
     _api = "dc_hip_reference_"
     _assign_open = "dc_hip_assign_open_dev"
+    _cols = (1, 64, "the resident reference of the pruned cross sweeps takes 1..64 columns")
 
     def __init__(self, reference, max_batch, max_radius=None, radius=None, ref_states=None):
-        self._h = None
-        self._n_ref, self._n_cols = _check_coords(reference)
-        if not 1 <= self._n_cols <= 64:
-            raise ValueError(f"n_cols={self._n_cols}: the resident reference of the pruned cross sweeps takes 1..64 columns")
-        self._max_batch = int(max_batch)
-        if self._n_ref < 1 or self._max_batch < 1:
-            raise ValueError(f"a reference of {self._n_ref} rows, batches of {self._max_batch}: both must be positive")
-        if (radius is None) != (ref_states is None):
-            raise ValueError("radius and ref_states go together")
+        self._init(reference, max_batch, radius, ref_states, max_radius)
+
+    def _open_args(self, radius, max_radius):
         max_radius = radius if max_radius is None else max_radius
         if max_radius is None:
             raise ValueError("max_radius (or radius) is needed: the population scale is fixed when the reference is opened")
-        states = None if ref_states is None else np.ascontiguousarray(ref_states, dtype=np.int32)
-        if states is not None and states.shape != (self._n_ref,):
-            raise ValueError(f"ref_states must hold one state per reference row ({self._n_ref}), got shape {states.shape}")
-        self._ref, self._queries, self._fe_ref = reference, None, None
-        self.device = reference.device
         self.max_radius = float(max_radius)
-        need = int(capi.lib.dc_hip_reference_workspace_bytes(self._n_ref, self._n_cols, self._max_batch))
-        self._ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            capi.check(capi.lib.dc_hip_reference_open_dev(_dev(reference), self._n_ref, self._n_cols, self._max_batch,
-                                                          self.max_radius, _dev(self._ws), need, _stream_ptr(), C.byref(h)),
-                       "dc_hip_reference_open_dev")
-        self._h = h
-        self.radius, self.pops_ref, self.max_pop, self.fe_ref, self._states_r = radius, None, None, None, None
-        if radius is not None:
-            self._states_r = torch.as_tensor(states, device=self.device)
-            self.pops_ref = calculate_populations_partial(reference, [radius], variant="auto")[0].contiguous()
-            self.max_pop = int(self.pops_ref.max().item())
-            self.fe_ref = calculate_free_energies(self.pops_ref)
-            self.set_free_energies(self.fe_ref)
+        return (self.max_radius,)
+
+    def _self_populations(self, reference, radius):
+        return calculate_populations_partial(reference, [radius], variant="auto")
 
     def info(self):
         """(tiles, mfmas, shares, answered, reference_preparations) of the last sweep (dc_hip_reference_info_dev)"""
