@@ -53,6 +53,8 @@ SYMBOLS = (
     "dc_hip_wide_pruned_workspace_bytes", "dc_hip_populations_wide_pruned_dev", "dc_hip_wide_pruned_order_dev",
     "dc_hip_radius_pairs_wide_pruned_dev", "dc_hip_radius_min_edge_wide_pruned_dev", "dc_hip_radius_forest_wide_pruned",
     "dc_hip_nearest_neighbors_wide_pruned_dev",
+    "dc_hip_xwide_pruned_workspace_bytes", "dc_hip_populations_xwide_pruned_dev", "dc_hip_nearest_neighbors_xwide_pruned_dev",
+    "dc_hip_xwide_pruned_order_dev",
     "dc_hip_cross_wide_pruned_workspace_bytes", "dc_hip_populations_cross_wide_pruned_dev", "dc_hip_cross_wide_pruned_order_dev",
     "dc_hip_nearest_neighbors_cross_wide_pruned_dev",
     "dc_hip_neighbors_block_rows_wide", "dc_hip_neighbors_block_pack_wide_dev", "dc_hip_neighbors_block_unpack_wide_dev",
@@ -242,6 +244,12 @@ def _load():
     lib.dc_hip_radius_forest_wide_pruned.argtypes = lib.dc_hip_radius_forest_wide.argtypes
     lib.dc_hip_nearest_neighbors_wide_pruned_dev.restype = i32
     lib.dc_hip_nearest_neighbors_wide_pruned_dev.argtypes = lib.dc_hip_nearest_neighbors_wide_dev.argtypes
+    for xwide, wide in (("dc_hip_xwide_pruned_workspace_bytes", "dc_hip_wide_pruned_workspace_bytes"),
+                        ("dc_hip_populations_xwide_pruned_dev", "dc_hip_populations_wide_pruned_dev"),
+                        ("dc_hip_nearest_neighbors_xwide_pruned_dev", "dc_hip_nearest_neighbors_wide_pruned_dev"),
+                        ("dc_hip_xwide_pruned_order_dev", "dc_hip_wide_pruned_order_dev")):
+        getattr(lib, xwide).restype = getattr(lib, wide).restype     # (257..1024 columns: the lists of their namesakes)
+        getattr(lib, xwide).argtypes = getattr(lib, wide).argtypes
     lib.dc_hip_cross_wide_pruned_workspace_bytes.restype = sz
     lib.dc_hip_cross_wide_pruned_workspace_bytes.argtypes = [sz, sz, sz, sz]
     lib.dc_hip_populations_cross_wide_pruned_dev.restype = i32

@@ -1,6 +1,7 @@
 // dc_mfma_wide.hip -- host side of the matrix-core sweeps for rows of 65..256 columns: workspace, preparation and
 // launches (kernels: dc_mfma_wide_kernels.hpp).  The unpruned self and cross sweeps also serve 257..1024 columns, in the
-// layout of those widths (dc_hip_*_xwide_dev).
+// layout of those widths (dc_hip_*_xwide_dev), and so do the pruned self population and neighbour sweeps
+// (dc_hip_*_xwide_pruned_dev).
 #include "dc_mfma_wide_kernels.hpp"
 
 namespace dc {
@@ -217,6 +218,13 @@ size_t wide_pruned_workspace_bytes(size_t n_rows, size_t n_cols) {
   return wide_pruned_layout(n_rows, n_cols).total;
 }
 
+// 257..1024 columns: the same regions behind the head of those widths.  wide_pruned_prepare,
+// launch_pop_wide_pruned, launch_nn_wide_pruned and wide_pruned_order read the layout of the width they are given
+size_t xwide_pruned_workspace_bytes(size_t n_rows, size_t n_cols) {
+  if (!xwide_mfma_supports(n_cols) || n_rows == 0) return 0;
+  return wide_pruned_layout(n_rows, n_cols).total;
+}
+
 int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t s, const float* d_fe) {
   const WidePrunedLayout P = wide_pruned_layout(n_rows, n_cols);
   char* p = (char*)d_ws;
@@ -253,7 +261,7 @@ int wide_pruned_args(const WidePrunedLayout& P, uint32_t n_rows, uint32_t n_cols
   X.boxes = (const float4*)(p + P.off_boxes);
   X.seg = (uint32_t)segment;
   X.n_seg = segments_u32(n_segments);
-  X.far2 = wide_prune_far2(largest_radius2(rad2, n_rad));
+  X.far2 = wide_prune_far2(largest_radius2(rad2, n_rad), wide_pop_floor(n_cols));
   X.perm = (const uint32_t*)(p + P.off_perm);
   const uint32_t q_blocks = (uint32_t)((P.blocks - segment + n_segments - 1) / n_segments);
   *grid = dim3(wide_grid_size(q_blocks, wide_shares(P.blocks)));
@@ -357,7 +365,7 @@ int launch_nn_wide_pruned(const float* d_fe, uint32_t n_rows, uint32_t n_cols, s
   for (uint32_t ring = kWideRingSeed; ring <= kWideRing2; ++ring) {
     if (ring != kWideRingSeed)
       hipLaunchKernelGGL(wide_nn_bounds_kernel, dim3(P.blocks), dim3(128), 0, s, (const unsigned long long*)X.merge, n_rows,
-                         ring - 1u, far2 + (size_t)(ring - 1u) * P.blocks);
+                         ring - 1u, far2 + (size_t)(ring - 1u) * P.blocks, wide_nn_floor(n_cols));
     X.ring = ring;
     hipLaunchKernelGGL((wide_sweep_kernel<kWideNn, 1, kSelf, true>), grid, dim3(256), 0, s, X);
   }
@@ -753,7 +761,7 @@ int nn_wide_cross_pruned(const WideCrossPrunedLayout& P, const WideCrossNnPlaces
   for (uint32_t ring = kWideRingSeed; ring <= last_ring; ++ring) {
     if (ring != kWideRingSeed)
       hipLaunchKernelGGL(wide_nn_bounds_kernel, dim3(blocks_q), dim3(128), 0, s, (const unsigned long long*)X.merge, n_q, ring - 1u,
-                         far2 + (size_t)(ring - 1u) * P.blocks_q);
+                         far2 + (size_t)(ring - 1u) * P.blocks_q, wide_nn_floor(n_cols));
     X.ring = ring;
     hipLaunchKernelGGL((wide_sweep_kernel<kWideNn, 1, kAgainst, true>), grid, dim3(256), 0, s, X);
   }

@@ -56,6 +56,11 @@ void launch_min_edge_wide_mfma(const float* d_coords, uint32_t n_rows, uint32_t 
 // bytes: the workspace of the unpruned sweeps at its head (header, images, norms), then the order, the gathered rows, the
 // boxes, the counts and the sort's scratch; 0 if the column count is not served or there are no rows; monotone in n_rows
 size_t wide_pruned_workspace_bytes(size_t n_rows, size_t n_cols);
+// ... and of the pruned self population and neighbour sweeps at 257..1024 columns (dc_hip_*_xwide_pruned_dev, DESIGN.md
+// 4.33): the same regions behind the head of those widths; 0 outside them.  wide_pruned_prepare, launch_pop_wide_pruned,
+// launch_nn_wide_pruned and wide_pruned_order serve both families and read the layout of the width they are given; the
+// pruning rules take the floors of the width (dc_wide_prune.hpp)
+size_t xwide_pruned_workspace_bytes(size_t n_rows, size_t n_cols);
 // statistics, order, gathered rows, boxes and images, on the stream, no host synchronisation; returns 0 on success
 // (d_fe: the neighbour call's free energies, a NaN among them flags the data like a non-finite row)
 int wide_pruned_prepare(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t stream,

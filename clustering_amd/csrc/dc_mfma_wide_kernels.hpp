@@ -53,6 +53,8 @@
 // in three launches -- the blocks next to the query block, the blocks within the bound of its nearest neighbours, the
 // blocks within the bound of its lower-free-energy neighbours that hold a lower row (dc_wide_prune.hpp) --, the later
 // ones starting from the merged words of the earlier; the words are placed by position and name rows.
+// Both pruned self sweeps also serve rows of 257..1024 columns (dc_hip_*_xwide_pruned_dev): the same
+// instances over a longer chain, with the factor of wide_nn_start and the floors of the two rules taken for the width.
 // The pruned cross population sweep (dc_hip_populations_cross_wide_pruned_dev) is the pruned population
 // sweep over a rectangle: the query range and the reference each in an order of its own on ONE cell grid, a set of boxes
 // each; the kernel works in positions of the two orders, the scatter behind it writes rows of the query array.
@@ -203,12 +205,14 @@ __host__ __device__ inline float wide_cut_ratio(const WideBand& b) {
 // that row's real d2 <= d2_c / (1 - u)^(D+1) <= d2_c (1 + 1.6e-5) at D <= 256, and its accumulator is at most
 // S d2 (1 + kappa) + e0 by the band: m0 is that, rounded up.  Every reference whose canonical sum is <= d2_c has an
 // accumulator <= m0 <= cut(m0) as well, so all that could beat or tie the word are still raised.
-// (The constant 2.0e-5 below holds at D <= 256 only: at 1024 columns (1 - u)^-(D+1) - 1 is 6.1e-5.  The pruned sweeps stop
-//  at kWideMaxCols, and the unpruned sweeps of 257..1024 columns, DESIGN.md 4.31, never call this.)
-__device__ __forceinline__ float wide_nn_start(unsigned long long word, float S, const WideBand& b) {
+// grow: the factor for (1 - u)^-(D+1).  1 + 2.0e-5 holds at D <= 256 only; at 1024 columns the term is 6.1e-5, and the
+// pruned self instance, which serves 257..1024 columns too, takes 1 + 7.0e-5 there (wide_nn_grow).
+constexpr float kWideNnGrow = 1.0f + 2.0e-5f, kXWideNnGrow = 1.0f + 7.0e-5f;
+__device__ __forceinline__ float wide_nn_grow(uint32_t D) { return D <= (uint32_t)kWideMaxCols ? kWideNnGrow : kXWideNnGrow; }
+__device__ __forceinline__ float wide_nn_start(unsigned long long word, float S, const WideBand& b, float grow = kWideNnGrow) {
   if (word == ~0ull) return INFINITY;
   const float d2c = __uint_as_float((uint32_t)(word >> 32));
-  const float m = ((S * d2c) * (1.0f + 2.0e-5f)) * (1.0f + b.kappa) + b.e0;
+  const float m = ((S * d2c) * grow) * (1.0f + b.kappa) + b.e0;
   return m + fabsf(m) * kWideRoundMargin;
 }
 
@@ -548,10 +552,11 @@ __global__ __launch_bounds__(128) void wide_nn_gather_kernel(const uint32_t* __r
   __syncthreads();
   if (threadIdx.x == 0) fe_range[blockIdx.x] = make_float2(fminf(part[0].x, part[1].x), fmaxf(part[0].y, part[1].y));
 }
-// ... between its launches: far2[qb] = wide_nn_far2(B), B the largest d2 in the words of the block's live positions,
-// +inf if one of them holds none (half: 0 the nn words, 1 the hd words); one thread per position, one result per block
+// ... between its launches: far2[qb] = wide_nn_far2(B, floor), B the largest d2 in the words of the block's live positions,
+// +inf if one of them holds none (half: 0 the nn words, 1 the hd words; floor: wide_nn_floor of the width); one thread
+// per position, one result per block
 __global__ __launch_bounds__(128) void wide_nn_bounds_kernel(const unsigned long long* __restrict__ merge, uint32_t n_rows,
-                                                             uint32_t half, float* __restrict__ far2) {
+                                                             uint32_t half, float* __restrict__ far2, float floor) {
   __shared__ float part[2];
   const uint32_t p = blockIdx.x * kWideBlockRows + threadIdx.x;
   float b = 0.0f;   // (d2 >= 0; a dead position does not raise the bound)
@@ -563,7 +568,7 @@ __global__ __launch_bounds__(128) void wide_nn_bounds_kernel(const unsigned long
   for (int off = 32; off > 0; off >>= 1) b = fmaxf(b, __shfl_xor(b, off, 64));
   if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = b;
   __syncthreads();
-  if (threadIdx.x == 0) far2[blockIdx.x] = wide_nn_far2(fmaxf(part[0], part[1]));
+  if (threadIdx.x == 0) far2[blockIdx.x] = wide_nn_far2(fmaxf(part[0], part[1]), floor);
 }
 // ... and behind them: the words of position p to row perm[p] ("none", the caller's preset, stays where nothing was found
 // and on the rows of other segments); stands down with the sweep
@@ -1115,9 +1120,11 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
       feq[qt] = (live[qt] && has_fe) ? q_fe[jq[qt]] : -INFINITY;   // (a dead lane, nn only: no reference lies lower)
       if constexpr (PR) {
         // rings 1 and 2 start from the words of the launches before: a bound on the accumulator of the row a word names
+        // (the cross instance stops at kWideMaxCols and keeps its constant: it has no register to spare, see kFresh)
         if (X.ring != kWideRingSeed && live[qt]) {
-          m_nn[qt] = wide_nn_start(X.merge[jq[qt]], sc.s2, band);
-          m_hd[qt] = wide_nn_start(X.merge[(size_t)(SM == kAgainst ? n_q : X.n_rows) + jq[qt]], sc.s2, band);
+          const float grow = (SM == kAgainst) ? kWideNnGrow : wide_nn_grow(D);
+          m_nn[qt] = wide_nn_start(X.merge[jq[qt]], sc.s2, band, grow);
+          m_hd[qt] = wide_nn_start(X.merge[(size_t)(SM == kAgainst ? n_q : X.n_rows) + jq[qt]], sc.s2, band, grow);
         }
       }
     }

@@ -4,7 +4,7 @@
 //     box_gap2(query box, reference box)  <  far2 = 1.0001f x (the largest fl32(r^2) of the launch),
 // the rule of pop_pruned_kernel.  A pair of frames is at least as far apart as the boxes of its blocks, so a block that
 // does not survive holds no pair inside any radius of the launch -- with the roundings of the gap and of the canonical
-// sum of up to 256 columns inside the margin (the proof: DESIGN §4.22).
+// sum of up to 256 columns inside the margin (the proof: DESIGN §4.22; up to 1024 columns: §4.33).
 // Plain C++ that compiles for the device (wide_sweep_kernel's pruned form) and for the host
 // (tests/cpp/test_wide_prune.cpp holds the rule to long-double arithmetic).
 #pragma once
@@ -30,8 +30,19 @@ DC_PRUNE_FN float wide_box_gap2(const WideBox& a, const WideBox& b) {
   return dx * dx + dy * dy;
 }
 
-// r2max: the largest fl32(r^2) of the launch (a number >= 0 or +inf; a NaN radius came in as 0)
-DC_PRUNE_FN float wide_prune_far2(float r2max) { return 1.0001f * r2max; }
+// The smallest bound the steps of the proofs are argued for.  A product that underflows -- a square of the
+// gap, a square of the canonical sum -- loses up to 2^-149 absolutely, (D + 2) 2^-149 in all; against a bound X the chain
+// of the proof then ends at X (1.0001 (1 - u) (1 + u)^-4 (1 - u)^(D+2) - (D + 2) 2^-149 / X), which is above X only for
+// X > 0.37 FLT_MIN at 256 columns and X > 3.2 FLT_MIN at 1024.  Up to 256 columns the rules keep the constants they were
+// written with (no floor for a radius, FLT_MIN for a neighbour bound); beyond, both take 16 FLT_MIN = 2^-122, where the
+// chain ends at 1.00003 X at 1024 columns (tests/cpp/test_xwide_prune.cpp evaluates it in long doubles).
+constexpr float kWidePruneFloorXWide = 1.8807909613156436e-37f;   // 2^-122, exact
+DC_PRUNE_FN float wide_pop_floor(unsigned n_cols) { return n_cols <= 256u ? 0.0f : kWidePruneFloorXWide; }
+DC_PRUNE_FN float wide_nn_floor(unsigned n_cols) { return n_cols <= 256u ? 1.17549435e-38f : kWidePruneFloorXWide; }
+
+// r2max: the largest fl32(r^2) of the launch (a number >= 0 or +inf; a NaN radius came in as 0).  floor: wide_pop_floor
+// of the width -- a positive radius below it prunes as the floor does (r2max = 0 keeps nothing at any floor)
+DC_PRUNE_FN float wide_prune_far2(float r2max, float floor = 0.0f) { return 1.0001f * (r2max > 0.0f ? fmaxf(r2max, floor) : r2max); }
 
 // r2 = 0 keeps nothing (no pair has d2 < 0), r2 = +inf every block with a live row
 DC_PRUNE_FN bool wide_prune_survives(const WideBox& query, const WideBox& ref, float far2) {
@@ -72,8 +83,9 @@ DC_PRUNE_FN bool wide_cross_is_seed(unsigned seed_of_query_block, unsigned ref_b
 
 // B: the largest exact d2 among the block's live rows so far (+inf: a row has none).  1.0001 as wide_prune_far2; below
 // the smallest normal float the relative bounds of the proof do not hold, so the bound never falls below it (B = 0, a
-// block of duplicates, keeps the blocks at gap 0: a duplicate of a lower row may sit in any of them)
-DC_PRUNE_FN float wide_nn_far2(float B) { return 1.0001f * fmaxf(B, 1.17549435e-38f); }
+// block of duplicates, keeps the blocks at gap 0: a duplicate of a lower row may sit in any of them).  floor:
+// wide_nn_floor of the width; the default is the rule of 65..256 columns
+DC_PRUNE_FN float wide_nn_far2(float B, float floor = 1.17549435e-38f) { return 1.0001f * fmaxf(B, floor); }
 
 DC_PRUNE_FN int wide_nn_ring(bool seed, float gap2, float far2_nn, float far2_hd, float fe_min_ref, float fe_max_query) {
   if (seed) return kWideRingSeed;

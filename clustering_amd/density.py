@@ -51,6 +51,8 @@ _SIZES = {
     # ... and the unpruned self and cross sweeps for rows of 257..1024 columns (a layout of their own)
     "xwide": capi.lib.dc_hip_xwide_workspace_bytes,
     "xwide_against": capi.lib.dc_hip_cross_xwide_workspace_bytes,
+    # ... and their pruned self sweeps
+    "xwide_pruned": capi.lib.dc_hip_xwide_pruned_workspace_bytes,
 }
 
 
@@ -276,6 +278,40 @@ def xwide_sweep_info(device):
     return _wide_info("xwide", device)
 
 
+# ---- ... and their pruned self sweeps (include/dc_density.h, the PRUNED sweeps at 257..1024 columns) -----------------
+def calculate_populations_xwide_pruned(coords, radii, segment=0, n_segments=0, out=None):
+    """calculate_populations_wide_pruned for rows of 257..1024 columns (dc_hip_populations_xwide_pruned_dev): the
+    populations of calculate_populations_xwide and of variant="direct" bit for bit, without the block pairs that cannot
+    hold a pair within the radii.  Segments as calculate_populations_wide_pruned takes them.  In a cached workspace of its
+    own kind (xwide_pruned_info reads its counters, xwide_pruned_order its order).  Other column counts raise."""
+    n_rows, n_cols = _check_coords(coords)
+    out = _populations("dc_hip_populations_xwide_pruned_dev", "xwide_pruned", coords.device, (_dev(coords), n_rows, n_cols),
+                       (n_rows, n_cols), radii, (segment, n_segments), out)
+    _shapes["xwide_pruned"][str(coords.device)] = (n_rows, n_cols)
+    return out
+
+
+def nearest_neighbors_xwide_pruned(coords, fe, segment=0, n_segments=0):
+    """nearest_neighbors_wide_pruned for rows of 257..1024 columns (dc_hip_nearest_neighbors_xwide_pruned_dev): the four
+    arrays of nearest_neighbors_xwide bit for bit.  In the cached workspace of calculate_populations_xwide_pruned."""
+    out = _neighbors("dc_hip_nearest_neighbors_xwide_pruned_dev", "xwide_pruned", coords, fe, (segment, n_segments))
+    _shapes["xwide_pruned"][str(coords.device)] = tuple(coords.shape)
+    return out
+
+
+def xwide_pruned_info(device):
+    """(tiles, mfmas, exact_pairs) of the last pruned sweep of 257..1024 columns on this device, as wide_pruned_info gives
+    them: the EVALUATED tile pairs; (0, 0, 0) when the direct kernel answered (flagged data), the segment held no block, or
+    no such sweep has run."""
+    return _wide_info("xwide_pruned", device)
+
+
+def xwide_pruned_order(device):
+    """the spatial order of the last pruned sweep of 257..1024 columns on this device: int32 [n_rows], position -> row
+    (dc_hip_xwide_pruned_order_dev)."""
+    return _pruned_order("xwide_pruned", "dc_hip_xwide_pruned_order_dev", device)
+
+
 # ---- ... the pruned self population sweep (include/dc_density.h, the PRUNED wide sweep) ------------------------------
 def calculate_populations_wide_pruned(coords, radii, segment=0, n_segments=0, out=None):
     """calculate_populations_wide without the block pairs that cannot hold a pair within the radii
@@ -310,13 +346,17 @@ def wide_pruned_info(device):
 def wide_pruned_order(device):
     """the spatial order of the last calculate_populations_wide_pruned on this device: int32 [n_rows], position -> row
     (block b of the order: positions 128 b .. 128 b + 127) (dc_hip_wide_pruned_order_dev)."""
-    ws, shape = _cached("wide_pruned", device), _shapes["wide_pruned"].get(str(device))
+    return _pruned_order("wide_pruned", "dc_hip_wide_pruned_order_dev", device)
+
+
+def _pruned_order(kind, fn, device):
+    """the order reader of a pruned self kind: the library's ``fn`` for the shape of the last call in that workspace"""
+    ws, shape = _cached(kind, device), _shapes[kind].get(str(device))
     if ws.buf is None or shape is None:
         raise ValueError("no pruned wide sweep has run on this device")
     perm = torch.empty(shape[0], dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        capi.check(capi.lib.dc_hip_wide_pruned_order_dev(_dev(ws.buf), shape[0], shape[1], _dev(perm), _stream_ptr()),
-                   "dc_hip_wide_pruned_order_dev")
+        capi.check(getattr(capi.lib, fn)(_dev(ws.buf), shape[0], shape[1], _dev(perm), _stream_ptr()), fn)
     return perm
 
 

@@ -594,8 +594,8 @@ DC_API int dc_hip_nearest_neighbors_cross_wide_dev(const float* d_query, size_t 
  * header, the operand images from byte 13 312 on; about 6 KB per row and image at 1024 columns), so a workspace of one
  * family never serves the other: dc_hip_xwide_workspace_bytes / dc_hip_cross_xwide_workspace_bytes are 0 outside
  * 257..1024 columns, for no rows and for an empty side, and monotone in the row counts.  The info head is that of the
- * wide sweeps: dc_hip_wide_info_dev reads the counters of the last call.  No pruned form, no session and no resident
- * reference exists at these widths; no dc_variant value selects them. */
+ * wide sweeps: dc_hip_wide_info_dev reads the counters of the last call.  The pruned self sweeps follow below; no pruned
+ * cross form, no session and no resident reference exists at these widths; no dc_variant value selects them. */
 DC_API size_t dc_hip_xwide_workspace_bytes(size_t n_rows, size_t n_cols, size_t n_radii);
 DC_API int dc_hip_populations_xwide_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* radii,
                                         size_t n_radii, size_t i_from, size_t i_to, uint32_t* d_pops, void* d_ws,
@@ -613,6 +613,29 @@ DC_API int dc_hip_nearest_neighbors_cross_xwide_dev(const float* d_query, size_t
                                                     const float* d_fe_ref, size_t i_from, size_t i_to,
                                                     uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                                                     float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
+/* ---- ... and the PRUNED self population and neighbour sweeps at 257..1024 columns ------------------------------------------
+ * dc_hip_populations_wide_pruned_dev and dc_hip_nearest_neighbors_wide_pruned_dev at 257..1024 columns: the spatial order
+ * on columns 0 / 1, the block boxes, the segments (every n_segments-th query block of the order; n_segments == 0: the
+ * whole sweep, `segment` is not read) and the three launches of the neighbour sweep are theirs, the pruning rules take
+ * the floors of these widths.  Results are bit-identical to dc_hip_populations_xwide_dev /
+ * dc_hip_nearest_neighbors_xwide_dev and to DC_VARIANT_DIRECT.  Each entry point takes the argument list of its
+ * _wide_pruned_ namesake and refuses in the same order, before a device is touched, naming itself; n_cols outside
+ * 257..1024: DC_ERR_INVALID_ARGUMENT; a workspace smaller than dc_hip_xwide_pruned_workspace_bytes (or none):
+ * DC_ERR_WORKSPACE.  dc_hip_xwide_pruned_workspace_bytes: 0 outside 257..1024 columns and for no rows, monotone in
+ * n_rows, never below dc_hip_xwide_workspace_bytes (the head is that layout); dc_hip_wide_pruned_workspace_bytes stays 0
+ * at these widths and the _wide_pruned_ entry points refuse them.  Flagged data and NaN free energies: the gated direct
+ * kernel answers (beyond 400 columns the column-chunked one), a segment call the row block of
+ * dc_hip_populations_segment_dev / dc_hip_nearest_neighbors_segment_dev, no host synchronisation.  dc_hip_wide_info_dev
+ * reads the counters of the last call (EVALUATED tile pairs), dc_hip_xwide_pruned_order_dev its order. */
+DC_API size_t dc_hip_xwide_pruned_workspace_bytes(size_t n_rows, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_populations_xwide_pruned_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* radii,
+                                               size_t n_radii, size_t segment, size_t n_segments, uint32_t* d_pops,
+                                               void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_nearest_neighbors_xwide_pruned_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* d_fe,
+                                                     size_t segment, size_t n_segments, uint32_t* d_nn_idx, float* d_nn_d2,
+                                                     uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
+                                                     void* stream);
+DC_API int dc_hip_xwide_pruned_order_dev(const void* d_ws, size_t n_rows, size_t n_cols, uint32_t* d_perm, void* stream);
 /* ---- ... the PRUNED wide cross population sweep (65..256 columns) ----------------------------------------------------------
  * dc_hip_populations_cross_wide_dev's populations bit for bit, without the block pairs that cannot hold a pair within
  * the call's radii.  Statistics, origin and scale are those of the cross form.  ONE cell grid on columns 0 / 1 covers the
