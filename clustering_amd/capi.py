@@ -57,6 +57,8 @@ SYMBOLS = (
     "dc_hip_xwide_pruned_order_dev",
     "dc_hip_cross_wide_pruned_workspace_bytes", "dc_hip_populations_cross_wide_pruned_dev", "dc_hip_cross_wide_pruned_order_dev",
     "dc_hip_nearest_neighbors_cross_wide_pruned_dev",
+    "dc_hip_cross_xwide_pruned_workspace_bytes", "dc_hip_populations_cross_xwide_pruned_dev", "dc_hip_cross_xwide_pruned_order_dev",
+    "dc_hip_nearest_neighbors_cross_xwide_pruned_dev",
     "dc_hip_neighbors_block_rows_wide", "dc_hip_neighbors_block_pack_wide_dev", "dc_hip_neighbors_block_unpack_wide_dev",
     "dc_hip_wide_layout_status_dev", "dc_hip_session_open_flags", "dc_hip_session_wide",
     "dc_hip_reference_wide_workspace_bytes", "dc_hip_reference_wide_open_dev", "dc_hip_reference_wide_close",
@@ -258,6 +260,12 @@ def _load():
     lib.dc_hip_cross_wide_pruned_order_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp]
     lib.dc_hip_nearest_neighbors_cross_wide_pruned_dev.restype = i32
     lib.dc_hip_nearest_neighbors_cross_wide_pruned_dev.argtypes = lib.dc_hip_nearest_neighbors_cross_wide_dev.argtypes
+    for xwide, wide in (("dc_hip_cross_xwide_pruned_workspace_bytes", "dc_hip_cross_wide_pruned_workspace_bytes"),
+                        ("dc_hip_populations_cross_xwide_pruned_dev", "dc_hip_populations_cross_wide_pruned_dev"),
+                        ("dc_hip_nearest_neighbors_cross_xwide_pruned_dev", "dc_hip_nearest_neighbors_cross_wide_pruned_dev"),
+                        ("dc_hip_cross_xwide_pruned_order_dev", "dc_hip_cross_wide_pruned_order_dev")):
+        getattr(lib, xwide).restype = getattr(lib, wide).restype     # (257..1024 columns: the lists of their namesakes)
+        getattr(lib, xwide).argtypes = getattr(lib, wide).argtypes
     lib.dc_hip_neighbors_block_rows_wide.restype = sz
     lib.dc_hip_neighbors_block_rows_wide.argtypes = [sz, sz, sz]
     lib.dc_hip_neighbors_block_pack_wide_dev.restype = i32

@@ -1,7 +1,7 @@
 // dc_mfma_wide.hip -- host side of the matrix-core sweeps for rows of 65..256 columns: workspace, preparation and
 // launches (kernels: dc_mfma_wide_kernels.hpp).  The unpruned self and cross sweeps also serve 257..1024 columns, in the
 // layout of those widths (dc_hip_*_xwide_dev), and so do the pruned self population and neighbour sweeps
-// (dc_hip_*_xwide_pruned_dev).
+// (dc_hip_*_xwide_pruned_dev) and the pruned cross ones (dc_hip_*_cross_xwide_pruned_dev).
 #include "dc_mfma_wide_kernels.hpp"
 
 namespace dc {
@@ -261,7 +261,7 @@ int wide_pruned_args(const WidePrunedLayout& P, uint32_t n_rows, uint32_t n_cols
   X.boxes = (const float4*)(p + P.off_boxes);
   X.seg = (uint32_t)segment;
   X.n_seg = segments_u32(n_segments);
-  X.far2 = wide_prune_far2(largest_radius2(rad2, n_rad), wide_pop_floor(n_cols));
+  X.far2 = wide_prune_far2_at(largest_radius2(rad2, n_rad), n_cols);
   X.perm = (const uint32_t*)(p + P.off_perm);
   const uint32_t q_blocks = (uint32_t)((P.blocks - segment + n_segments - 1) / n_segments);
   *grid = dim3(wide_grid_size(q_blocks, wide_shares(P.blocks)));
@@ -626,6 +626,14 @@ size_t wide_cross_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_
   return wide_cross_pruned_layout(n_query, n_ref, n_cols).total;
 }
 
+// 257..1024 columns: the same regions behind the head of those widths.  wide_cross_pruned_prepare,
+// launch_pop_wide_cross_pruned, launch_nn_wide_cross_pruned and wide_cross_pruned_order read the layout of the width they
+// are given
+size_t xwide_cross_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols) {
+  if (!xwide_mfma_supports(n_cols) || n_query == 0 || n_ref == 0) return 0;
+  return wide_cross_pruned_layout(n_query, n_ref, n_cols).total;
+}
+
 int wide_cross_pruned_prepare(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
                               uint32_t i_from, uint32_t i_to, void* d_ws, hipStream_t s) {
   const WideCrossPrunedLayout P = wide_cross_pruned_layout(n_query, n_ref, n_cols);
@@ -682,7 +690,7 @@ int pop_wide_cross_pruned(const WideCrossPrunedLayout& P, uint32_t n_query, uint
   X.qboxes = (const float4*)(p + P.off_boxes_q);
   X.seg = 0;
   X.n_seg = 1;
-  X.far2 = wide_prune_far2(largest_radius2(rad2, n_rad));
+  X.far2 = wide_prune_far2_at(largest_radius2(rad2, n_rad), n_cols);   // (up to 256 columns: no floor)
   launch_pop_instance<kAgainst, true>(X, n_rad, dim3(wide_grid_size((n_q + kWideBlockRows - 1u) / kWideBlockRows, wide_shares(P.blocks_r))),
                                       s);
   hipLaunchKernelGGL(wide_prune_scatter_kernel, dim3((n_q + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)p,

@@ -143,6 +143,11 @@ int launch_nn_wide_against(const float* d_query, uint32_t n_query, const float* 
 // sets of boxes, the counts and the sort's scratch; 0 if the column count is not served or either set is empty; monotone
 // in either row count
 size_t wide_cross_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols);
+// ... and of the pruned cross population and neighbour sweeps at 257..1024 columns (dc_hip_*_cross_xwide_pruned_dev,
+// DESIGN.md 4.34): the same regions behind the head of those widths; 0 outside them.  wide_cross_pruned_prepare,
+// launch_pop_wide_cross_pruned, launch_nn_wide_cross_pruned and wide_cross_pruned_order serve both families and read the
+// layout of the width they are given; the pruning rules take the floors of the width (dc_wide_prune.hpp)
+size_t xwide_cross_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols);
 // on the stream, no host synchronisation; i_from < i_to <= n_query, n_ref > 0; returns 0 on success
 int wide_cross_pruned_prepare(const float* d_query, uint32_t n_query, const float* d_ref, uint32_t n_ref, uint32_t n_cols,
                               uint32_t i_from, uint32_t i_to, void* d_ws, hipStream_t stream);

@@ -61,6 +61,8 @@
 // The pruned cross neighbour sweep (dc_hip_nearest_neighbors_cross_wide_pruned_dev) joins the two: the
 // three launches of 4.24 on the two orders of 4.25, the seed of a query block being the one reference block whose box
 // centre is nearest to its own (wide_cross_seed_kernel).
+// Both pruned cross sweeps also serve rows of 257..1024 columns (dc_hip_*_cross_xwide_pruned_dev), as the
+// pruned self sweeps do: the same instances, the factor and the floors of the width.
 #pragma once
 #include "dc_mfma_kernels.hpp"
 #include "dc_mfma_wide.hpp"
@@ -202,13 +204,13 @@ __host__ __device__ inline float wide_cut_ratio(const WideBand& b) {
 
 // The pruned neighbour sweep: the running minimum a lane starts a later launch with, from the merged word
 // of the launches before (~0: nothing found -> +inf).  The word holds the canonical float sum d2_c of the row it names;
-// that row's real d2 <= d2_c / (1 - u)^(D+1) <= d2_c (1 + 1.6e-5) at D <= 256, and its accumulator is at most
+// that row's real d2 <= d2_c / (1 - u)^(D+2) <= d2_c (1 + 1.6e-5) at D <= 256, and its accumulator is at most
 // S d2 (1 + kappa) + e0 by the band: m0 is that, rounded up.  Every reference whose canonical sum is <= d2_c has an
 // accumulator <= m0 <= cut(m0) as well, so all that could beat or tie the word are still raised.
-// grow: the factor for (1 - u)^-(D+1).  1 + 2.0e-5 holds at D <= 256 only; at 1024 columns the term is 6.1e-5, and the
-// pruned self instance, which serves 257..1024 columns too, takes 1 + 7.0e-5 there (wide_nn_grow).
-constexpr float kWideNnGrow = 1.0f + 2.0e-5f, kXWideNnGrow = 1.0f + 7.0e-5f;
-__device__ __forceinline__ float wide_nn_grow(uint32_t D) { return D <= (uint32_t)kWideMaxCols ? kWideNnGrow : kXWideNnGrow; }
+// grow: the factor for (1 - u)^-(D+2).  1 + 2.0e-5 holds at D <= 256 only; at 1024 columns the term is 6.1e-5, and the
+// pruned self and cross instances, which serve 257..1024 columns too, take 1 + 7.0e-5 there
+// (wide_nn_grow; the constants and the select stand in dc_wide_prune.hpp, where the host tests reach them).
+static_assert(kWideMaxCols == 256, "wide_nn_grow, wide_pop_floor and wide_nn_floor change at this width");
 __device__ __forceinline__ float wide_nn_start(unsigned long long word, float S, const WideBand& b, float grow = kWideNnGrow) {
   if (word == ~0ull) return INFINITY;
   const float d2c = __uint_as_float((uint32_t)(word >> 32));
@@ -1120,9 +1122,10 @@ __global__ __launch_bounds__(256, 2) void wide_sweep_kernel(WideKernelArgs<PR, M
       feq[qt] = (live[qt] && has_fe) ? q_fe[jq[qt]] : -INFINITY;   // (a dead lane, nn only: no reference lies lower)
       if constexpr (PR) {
         // rings 1 and 2 start from the words of the launches before: a bound on the accumulator of the row a word names
-        // (the cross instance stops at kWideMaxCols and keeps its constant: it has no register to spare, see kFresh)
+        // (the factor of the width, in the self and in the cross instance: a wave-uniform select on D, no register of a
+        //  lane's -- the cross instance has none to spare, see kFresh)
         if (X.ring != kWideRingSeed && live[qt]) {
-          const float grow = (SM == kAgainst) ? kWideNnGrow : wide_nn_grow(D);
+          const float grow = wide_nn_grow(D);
           m_nn[qt] = wide_nn_start(X.merge[jq[qt]], sc.s2, band, grow);
           m_hd[qt] = wide_nn_start(X.merge[(size_t)(SM == kAgainst ? n_q : X.n_rows) + jq[qt]], sc.s2, band, grow);
         }

@@ -43,6 +43,15 @@ DC_PRUNE_FN float wide_nn_floor(unsigned n_cols) { return n_cols <= 256u ? 1.175
 // r2max: the largest fl32(r^2) of the launch (a number >= 0 or +inf; a NaN radius came in as 0).  floor: wide_pop_floor
 // of the width -- a positive radius below it prunes as the floor does (r2max = 0 keeps nothing at any floor)
 DC_PRUNE_FN float wide_prune_far2(float r2max, float floor = 0.0f) { return 1.0001f * (r2max > 0.0f ? fmaxf(r2max, floor) : r2max); }
+// ... as every launcher of a pruned population sweep forms it, self and cross: under the floor of the launch's width
+DC_PRUNE_FN float wide_prune_far2_at(float r2max, unsigned n_cols) { return wide_prune_far2(r2max, wide_pop_floor(n_cols)); }
+
+// The factor of wide_nn_start (dc_mfma_wide_kernels.hpp) for (1 - u)^-(D+2), u = 2^-24: the real d2 of a row is at most its
+// canonical float sum times this, in whatever order the sum is formed.  1 + 2.0e-5 holds up to 256 columns
+// (the term is 1.54e-5 there); at 512 columns the term is 3.06e-5, at 1024 6.12e-5, and both pruned neighbour instances,
+// self and cross, take 1 + 7.0e-5 beyond 256 columns (tests/cpp/test_xwide_cross_prune.cpp holds the premise to long doubles).
+constexpr float kWideNnGrow = 1.0f + 2.0e-5f, kXWideNnGrow = 1.0f + 7.0e-5f;
+DC_PRUNE_FN float wide_nn_grow(unsigned n_cols) { return n_cols <= 256u ? kWideNnGrow : kXWideNnGrow; }
 
 // r2 = 0 keeps nothing (no pair has d2 < 0), r2 = +inf every block with a live row
 DC_PRUNE_FN bool wide_prune_survives(const WideBox& query, const WideBox& ref, float far2) {

@@ -53,6 +53,8 @@ _SIZES = {
     "xwide_against": capi.lib.dc_hip_cross_xwide_workspace_bytes,
     # ... and their pruned self sweeps
     "xwide_pruned": capi.lib.dc_hip_xwide_pruned_workspace_bytes,
+    # ... and their pruned cross sweeps
+    "xwide_against_pruned": capi.lib.dc_hip_cross_xwide_pruned_workspace_bytes,
 }
 
 
@@ -573,10 +575,10 @@ def assign_frames_xwide(queries, reference, radius, ref_states):
 
 
 # ---- ... the pruned cross population sweep (include/dc_density.h, the PRUNED wide cross sweep) -----------------------
-def _record_against_pruned(queries, sizes, i_from, i_to):
+def _record_against_pruned(queries, sizes, i_from, i_to, kind="wide_against_pruned"):
     """(rows of the query range, n_ref, n_cols) of a pruned wide cross call that passed: what its order reader asks for"""
     n_q, n_ref, n_cols = sizes
-    _shapes["wide_against_pruned"][str(queries.device)] = (max((n_q if i_to is None else i_to) - i_from, 0), n_ref, n_cols)
+    _shapes[kind][str(queries.device)] = (max((n_q if i_to is None else i_to) - i_from, 0), n_ref, n_cols)
 
 
 def calculate_populations_against_wide_pruned(queries, reference, radii, i_from=0, i_to=None, out=None):
@@ -617,15 +619,18 @@ def wide_against_pruned_order(device):
     device, position -> row:
     (perm_q int32 [i_to - i_from], rows of the queries; perm_r int32 [n_ref]); block b of either order is its
     positions 128 b .. 128 b + 127 (dc_hip_cross_wide_pruned_order_dev)."""
-    ws, shape = _cached("wide_against_pruned", device), _shapes["wide_against_pruned"].get(str(device))
+    return _against_pruned_order("wide_against_pruned", "dc_hip_cross_wide_pruned_order_dev", device)
+
+
+def _against_pruned_order(kind, fn, device):
+    """the order reader of a pruned cross kind: the library's ``fn`` for the shape of the last call in that workspace"""
+    ws, shape = _cached(kind, device), _shapes[kind].get(str(device))
     if ws.buf is None or shape is None:
         raise ValueError("no pruned wide cross sweep has run on this device")
     perm_q = torch.empty(shape[0], dtype=torch.int32, device=device)
     perm_r = torch.empty(shape[1], dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        capi.check(capi.lib.dc_hip_cross_wide_pruned_order_dev(_dev(ws.buf), shape[0], shape[1], shape[2], _dev(perm_q),
-                                                               _dev(perm_r), _stream_ptr()),
-                   "dc_hip_cross_wide_pruned_order_dev")
+        capi.check(getattr(capi.lib, fn)(_dev(ws.buf), shape[0], shape[1], shape[2], _dev(perm_q), _dev(perm_r), _stream_ptr()), fn)
     return perm_q, perm_r
 
 
@@ -645,6 +650,53 @@ def assign_frames_wide_pruned(queries, reference, radius, ref_states, pruned_nei
     return _assign_frames(queries, reference, radius, ref_states, _check_pair_wide(queries, reference), calculate_populations_wide,
                           calculate_populations_against_wide_pruned,
                           nearest_reference_wide_pruned if pruned_neighbours else nearest_reference_wide)
+
+
+# ---- ... and both pruned cross sweeps for rows of 257..1024 columns (include/dc_density.h) -----------
+def calculate_populations_against_xwide_pruned(queries, reference, radii, i_from=0, i_to=None, out=None):
+    """calculate_populations_against_wide_pruned for rows of 257..1024 columns
+    (dc_hip_populations_cross_xwide_pruned_dev): the populations of calculate_populations_against_xwide and of
+    variant="direct" bit for bit, without the block pairs that cannot hold a pair within the radii.  In a cached workspace
+    of its own kind (xwide_against_pruned_info reads its counters, xwide_against_pruned_order its two orders).  Other
+    column counts raise."""
+    sizes = _check_pair_xwide(queries, reference)
+    out = _populations_against("dc_hip_populations_cross_xwide_pruned_dev", "xwide_against_pruned", queries, reference, sizes,
+                               radii, i_from, i_to, out)
+    _record_against_pruned(queries, sizes, i_from, i_to, "xwide_against_pruned")
+    return out
+
+
+def nearest_reference_xwide_pruned(queries, reference, fe_query=None, fe_ref=None, i_from=0, i_to=None):
+    """nearest_reference_wide_pruned for rows of 257..1024 columns (dc_hip_nearest_neighbors_cross_xwide_pruned_dev): the
+    four arrays of nearest_reference_xwide bit for bit; without free energies hd_idx / hd_d2 are None.  In the cached
+    workspace of calculate_populations_against_xwide_pruned."""
+    sizes = _check_pair_xwide(queries, reference)
+    out = _nearest("dc_hip_nearest_neighbors_cross_xwide_pruned_dev", "xwide_against_pruned", queries, reference, sizes, fe_query,
+                   fe_ref, i_from, i_to)
+    _record_against_pruned(queries, sizes, i_from, i_to, "xwide_against_pruned")
+    return out
+
+
+def xwide_against_pruned_info(device):
+    """(tiles, mfmas, exact_pairs) of the last pruned cross sweep of 257..1024 columns on this device, as
+    wide_against_pruned_info gives them: the EVALUATED tile pairs (the neighbour call: summed over its launches);
+    (0, 0, 0) when the direct kernel answered (flagged data), nothing was swept, or no such sweep has run."""
+    return _wide_info("xwide_against_pruned", device)
+
+
+def xwide_against_pruned_order(device):
+    """both spatial orders of the last pruned cross sweep of 257..1024 columns on this device, position -> row, as
+    wide_against_pruned_order gives them (dc_hip_cross_xwide_pruned_order_dev)."""
+    return _against_pruned_order("xwide_against_pruned", "dc_hip_cross_xwide_pruned_order_dev", device)
+
+
+def assign_frames_xwide_pruned(queries, reference, radius, ref_states, pruned_neighbours=False):
+    """assign_frames_xwide on the pruned sweeps: the reference's own populations through
+    calculate_populations_xwide_pruned, the queries' through calculate_populations_against_xwide_pruned; the same dict,
+    the same values.  pruned_neighbours=True: the nearest reference frames through nearest_reference_xwide_pruned as well."""
+    return _assign_frames(queries, reference, radius, ref_states, _check_pair_xwide(queries, reference),
+                          calculate_populations_xwide_pruned, calculate_populations_against_xwide_pruned,
+                          nearest_reference_xwide_pruned if pruned_neighbours else nearest_reference_xwide)
 
 
 class Reference:

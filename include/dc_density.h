@@ -594,8 +594,9 @@ DC_API int dc_hip_nearest_neighbors_cross_wide_dev(const float* d_query, size_t 
  * header, the operand images from byte 13 312 on; about 6 KB per row and image at 1024 columns), so a workspace of one
  * family never serves the other: dc_hip_xwide_workspace_bytes / dc_hip_cross_xwide_workspace_bytes are 0 outside
  * 257..1024 columns, for no rows and for an empty side, and monotone in the row counts.  The info head is that of the
- * wide sweeps: dc_hip_wide_info_dev reads the counters of the last call.  The pruned self sweeps follow below; no pruned
- * cross form, no session and no resident reference exists at these widths; no dc_variant value selects them. */
+ * wide sweeps: dc_hip_wide_info_dev reads the counters of the last call.  The pruned self sweeps follow below, the
+ * pruned cross sweeps behind those of 65..256 columns; no session and no resident reference exists at these widths; no
+ * dc_variant value selects them. */
 DC_API size_t dc_hip_xwide_workspace_bytes(size_t n_rows, size_t n_cols, size_t n_radii);
 DC_API int dc_hip_populations_xwide_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* radii,
                                         size_t n_radii, size_t i_from, size_t i_to, uint32_t* d_pops, void* d_ws,
@@ -690,6 +691,35 @@ DC_API int dc_hip_nearest_neighbors_cross_wide_pruned_dev(const float* d_query, 
                                                           const float* d_fe_ref, size_t i_from, size_t i_to,
                                                           uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
                                                           float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
+/* ---- ... and both PRUNED wide cross sweeps at 257..1024 columns ------------------------------------------------------------
+ * dc_hip_populations_cross_wide_pruned_dev and dc_hip_nearest_neighbors_cross_wide_pruned_dev at 257..1024 columns: the
+ * one cell grid on columns 0 / 1, the two orders, the block boxes, the seed block and the three launches of the neighbour
+ * sweep are theirs; the pruning rules take the floors of these widths (a positive radius below 2^-61 prunes as 2^-61
+ * does) and the later launches of the neighbour sweep start from bounds formed with the factor of these widths.  Results
+ * are bit-identical to dc_hip_populations_cross_xwide_dev / dc_hip_nearest_neighbors_cross_xwide_dev and to
+ * DC_VARIANT_DIRECT.  Each entry point takes the argument list of its _cross_wide_pruned_ namesake and refuses in the same
+ * order, before a device is touched, naming itself; n_cols outside 257..1024: DC_ERR_INVALID_ARGUMENT; a workspace
+ * smaller than dc_hip_cross_xwide_pruned_workspace_bytes (or none): DC_ERR_WORKSPACE.
+ * dc_hip_cross_xwide_pruned_workspace_bytes: 0 outside 257..1024 columns and for an empty side, monotone in either row
+ * count, never below dc_hip_cross_xwide_workspace_bytes (the head is that layout); a workspace of one family never serves
+ * the other: dc_hip_cross_wide_pruned_workspace_bytes stays 0 at these widths and the _cross_wide_pruned_ entry points
+ * refuse them.  Flagged data -- a non-finite or overflow-prone row in Q or in R, a NaN free energy -- is answered by the
+ * gated direct kernel (beyond 400 columns the column-chunked one), no host synchronisation; the counters then read
+ * (0, 0, 0).  dc_hip_wide_info_dev reads the counters of the last call (EVALUATED tile pairs),
+ * dc_hip_cross_xwide_pruned_order_dev its two orders (a self order or an order of the 65..256 family is refused).  No
+ * resident reference, assigner path or CLI mode runs them; no dc_variant value selects them. */
+DC_API size_t dc_hip_cross_xwide_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_populations_cross_xwide_pruned_dev(const float* d_query, size_t n_query, const float* d_ref, size_t n_ref,
+                                                     size_t n_cols, const float* radii, size_t n_radii, size_t i_from,
+                                                     size_t i_to, uint32_t* d_pops, void* d_ws, size_t ws_bytes,
+                                                     void* stream);
+DC_API int dc_hip_nearest_neighbors_cross_xwide_pruned_dev(const float* d_query, size_t n_query, const float* d_ref,
+                                                           size_t n_ref, size_t n_cols, const float* d_fe_query,
+                                                           const float* d_fe_ref, size_t i_from, size_t i_to,
+                                                           uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
+                                                           float* d_hd_d2, void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_cross_xwide_pruned_order_dev(const void* d_ws, size_t n_query_range, size_t n_ref, size_t n_cols,
+                                               uint32_t* d_perm_q, uint32_t* d_perm_r, void* stream);
 
 /* ---- ... and a RESIDENT REFERENCE for the two (65..256 columns) -------------------------------------------------------------
  * The two pruned wide cross sweeps for a caller who streams batches of queries against ONE reference: the reference is
