@@ -70,8 +70,13 @@ SYMBOLS = (
     "dc_hip_assign_workspace_bytes", "dc_hip_assign_open_dev", "dc_hip_assign_open_wide_dev", "dc_hip_assign_close",
     "dc_hip_assign_batch_dev",
     "dc_hip_assigner_open", "dc_hip_assigner_reference", "dc_hip_assigner_path", "dc_hip_assigner_assign", "dc_hip_assigner_close",
+    "dc_hip_reference_xwide_workspace_bytes", "dc_hip_reference_xwide_open_dev", "dc_hip_reference_xwide_close",
+    "dc_hip_reference_xwide_set_free_energies_dev", "dc_hip_reference_xwide_stage_dev", "dc_hip_reference_xwide_populations_dev",
+    "dc_hip_reference_xwide_nearest_dev", "dc_hip_reference_xwide_info_dev", "dc_hip_reference_xwide_order_dev",
+    "dc_hip_assign_open_xwide_dev", "dc_hip_assigner_open_flags",
 )
 SESSION_WIDE_SWEEPS = 0x1     # DC_SESSION_WIDE_SWEEPS (dc_hip_session_open_flags)
+ASSIGNER_XWIDE_REFERENCE = 0x1   # DC_ASSIGNER_XWIDE_REFERENCE (dc_hip_assigner_open_flags)
 
 
 class DensityLibraryError(RuntimeError):
@@ -278,9 +283,10 @@ def _load():
     lib.dc_hip_session_open_flags.argtypes = [vp, sz, sz, C.POINTER(C.c_int), i32, C.c_uint, C.POINTER(vp)]
     lib.dc_hip_session_wide.restype = i32
     lib.dc_hip_session_wide.argtypes = [vp]
-    # the two resident reference handles (wide: 65..256 columns, narrow: 1..64): one list per step, and the three that differ
+    # the three resident reference handles (wide: 65..256 columns, xwide: 257..1024, narrow: 1..64): one list per step, and the three that differ
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
     for api, open_extra, third_counter, order_extra in (("dc_hip_reference_wide_", [], u64p, []),
+                                                        ("dc_hip_reference_xwide_", [], u64p, []),   # (257..1024 columns)
                                                         ("dc_hip_reference_", [C.c_float], u32p, [i32])):
         for step, restype, argtypes in (("workspace_bytes", sz, [sz, sz, sz]),
                                         ("open_dev", i32, [vp, sz, sz, sz] + open_extra + [vp, sz, vp, C.POINTER(vp)]),
@@ -299,12 +305,16 @@ def _load():
     lib.dc_hip_assign_open_dev.argtypes = [vp, vp, C.c_uint32, C.c_float, vp, sz, vp, C.POINTER(vp)]
     lib.dc_hip_assign_open_wide_dev.restype = i32
     lib.dc_hip_assign_open_wide_dev.argtypes = lib.dc_hip_assign_open_dev.argtypes
+    lib.dc_hip_assign_open_xwide_dev.restype = i32
+    lib.dc_hip_assign_open_xwide_dev.argtypes = lib.dc_hip_assign_open_dev.argtypes
     lib.dc_hip_assign_close.restype = None
     lib.dc_hip_assign_close.argtypes = [vp]
     lib.dc_hip_assign_batch_dev.restype = i32
     lib.dc_hip_assign_batch_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.dc_hip_assigner_open.restype = i32
     lib.dc_hip_assigner_open.argtypes = [vp, sz, sz, vp, C.c_float, sz, i32, C.POINTER(vp)]
+    lib.dc_hip_assigner_open_flags.restype = i32
+    lib.dc_hip_assigner_open_flags.argtypes = [vp, sz, sz, vp, C.c_float, sz, i32, C.c_uint, C.POINTER(vp)]
     lib.dc_hip_assigner_reference.restype = i32
     lib.dc_hip_assigner_reference.argtypes = [vp, vp, vp, C.POINTER(C.c_uint32)]
     lib.dc_hip_assigner_path.restype = i32

@@ -803,7 +803,7 @@ int assign_main(int argc, char** argv) {
   must(dc_hip_assigner_open(ref.data(), n_ref, n_cols, states_ref.data(), radius, std::min(batch, n_query), 0, &assigner),
        "preparing the reference");
   static const char* const kPaths[] = {"the resident reference of 1..64 columns", "the resident reference of 65..256 columns",
-                                       "the per-call cross sweeps"};
+                                       "the per-call cross sweeps", "the resident reference of 257..1024 columns"};
   std::uint32_t max_pop = 0;
   must(dc_hip_assigner_reference(assigner, nullptr, nullptr, &max_pop), "reading the reference");
   LOG("    served by: %s\n    max_pop of the reference: %u\n", kPaths[dc_hip_assigner_path(assigner)], max_pop);

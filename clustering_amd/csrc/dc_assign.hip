@@ -1,6 +1,6 @@
 // dc_assign.hip -- assigning new frames to a clustered reference (include/dc_density.h "assigner").
 //   dc_hip_assign_*    device level: one batch = stage, populations at the radius, free energies by table, nearest,
-//                      state pick -- five stream-ordered steps on a resident reference handle of either kind (the one
+//                      state pick -- five stream-ordered steps on a resident reference handle of any kind (the one
 //                      struct and the shared bodies of dc_assign.hpp), or on the per-call cross entry points
 //   dc_hip_assigner_*  host level: owns the reference, its self sweep, the handle and two batch slots; uploads and
 //                      downloads on a copy stream beside the sweeps
@@ -55,7 +55,8 @@ __global__ void assign_pick_kernel(const uint32_t* __restrict__ nn_idx, const ui
 
 constexpr uint32_t kThreads = 256;
 
-// a reference no handle takes (rows wider than 256 columns, or beyond the narrow handle's 2^24 positions): the per-call
+// a reference no handle takes (rows wider than 1024 columns, rows of 257..1024 columns unless the open call asked for their
+// resident reference, or a reference beyond the narrow handle's 2^24 positions): the per-call
 // cross entry points under DC_VARIANT_AUTO behind the three steps a batch takes of a handle
 struct CrossRef {
   const float* d_ref = nullptr;
@@ -154,7 +155,7 @@ int assign_open(const char* fn, dc::ReferenceHandle* ref, CrossRef* cross, const
   return DC_OK;
 }
 
-// dc_hip_assign_open[_wide]_dev
+// dc_hip_assign_open[_wide|_xwide]_dev
 int assign_open_on(const char* fn, dc::ReferenceHandle* ref, const int32_t* d_states_ref, uint32_t max_pop, float radius, void* d_ws,
                    size_t ws_bytes, void* stream, dc_assign** out) {
   if (!out) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer (out)", fn);
@@ -180,6 +181,11 @@ int dc_hip_assign_open_dev(dc_reference* ref, const int32_t* d_states_ref, uint3
 int dc_hip_assign_open_wide_dev(dc_reference_wide* ref, const int32_t* d_states_ref, uint32_t max_pop, float radius, void* d_ws,
                                 size_t ws_bytes, void* stream, dc_assign** out) {
   return assign_open_on("dc_hip_assign_open_wide_dev", dc::handle(ref), d_states_ref, max_pop, radius, d_ws, ws_bytes, stream, out);
+}
+
+int dc_hip_assign_open_xwide_dev(dc_reference_xwide* ref, const int32_t* d_states_ref, uint32_t max_pop, float radius, void* d_ws,
+                                 size_t ws_bytes, void* stream, dc_assign** out) {
+  return assign_open_on("dc_hip_assign_open_xwide_dev", dc::handle(ref), d_states_ref, max_pop, radius, d_ws, ws_bytes, stream, out);
 }
 
 void dc_hip_assign_close(dc_assign* a) {
@@ -262,12 +268,13 @@ struct Slot {
 
 struct dc_assigner {
   int device = 0, path = 0;
+  unsigned flags = 0;                              // DC_ASSIGNER_* of the open call
   size_t n_ref = 0, n_cols = 0, max_batch = 0;
   float radius = 0.0f;
   uint32_t max_pop = 0;
   hipStream_t compute = nullptr, copy = nullptr;   // (one stream under DC_ASSIGN_OVERLAP=0)
   std::vector<void*> bufs;                         // device memory, freed at close
-  dc::ReferenceHandle* ref = nullptr;              // the handle of paths 0 (narrow) and 1 (wide)
+  dc::ReferenceHandle* ref = nullptr;              // the handle of paths 0 (narrow), 1 (wide) and 3 (xwide)
   CrossRef cross;
   dc_assign* assign = nullptr;
   std::vector<uint32_t> pops_ref;
@@ -284,8 +291,7 @@ hipError_t dev_alloc(dc_assigner* a, void** p, size_t bytes) {
   return e;
 }
 
-int assigner_build(dc_assigner* a, const float* ref, const int32_t* states_ref) {
-  const char* fn = "dc_hip_assigner_open";
+int assigner_build(dc_assigner* a, const char* fn, const float* ref, const int32_t* states_ref) {
   const size_t n_ref = a->n_ref, n_cols = a->n_cols, max_batch = a->max_batch;
   DC_ASSIGN_TRY(hipSetDevice(a->device));
   DC_ASSIGN_TRY(hipStreamCreate(&a->compute));
@@ -301,16 +307,22 @@ int assigner_build(dc_assigner* a, const float* ref, const int32_t* states_ref) 
   DC_ASSIGN_TRY(dev_alloc(a, &d_fe, sizeof(float) * n_ref));
   DC_ASSIGN_TRY(hipMemcpyAsync(d_ref, ref, sizeof(float) * n_ref * n_cols, hipMemcpyHostToDevice, s));
   DC_ASSIGN_TRY(hipMemcpyAsync(d_states, states_ref, sizeof(int32_t) * n_ref, hipMemcpyHostToDevice, s));
-  // the reference's self sweep at the radius, once: the pruned wide sweep at 65..256 columns, "auto" otherwise
+  // the reference's self sweep at the radius, once: the pruned wide sweep at 65..256 columns, the pruned extra-wide one at
+  // 257..1024 where the open call asked for the resident reference of those widths, "auto" otherwise
   const bool wide = n_cols >= 65 && n_cols <= 256;
+  const bool xwide = (a->flags & DC_ASSIGNER_XWIDE_REFERENCE) != 0u && n_cols >= 257 && n_cols <= 1024;
   {
-    const size_t ws = wide ? dc_hip_wide_pruned_workspace_bytes(n_ref, n_cols, 1) : dc_hip_workspace_bytes(n_ref, n_cols, 1);
+    const size_t ws = wide    ? dc_hip_wide_pruned_workspace_bytes(n_ref, n_cols, 1)
+                      : xwide ? dc_hip_xwide_pruned_workspace_bytes(n_ref, n_cols, 1)
+                              : dc_hip_workspace_bytes(n_ref, n_cols, 1);
     void* d_ws = nullptr;
     if (ws) DC_ASSIGN_TRY(hipMalloc(&d_ws, ws));
-    int rc = wide ? dc_hip_populations_wide_pruned_dev((const float*)d_ref, n_ref, n_cols, &a->radius, 1, 0, 0, (uint32_t*)d_pops, d_ws,
-                                                       ws, s)
-                  : dc_hip_populations_dev((const float*)d_ref, n_ref, n_cols, &a->radius, 1, 0, n_ref, (uint32_t*)d_pops, d_ws, ws,
-                                           DC_VARIANT_AUTO, s);
+    int rc = wide    ? dc_hip_populations_wide_pruned_dev((const float*)d_ref, n_ref, n_cols, &a->radius, 1, 0, 0, (uint32_t*)d_pops, d_ws,
+                                                          ws, s)
+             : xwide ? dc_hip_populations_xwide_pruned_dev((const float*)d_ref, n_ref, n_cols, &a->radius, 1, 0, 0, (uint32_t*)d_pops,
+                                                           d_ws, ws, s)
+                     : dc_hip_populations_dev((const float*)d_ref, n_ref, n_cols, &a->radius, 1, 0, n_ref, (uint32_t*)d_pops, d_ws, ws,
+                                              DC_VARIANT_AUTO, s);
     if (rc == DC_OK) rc = dc_hip_free_energies_dev((const uint32_t*)d_pops, n_ref, (float*)d_fe, &a->max_pop, s);   // (synchronises)
     if (d_ws) (void)hipFree(d_ws);
     if (rc) return rc;
@@ -324,22 +336,24 @@ int assigner_build(dc_assigner* a, const float* ref, const int32_t* states_ref) 
   void *d_hws = nullptr, *d_aws = nullptr;
   const size_t aws = dc_hip_assign_workspace_bytes(n_ref, max_batch);
   DC_ASSIGN_TRY(dev_alloc(a, &d_aws, aws));
-  a->path = wide ? 1 : (n_cols <= 64 ? 0 : 2);
+  a->path = wide ? 1 : (xwide ? 3 : (n_cols <= 64 ? 0 : 2));
   if (a->path != 2) {
-    const dc::ReferenceKind& k = wide ? dc::kReferenceWide : dc::kReferenceNarrow;
-    const size_t hws = (wide ? dc_hip_reference_wide_workspace_bytes : dc_hip_reference_workspace_bytes)(n_ref, n_cols, max_batch);
+    const bool narrow = a->path == 0;
+    const dc::ReferenceKind& k = wide ? dc::kReferenceWide : (xwide ? dc::kReferenceXWide : dc::kReferenceNarrow);
+    const size_t hws = (wide    ? dc_hip_reference_wide_workspace_bytes
+                        : xwide ? dc_hip_reference_xwide_workspace_bytes
+                                : dc_hip_reference_workspace_bytes)(n_ref, n_cols, max_batch);
     DC_ASSIGN_TRY(dev_alloc(a, &d_hws, hws));
-    const int rc = dc::handle_open(k, (const float*)d_ref, n_ref, n_cols, max_batch, wide ? INFINITY : a->radius, d_hws, hws, s, &a->ref);
-    if (rc == DC_ERR_TOO_LARGE && !wide)
+    const int rc = dc::handle_open(k, (const float*)d_ref, n_ref, n_cols, max_batch, narrow ? a->radius : INFINITY, d_hws, hws, s, &a->ref);
+    if (rc == DC_ERR_TOO_LARGE && narrow)
       a->path = 2;   // (a reference beyond the narrow handle's 2^24 positions: the per-call entry points serve it)
     else if (rc)
       return rc;
   }
   if (a->path != 2) {
+    const char* open_fn = wide ? "dc_hip_assign_open_wide_dev" : (xwide ? "dc_hip_assign_open_xwide_dev" : "dc_hip_assign_open_dev");
     if (int rc = dc::handle_set_free_energies(*a->ref->kind, a->ref, (const float*)d_fe, s)) return rc;
-    if (int rc = assign_open_on(wide ? "dc_hip_assign_open_wide_dev" : "dc_hip_assign_open_dev", a->ref, (const int32_t*)d_states, a->max_pop,
-                                a->radius, d_aws, aws, s, &a->assign))
-      return rc;
+    if (int rc = assign_open_on(open_fn, a->ref, (const int32_t*)d_states, a->max_pop, a->radius, d_aws, aws, s, &a->assign)) return rc;
   } else {
     CrossRef& c = a->cross;
     c.d_ref = (const float*)d_ref, c.d_fe_ref = (const float*)d_fe, c.n_ref = n_ref, c.n_cols = n_cols;
@@ -407,15 +421,12 @@ int assign_chunks(dc_assigner* a, const float* queries, size_t n_query, void* co
   return slot_flush(a->slot[(n_chunks - 1) & 1], outs);
 }
 
-}  // namespace
-
-extern "C" {
-
-int dc_hip_assigner_open(const float* ref, size_t n_ref, size_t n_cols, const int32_t* states_ref, float radius, size_t max_batch,
-                         int device, dc_assigner** out) {
-  const char* fn = "dc_hip_assigner_open";
+// dc_hip_assigner_open[_flags]
+int assigner_open(const char* fn, const float* ref, size_t n_ref, size_t n_cols, const int32_t* states_ref, float radius,
+                  size_t max_batch, int device, unsigned flags, dc_assigner** out) {
   if (!out) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer (out)", fn);
   *out = nullptr;
+  if (flags & ~DC_ASSIGNER_XWIDE_REFERENCE) return failf(DC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", fn, flags & ~DC_ASSIGNER_XWIDE_REFERENCE);
   if (n_cols == 0 || n_ref == 0 || max_batch == 0)
     return failf(DC_ERR_INVALID_ARGUMENT, "%s: n_ref=%zu, n_cols=%zu, max_batch=%zu must be positive", fn, n_ref, n_cols, max_batch);
   if (!ref || !states_ref) return failf(DC_ERR_INVALID_ARGUMENT, "%s: null pointer", fn);
@@ -430,14 +441,30 @@ int dc_hip_assigner_open(const float* ref, size_t n_ref, size_t n_cols, const in
   if (device < 0 || device >= n_dev) return failf(DC_ERR_INVALID_ARGUMENT, "%s: device %d out of range [0,%d)", fn, device, n_dev);
   DeviceGuard guard;
   dc_assigner* a = new dc_assigner;
-  a->device = device, a->n_ref = n_ref, a->n_cols = n_cols, a->max_batch = max_batch, a->radius = radius;
-  if (int rc = assigner_build(a, ref, states_ref)) {
+  a->device = device, a->n_ref = n_ref, a->n_cols = n_cols, a->max_batch = max_batch, a->radius = radius, a->flags = flags;
+  if (int rc = assigner_build(a, fn, ref, states_ref)) {
     const std::string msg = dc_hip_last_error();   // (close may run calls of its own)
     dc_hip_assigner_close(a);
     return dc::set_error(rc, msg.c_str());
   }
   *out = a;
   return DC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// flags = 0 unless the environment holds DC_ASSIGN_XWIDE=1 (read at every open, as DC_SESSION_WIDE is for sessions)
+int dc_hip_assigner_open(const float* ref, size_t n_ref, size_t n_cols, const int32_t* states_ref, float radius, size_t max_batch,
+                         int device, dc_assigner** out) {
+  const char* v = getenv("DC_ASSIGN_XWIDE");
+  const unsigned flags = (v && v[0] == '1' && v[1] == '\0') ? DC_ASSIGNER_XWIDE_REFERENCE : 0u;
+  return assigner_open("dc_hip_assigner_open", ref, n_ref, n_cols, states_ref, radius, max_batch, device, flags, out);
+}
+
+int dc_hip_assigner_open_flags(const float* ref, size_t n_ref, size_t n_cols, const int32_t* states_ref, float radius, size_t max_batch,
+                               int device, unsigned flags, dc_assigner** out) {
+  return assigner_open("dc_hip_assigner_open_flags", ref, n_ref, n_cols, states_ref, radius, max_batch, device, flags, out);
 }
 
 int dc_hip_assigner_reference(const dc_assigner* a, uint32_t* pops_ref, float* fe_ref, uint32_t* max_pop) {

@@ -14,8 +14,9 @@ namespace dc {
 // what differs between the kinds of handle: a constant table of function pointers and names (dc_capi.hip)
 struct ReferenceKind;
 extern const ReferenceKind kReferenceNarrow, kReferenceWide;   // rows of 1..64 columns (4.29), of 65..256 (4.28)
+extern const ReferenceKind kReferenceXWide;                    // ... of 257..1024 (4.36)
 
-// a resident reference of either kind
+// a resident reference of any kind
 struct ReferenceHandle {
   const ReferenceKind* kind = nullptr;
   const float* d_ref = nullptr;     // borrowed until close
@@ -29,7 +30,7 @@ struct ReferenceHandle {
   uint32_t preparations = 0;        // runs of the reference's half of the preparation
 };
 
-// The bodies of the handles' entry points, one per step for both kinds: dc_hip_reference[_wide]_<step>_dev is
+// The bodies of the handles' entry points, one per step for every kind: dc_hip_reference[_wide|_xwide]_<step>_dev is
 // handle_<step>(its kind, ...).  k names the entry point in every refusal, a null handle's among them.
 int handle_open(const ReferenceKind& k, const float* d_ref, size_t n_ref, size_t n_cols, size_t max_batch, float max_radius,
                 void* d_ws, size_t ws_bytes, void* stream, ReferenceHandle** out);
@@ -46,9 +47,10 @@ void fe_table(std::vector<float>& table, uint32_t max_pop);
 
 int set_error(int code, const char* msg);
 
-// The public types of the two kinds (include/dc_density.h) stay distinct names and are never defined: a pointer to
-// either is a ReferenceHandle* under that name.
+// The public types of the three kinds (include/dc_density.h) stay distinct names and are never defined: a pointer to
+// any is a ReferenceHandle* under that name.
 inline ReferenceHandle* handle(dc_reference* h) { return reinterpret_cast<ReferenceHandle*>(h); }
 inline ReferenceHandle* handle(dc_reference_wide* h) { return reinterpret_cast<ReferenceHandle*>(h); }
+inline ReferenceHandle* handle(dc_reference_xwide* h) { return reinterpret_cast<ReferenceHandle*>(h); }
 
 }  // namespace dc

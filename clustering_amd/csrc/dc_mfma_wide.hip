@@ -805,7 +805,8 @@ int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n
   return 0;
 }
 
-// ---- the resident reference of the pruned cross sweeps (dc_hip_reference_wide_*) --------------------------
+// ---- the resident reference of the pruned cross sweeps (dc_hip_reference_wide_*; at 257..1024 columns
+// ---- dc_hip_reference_xwide_*, 4.36: the same functions in the layout of that width) ------------------------------------
 // The preparation of wide_cross_pruned_prepare in two halves: the reference's, once, under statistics that do not depend
 // on a batch (dc_mfma_wide_kernels.hpp, "the resident reference"), and a batch's.  The sweeps are launch_pop_wide_cross_pruned
 // and launch_nn_wide_cross_pruned as they stand, in a workspace of three regions:
@@ -835,7 +836,7 @@ WideReferenceLayout wide_reference_layout(size_t n_ref, size_t n_cols, size_t ma
   P.blocks_q = L.Tqp / kWideBlockTiles;
   const size_t tile_bytes = (size_t)16 * 64 * L.NM;
   const size_t n_max = max_batch > n_ref ? max_batch : n_ref;
-  size_t at = kWideOffImages;
+  size_t at = wide_off_images(n_cols);   // (up to 256 columns kWideOffImages; beyond, behind [1024] sums and means)
   auto take = [&at](size_t bytes) {
     const size_t off = at;
     at = align256(at + bytes);
@@ -889,21 +890,27 @@ size_t wide_reference_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_ba
   if (!wide_mfma_supports(n_cols) || n_ref == 0 || max_batch == 0) return 0;
   return wide_reference_layout(n_ref, n_cols, max_batch).P.total;
 }
+// ... and of the third kind (dc_hip_reference_xwide_*): rows of 257..1024 columns.  Every other function of
+// the resident form reads the layout of the width it is given, as wide_cross_pruned_prepare does, and serves both kinds.
+size_t xwide_reference_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_batch) {
+  if (!xwide_mfma_supports(n_cols) || n_ref == 0 || max_batch == 0) return 0;
+  return wide_reference_layout(n_ref, n_cols, max_batch).P.total;
+}
 
 int wide_reference_open(const float* d_ref, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws, hipStream_t s) {
   const WideReferenceLayout R = wide_reference_layout(n_ref, n_cols, max_batch);
   char* p = (char*)d_ws;
   uint32_t* hdr = (uint32_t*)p;
-  const float* means = (const float*)(p + kWideOffMeans);
+  float* means = (float*)(p + wide_off_means(n_cols));
   // statistics of the reference alone (wide_stats_launches without the free energies and with the resident scale)
-  if (hipMemsetAsync(d_ws, 0, kWideOffImages, s) != hipSuccess) return -1;
+  if (hipMemsetAsync(d_ws, 0, wide_off_images(n_cols), s) != hipSuccess) return -1;
   const size_t elems = (size_t)n_ref * n_cols;
   hipLaunchKernelGGL(wide_colsum_kernel, dim3((uint32_t)min_sz(1024, (elems + 255) / 256)), dim3(256), 0, s, d_ref, n_ref, n_cols,
                      (double*)(p + kWideOffSums));
   hipLaunchKernelGGL(wide_mean_kernel, dim3(1), dim3(256), 0, s, (const double*)(p + kWideOffSums), (size_t)n_ref, n_cols,
-                     (float*)(p + kWideOffMeans));
+                     means);
   hipLaunchKernelGGL(wide_rowstats_kernel, dim3((uint32_t)min_sz(4096, ((size_t)n_ref + 3) / 4)), dim3(256), 0, s, d_ref, n_ref,
-                     n_cols, means, hdr);
+                     n_cols, (const float*)means, hdr);
   hipLaunchKernelGGL(wide_res_scale_kernel, dim3(1), dim3(1), 0, s, hdr);
   if (hipMemsetD32Async((hipDeviceptr_t)(hdr + kWideHdrOrderLaidOut), (int)max_batch, 1, s) != hipSuccess) return -1;
   // the grid: the reference's extent, the cell from its count; its order, gathered rows, boxes, A image and norms
@@ -917,7 +924,7 @@ int wide_reference_open(const float* d_ref, uint32_t n_ref, uint32_t n_cols, uin
   const WideLayout& L = R.P.L;
   const size_t frags = (size_t)L.Tp * L.NM * 64;
   hipLaunchKernelGGL(wide_image_kernel, dim3((uint32_t)((frags + 255) / 256)), dim3(256), 0, s, (const float*)(p + R.P.off_coords_r),
-                     n_ref, n_cols, L.NM, L.Tp, means, (const uint32_t*)p, (uint4*)(p + L.off_img_a), (uint4*)nullptr,
+                     n_ref, n_cols, L.NM, L.Tp, (const float*)means, (const uint32_t*)p, (uint4*)(p + L.off_img_a), (uint4*)nullptr,
                      (float*)(p + L.off_norms));
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -945,11 +952,19 @@ int wide_reference_stage(const float* d_query, uint32_t n_query, uint32_t n_ref,
   const WideReferenceLayout R = wide_reference_layout(n_ref, n_cols, max_batch);
   char* p = (char*)d_ws;
   uint32_t* hdr = (uint32_t*)p;
-  const float* means = (const float*)(p + kWideOffMeans);
+  const float* means = (const float*)(p + wide_off_means(n_cols));
   hipLaunchKernelGGL(wide_res_batch_reset_kernel, dim3(1), dim3(64), 0, s, hdr);
   if (n_query == 0) return hipGetLastError() == hipSuccess ? 0 : -1;
-  hipLaunchKernelGGL(wide_res_gate_kernel, dim3((uint32_t)min_sz(4096, ((size_t)n_query + 3) / 4)), dim3(256), 0, s, d_query, n_query,
-                     n_cols, means, hdr, (uint32_t*)(p + R.P.off_keys), (uint32_t*)(p + R.P.off_vals), n_ref);
+  // the gate: four columns per lane up to 256 columns, sixteen beyond
+  const dim3 gate_grid((uint32_t)min_sz(4096, ((size_t)n_query + 3) / 4));
+  uint32_t* keys = (uint32_t*)(p + R.P.off_keys);
+  uint32_t* vals = (uint32_t*)(p + R.P.off_vals);
+  if (n_cols <= kWideMaxCols)
+    hipLaunchKernelGGL(wide_res_gate_kernel<kWideGateSlots>, gate_grid, dim3(256), 0, s, d_query, n_query, n_cols, means, hdr, keys,
+                       vals, n_ref);
+  else
+    hipLaunchKernelGGL(wide_res_gate_kernel<kXWideGateSlots>, gate_grid, dim3(256), 0, s, d_query, n_query, n_cols, means, hdr, keys,
+                       vals, n_ref);
   if (wide_reference_order(R, d_query, n_query, n_cols, R.P.off_perm_q, R.P.off_coords_q, R.P.off_boxes_q, kWideHdrOrderQuery,
                            kWideOrderMarkQuery, d_ws, s) != 0)
     return -1;

@@ -180,6 +180,9 @@ int wide_cross_pruned_order(const void* d_ws, uint32_t n_query_range, uint32_t n
 // bytes: a resident region sized by (n_ref, n_cols), a batch region sized by (max_batch, n_cols), the sort's scratch sized
 // by the larger count; 0 if the column count is not served or a count is zero; monotone in each argument
 size_t wide_reference_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_batch);
+// ... of the third kind, rows of 257..1024 columns (dc_hip_reference_xwide_*): 0 outside those widths.  The
+// functions below read the layout of the width they are given and serve both kinds
+size_t xwide_reference_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_batch);
 int wide_reference_open(const float* d_ref, uint32_t n_ref, uint32_t n_cols, uint32_t max_batch, void* d_ws, hipStream_t stream);
 // the reference's free energies: copied by row (what the direct kernel reads), gathered by position, the least per block;
 // a NaN among them raises a word of its own, which only a neighbour sweep with free energies reads

@@ -731,28 +731,33 @@ __global__ void wide_res_batch_reset_kernel(uint32_t* __restrict__ hdr) {
 }
 
 // The gate of a batch, its ONE pass over the rows: a wave per row, the columns across its lanes (the resident means in
-// registers, four per lane).  |x - mean|^2 as wide_rowstats_kernel forms it against the resident means; the batch's flag
+// registers, SLOTS per lane: 4 for rows of 65..256 columns, 16 for 257..1024).  |x - mean|^2 as
+// wide_rowstats_kernel forms it against the resident means; the batch's flag
 // is raised by a row that is non-finite, beyond kNormLimit or beyond M_res (header word 0).  Columns 0 / 1 of the row are
 // in lanes 0 / 1: lane 0 writes the row's cell key on the reference's grid (clamped) and its value for the sort.
 // Stands in for a column-sum pass, a statistics pass, an extent pass and a key pass over the batch.  No LDS.
+constexpr uint32_t kWideGateSlots = 4, kXWideGateSlots = 16;
+template <uint32_t SLOTS>
 __global__ __launch_bounds__(256) void wide_res_gate_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D,
                                                             const float* __restrict__ means, uint32_t* __restrict__ hdr,
                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                             uint32_t n_grid) {
-  static_assert(kWideMaxCols <= 4 * 64 && kWideMinCols > 64, "four columns per lane at most; lanes 0 / 1 hold columns 0 / 1");
+  static_assert(kWideMaxCols <= kWideGateSlots * 64 && kXWideMaxCols <= kXWideGateSlots * 64 && kWideMinCols > 64,
+                "SLOTS columns per lane at most; lanes 0 / 1 hold columns 0 / 1");
+  static_assert(SLOTS == kWideGateSlots || SLOTS == kXWideGateSlots, "the two instances");
   const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
   const float M_res = __uint_as_float(hdr[0]);
   const WidePruneGrid g = wide_prune_grid(hdr, n_grid);
-  float mu[4];
+  float mu[SLOTS];
 #pragma unroll
-  for (uint32_t q = 0; q < 4u; ++q) mu[q] = (lane + 64u * q < D) ? means[lane + 64u * q] : 0.0f;
+  for (uint32_t q = 0; q < SLOTS; ++q) mu[q] = (lane + 64u * q < D) ? means[lane + 64u * q] : 0.0f;
   bool bad = false;
   for (uint32_t row = wave; row < n_rows; row += n_waves) {
     const float* x = coords + (size_t)row * D;
     double nrm = 0.0;
     float first = 0.0f;
 #pragma unroll
-    for (uint32_t q = 0; q < 4u; ++q)
+    for (uint32_t q = 0; q < SLOTS; ++q)
       if (lane + 64u * q < D) {
         const float xk = x[lane + 64u * q];
         if (q == 0u) first = xk;

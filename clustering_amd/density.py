@@ -951,6 +951,23 @@ class NarrowReference(Reference):
         return perm_q, perm_r
 
 
+class XWideReference(Reference):
+    """A resident reference for the pruned cross sweeps of rows of 257..1024 columns (dc_hip_reference_xwide_*): Reference's
+    methods, for calculate_populations_against_xwide_pruned and nearest_reference_xwide_pruned.
+
+        with XWideReference(reference, max_batch=20000, radius=r, ref_states=states) as ref:
+            for batch in batches:
+                out = ref.assign(batch)   # the dict of assign_frames_xwide_pruned, the same values
+
+    With ``radius`` and ``ref_states`` the construction runs calculate_populations_xwide_pruned on the reference ONCE."""
+    _api = "dc_hip_reference_xwide_"
+    _assign_open = "dc_hip_assign_open_xwide_dev"
+    _cols = (257, 1024, "the extra-wide matrix-core sweeps take 257..1024 columns")
+
+    def _self_populations(self, reference, radius):
+        return calculate_populations_xwide_pruned(reference, [radius])
+
+
 class Assigner:
     """The host-pointer assigner (dc_hip_assigner_*): what `clustering assign` and a C / C++ host run.  The library owns
     the device memory: it uploads ``reference_host`` [n_ref, n_cols] and ``ref_states`` [n_ref], runs the reference's
@@ -960,9 +977,10 @@ class Assigner:
             out = a.assign(queries_host)      # dict of numpy arrays: the values of assign_frames[_wide_pruned]
 
     ``path``: 0 the narrow handle (1..64 columns), 1 the wide handle (65..256), 2 the per-call cross entry points (any
-    other width, or a reference the narrow handle refuses as too large)."""
+    other width, or a reference the narrow handle refuses as too large), 3 the resident reference of 257..1024 columns
+    (``xwide=True``, or DC_ASSIGN_XWIDE=1 in the environment; the same values as path 2)."""
 
-    def __init__(self, reference_host, ref_states, radius, max_batch, device=0):
+    def __init__(self, reference_host, ref_states, radius, max_batch, device=0, xwide=False):
         self._h = None
         ref = np.ascontiguousarray(reference_host, dtype=np.float32)
         states = np.ascontiguousarray(ref_states, dtype=np.int32)
@@ -970,9 +988,13 @@ class Assigner:
             raise ValueError("reference_host must be [n_ref, n_cols] and ref_states hold one state per reference row")
         self.n_ref, self.n_cols = ref.shape
         h = C.c_void_p()
-        capi.check(capi.lib.dc_hip_assigner_open(ref.ctypes.data_as(C.c_void_p), self.n_ref, self.n_cols,
-                                                 states.ctypes.data_as(C.c_void_p), float(radius), int(max_batch), int(device),
-                                                 C.byref(h)), "dc_hip_assigner_open")
+        args = (ref.ctypes.data_as(C.c_void_p), self.n_ref, self.n_cols, states.ctypes.data_as(C.c_void_p), float(radius),
+                int(max_batch), int(device))
+        if xwide:
+            capi.check(capi.lib.dc_hip_assigner_open_flags(*args, capi.ASSIGNER_XWIDE_REFERENCE, C.byref(h)),
+                       "dc_hip_assigner_open_flags")
+        else:
+            capi.check(capi.lib.dc_hip_assigner_open(*args, C.byref(h)), "dc_hip_assigner_open")
         self._h = h
 
     def close(self):

@@ -707,7 +707,8 @@ DC_API int dc_hip_nearest_neighbors_cross_wide_pruned_dev(const float* d_query, 
  * gated direct kernel (beyond 400 columns the column-chunked one), no host synchronisation; the counters then read
  * (0, 0, 0).  dc_hip_wide_info_dev reads the counters of the last call (EVALUATED tile pairs),
  * dc_hip_cross_xwide_pruned_order_dev its two orders (a self order or an order of the 65..256 family is refused).  No
- * resident reference, assigner path or CLI mode runs them; no dc_variant value selects them. */
+ * dc_variant value selects them; the resident reference dc_reference_xwide below runs them, and through it the assigner's
+ * path 3. */
 DC_API size_t dc_hip_cross_xwide_pruned_workspace_bytes(size_t n_query, size_t n_ref, size_t n_cols, size_t n_radii);
 DC_API int dc_hip_populations_cross_xwide_pruned_dev(const float* d_query, size_t n_query, const float* d_ref, size_t n_ref,
                                                      size_t n_cols, const float* radii, size_t n_radii, size_t i_from,
@@ -774,6 +775,40 @@ DC_API int dc_hip_reference_wide_info_dev(dc_reference_wide* reference, uint64_t
                                           uint64_t* exact_pairs, uint32_t* answered, uint32_t* reference_preparations,
                                           void* stream);
 DC_API int dc_hip_reference_wide_order_dev(dc_reference_wide* reference, uint32_t* d_perm_q, uint32_t* d_perm_r, void* stream);
+
+/* ---- ... and a RESIDENT REFERENCE for rows of 257..1024 columns ----------------------------------------------------------------
+ * dc_reference_wide for the two pruned cross sweeps of 257..1024 columns (dc_hip_*_cross_xwide_pruned_dev): the same
+ * resident form -- origin, grid and scale from the reference alone, the scale that of FOUR TIMES its largest
+ * |x - mean|^2, one gate pass per batch -- in the workspace layout of these widths.  Each entry point takes the argument
+ * list of its _wide_ namesake, keeps its contract and refuses in the same order, before a device is touched, naming
+ * itself; n_cols outside 257..1024: DC_ERR_INVALID_ARGUMENT.  Results are those of dc_hip_populations_cross_xwide_dev /
+ * dc_hip_nearest_neighbors_cross_xwide_dev and of DC_VARIANT_DIRECT, bit for bit.
+ * dc_hip_reference_xwide_workspace_bytes: 0 outside 257..1024 columns or for a zero count, monotone in each argument; a
+ * workspace of one kind never serves the other (dc_hip_reference_wide_workspace_bytes stays 0 at these widths).
+ * Flagged data -- `answered` 1..3 as above -- is answered by the gated direct kernels (beyond 400 columns the
+ * column-chunked ones), no host synchronisation.
+ * The band is formed from 4 M_ref where a per-call sweep forms it from the batch's and the reference's own extent: more
+ * pairs take the exact path (each a canonical sum of n_cols terms).  Measured on dense data (20 000 x 100 000 x 512,
+ * 2 000 x 100 000 x 512, 10 000 x 50 000 x 1024, one MI355X): stage + populations takes 0.46, 0.73 and 0.45 x the speed of
+ * one dc_hip_populations_cross_xwide_pruned_dev call (3.9 x the exact pairs), stage + populations + nearest 0.57, 0.99 and
+ * 0.52 x.  For ONE batch per reference, or for the least time per population call, use the per-call entry points above.  The
+ * handle pays where the reference's own work repeats: a whole assignment of a batch (reference self sweep included on the
+ * other side) is 1.9 - 10.9 x faster on it, the host assigner's path 3 3.2 - 9.8 x faster than path 2. */
+typedef struct dc_reference_xwide dc_reference_xwide;
+DC_API size_t dc_hip_reference_xwide_workspace_bytes(size_t n_ref, size_t n_cols, size_t max_batch);
+DC_API int dc_hip_reference_xwide_open_dev(const float* d_ref, size_t n_ref, size_t n_cols, size_t max_batch, void* d_ws,
+                                           size_t ws_bytes, void* stream, dc_reference_xwide** out);
+DC_API void dc_hip_reference_xwide_close(dc_reference_xwide* reference);
+DC_API int dc_hip_reference_xwide_set_free_energies_dev(dc_reference_xwide* reference, const float* d_fe_ref, void* stream);
+DC_API int dc_hip_reference_xwide_stage_dev(dc_reference_xwide* reference, const float* d_query, size_t n_query, void* stream);
+DC_API int dc_hip_reference_xwide_populations_dev(dc_reference_xwide* reference, const float* radii, size_t n_radii,
+                                                  uint32_t* d_pops, void* stream);
+DC_API int dc_hip_reference_xwide_nearest_dev(dc_reference_xwide* reference, const float* d_fe_query, uint32_t* d_nn_idx,
+                                              float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* stream);
+DC_API int dc_hip_reference_xwide_info_dev(dc_reference_xwide* reference, uint64_t* tiles, uint64_t* mfmas,
+                                           uint64_t* exact_pairs, uint32_t* answered, uint32_t* reference_preparations,
+                                           void* stream);
+DC_API int dc_hip_reference_xwide_order_dev(dc_reference_xwide* reference, uint32_t* d_perm_q, uint32_t* d_perm_r, void* stream);
 
 /* ---- ... and the radius graph on the wide self sweep (65..256 columns) --------------------------------------------------
  * The one-radius population sweep with a sink on its two decision points, the accumulator window and the exact drain.
@@ -886,6 +921,9 @@ DC_API int dc_hip_assign_open_dev(dc_reference* reference, const int32_t* d_stat
                                   void* d_ws, size_t ws_bytes, void* stream, dc_assign** out);
 DC_API int dc_hip_assign_open_wide_dev(dc_reference_wide* reference, const int32_t* d_states_ref, uint32_t max_pop,
                                        float radius, void* d_ws, size_t ws_bytes, void* stream, dc_assign** out);
+/* ... on the resident reference of 257..1024 columns: the same call */
+DC_API int dc_hip_assign_open_xwide_dev(dc_reference_xwide* reference, const int32_t* d_states_ref, uint32_t max_pop,
+                                        float radius, void* d_ws, size_t ws_bytes, void* stream, dc_assign** out);
 DC_API void dc_hip_assign_close(dc_assign* assign);
 DC_API int dc_hip_assign_batch_dev(dc_assign* assign, const float* d_query, size_t n_query, int32_t* d_states,
                                    uint32_t* d_pops, float* d_fe, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx,
@@ -900,9 +938,12 @@ DC_API int dc_hip_assign_batch_dev(dc_assign* assign, const float* d_query, size
  *              one max_radius = radius), sets its free energies and opens the assigner above.  ANY width is served: rows
  *              wider than 256 columns, and a reference the narrow handle refuses as too large, go through the per-call
  *              entry points (dc_hip_populations_cross_dev / dc_hip_nearest_neighbors_cross_dev, DC_VARIANT_AUTO) with the
- *              same table and pick kernels; that path makes no stream-order promise.  Synchronises
+ *              same table and pick kernels; that path makes no stream-order promise.  Rows of 257..1024 columns take the
+ *              resident reference of those widths instead where the open call asks for it (dc_hip_assigner_open_flags,
+ *              DC_ASSIGN_XWIDE=1: below).  Synchronises
  *   reference  the self sweep's populations [n_ref], free energies [n_ref] and maximum; any pointer may be NULL
- *   path       0 the narrow handle, 1 the wide handle, 2 the per-call cross entry points (-1 for a NULL assigner)
+ *   path       0 the narrow handle, 1 the wide handle, 2 the per-call cross entry points, 3 the resident reference of
+ *              257..1024 columns (-1 for a NULL assigner)
  *   assign     any n_query, in chunks of max_batch through two batch slots: the upload of chunk k + 1 and the download of
  *              chunk k - 1 run on a copy stream, ordered by events, beside the sweeps of chunk k.  `states` [n_query] is
  *              required, the six other arrays [n_query] may be NULL; 0 rows: DC_OK.  Returns when every output is written.
@@ -914,6 +955,18 @@ DC_API int dc_hip_assign_batch_dev(dc_assign* assign, const float* d_query, size
 typedef struct dc_assigner dc_assigner;
 DC_API int dc_hip_assigner_open(const float* ref, size_t n_ref, size_t n_cols, const int32_t* states_ref, float radius,
                                 size_t max_batch, int device, dc_assigner** out);
+/* dc_hip_assigner_open with flags.  DC_ASSIGNER_XWIDE_REFERENCE: at 257..1024 columns the reference's self sweep is
+ * dc_hip_populations_xwide_pruned_dev and the batches go through the resident reference of those widths
+ * (dc_hip_reference_xwide_*, dc_hip_assign_open_xwide_dev): dc_hip_assigner_path returns 3, every output equals path 2's
+ * bit for bit.  A failure of that handle's open is returned (only the narrow handle's DC_ERR_TOO_LARGE falls back to
+ * path 2).  Outside those widths the flag changes nothing.  Unknown bits: DC_ERR_INVALID_ARGUMENT, before a device is
+ * touched.  WITHOUT the flag these widths stay on path 2, the direct kernels.
+ * dc_hip_assigner_open is flags = 0, unless the environment holds DC_ASSIGN_XWIDE=1, which sets
+ * DC_ASSIGNER_XWIDE_REFERENCE (read at every open: the hosts that call the old entry point, `clustering assign` among
+ * them, opt in). */
+#define DC_ASSIGNER_XWIDE_REFERENCE 0x1u
+DC_API int dc_hip_assigner_open_flags(const float* ref, size_t n_ref, size_t n_cols, const int32_t* states_ref, float radius,
+                                      size_t max_batch, int device, unsigned flags, dc_assigner** out);
 DC_API int dc_hip_assigner_reference(const dc_assigner* assigner, uint32_t* pops_ref, float* fe_ref, uint32_t* max_pop);
 DC_API int dc_hip_assigner_path(const dc_assigner* assigner);
 DC_API int dc_hip_assigner_assign(dc_assigner* assigner, const float* queries, size_t n_query, int32_t* states,
