@@ -74,6 +74,10 @@ SYMBOLS = (
     "dc_hip_reference_xwide_set_free_energies_dev", "dc_hip_reference_xwide_stage_dev", "dc_hip_reference_xwide_populations_dev",
     "dc_hip_reference_xwide_nearest_dev", "dc_hip_reference_xwide_info_dev", "dc_hip_reference_xwide_order_dev",
     "dc_hip_assign_open_xwide_dev", "dc_hip_assigner_open_flags",
+    "dc_hip_radius_pairs_xwide_dev", "dc_hip_radius_min_edge_xwide_dev", "dc_hip_radius_forest_xwide",
+    "dc_hip_radius_pairs_xwide_pruned_dev", "dc_hip_radius_min_edge_xwide_pruned_dev", "dc_hip_radius_forest_xwide_pruned",
+    "dc_hip_neighbors_block_rows_xwide", "dc_hip_neighbors_block_pack_xwide_dev", "dc_hip_neighbors_block_unpack_xwide_dev",
+    "dc_hip_xwide_layout_status_dev",
 )
 SESSION_WIDE_SWEEPS = 0x1     # DC_SESSION_WIDE_SWEEPS (dc_hip_session_open_flags)
 ASSIGNER_XWIDE_REFERENCE = 0x1   # DC_ASSIGNER_XWIDE_REFERENCE (dc_hip_assigner_open_flags)
@@ -279,6 +283,18 @@ def _load():
     lib.dc_hip_neighbors_block_unpack_wide_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp]
     lib.dc_hip_wide_layout_status_dev.restype = i32
     lib.dc_hip_wide_layout_status_dev.argtypes = [vp, C.POINTER(C.c_int), vp]
+    for xwide, wide in (("dc_hip_radius_pairs_xwide_dev", "dc_hip_radius_pairs_wide_dev"),
+                        ("dc_hip_radius_min_edge_xwide_dev", "dc_hip_radius_min_edge_wide_dev"),
+                        ("dc_hip_radius_forest_xwide", "dc_hip_radius_forest_wide"),
+                        ("dc_hip_radius_pairs_xwide_pruned_dev", "dc_hip_radius_pairs_wide_pruned_dev"),
+                        ("dc_hip_radius_min_edge_xwide_pruned_dev", "dc_hip_radius_min_edge_wide_pruned_dev"),
+                        ("dc_hip_radius_forest_xwide_pruned", "dc_hip_radius_forest_wide_pruned"),
+                        ("dc_hip_neighbors_block_rows_xwide", "dc_hip_neighbors_block_rows_wide"),
+                        ("dc_hip_neighbors_block_pack_xwide_dev", "dc_hip_neighbors_block_pack_wide_dev"),
+                        ("dc_hip_neighbors_block_unpack_xwide_dev", "dc_hip_neighbors_block_unpack_wide_dev"),
+                        ("dc_hip_xwide_layout_status_dev", "dc_hip_wide_layout_status_dev")):
+        getattr(lib, xwide).restype = getattr(lib, wide).restype     # (257..1024 columns: the lists of their namesakes)
+        getattr(lib, xwide).argtypes = getattr(lib, wide).argtypes
     lib.dc_hip_session_open_flags.restype = i32
     lib.dc_hip_session_open_flags.argtypes = [vp, sz, sz, C.POINTER(C.c_int), i32, C.c_uint, C.POINTER(vp)]
     lib.dc_hip_session_wide.restype = i32

@@ -524,19 +524,32 @@ int wide_order_hash(void* d_ws, uint32_t n_rows, uint32_t n_cols, hipStream_t s)
 }
 }  // namespace
 
-size_t wide_nn_block_rows(size_t n_rows, size_t n_cols, size_t n_segments) {
-  if (!wide_mfma_supports(n_cols) || n_segments == 0 || n_rows == 0) return 0;
+namespace {
+// rows of a block of n_rows rows dealt to n_segments (both positive): no function of the width
+size_t nn_block_rows_of(size_t n_rows, size_t n_segments) {
   const size_t row_block = n_rows - (n_segments - 1) * (n_rows / n_segments);   // the last (largest) row block
   const size_t blocks = (n_rows + kWideBlockRows - 1) / kWideBlockRows;
   const size_t most = (blocks + n_segments - 1) / n_segments;   // segment 0 owns the most blocks of the order
   const size_t by_position = most * kWideBlockRows;
   return (row_block > by_position ? row_block : by_position) + kWideBlockHdrRows;
 }
+}  // namespace
+
+size_t wide_nn_block_rows(size_t n_rows, size_t n_cols, size_t n_segments) {
+  if (!wide_mfma_supports(n_cols) || n_segments == 0 || n_rows == 0) return 0;
+  return nn_block_rows_of(n_rows, n_segments);
+}
+
+// 257..1024 columns: the same blocks; the launchers below read the layout of the width they are given
+size_t xwide_nn_block_rows(size_t n_rows, size_t n_cols, size_t n_segments) {
+  if (!xwide_mfma_supports(n_cols) || n_segments == 0 || n_rows == 0) return 0;
+  return nn_block_rows_of(n_rows, n_segments);
+}
 
 int launch_nn_block_pack_wide(const uint32_t* d_nn_idx, const float* d_nn_d2, const uint32_t* d_hd_idx, const float* d_hd_d2,
                               uint32_t n_rows, uint32_t n_cols, uint32_t segment, uint32_t n_segments, void* d_ws, uint32_t* d_block,
                               hipStream_t s) {
-  const uint32_t rows = (uint32_t)wide_nn_block_rows(n_rows, n_cols, n_segments);
+  const uint32_t rows = (uint32_t)nn_block_rows_of(n_rows, n_segments);   // (either family: the caller checked the width)
   if (wide_order_hash(d_ws, n_rows, n_cols, s) != 0) return -1;
   const char* p = (const char*)d_ws;
   hipLaunchKernelGGL(wide_block_pack_kernel, dim3((rows + 255u) / 256u), dim3(256), 0, s, d_nn_idx, d_nn_d2, d_hd_idx, d_hd_d2, n_rows,
@@ -547,7 +560,7 @@ int launch_nn_block_pack_wide(const uint32_t* d_nn_idx, const float* d_nn_d2, co
 
 int launch_nn_block_unpack_wide(const uint32_t* d_blocks, uint32_t n_rows, uint32_t n_cols, uint32_t n_segments, void* d_ws,
                                 uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, hipStream_t s) {
-  const uint32_t rows = (uint32_t)wide_nn_block_rows(n_rows, n_cols, n_segments);
+  const uint32_t rows = (uint32_t)nn_block_rows_of(n_rows, n_segments);   // (either family: the caller checked the width)
   if (wide_order_hash(d_ws, n_rows, n_cols, s) != 0) return -1;
   char* p = (char*)d_ws;
   hipLaunchKernelGGL(wide_block_unpack_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, d_blocks, n_rows, n_cols, n_segments,

@@ -107,6 +107,9 @@ int wide_clear_counters(void* d_ws, hipStream_t stream);
 // rows of a block: the larger of the largest segment in positions and the largest row block, plus the header; 0 if the
 // column count is not served, for no rows and for no segments
 size_t wide_nn_block_rows(size_t n_rows, size_t n_cols, size_t n_segments);
+// ... of 257..1024 columns (dc_hip_neighbors_block_*_xwide_dev): the same number, 0 outside those widths.
+// The pack, the unpack and the status below serve both families, in the layout of the width they are given
+size_t xwide_nn_block_rows(size_t n_rows, size_t n_cols, size_t n_segments);
 int launch_nn_block_pack_wide(const uint32_t* d_nn_idx, const float* d_nn_d2, const uint32_t* d_hd_idx, const float* d_hd_d2,
                               uint32_t n_rows, uint32_t n_cols, uint32_t segment, uint32_t n_segments, void* d_ws, uint32_t* d_block,
                               hipStream_t stream);

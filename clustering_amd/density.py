@@ -1178,10 +1178,13 @@ def radius_forest(coords_host, r2, rank, device=0):
 
 
 # ---- the radius graph on the wide matrix-core sweep (65..256 columns; include/dc_density.h) -------------------------
-def _check_coords_wide(coords):
-    """_check_coords, the column count (refused here as the library refuses it: 65..256) first"""
-    if isinstance(coords, (torch.Tensor, np.ndarray)) and coords.ndim == 2 and not 65 <= coords.shape[1] <= 256:
-        raise ValueError(f"n_cols={coords.shape[1]}: the wide matrix-core sweeps take 65..256 columns")
+_WIDE_COLS, _XWIDE_COLS = (65, 256), (257, 1024)   # the widths of the two families of wide matrix-core sweeps
+
+
+def _check_coords_wide(coords, cols=_WIDE_COLS):
+    """_check_coords, the column count (refused here as the library refuses it: 65..256, or the ``cols`` of the family) first"""
+    if isinstance(coords, (torch.Tensor, np.ndarray)) and coords.ndim == 2 and not cols[0] <= coords.shape[1] <= cols[1]:
+        raise ValueError(f"n_cols={coords.shape[1]}: the wide matrix-core sweeps take {cols[0]}..{cols[1]} columns")
     return _check_coords(coords) if isinstance(coords, torch.Tensor) else coords.shape
 
 
@@ -1194,8 +1197,8 @@ def radius_pairs_wide(coords, r2, capacity=None):
     return _radius_pairs_wide("dc_hip_radius_pairs_wide_dev", "wide", coords, r2, capacity)
 
 
-def _radius_pairs_wide(fn, kind, coords, r2, capacity):
-    n_rows, n_cols = _check_coords_wide(coords)
+def _radius_pairs_wide(fn, kind, coords, r2, capacity, cols=_WIDE_COLS):
+    n_rows, n_cols = _check_coords_wide(coords, cols)
     dev = coords.device
     pops = torch.empty(n_rows, dtype=torch.int32, device=dev)
     count = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -1214,7 +1217,7 @@ def _radius_pairs_wide(fn, kind, coords, r2, capacity):
     pairs = torch.empty((max(capacity, 1), 2), dtype=torch.int32, device=dev)
     n = sweep(pairs, capacity)
     if n > capacity:
-        return _radius_pairs_wide(fn, kind, coords, r2, n)
+        return _radius_pairs_wide(fn, kind, coords, r2, n, cols)
     return pairs[:n].to(torch.int64), pops
 
 
@@ -1227,8 +1230,8 @@ def radius_min_edge_wide(coords, r2, comp, rank, segment=0, n_segments=0):
     return _radius_min_edge_wide("dc_hip_radius_min_edge_wide_dev", "wide", coords, r2, comp, rank, segment, n_segments)
 
 
-def _radius_min_edge_wide(fn, kind, coords, r2, comp, rank, segment, n_segments):
-    n_rows, n_cols = _check_coords_wide(coords)
+def _radius_min_edge_wide(fn, kind, coords, r2, comp, rank, segment, n_segments, cols=_WIDE_COLS):
+    n_rows, n_cols = _check_coords_wide(coords, cols)
     dev = coords.device
     for t in (comp, rank):
         assert t.is_cuda and t.dtype == torch.int32 and t.shape == (n_rows,) and t.is_contiguous()
@@ -1249,9 +1252,9 @@ def radius_forest_wide(coords_host, r2, rank, device=0):
     return _radius_forest_wide("dc_hip_radius_forest_wide", coords_host, r2, rank, device)
 
 
-def _radius_forest_wide(fn, coords_host, r2, rank, device):
+def _radius_forest_wide(fn, coords_host, r2, rank, device, cols=_WIDE_COLS):
     coords_host = np.ascontiguousarray(coords_host, dtype=np.float32)
-    n_rows, n_cols = _check_coords_wide(coords_host)
+    n_rows, n_cols = _check_coords_wide(coords_host, cols)
     rank = np.ascontiguousarray(rank, dtype=np.uint32)
     assert rank.shape == (n_rows,)
     edges = np.empty((max(n_rows - 1, 1), 2), dtype=np.uint32)
@@ -1289,6 +1292,50 @@ def radius_forest_wide_pruned(coords_host, r2, rank, device=0):
     """radius_forest_wide on the pruned sweep (dc_hip_radius_forest_wide_pruned): the same edges and rounds; the order
     is built once per forest."""
     return _radius_forest_wide("dc_hip_radius_forest_wide_pruned", coords_host, r2, rank, device)
+
+
+# ---- ... and both forms at 257..1024 columns (include/dc_density.h, the radius graph at 257..1024 columns) -----------
+def radius_pairs_xwide(coords, r2, capacity=None):
+    """radius_pairs_wide for rows of 257..1024 columns (dc_hip_radius_pairs_xwide_dev): the same contract, in the cached
+    workspace of the unpruned sweeps of those widths (xwide_sweep_info reads its counters).  Other column counts raise."""
+    return _radius_pairs_wide("dc_hip_radius_pairs_xwide_dev", "xwide", coords, r2, capacity, _XWIDE_COLS)
+
+
+def radius_min_edge_xwide(coords, r2, comp, rank, segment=0, n_segments=0):
+    """radius_min_edge_wide for rows of 257..1024 columns (dc_hip_radius_min_edge_xwide_dev): a segment is the
+    reference's row block.  Other column counts raise."""
+    return _radius_min_edge_wide("dc_hip_radius_min_edge_xwide_dev", "xwide", coords, r2, comp, rank, segment, n_segments,
+                                 _XWIDE_COLS)
+
+
+def radius_forest_xwide(coords_host, r2, rank, device=0):
+    """radius_forest_wide for rows of 257..1024 columns (dc_hip_radius_forest_xwide).  Other column counts raise."""
+    return _radius_forest_wide("dc_hip_radius_forest_xwide", coords_host, r2, rank, device, _XWIDE_COLS)
+
+
+def radius_pairs_xwide_pruned(coords, r2, capacity=None):
+    """radius_pairs_wide_pruned for rows of 257..1024 columns (dc_hip_radius_pairs_xwide_pruned_dev): the set of pairs of
+    radius_pairs_xwide -- in no order within a pair -- and the same populations.  In the cached workspace of the pruned
+    sweeps of those widths (xwide_pruned_info reads its counters, xwide_pruned_order its order)."""
+    out = _radius_pairs_wide("dc_hip_radius_pairs_xwide_pruned_dev", "xwide_pruned", coords, r2, capacity, _XWIDE_COLS)
+    _shapes["xwide_pruned"][str(coords.device)] = tuple(coords.shape)
+    return out
+
+
+def radius_min_edge_xwide_pruned(coords, r2, comp, rank, segment=0, n_segments=0):
+    """radius_min_edge_wide_pruned for rows of 257..1024 columns (dc_hip_radius_min_edge_xwide_pruned_dev): the whole
+    round is array-equal to radius_min_edge_xwide; n_segments > 0: the query blocks segment, segment + n_segments, ... of
+    the order (partials merge by unsigned minimum / summation)."""
+    out = _radius_min_edge_wide("dc_hip_radius_min_edge_xwide_pruned_dev", "xwide_pruned", coords, r2, comp, rank,
+                                segment, n_segments, _XWIDE_COLS)
+    _shapes["xwide_pruned"][str(coords.device)] = tuple(coords.shape)
+    return out
+
+
+def radius_forest_xwide_pruned(coords_host, r2, rank, device=0):
+    """radius_forest_xwide on the pruned sweep (dc_hip_radius_forest_xwide_pruned): the same edges and rounds; the order
+    is built once per forest."""
+    return _radius_forest_wide("dc_hip_radius_forest_xwide_pruned", coords_host, r2, rank, device, _XWIDE_COLS)
 
 
 def pack_neighbors(nn_idx, nn_d2, hd_idx, hd_d2):
@@ -1439,6 +1486,35 @@ def unpack_neighbor_blocks_wide(coords, blocks, n_segments, out=None, check=True
     out, _ = _unpack_blocks("dc_hip_neighbors_block_unpack_wide_dev", "wide_pruned", neighbor_block_rows_wide, coords, blocks,
                             n_segments, out, check)
     if check and coords.shape[0] and wide_layout_status(coords.device):
+        raise RuntimeError("neighbour blocks of the ranks were packed under different layouts")
+    return out
+
+
+# ---- ... and of the pruned neighbour sweep of 257..1024 columns --------------------------------------------------------
+def neighbor_block_rows_xwide(n_rows, n_cols, n_segments):
+    """neighbor_block_rows_wide for 257..1024 columns (dc_hip_neighbors_block_rows_xwide); 0 outside them"""
+    return int(capi.lib.dc_hip_neighbors_block_rows_xwide(n_rows, n_cols, n_segments))
+
+
+def pack_neighbor_block_xwide(coords, nn_idx, nn_d2, hd_idx, hd_d2, segment, n_segments, out=None):
+    """pack_neighbor_block_wide for 257..1024 columns (dc_hip_neighbors_block_pack_xwide_dev); call right after
+    nearest_neighbors_xwide_pruned(coords, fe, segment, n_segments) on the same device."""
+    return _pack_block("dc_hip_neighbors_block_pack_xwide_dev", "xwide_pruned", neighbor_block_rows_xwide, coords,
+                       (nn_idx, nn_d2, hd_idx, hd_d2), segment, n_segments, out)
+
+
+def xwide_layout_status(device):
+    """True if the last dc_hip_neighbors_block_unpack_xwide_dev in this device's workspace of the pruned sweeps of 257..1024
+    columns REFUSED its blocks (nothing was unpacked) -- dc_hip_xwide_layout_status_dev; synchronises"""
+    return _layout_status("dc_hip_xwide_layout_status_dev", "xwide_pruned", device)
+
+
+def unpack_neighbor_blocks_xwide(coords, blocks, n_segments, out=None, check=True):
+    """unpack_neighbor_blocks_wide for 257..1024 columns (dc_hip_neighbors_block_unpack_xwide_dev), in the workspace of the
+    pruned sweeps of those widths on this device, which must hold the order the blocks were packed by."""
+    out, _ = _unpack_blocks("dc_hip_neighbors_block_unpack_xwide_dev", "xwide_pruned", neighbor_block_rows_xwide, coords, blocks,
+                            n_segments, out, check)
+    if check and coords.shape[0] and xwide_layout_status(coords.device):
         raise RuntimeError("neighbour blocks of the ranks were packed under different layouts")
     return out
 

@@ -557,6 +557,27 @@ DC_API int dc_hip_neighbors_block_unpack_wide_dev(const uint32_t* d_blocks, size
                                                   void* d_ws, size_t ws_bytes, uint32_t* d_nn_idx, float* d_nn_d2,
                                                   uint32_t* d_hd_idx, float* d_hd_d2, void* stream);
 DC_API int dc_hip_wide_layout_status_dev(const void* d_ws, int* mismatch, void* stream);
+/* ---- ... and the same blocks at 257..1024 columns ---------------------------------------------------------------------------
+ * The four calls above behind dc_hip_nearest_neighbors_xwide_pruned_dev(segment g, G), in its workspace
+ * (dc_hip_xwide_pruned_workspace_bytes(n_rows, n_cols, 1)): the same bodies and kernels in the layout of these widths.  Each
+ * takes the argument list of its _wide namesake, keeps its contract -- blocks by local position; row blocks on flagged
+ * data, chosen on the device from the word the sweep's gate read; the layout header with the hash of the order; an unpack
+ * that compares all G headers with the header of its own workspace before it writes anything; a workspace that holds no
+ * signed order of this shape packs under a mark no unpack accepts; rows read from the order are checked against n_rows
+ * -- and refuses in the same order with the same codes, before a device is touched, naming itself.  n_cols outside
+ * 257..1024: DC_ERR_INVALID_ARGUMENT; dc_hip_neighbors_block_rows_xwide is 0 there (the same number as
+ * dc_hip_neighbors_block_rows_wide otherwise: a block is no function of the width).  The header does not carry the width:
+ * what an unpack holds a block to is the layout -- shape, deal and the hash of the order -- so a block packed at another
+ * width is refused through the order it was packed by. */
+DC_API size_t dc_hip_neighbors_block_rows_xwide(size_t n_rows, size_t n_cols, size_t n_segments);
+DC_API int dc_hip_neighbors_block_pack_xwide_dev(const uint32_t* d_nn_idx, const float* d_nn_d2, const uint32_t* d_hd_idx,
+                                                 const float* d_hd_d2, size_t n_rows, size_t n_cols, size_t segment,
+                                                 size_t n_segments, void* d_ws, size_t ws_bytes, uint32_t* d_block,
+                                                 void* stream);
+DC_API int dc_hip_neighbors_block_unpack_xwide_dev(const uint32_t* d_blocks, size_t n_rows, size_t n_cols, size_t n_segments,
+                                                   void* d_ws, size_t ws_bytes, uint32_t* d_nn_idx, float* d_nn_d2,
+                                                   uint32_t* d_hd_idx, float* d_hd_d2, void* stream);
+DC_API int dc_hip_xwide_layout_status_dev(const void* d_ws, int* mismatch, void* stream);
 /* ---- ... and their cross form: query frames against a reference trajectory at 65..256 columns ------------------------
  * The wide sweep over a rectangle Q x R: the contract of the "cross sweeps" block above -- populations without a self
  * term, nn[q] the lexicographic minimum of (d2, j) over ALL j with no exclusion, nn_hd[q] the same over
@@ -870,6 +891,47 @@ DC_API int dc_hip_radius_min_edge_wide_pruned_dev(const float* d_coords, size_t 
 DC_API int dc_hip_radius_forest_wide_pruned(const float* coords, size_t n_rows, size_t n_cols, float r2,
                                             const uint32_t* rank, int device, uint32_t* edges, size_t* n_edges,
                                             uint32_t* n_rounds);
+
+/* ---- ... and the radius graph at 257..1024 columns, unpruned and pruned ---------------------------------------------------
+ * The six calls above in the layouts of these widths: the same bodies, the same two kernel instances over a chain of up
+ * to 193 MFMAs.  Each takes the argument list of its _wide_ / _wide_pruned_ namesake, keeps its contract -- every
+ * unordered pair with canonical d2 < r2 exactly once (the pruned form: in no order within a pair); *d_count exact beyond
+ * the capacity and exactly `capacity` distinct valid pairs written; a NaN, 0 or negative r2 holds no pair; both min-edge
+ * outputs preset by the call; an unpruned min-edge segment is the reference's row block, a pruned one every
+ * n_segments-th query block of the order (d_best merges by unsigned minimum, d_pops by summation); the order is built
+ * once per forest; the same min-edge row limit -- and refuses in the same order with the same codes, before a device is
+ * touched, naming itself.  n_cols outside 257..1024: DC_ERR_INVALID_ARGUMENT.
+ * Workspace: dc_hip_xwide_workspace_bytes(n_rows, n_cols, 1) for the unpruned calls,
+ * dc_hip_xwide_pruned_workspace_bytes(n_rows, n_cols, 1) for the pruned ones; a workspace of one family never serves the
+ * other.  dc_hip_wide_info_dev reads the counters of the last call (the pruned calls: the EVALUATED tile pairs),
+ * dc_hip_xwide_pruned_order_dev the order of a pruned call.
+ * The box rule of the pruned calls at these widths: a reference block is kept iff the squared gap of its box to the query
+ * block's is below far2 = 1.0001 x max(r2, 2^-122) for r2 > 0 (far2 = 0, no block, otherwise) -- the floor of
+ * dc_hip_populations_xwide_pruned_dev, not the bare 1.0001 x r2 of 65..256 columns: below about 0.37 FLT_MIN the canonical
+ * sum of 1024 terms can round under a gap that 1.0001 x r2 already excludes.
+ * Flagged data: the gated direct kernels answer on the original rows without a host synchronisation -- the generic
+ * direct kernel up to 400 columns, the column-chunked one beyond --, counters (0, 0, 0).
+ * No dc_variant value selects these calls; dc_hip_radius_pairs_dev, dc_hip_radius_min_edge[_segment]_dev,
+ * dc_hip_radius_forest, the sessions and the CLI keep sending these widths to the direct kernels. */
+DC_API int dc_hip_radius_pairs_xwide_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2, uint32_t* d_pops,
+                                         uint32_t* d_pairs, size_t capacity, unsigned long long* d_count, void* d_ws,
+                                         size_t ws_bytes, void* stream);
+DC_API int dc_hip_radius_min_edge_xwide_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
+                                            const uint32_t* d_comp, const uint32_t* d_rank, size_t segment,
+                                            size_t n_segments, unsigned long long* d_best, uint32_t* d_pops, void* d_ws,
+                                            size_t ws_bytes, void* stream);
+DC_API int dc_hip_radius_forest_xwide(const float* coords, size_t n_rows, size_t n_cols, float r2, const uint32_t* rank,
+                                      int device, uint32_t* edges, size_t* n_edges, uint32_t* n_rounds);
+DC_API int dc_hip_radius_pairs_xwide_pruned_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
+                                                uint32_t* d_pops, uint32_t* d_pairs, size_t capacity,
+                                                unsigned long long* d_count, void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_radius_min_edge_xwide_pruned_dev(const float* d_coords, size_t n_rows, size_t n_cols, float r2,
+                                                   const uint32_t* d_comp, const uint32_t* d_rank, size_t segment,
+                                                   size_t n_segments, unsigned long long* d_best, uint32_t* d_pops,
+                                                   void* d_ws, size_t ws_bytes, void* stream);
+DC_API int dc_hip_radius_forest_xwide_pruned(const float* coords, size_t n_rows, size_t n_cols, float r2,
+                                             const uint32_t* rank, int device, uint32_t* edges, size_t* n_edges,
+                                             uint32_t* n_rounds);
 
 /* the last wide sweep CALL in that workspace -- a self sweep (dc_hip_*_wide_dev, the radius graph included) or a cross sweep
  * (dc_hip_*_cross_wide_dev), the counters sit at the same place of either workspace: 32x32 tile pairs evaluated, MFMA instructions issued, frame pairs sent
