@@ -78,6 +78,7 @@ SYMBOLS = (
     "dc_hip_radius_pairs_xwide_pruned_dev", "dc_hip_radius_min_edge_xwide_pruned_dev", "dc_hip_radius_forest_xwide_pruned",
     "dc_hip_neighbors_block_rows_xwide", "dc_hip_neighbors_block_pack_xwide_dev", "dc_hip_neighbors_block_unpack_xwide_dev",
     "dc_hip_xwide_layout_status_dev",
+    "dc_hip_fp32_workspace_bytes", "dc_hip_fp32_plan", "dc_hip_populations_fp32_dev", "dc_hip_nearest_neighbors_fp32_dev",
 )
 SESSION_WIDE_SWEEPS = 0x1     # DC_SESSION_WIDE_SWEEPS (dc_hip_session_open_flags)
 ASSIGNER_XWIDE_REFERENCE = 0x1   # DC_ASSIGNER_XWIDE_REFERENCE (dc_hip_assigner_open_flags)
@@ -219,6 +220,14 @@ def _load():
     lib.dc_hip_populations_wide_dev.argtypes = [vp, sz, sz, C.POINTER(C.c_float), sz, sz, sz, vp, vp, sz, vp]
     lib.dc_hip_nearest_neighbors_wide_dev.restype = i32
     lib.dc_hip_nearest_neighbors_wide_dev.argtypes = [vp, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]
+    # the fp32-input MFMA sweeps for 1..32 columns: the argument lists of the wide sweeps, and their host-side planner
+    for fp32, wide in (("dc_hip_fp32_workspace_bytes", "dc_hip_wide_workspace_bytes"),
+                       ("dc_hip_populations_fp32_dev", "dc_hip_populations_wide_dev"),
+                       ("dc_hip_nearest_neighbors_fp32_dev", "dc_hip_nearest_neighbors_wide_dev")):
+        getattr(lib, fp32).restype = getattr(lib, wide).restype
+        getattr(lib, fp32).argtypes = getattr(lib, wide).argtypes
+    lib.dc_hip_fp32_plan.restype = i32
+    lib.dc_hip_fp32_plan.argtypes = [sz, sz, sz, C.POINTER(C.c_uint32)]
     lib.dc_hip_wide_info_dev.restype = i32
     lib.dc_hip_wide_info_dev.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     lib.dc_hip_cross_wide_workspace_bytes.restype = sz

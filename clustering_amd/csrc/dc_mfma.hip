@@ -4,6 +4,7 @@
 #include "dc_against.hpp"
 #include "dc_against_nn.hpp"
 #include "dc_against_ref.hpp"
+#include "dc_mfma32_band.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -1045,6 +1046,7 @@ const SweepSwitches& sweep_switches() {
     if ((v = env("DC_NN_FE_BITS"))) w.nn_fe_bits = atoi(v);
     w.mfma32_wpb = (uint32_t)one_of_124(env("DC_MFMA32_WPB"), 1);
     if ((v = env("DC_MFMA32_CHUNKS"))) w.mfma32_chunks = (uint32_t)atoi(v);
+    if ((v = env("DC_MFMA32_POISON_PADS"))) w.mfma32_poison_pads = v[0] == '1';
     if ((v = env("DC_SWEEP_DISPATCH"))) w.tickets = strcmp(v, "static") != 0;
     if ((v = env("DC_SWEEP_SLOTS"))) w.sweep_slots = (uint32_t)std::max(atoi(v), 0);
     return w;
@@ -2566,26 +2568,39 @@ int reference_order_copy(const void* d_ws, int which, uint32_t n_query, uint32_t
 // ---- DC_VARIANT_MFMA32: the fp32-input MFMA instance (dc_mfma32.hpp) ---------------------------------------------
 bool mfma32_supports(size_t n_cols) { return n_cols == 9 || n_cols == 10; }
 
+// the two orders of the fp32-input sweeps, left in the workspace (L.off_perm; the neighbour order with invpos, pq and the
+// sorted free energies beside it) -- for launch_*_mfma32 below and for the sweeps of dc_mfma32_general.hip
+int mfma32_order_pop(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t stream) {
+  const Layout L = make_layout(n_rows, n_cols);
+  char* p = (char*)d_ws;
+  // the frames in the order of their 2-D cells (cell32_key_kernel; about 64 frames per cell of the bounding box of columns
+  // 0 / 1, at most 256 x 256 cells: 16-bit keys, two passes of the library's sort)
+  const SortBufs S = sort_bufs(d_ws, L, L.fixed_end, sort_temp_bytes(n_rows));
+  uint32_t G = 1, g_bits = 0;
+  while (G < 256u && (size_t)(2u * G) * (2u * G) * 64u <= (size_t)n_rows) { G *= 2u; ++g_bits; }
+  hipLaunchKernelGGL(cell32_key_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, stream, d_coords, n_rows, n_cols,
+                     (const uint32_t*)p, G, S.keys_in, S.vals_in);
+  return S.run((uint32_t*)(p + L.off_perm), n_rows, stream, 2u * g_bits);
+}
+
+int mfma32_order_nn(uint32_t n_rows, uint32_t n_cols, const float* d_fe, void* d_ws, hipStream_t stream) {
+  const Layout L = make_layout(n_rows, n_cols);
+  return order_by_fe(n_rows, L.T, d_fe, d_fe, n_rows, fe_order(d_ws, L, L.fixed_end, n_rows), d_ws, stream);
+}
+
 void launch_pop_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
                        const Rad2& rad2, int n_rad, uint32_t* d_pops, void* d_ws, hipStream_t stream) {
   const Layout L = make_layout(n_rows, n_cols);
   char* p = (char*)d_ws;
   float* img = (float*)(p + L.off_img);
   float* norms = (float*)(p + L.off_norm);
-  // the frames in the order of their 2-D cells (cell32_key_kernel; about 64 frames per cell of the bounding box of columns
-  // 0 / 1, at most 256 x 256 cells: 16-bit keys, two passes of the library's sort)
-  const SortBufs S = sort_bufs(d_ws, L, L.fixed_end, sort_temp_bytes(n_rows));
-  uint32_t* perm = (uint32_t*)(p + L.off_perm);
-  uint32_t G = 1, g_bits = 0;
-  while (G < 256u && (size_t)(2u * G) * (2u * G) * 64u <= (size_t)n_rows) { G *= 2u; ++g_bits; }
-  hipLaunchKernelGGL(cell32_key_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, stream, d_coords, n_rows, n_cols,
-                     (const uint32_t*)p, G, S.keys_in, S.vals_in);
-  if (S.run(perm, n_rows, stream, 2u * g_bits) != 0) return;
+  const uint32_t* perm = (const uint32_t*)(p + L.off_perm);
+  if (mfma32_order_pop(d_coords, n_rows, n_cols, d_ws, stream) != 0) return;
   // (ONE image for all radii of the call, scaled for the largest: the band of a smaller radius is narrower than 1)
   float r2max = 0.0f;
   for (int r = 0; r < n_rad; ++r) r2max = std::max(r2max, rad2.v[r]);
   hipLaunchKernelGGL(image32_kernel, dim3((32 * L.T + 255) / 256), dim3(256), 0, stream, d_coords, n_rows, n_cols, L.T,
-                     (const float*)(p + kHdrMeans), (const uint32_t*)perm, (const uint32_t*)p, r2max, img, norms);
+                     (const float*)(p + kHdrMeans), (const uint32_t*)perm, (const uint32_t*)p, r2max, (uint32_t)kS32, sweep_switches().mfma32_poison_pads, img, norms);
   constexpr int kTQ = 8;
   // (two waves per SIMD at eight query tiles per wave: 2 048 wave slots; DC_MFMA32_CHUNKS for measurements)
   const uint32_t env_chunks = sweep_switches().mfma32_chunks;
@@ -2617,10 +2632,10 @@ void launch_nn_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, c
   float* img_s = (float*)(p + L.off_img_s);
   float* norms_s = (float*)(p + L.off_norm_s);
   hipLaunchKernelGGL(image32_kernel, grid_t, blk, 0, stream, d_coords, n_rows, n_cols, L.T, (const float*)(p + kHdrMeans),
-                     (const uint32_t*)nullptr, (const uint32_t*)p, -1.0f, img, norms);
-  if (order_by_fe(n_rows, L.T, d_fe, d_fe, n_rows, B, d_ws, stream) != 0) return;
+                     (const uint32_t*)nullptr, (const uint32_t*)p, -1.0f, (uint32_t)kS32, sweep_switches().mfma32_poison_pads, img, norms);
+  if (mfma32_order_nn(n_rows, n_cols, d_fe, d_ws, stream) != 0) return;
   hipLaunchKernelGGL(image32_kernel, grid_t, blk, 0, stream, d_coords, n_rows, n_cols, L.T, (const float*)(p + kHdrMeans),
-                     (const uint32_t*)B.perm, (const uint32_t*)p, -1.0f, img_s, norms_s);
+                     (const uint32_t*)B.perm, (const uint32_t*)p, -1.0f, (uint32_t)kS32, sweep_switches().mfma32_poison_pads, img_s, norms_s);
   constexpr int kTQ = 4;
   const uint32_t env_chunks = sweep_switches().mfma32_chunks;
   // ONE wave per workgroup: a workgroup holds its wave slots until its last wave is done, and the waves of this sweep

@@ -40,6 +40,7 @@ struct SweepSwitches {
   int nn_fe_bits = -1;            // DC_NN_FE_BITS: free-energy bits of the neighbour ordering's key (-1: default)
   uint32_t mfma32_wpb = 1;        // DC_MFMA32_WPB=1 / 2 / 4: waves per workgroup of the fp32-MFMA instance
   uint32_t mfma32_chunks = 0;     // DC_MFMA32_CHUNKS: its reference shares (0: chosen by size)
+  bool mfma32_poison_pads = false;   // DC_MFMA32_POISON_PADS=1 (tests): NaN instead of 0 in the pad floats of the fp32 image
   bool tickets = true;            // DC_SWEEP_DISPATCH=static / tickets: the per-wave pruned sweeps on one workgroup per unit /
                                   // on persistent workgroups that draw their units (dc_mfma_kernels.hpp for_each_unit)
   uint32_t sweep_slots = 0;       // DC_SWEEP_SLOTS: most persistent workgroups of a ticketed launch (0: all that can be resident)
@@ -118,6 +119,37 @@ void launch_pop_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, 
 void launch_nn_mfma32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, uint32_t i_from,
                       uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws,
                       hipStream_t stream);
+// ... and its two orders alone, left in the workspace: the frames by the cells of columns 0 / 1 (L.off_perm), the
+// frames by free energy (off_perm, off_invpos, off_pq, off_fe_s); non-zero when the sort failed
+int mfma32_order_pop(const float* d_coords, uint32_t n_rows, uint32_t n_cols, void* d_ws, hipStream_t stream);
+int mfma32_order_nn(uint32_t n_rows, uint32_t n_cols, const float* d_fe, void* d_ws, hipStream_t stream);
+
+// ---- the same sweeps for n_cols 1..32 and up to 8 radii per pass of the MFMAs (dc_mfma32_general.hip; the entry
+// points dc_hip_*_fp32_dev; the workspace of mfma_workspace_bytes; need mfma_prepare first) ------------------------
+constexpr size_t kFp32MaxCols = 32;
+// How one call is run: decided on the host from the sizes alone (and the DC_MFMA32_* switches), no device involved.
+struct Fp32Plan {
+  uint32_t steps;            // K-steps of the kernel instance: ceil(n_cols / 2), or one zero step more (fp32_steps)
+  uint32_t lane_floats;      // floats per lane and tile of the operand image: steps rounded up to a multiple of four
+  uint32_t tq_pop, tq_nn;    // query tiles per wave of the population sweeps of this call and of the neighbour sweep
+  uint32_t radii_per_sweep;  // radii that share one pass of the MFMAs
+  uint32_t sweeps;           // population sweeps of the call: ceil(n_radii / radii_per_sweep)
+  uint32_t chunks_pop, chunks_nn;   // reference chunks (chunks32)
+  uint32_t lds_pop, lds_nn;  // dynamic LDS per workgroup, bytes
+  uint32_t image_bytes;      // operand image, bytes per tile of 32 rows
+  uint32_t region_bytes;     // ... and what make_layout keeps for it
+};
+bool fp32_supports(size_t n_cols);
+uint32_t fp32_steps(size_t n_cols);
+// (asserts that image and norms fit the regions of make_layout; n_rows >= 1, n_cols 1..32, n_radii >= 1)
+Fp32Plan fp32_plan(size_t n_rows, size_t n_cols, size_t n_radii);
+// rad2: the n_radii squared radii of the call in the caller's order (numbers: see radius2 in dc_capi.hip); ONE image,
+// scaled for the largest, serves every sweep of the call; d_pops: [n_radii][n_rows], rows [i_from, i_to) written
+void launch_pop_fp32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from, uint32_t i_to,
+                     const float* rad2, size_t n_radii, uint32_t* d_pops, void* d_ws, hipStream_t stream);
+void launch_nn_fp32(const float* d_coords, uint32_t n_rows, uint32_t n_cols, const float* d_fe, uint32_t i_from,
+                    uint32_t i_to, uint32_t* d_nn_idx, float* d_nn_d2, uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws,
+                    hipStream_t stream);
 // population sweep over spatially ordered frames with tile-pair pruning (needs mfma_prepare first)
 // comp_clean: mfma_prepare(pruned) of this call has zero-filled the component region of the workspace
 void launch_pop_pruned(const float* d_coords, uint32_t n_rows, uint32_t n_cols, uint32_t i_from,

@@ -1,5 +1,7 @@
 // dc_mfma32.hpp -- the literal fp32-MFMA variant of the two sweeps (v_mfma_f32_32x32x2_f32), every pair evaluated
-// (included by dc_mfma.hip after dc_mfma_kernels.hpp, inside namespace dc::{anonymous}; DC_VARIANT_MFMA32).
+// (included by dc_mfma.hip -- DC_VARIANT_MFMA32, n_cols 9 .. 10 -- and by dc_mfma32_general.hip -- the entry points
+// dc_hip_*_fp32_dev, n_cols 1 .. 32, up to 8 radii per sweep -- after dc_mfma_kernels.hpp and dc_mfma32_band.hpp, inside
+// namespace dc::{anonymous}).
 //
 // BASELINE.json's north star names "an MFMA-tiled fp32 variant whose utilisation is evidenced by rocprof" with a target
 // of 60 % of the fp32 MFMA roofline (157.3 TFLOP/s: on gfx950 the fp32-input MFMA runs at the VECTOR rate and, measured,
@@ -10,7 +12,8 @@
 //     acc = |y'|^2 - 2 x'.y'  (A = centred reference coordinates, B = -2 centred query coordinates, C = |y'|^2)
 //     eps = 1.25 u [(4 K + 10) M + (D / 4 + 12) d2cap],  K = 2 S multiply-adds per chain, M = max |x'|^2
 // (the fp32 MFMA is a chain of fmaf: products exact to one rounding each, 2 S + 2 roundings around values <= 4 M).
-// Operand image: img32[(t * 64 + l) * 8 + s] = y'[32 t + (l & 31)][2 s + (l >> 5)], norms32[32 t + c] = |y'|^2.
+// Operand image: img32[(t * 64 + l) * 8 + s] = y'[32 t + (l & 31)][2 s + (l >> 5)], norms32[32 t + c] = |y'|^2; for S
+// K-steps the 8 is lane32(S) = S rounded up to a multiple of four floats (columns beyond n_cols and the pad floats: 0).
 //
 // Round 6 -- what the fp32-input MFMA wants from the code around it (scratch/ub/mfma32_sched.hip, one MI355X, ns per
 // chain and SIMD at two waves per SIMD; five dependent MFMAs alone: 137.4):
@@ -27,31 +30,12 @@
 // (rounding of c x'), 2 u thr (fl(c c), fl(S r^2)) and u (M + 2 thr) / 2 (the two subtractions that form the per-query
 // constant): 1.25 u [(4 K + 13) M + (D / 4 + 18) r^2] in data units, and c is the largest scale at which that is < 1.
 constexpr int kS32 = 5;   // K-steps: n_cols 9 .. 10
-constexpr int kLane32 = 8;    // floats per lane and tile in the operand image (S of them used: one dwordx4 + one dword)
+constexpr int kLane32 = 8;    // floats per lane and tile in the operand image at S = 5 (one dwordx4 + one dword)
+// ... and for any S (dc_mfma32_general.hip, n_cols 1..32): a lane's S fragments side by side, padded to whole dwordx4
+constexpr int lane32(int S) { return (S + 3) & ~3; }
+static_assert(lane32(kS32) == kLane32, "the 9..10-column instance is the S = 5 member of the family");
 constexpr int kNormBatch32 = 8;   // tiles whose row norms one LDS-DMA of a wave fetches (64 lanes x 16 B = 8 x 32 floats)
 constexpr int kClump32 = 4;   // chains (query tiles) whose MFMAs are issued back to back in front of their epilogues
-
-__host__ __device__ inline float guard_eps32(float M, float d2cap, int K, int D) {
-  const double u = 5.9604644775390625e-8;
-  const double cap = (d2cap > 0.0f) ? (double)d2cap : 0.0;
-  return next_up((float)(1.25 * u * ((4.0 * K + 10.0) * (double)M + (0.25 * D + 12.0) * cap)));
-}
-
-// scale c of the population image: the largest one at which the band of the scaled chain (see the header) stays below 1
-// for squared radii up to r2max.  Every thread of the image pass and of the sweep evaluates this from the same words.
-__host__ __device__ inline float scale32_pop(float M, float r2max, int K, int D) {
-  const double u = 5.9604644775390625e-8;
-  const double cap = (r2max > 0.0f) ? (double)r2max : 0.0;
-  const double eps1 = 1.25 * u * ((4.0 * K + 13.0) * (double)M + (0.25 * D + 18.0) * cap);   // band at scale 1
-  if (!(eps1 > 1.0e-76)) return 0x1p63f;                                                     // (all rows equal, r = 0)
-  const float c = (float)(sqrt((1.0 - 1.0 / 65536.0) / eps1) * (1.0 - 1.0 / 1048576.0));
-  // kept in [2^-60, 2^63] (a smaller c is always admissible: the band scales with S = c^2), so that S and S r2 stay finite
-  // for every finite r2 -- at 2^64, S overflowed for data of spread ~1e-17 and every pair read as inside.  Only r2max =
-  // +inf (a radius whose fl32 square overflows) takes the lower clamp; M <= 1e36 and finite r2 keep c above 2^-56.  In
-  // such a launch chunk every finite radius gets thr ~ -1: all its pairs fall in the band and take the exact re-check
-  // (pop32_fix), O(n^2) exact distances -- slow, and correct.
-  return fminf(fmaxf(c, 0x1p-60f), 0x1p63f);
-}
 
 // Spatial order of the fp32 population sweep (round 6): the frames by the cell of a G x G grid on columns 0 / 1 (their
 // extents: header words 8..11).  Every pair is still evaluated on the matrix pipe -- what the order buys is that most
@@ -70,10 +54,12 @@ __global__ void cell32_key_kernel(const float* __restrict__ coords, uint32_t n_r
 }
 
 // fp32 operand image of rows in natural order (perm == nullptr) or gathered through perm; r2max >= 0: scaled by
-// scale32_pop (population sweeps), r2max < 0: unscaled (neighbour sweep, whose band is relative)
+// scale32_pop (population sweeps), r2max < 0: unscaled (neighbour sweep, whose band is relative).  poison (the test
+// switch DC_MFMA32_POISON_PADS): the pad floats S .. lane32(S) - 1 of every lane, which no kernel may use, hold NaN
+// instead of 0 -- a fragment read from the wrong slot then shows in the results (tests/test_gpu_fp32.py)
 __global__ void image32_kernel(const float* __restrict__ coords, uint32_t n_rows, uint32_t D, uint32_t T,
                                const float* __restrict__ means, const uint32_t* __restrict__ perm,
-                               const uint32_t* __restrict__ hdr, float r2max, float* __restrict__ img,
+                               const uint32_t* __restrict__ hdr, float r2max, uint32_t S, bool poison, float* __restrict__ img,
                                float* __restrict__ norms) {
   const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= 32 * T) return;
@@ -81,16 +67,18 @@ __global__ void image32_kernel(const float* __restrict__ coords, uint32_t n_rows
   const bool live = row < n_rows;
   const uint32_t src = live ? (perm ? perm[row] : row) : 0u;
   const bool scaled = r2max >= 0.0f;
-  const float cs = scaled ? scale32_pop(__uint_as_float(hdr[0]), r2max, 2 * kS32, (int)D) : 1.0f;
+  const float cs = scaled ? scale32_pop(__uint_as_float(hdr[0]), r2max, 2 * (int)S, (int)D) : 1.0f;
+  const uint32_t lane_floats = (uint32_t)lane32((int)S);
   double nrm = 0.0;
-  for (uint32_t k = 0; k < 2 * (uint32_t)kS32; ++k) {
+  for (uint32_t k = 0; k < 2 * lane_floats; ++k) {   // (columns D .. 2 S - 1 and the pad floats S .. lane_floats - 1: zero)
     float v = 0.0f;
     if (live && k < D) {
       v = coords[(size_t)src * D + k] - means[k];
       if (scaled) v = cs * v;
     }
     nrm += (double)v * (double)v;
-    img[((size_t)t * 64 + c + 32 * (k & 1)) * kLane32 + (k >> 1)] = v;   // (lane-contiguous: see load_frag32)
+    if (poison && (k >> 1) >= S) v = __uint_as_float(0x7FC00000u);
+    img[((size_t)t * 64 + c + 32 * (k & 1)) * lane_floats + (k >> 1)] = v;   // (lane-contiguous: see load_frag32)
   }
   norms[row] = live ? (float)nrm : INFINITY;   // pad rows: never inside, never a candidate
 }
@@ -101,16 +89,40 @@ __global__ void image32_kernel(const float* __restrict__ coords, uint32_t n_rows
 // front of the tile: 190 -> 215 ms).  So the image keeps a lane's S fragments side by side (one dwordx4 + one dword),
 // and the row norms -- the same 16 values for all lanes of a half-wave -- come through a wave-private LDS ring that ONE
 // LDS-DMA per kNormBatch32 tiles fills (ds_read_b128 costs next to nothing among MFMAs): 2 1/8 instead of 9 per tile.
+// Any S: ceil(S / 4) loads per lane and tile -- whole dwordx4, and for the last S % 4 fragments one dword (S % 4 = 1, as
+// the instance of 9..10 columns has it: a dwordx4 there would hold three more registers for nothing) or one dwordx4 whose
+// last element is a pad float (S % 4 = 3).  No instance has S % 4 = 2.
 template <int S>
 __device__ __forceinline__ void load_frag32(const float* __restrict__ img, uint32_t t, int lane, float (&a)[S]) {
-  static_assert(S == 5, "one dwordx4 and one dword per lane");
-  const float* ip = img + ((size_t)t * 64 + lane) * kLane32;
-  const float4 v = *reinterpret_cast<const float4*>(ip);
-  a[0] = v.x;
-  a[1] = v.y;
-  a[2] = v.z;
-  a[3] = v.w;
-  a[4] = ip[4];
+  static_assert(S >= 1 && S <= 16 && S % 4 != 2, "n_cols 1..32; instances S = 1, 3, ..., 15, 16");
+  constexpr int kLaneS = lane32(S);
+  const float* ip = img + ((size_t)t * 64 + lane) * kLaneS;
+  if constexpr (S == 5) {   // (spelt as it was: DC_VARIANT_MFMA32's two instances stay as they were built)
+    const float4 v = *reinterpret_cast<const float4*>(ip);
+    a[0] = v.x;
+    a[1] = v.y;
+    a[2] = v.z;
+    a[3] = v.w;
+    a[4] = ip[4];
+    return;
+  }
+#pragma unroll
+  for (int s = 0; s + 4 <= S; s += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(ip + s);
+    a[s] = v.x;
+    a[s + 1] = v.y;
+    a[s + 2] = v.z;
+    a[s + 3] = v.w;
+  }
+  constexpr int s4 = S & ~3;
+  if constexpr (S % 4 == 1) {
+    a[s4] = ip[s4];
+  } else if constexpr (S % 4 == 3) {
+    const float4 v = *reinterpret_cast<const float4*>(ip + s4);   // (.w: a pad float, zero)
+    a[s4] = v.x;
+    a[s4 + 1] = v.y;
+    a[s4 + 2] = v.z;
+  }
 }
 // the wave's ring of row norms: two batches of kNormBatch32 tiles; batch i of the chunk (tiles tb + 8 i ...) in slot i & 1
 struct Norms32 {
@@ -178,6 +190,7 @@ __global__ __launch_bounds__(256, 2) void pop_mfma32_kernel(
     const float* __restrict__ norms, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ hdr, uint32_t T,
     uint32_t i_from, uint32_t i_to, float r2, float r2max, uint32_t* __restrict__ pops) {
   static_assert(TQ % kClump32 == 0, "query tiles are handled in clumps");
+  constexpr int kLaneS = lane32(S);   // (a constant of the instance, as kLane32 was: the call in the index expression compiles differently)
   extern __shared__ __attribute__((aligned(16))) float pop32_lds[];   // per wave: the ring of row norms (Norms32)
   if (hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
   const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
@@ -209,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void pop_mfma32_kernel(
     any_live |= livemask[qt];
     const uint32_t tl = tile < T ? tile : T - 1;
 #pragma unroll
-    for (int s = 0; s < S; ++s) b[qt][s] = -2.0f * img[((size_t)tl * 64 + lane) * kLane32 + s];
+    for (int s = 0; s < S; ++s) b[qt][s] = -2.0f * img[((size_t)tl * 64 + lane) * kLaneS + s];
     const float lo = thr - (live ? norms[tl * 32 + c] : INFINITY);   // -inf for an idle lane: t = +inf, outside, no band
     nlo[qt] = f32x2{-lo, -lo};
     cnt[qt] = 0;
@@ -302,6 +315,168 @@ __global__ __launch_bounds__(256, 2) void pop_mfma32_kernel(
   }
 }
 
+// Several radii in ONE pass of the MFMAs (n_rad <= 8 of rad2, in the caller's order: unsorted, equal, 0, +inf; the C
+// API has turned a NaN radius into r^2 = 0).  The image is scaled for the call's largest radius (r2max), and the
+// per-chain tile minimum is tested against that radius alone: thr = fl(fl(c c) r^2) - 1 is monotone in r^2, so a chain
+// that fails the test for r2max fails it for every radius.  A chain that passes goes to pop32_multi_chain, which per
+// radius does exactly what pop_mfma32_kernel does for one: the radius's own tile test, the two-bit string, the band
+// pairs to pop32_fix.  What the sweep keeps per radius lives in LDS, not in registers -- the thresholds and squared
+// radii (wave-uniform) and the counts cnt[TQ][n_rad][64 lanes] -- so the main loop holds what the one-radius kernel
+// holds and one more register per query tile (the row norm):
+//   every chain                   as for one radius: 8 v_min3 + 2, one wave-level test per clump
+//   chain passes for r2max        one call (the accumulator tile by value), and per radius 1 ds_read (thr), 1 v_sub (the
+//                                 per-query constant), 1 v_add + 1 v_cmp (its tile test)
+//   ... and for the radius        8 v_pk_add_f32 + 16 v_alignbit + v_and + v_bcnt (string, count) + ds_read / v_add /
+//                                 ds_write of the lane's own count: 30 VALU, 2 LDS
+//   band pairs                    pop32_fix with that radius
+// Per-wave LDS: the norms ring, thr[8], r2[8], cnt (pop32m_wave_words).
+constexpr uint32_t kPop32mThr = 2 * kNormBatch32 * 32, kPop32mR2 = kPop32mThr + 8, kPop32mCnt = kPop32mR2 + 8;
+constexpr uint32_t pop32m_wave_words(int tq, int n_rad) { return kPop32mCnt + (uint32_t)(tq * n_rad) * 64u; }
+
+// wl: the wave's LDS block; cnt: the lane's own count of radius 0 of this query tile (radius r: + 64 r)
+typedef __attribute__((address_space(3))) float Lds32f;   // (LDS pointers handed to a function: ds_ instead of flat_ accesses)
+typedef __attribute__((address_space(3))) uint32_t Lds32u;
+__device__ __attribute__((noinline)) void pop32_multi_chain(f32x16 acc, float am, float nq, const Lds32f* wl, Lds32u* cnt,
+                                                            int n_rad, const float* __restrict__ coords,
+                                                            const uint32_t* __restrict__ perm, uint32_t n_rows, uint32_t n_cols,
+                                                            uint32_t jq, uint32_t t, int h) {
+  for (int r = 0; r < n_rad; ++r) {
+    const float nl = -(wl[kPop32mThr + r] - nq);
+    if (__builtin_amdgcn_ballot_w64(am + nl < 2.0f) == 0) continue;   // (every pair of this chain is outside THIS radius)
+    const uint32_t bits = pop32_string(acc, f32x2{nl, nl});
+    uint32_t n = __builtin_popcount(inside_of(bits));
+    const uint32_t bq = band_of(bits);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(bq != 0) != 0, 0))
+      n += pop32_fix(coords, perm, n_rows, n_cols, wl[kPop32mR2 + r], bq, jq, t, h);
+    cnt[64 * r] += n;
+  }
+}
+
+// NC: chains (query tiles) per clump -- NC, or 2 where four accumulator tiles do not fit beside b[TQ][S] (S >= 11)
+template <int S, int TQ, int NC>
+__global__ __launch_bounds__(256, 2) void pop_mfma32_multi_kernel(
+    const float* __restrict__ coords, uint32_t n_rows, uint32_t n_cols, const float* __restrict__ img,
+    const float* __restrict__ norms, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ hdr, uint32_t T,
+    uint32_t i_from, uint32_t i_to, Rad2 rad2, int n_rad, float r2max, uint32_t* __restrict__ pops) {
+  static_assert(TQ % NC == 0, "query tiles are handled in clumps");
+  constexpr int kLaneS = lane32(S);
+  extern __shared__ __attribute__((aligned(16))) float pop32m_lds[];
+  if (hdr[1] != 0) return;   // non-finite / overflow-prone data: the gated direct kernel runs instead
+  const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+  const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t qt0 = wave * TQ;
+  if (qt0 >= T) return;   // whole wave leaves; no barriers in this kernel
+  const float cs = scale32_pop(__uint_as_float(hdr[0]), r2max, 2 * S, (int)n_cols);
+  auto thr_of = [cs](float r2) {   // (see pop_mfma32_kernel: only overflow is capped)
+    const float thr0 = (cs * cs) * r2 - 1.0f;
+    return (thr0 > FLT_MAX) ? FLT_MAX : thr0;
+  };
+  const float thr_max = thr_of(r2max);
+  float* wl = pop32m_lds + (size_t)(threadIdx.x >> 6) * pop32m_wave_words(TQ, n_rad);
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(wl + kPop32mCnt) + lane;   // [TQ][n_rad][64]: this lane's
+  if (lane < kMaxRadiiPerLaunch) {
+    float r2 = 0.0f;
+#pragma unroll
+    for (int r = 0; r < kMaxRadiiPerLaunch; ++r) r2 = (lane == r && r < n_rad) ? rad2.v[r] : r2;
+    wl[kPop32mThr + lane] = thr_of(r2);
+    wl[kPop32mR2 + lane] = r2;
+  }
+  for (int k = 0; k < TQ * n_rad; ++k) cnt[64 * k] = 0;
+
+  float b[TQ][S];
+  float nq[TQ], nlo_max[TQ];   // the query's row norm (+inf: idle lane -> t = +inf, outside, no band), -(thr_max - norm)
+  uint32_t jq[TQ];
+  uint64_t livemask[TQ];
+  uint64_t any_live = 0;
+#pragma unroll
+  for (int qt = 0; qt < TQ; ++qt) {
+    const uint32_t tile = qt0 + qt, pos = tile * 32 + c;
+    jq[qt] = (tile < T && pos < n_rows) ? perm[pos] : 0xFFFFFFFFu;
+    const bool live = (jq[qt] >= i_from) && (jq[qt] < i_to);   // (0xFFFFFFFF: beyond every range)
+    livemask[qt] = __builtin_amdgcn_ballot_w64(live);
+    any_live |= livemask[qt];
+    const uint32_t tl = tile < T ? tile : T - 1;
+#pragma unroll
+    for (int s = 0; s < S; ++s) b[qt][s] = -2.0f * img[((size_t)tl * 64 + lane) * kLaneS + s];
+    nq[qt] = live ? norms[tl * 32 + c] : INFINITY;
+    nlo_max[qt] = -(thr_max - nq[qt]);
+  }
+  if (any_live == 0) return;   // (a row range: none of this wave's positions belongs to it)
+  const uint32_t per = (T + gridDim.y - 1) / gridDim.y, tb = blockIdx.y * per, te = min(T, tb + per);
+  if (tb >= te) return;
+  const uint32_t nt = te - tb;
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // (thresholds and radii: written by lanes 0..7, read by all)
+  const Norms32 N{wl, norms + (size_t)tb * 32};
+  N.fetch(0, lane);
+  N.fetch(1, lane);
+  float a0[S], a1[S];
+  float4 n0[4], n1[4];
+  load_frag32<S>(img, tb, lane, a0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the first two batches of norms have landed)
+  N.read(0, h, n0);
+  auto tile_body = [&](const float (&a)[S], const float4 (&nv)[4], uint32_t t, auto&& prefetch) {   // (see pop_mfma32_kernel)
+    const f32x16 c0 = frag16(nv);
+#pragma unroll
+    for (int g = 0; g < TQ; g += NC) {
+      f32x16 acc[NC];
+      chains32<S, NC>(a, &b[g], c0, acc);
+      __builtin_amdgcn_sched_barrier(0);
+      prefetch(g / NC);
+      __builtin_amdgcn_sched_barrier(0);
+      float am[NC], dmin = INFINITY;   // smallest accumulator value of the lane's 16 elements
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        am[q] = INFINITY;
+        tile_min<0, 16>(acc[q], am[q]);
+        dmin = fminf(dmin, am[q] + nlo_max[g + q]);
+      }
+      if (__builtin_amdgcn_ballot_w64(dmin < 2.0f) != 0) {
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+          if (__builtin_amdgcn_ballot_w64(am[q] + nlo_max[g + q] < 2.0f) == 0) continue;   // (outside the largest radius)
+          pop32_multi_chain(acc[q], am[q], nq[g + q], (const Lds32f*)wl, (Lds32u*)(cnt + 64 * (g + q) * n_rad), n_rad, coords, perm, n_rows, n_cols,
+                            jq[g + q], t, h);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    keep_alive(c0);   // (see pop_mfma32_kernel)
+  };
+  for (uint32_t k = 0; k < nt; k += 2) {
+    tile_body(a0, n0, tb + k, [&](int part) {
+      if (part == 0) load_frag32<S>(img, tb + min(k + 1, nt - 1), lane, a1);
+      if (part == TQ / NC - 1) N.read(k + 1, h, n1);
+    });
+    if (k + 1 < nt) {
+      tile_body(a1, n1, tb + k + 1, [&](int part) {
+        if (part == 0) {
+          if (((k + 2) & (kNormBatch32 - 1)) == 0) N.fetch((k + 2) / kNormBatch32 + 1, lane);
+          load_frag32<S>(img, tb + min(k + 2, nt - 1), lane, a0);
+        }
+        if (part == TQ / NC - 1) N.read(k + 2, h, n0);
+      });
+    }
+  }
+#pragma unroll
+  for (int qt = 0; qt < TQ; ++qt) {
+    const bool writer = h == 0 && ((livemask[qt] >> lane) & 1);
+    const float dself = (writer && blockIdx.y == 0) ? exact_d2(coords, n_cols, jq[qt], jq[qt]) : 0.0f;
+    for (int r = 0; r < n_rad; ++r) {
+      const uint32_t mine = cnt[64 * (qt * n_rad + r)];
+      uint32_t total = mine + (uint32_t)__shfl_xor((int)mine, 32, 64);
+      if (writer) {
+        // (the self pair: see pop_mfma32_kernel)
+        if (blockIdx.y == 0) total += 1u - ((dself < wl[kPop32mR2 + r]) ? 1u : 0u);
+        uint32_t* out = pops + (size_t)r * n_rows + jq[qt];
+        if (gridDim.y == 1)
+          *out = total;
+        else
+          atomicAdd(out, total);
+      }
+    }
+  }
+}
+
 // Reference chunks of the fp32-input sweeps: every wave costs the same (all pairs are evaluated), so a launch whose
 // waves do not fill the chip's wave slots a whole number of times idles at its end -- 7 813 waves of four query tiles on
 // 2 048 slots: 3.81 rounds, 5 % lost; on 3 072 (three waves per SIMD) 2.54 rounds, 15 % lost.  The smallest chunk count
@@ -361,7 +536,8 @@ __global__ __launch_bounds__(256, 2) void nn_mfma32_kernel(
     const uint32_t* __restrict__ hdr, uint32_t T, uint32_t i_from, uint32_t i_to,
     unsigned long long* __restrict__ merge64, uint32_t* __restrict__ nn_idx, float* __restrict__ nn_d2, uint32_t* __restrict__ hd_idx,
     float* __restrict__ hd_d2) {
-  static_assert(TQ == kClump32, "one clump of chains per reference tile");
+  static_assert(TQ == kClump32 || TQ == 2, "one clump of chains per reference tile (two where four do not fit: S >= 7)");
+  constexpr int kLaneS = lane32(S);
   // dynamic LDS, per wave: the ring of row norms (Norms32), candidate list [kWaveQueue] x 8 B, exact incumbents
   // [2][TQ*32] x 8 B, query rows [TQ*32][n_cols]
   extern __shared__ __attribute__((aligned(16))) float nn32_lds[];
@@ -399,7 +575,7 @@ __global__ __launch_bounds__(256, 2) void nn_mfma32_kernel(
     livemask[qt] = __builtin_amdgcn_ballot_w64(live);
     const uint32_t tl = tile < T ? tile : T - 1;
 #pragma unroll
-    for (int s = 0; s < S; ++s) b[qt][s] = -2.0f * img[((size_t)tl * 64 + lane) * kLane32 + s];
+    for (int s = 0; s < S; ++s) b[qt][s] = -2.0f * img[((size_t)tl * 64 + lane) * kLaneS + s];
     const uint32_t jl = live ? jq[qt] : (n_rows - 1);
     pq[qt] = live ? pq_of[jl] : 0u;
     spos[qt] = live ? invpos[jl] : 0xFFFFFFFFu;

@@ -55,6 +55,8 @@ _SIZES = {
     "xwide_pruned": capi.lib.dc_hip_xwide_pruned_workspace_bytes,
     # ... and their pruned cross sweeps
     "xwide_against_pruned": capi.lib.dc_hip_cross_xwide_pruned_workspace_bytes,
+    # the fp32-input matrix-core sweeps for rows of 1..32 columns
+    "fp32": capi.lib.dc_hip_fp32_workspace_bytes,
 }
 
 
@@ -236,6 +238,37 @@ def nearest_neighbors_wide(coords, fe, i_from=0, i_to=None):
     """nearest_neighbors_partial for rows of 65..256 columns on the matrix cores (dc_hip_nearest_neighbors_wide_dev).
     -> (nn_idx int32, nn_d2 float32, hd_idx int32, hd_d2 float32), each [n_rows]; "none" is (n_rows+1, FLT_MAX)."""
     return _neighbors("dc_hip_nearest_neighbors_wide_dev", "wide", coords, fe, (i_from, i_to))
+
+
+# ---- fp32-input matrix-core sweeps for rows of 1..32 columns (include/dc_density.h "fp32" sweeps) -----------------
+def calculate_populations_fp32(coords, radii, i_from=None, i_to=None):
+    """calculate_populations_partial on the fp32-input matrix cores (dc_hip_populations_fp32_dev) for rows of 1..32
+    columns: the same populations bit for bit, every pair evaluated, up to 8 radii of the call sharing one pass of the
+    MFMAs (fp32_sweep_plan says how a call is run); radii in any order.  Other column counts raise.
+    -> torch.int32 [n_radii, n_rows], zero outside [i_from, i_to)."""
+    n_rows, n_cols = _check_coords(coords)
+    return _populations("dc_hip_populations_fp32_dev", "fp32", coords.device, (_dev(coords), n_rows, n_cols), (n_rows, n_cols),
+                        radii, (0 if i_from is None else i_from, n_rows if i_to is None else i_to), None)
+
+
+def nearest_neighbors_fp32(coords, fe, i_from=None, i_to=None):
+    """nearest_neighbors_partial on the fp32-input matrix cores (dc_hip_nearest_neighbors_fp32_dev), 1..32 columns.
+    -> (nn_idx int32, nn_d2 float32, hd_idx int32, hd_d2 float32), each [n_rows]; "none" is (n_rows+1, FLT_MAX)."""
+    return _neighbors("dc_hip_nearest_neighbors_fp32_dev", "fp32", coords, fe, (0 if i_from is None else i_from, i_to))
+
+
+def fp32_sweep_plan(n_rows, n_cols, n_radii):
+    """How the fp32 sweeps run a call of this shape (dc_hip_fp32_plan; decided on the host, no device needed) -> dict:
+    k_steps (MFMAs per chain: ceil(n_cols / 2), at some widths one zero step more), lane_floats (floats per lane and
+    tile of the operand image), tq_pop / tq_nn (query tiles per wave), radii_per_sweep, sweeps, chunks_pop / chunks_nn
+    (reference chunks), lds_pop / lds_nn (dynamic LDS bytes per workgroup), image_bytes_per_tile and
+    image_region_bytes_per_tile (what the workspace keeps for it)."""
+    out = (C.c_uint32 * 8)()
+    capi.check(capi.lib.dc_hip_fp32_plan(n_rows, n_cols, n_radii, out), "dc_hip_fp32_plan")
+    w = [int(v) for v in out]
+    return {"k_steps": w[0], "lane_floats": w[1], "tq_pop": w[2] & 0xFFFF, "tq_nn": w[2] >> 16,
+            "radii_per_sweep": w[3] & 0xFFFF, "sweeps": w[3] >> 16, "chunks_pop": w[4] & 0xFFFF, "chunks_nn": w[4] >> 16,
+            "lds_pop": w[5], "lds_nn": w[6], "image_bytes_per_tile": w[7] & 0xFFFF, "image_region_bytes_per_tile": w[7] >> 16}
 
 
 def _wide_info(kind, device):

@@ -70,7 +70,9 @@ typedef enum dc_variant {
                                  density_clustering.cpp:41-89); identical results */
   DC_VARIANT_MFMA32 = 4,      /* the literal fp32-input MFMA (v_mfma_f32_32x32x2_f32) Gram form, every pair evaluated:
                                  the instance BASELINE's "fraction of the fp32 MFMA roofline" is quoted on; n_cols
-                                 9..10 only, one radius per sweep; identical results (classifier + band + re-check) */
+                                 9..10 only, one radius per sweep; identical results (classifier + band + re-check).
+                                 The same kernels for 1..32 columns and several radii per sweep: the entry points
+                                 dc_hip_populations_fp32_dev / dc_hip_nearest_neighbors_fp32_dev below */
   DC_VARIANT_CROSS_PRUNED = 5 /* populations of new frames against a reference on the matrix cores with tile-pair
                                  pruning: both sets ordered by the cells of one grid on columns 0/1, tile pairs at
                                  least the largest radius apart skipped; n_cols <= 64; identical results.  ONLY
@@ -476,6 +478,44 @@ DC_API int dc_hip_populations_wide_dev(const float* d_coords, size_t n_rows, siz
                                        size_t n_radii, size_t i_from, size_t i_to, uint32_t* d_pops, void* d_ws,
                                        size_t ws_bytes, void* stream);
 DC_API int dc_hip_nearest_neighbors_wide_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* d_fe,
+                                             size_t i_from, size_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
+                                             uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
+                                             void* stream);
+/* ---- the fp32-input matrix-core sweeps for rows of 1..32 columns ("fp32" sweeps) ----------------------------------
+ * DC_VARIANT_MFMA32's kernels (v_mfma_f32_32x32x2_f32, every pair evaluated, classifier + band + canonical re-check)
+ * for every width the fp32 image fits the workspace of dc_hip_workspace_bytes, and with up to 8 radii of a call sharing
+ * ONE pass of the MFMAs: ceil(n_cols / 2) K-steps (at some widths one zero step more: dc_hip_fp32_plan), the image
+ * scaled for the call's largest radius, the per-chain tile test against that radius, the two-bit strings and the band
+ * re-check per radius.  Results: those of dc_hip_populations_dev / dc_hip_nearest_neighbors_dev bit for bit.  Entry
+ * points of their own: no dc_variant value selects them, DC_VARIANT_MFMA32 keeps serving 9..10 columns only.
+ *   dc_hip_populations_fp32_dev        replaces density_clustering_cuda.cu:45-137 (the radius loop of :112-131 inside
+ *                                      one sweep: d_pops[r * n_rows + i] in the caller's radius order; radii unsorted,
+ *                                      equal, 0, +inf or NaN as for dc_hip_populations_dev; more than 8: ceil(n / 8)
+ *                                      sweeps over the one image); rows outside [i_from, i_to): 0
+ *   dc_hip_nearest_neighbors_fp32_dev  replaces density_clustering_cuda.cu:184-284; rows outside the range: "none" =
+ *                                      (n_rows + 1, FLT_MAX)
+ *   dc_hip_fp32_workspace_bytes        dc_hip_workspace_bytes for 1..32 columns, 0 outside them (and for no rows)
+ *   dc_hip_fp32_plan                   how a call of that shape is run, decided on the host alone (no device needed):
+ *                                      out[0] K-steps, out[1] floats per lane and tile of the image (a multiple of 4),
+ *                                      out[2] query tiles per wave, population | neighbour << 16, out[3] radii per
+ *                                      sweep | sweeps << 16, out[4] reference chunks, population | neighbour << 16,
+ *                                      out[5] / out[6] dynamic LDS bytes per workgroup, population / neighbour,
+ *                                      out[7] image bytes per 32-row tile | bytes the workspace keeps for it << 16.
+ *                                      Query tiles, chunks and LDS are those of the call's FULL sweeps (radii per sweep
+ *                                      radii each); the last sweep of a call whose count is no multiple of 8 holds
+ *                                      fewer radii and is sized by the same rule: ask for that count to see it (one
+ *                                      radius runs the one-radius kernel, which may take more query tiles per wave)
+ * Flagged data (a non-finite or overflow-prone row, a NaN free energy) is answered by the direct kernels behind the
+ * device-side gate.  The switches DC_MFMA32_CHUNKS / DC_MFMA32_WPB apply.
+ * Refusals, all before a device is touched: n_cols outside 1..32, n_radii == 0, a NULL array or `out`, i_from > i_to or
+ * i_to > n_rows: DC_ERR_INVALID_ARGUMENT; n_rows + 1 beyond uint32 or more than 65535 radii: DC_ERR_TOO_LARGE; a workspace smaller than
+ * dc_hip_fp32_workspace_bytes, or none: DC_ERR_WORKSPACE.  n_rows == 0 or an empty range: DC_OK. */
+DC_API size_t dc_hip_fp32_workspace_bytes(size_t n_rows, size_t n_cols, size_t n_radii);
+DC_API int dc_hip_fp32_plan(size_t n_rows, size_t n_cols, size_t n_radii, uint32_t out[8]);
+DC_API int dc_hip_populations_fp32_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* radii,
+                                       size_t n_radii, size_t i_from, size_t i_to, uint32_t* d_pops, void* d_ws,
+                                       size_t ws_bytes, void* stream);
+DC_API int dc_hip_nearest_neighbors_fp32_dev(const float* d_coords, size_t n_rows, size_t n_cols, const float* d_fe,
                                              size_t i_from, size_t i_to, uint32_t* d_nn_idx, float* d_nn_d2,
                                              uint32_t* d_hd_idx, float* d_hd_d2, void* d_ws, size_t ws_bytes,
                                              void* stream);
